@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: paired reads/s mapped + quantified (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|3|4]
+    python bench.py --gpus N --steps K --warmup W [--config 1|3|4] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the infer hot path over one resident batch:
 pack -> map -> class counting -> effective lengths -> EM to the reference's
 stopping rule -> TPM, against the synthetic ~190k-transcript index (the ENSEMBL
 cDNA BASELINE.json names is not available offline; SURVEY.md 8(d) defines the
 seeded stand-in).  Inputs are resident in HBM when the timed region starts.
+
+A plain run sets up, warms up, times EXACTLY K steps and prints the JSON line (metric, value,
+ms_per_step, the phase times of the timed steps).  The index is built once per (seed, genes,
+generator and builder sources) and kept under .bench_cache/ (`__graft_entry__.build()` prepares
+the default one where a GPU is visible); later runs load it in seconds instead of building it.
+`--full` adds everything else the benchmark measures or checks -- the roofline from a counting
+launch, the parity checks, `cpu_baseline`, and on the default configuration `e2e` and
+`other_configs`.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(float64; a seeded sample of at most 2^20 elements for a larger array).
 
   --config 1 (default)  BASELINE configs[1]: 10 M 2x100 bp pairs per GPU
   --config 3            BASELINE configs[3]: 50 M single-end 150 bp reads (-s)
@@ -17,10 +26,10 @@ seeded stand-in).  Inputs are resident in HBM when the timed region starts.
 For N > 1 (launched by torch.distributed.run, one rank per GPU) reads shard
 across ranks with no collective while mapping and one RCCL all-reduce of
 f64[T] per EM step (--config 4: the merged table on every rank, the replicates
-shared out, no collective while they run); rank 0 prints ONE JSON line.  The
-default run (N = 1, --config 1) also carries `e2e`: the same workload timed
-from host arrays (PCIe inclusive) and from FASTQ text -- neither is `value` --
-and `other_configs`: a few timed steps of configs[3] and configs[4] on the
+shared out, no collective while they run); rank 0 prints ONE JSON line.  With
+--full, the default configuration (N = 1, --config 1) also carries `e2e`: the same
+workload timed from host arrays (PCIe inclusive) and from FASTQ text -- neither is
+`value` -- and `other_configs`: a few timed steps of configs[3] and configs[4] on the
 same index.
 """
 import argparse
@@ -65,6 +74,107 @@ def table_digest(map_result):
 
 def log(*a):
     print('[bench]', *a, file=sys.stderr, flush=True)
+
+
+CACHE_DIR = os.path.join(ROOT, '.bench_cache')
+# what decides the bytes of the synthetic index besides (seed, genes): the generator, the builder and
+# the container format
+INDEX_SOURCES = ('seekmer_amd/synth.py', 'seekmer_amd/index_builder.py', 'seekmer_amd/common.py',
+                 'seekmer_amd/_native.py', 'seekmer_amd/csrc/skm_synth.cpp', 'seekmer_amd/csrc/skm_builder.cpp',
+                 'include/seekmer_hip.h')
+
+
+def index_cache_path(seed, genes):
+    """The cached index of (seed, genes), named by a digest of INDEX_SOURCES: an edit to any of them
+    names a new file instead of reusing a stale one."""
+    import hashlib
+    h = hashlib.sha256()
+    for name in INDEX_SOURCES:
+        with open(os.path.join(ROOT, name), 'rb') as f:
+            h.update(f.read())
+    return os.path.join(CACHE_DIR, 'index_s%d_g%d_%s.npz' % (seed, genes, h.hexdigest()[:16]))
+
+
+def store_index(index, path):
+    """Write the index to `path` through a temporary file (a run that stops half-way leaves no torn
+    cache) and, in CACHE_DIR, drop the files of the same (seed, genes) from other sources.  Not being
+    able to store it is no error: the run goes on with the index it built."""
+    import glob
+    tmp = '%s.%d.tmp' % (path, os.getpid())
+    try:
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        index.save(tmp)
+        os.replace(tmp, path)
+    except OSError as e:
+        log('index not cached: %s' % e)
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        return
+    if os.path.dirname(os.path.abspath(path)) != CACHE_DIR:
+        return                         # (a path given with --index-cache: nothing beside it is ours)
+    stem = os.path.basename(path).rsplit('_', 1)[0]
+    for old in glob.glob(os.path.join(os.path.dirname(path), stem + '_*.npz')):
+        if old != path:
+            try:
+                os.unlink(old)
+            except OSError:
+                pass
+
+
+def bench_index(ids, pool, tx_offsets, path, rank, world, dist):
+    """The synthetic index from the cache at `path`; rank 0 builds and stores it first when it is not
+    there (one core for ~40 s at 20000 genes, against a second or two to load it)."""
+    from seekmer_amd import index_builder, parallel
+    built = None
+    if rank == 0 and not os.path.exists(path):
+        built = index_builder.build_pooled(ids, pool, tx_offsets)
+        store_index(built, path)
+    if dist is not None:
+        dist.barrier()
+    if not os.path.exists(path):
+        path = None                    # (could not be stored: rank 0 hands its own over as before)
+    index = parallel.shared_index(
+        lambda: built if built is not None else index_builder.build_pooled(ids, pool, tx_offsets), rank, world,
+        barrier=(dist.barrier if dist is not None else None), cache=path)
+    lengths = np.asarray(index.transcripts['length'])
+    if lengths.size != len(ids) or not np.array_equal(lengths, np.diff(tx_offsets)):
+        raise SystemExit('the cached index %s does not belong to this transcriptome' % path)
+    return index
+
+
+def prepare_index(seed=1, genes=20000):
+    """Build and cache the default run's index if it is not cached yet (`__graft_entry__.build()`)."""
+    from seekmer_amd import synth
+    path = index_cache_path(seed, genes)
+    if not os.path.exists(path):
+        t0 = time.perf_counter()
+        ids, pool, tx_offsets = synth.transcriptome(seed, genes)
+        bench_index(ids, pool, tx_offsets, path, 0, 1, None)
+        log('benchmark index cached in %.1fs: %s' % (time.perf_counter() - t0, path))
+    return path
+
+
+DUMP_LIMIT = 1 << 20        # elements per dumped array: 8 MiB of float64, 64 MiB in all at most
+
+
+def dump_outputs(folder, arrays):
+    """`--dump-outputs`: each array as float64 (every integer here is far below 2^53), whole when it
+    holds at most DUMP_LIMIT elements, otherwise the elements at DUMP_LIMIT flat positions drawn by a
+    fixed seed -- the same positions for the same size in every run and build."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_LIMIT:
+            pick = np.sort(np.random.default_rng(20261016).choice(a.size, DUMP_LIMIT, replace=False))
+            a = a.reshape(-1)[pick]
+        out[name] = a
+    if sum(a.nbytes for a in out.values()) > 64 << 20:
+        raise SystemExit('--dump-outputs: more than 64 MiB to write')
+    os.makedirs(folder, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(folder, name + '.npy'), a)
 
 
 def cpu_baseline(index, pool, tx_offsets, seed, read_len, sample_units, paired, bootstraps=0, gpu_table=None,
@@ -419,10 +529,12 @@ SHAPES = {1: (10_000_000, 100, True, 0), 3: (50_000_000, 150, False, 0), 4: (20_
           'north_star': (50_000_000, 100, True, 0)}
 
 
-def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=-1, with_cpu=True, with_e2e=False):
+def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=-1, with_cpu=True, with_e2e=False,
+            full=True, dump=None):
     """One configuration on the index that is already in HBM: `warmup` untimed steps, EXACTLY `steps`
-    timed ones between barrier + device synchronisation, the roofline of the map kernel from its own
-    HIP-event times, and (rank 0) the JSON line's dict."""
+    timed ones between barrier + device synchronisation, (rank 0, `dump`) the last step's outputs
+    written out, (`full`) the roofline of the map kernel from its own HIP-event times and a counting
+    launch, the parity checks and the legs asked for, and (rank 0) the JSON line's dict."""
     from seekmer_amd import infer, mapper, parallel, synth
     hip, _native, index, device = ctx['hip'], ctx['native'], ctx['index'], ctx['device']
     rank, world, dist, comm = ctx['rank'], ctx['world'], ctx['dist'], ctx['comm']
@@ -541,56 +653,24 @@ def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=
     if profile_stages and rank == 0:
         log('stage ms per step: ' + ', '.join('%s %.2f' % (k, 1e3 * v / (steps + warmup))
                                               for k, v in stage.items()))
+    if dump and rank == 0:
+        # what the last timed step handed its caller: TPM and EM step count, and the class table it
+        # left in HBM (export(): first-seen class order); with -b the bootstrap TPMs too
+        offsets, targets, counts, first_seen, fld = result.export()
+        outputs = {'tpm': state['tpm'], 'em_iterations': [state['iters']], 'class_offsets': offsets,
+                   'class_targets': targets, 'class_counts': counts, 'class_first_seen': first_seen,
+                   'fragment_length_counts': fld}
+        if bootstraps:
+            outputs['effective_lengths'] = state['eff']
+            outputs['bootstrap_tpm'] = state['boot_tpm']
+        dump_outputs(dump, outputs)
 
-    # ---------------- roofline of the dominant kernel
     launches = t_after['batches'] - t_before['batches']
     map_ns = (t_after['map_ns'] - t_before['map_ns']) / max(launches, 1)
     pack_ns = (t_after['pack_ns'] - t_before['pack_ns']) / max(launches, 1)
     class_ns = (t_after['class_ns'] - t_before['class_ns']) / max(launches, 1)
-    parity = {}
-    production = table_digest(result)      # the last timed step's table (bucket layout, production kernel)
-    result.set_stats(True)                 # counting build, untimed: access counts per launch
-    result.reset()
-    result.map_resident(d_bases, d_offsets, n_units, paired, read_len)
-    st = result.access_stats()
-    result.set_stats(False)
-    counting = table_digest(result)        # the same units through the reference's table layout
-    parity['counting_vs_production'] = {
-        'units': n_units, 'sizes': list(production[0]), 'digest': production[1],
-        'identical': production == counting,
-        'what': 'sizes() and sha256 of export() of the counting build\'s launch (reference table layout, the '
-                'launch whose access counters are the roofline\'s algorithmic bytes) == the production launch\'s'}
-    if bootstraps and world > 1:
-        # (rank 0's table then holds the other ranks' merged in: not the launch's own any more)
-        parity['counting_vs_production']['identical'] = None
-    elif production != counting:
-        raise SystemExit('parity check failed: counting build %s != production build %s' % (counting, production))
-    algorithmic = (st['read_bases'] + 16 * st['slots'] + 48 * st['contig_reads']
-                   + 8 * (st['targets_copied'] + st['targets_merged']) + 8 * st['seq_fetches']
-                   + 4 * st['tuple_ids'])
-    achieved = algorithmic / map_ns if map_ns else 0.0          # bytes/ns = GB/s
     sizes = result.sizes()
     em_bytes = int(sizes[1] * 28 + sizes[0] * 12 + n_tx * 40)     # B_em per EM step
-    # HBM traffic of the map launch: NOT measured by this run (a rocprofv3 --pmc pass is not
-    # something a benchmark can do to itself) -- quoted from the PMC passes of the same build over
-    # the same workload (FETCH_SIZE + WRITE_SIZE, separate --pmc runs, summary committed in
-    # profiles/), and only when this run IS that workload
-    traffic, traffic_source, miss_rate = None, None, None
-    try:
-        with open(os.path.join(ROOT, PMC_SUMMARY)) as f:
-            pmc = json.load(f)
-        if pmc.get('source_hash') != map_source_hash():
-            traffic_source = 'null: %s was collected from other kernel sources than this tree\'s' % PMC_SUMMARY
-        elif config == 1 and args.genes == 20000 and n_units == 10_000_000 and read_len == 100:
-            traffic = pmc['derived']['hbm_traffic_bytes']
-            traffic_source = 'quoted from %s (rocprofv3 --pmc passes of this build on this workload), ' \
-                             'not measured by this run; below the algorithmic bytes where the product ' \
-                             'proves k-mers absent without the bucket reads the reference\'s probe makes ' \
-                             '(signatures by minimizer, DESIGN.md 4)' % PMC_SUMMARY
-            miss_rate = pmc['per_launch']['TCC_MISS_sum'] / (map_ns * 1e-9)
-    except (OSError, KeyError, ValueError):
-        pass
-
     line = None
     if rank == 0:
         total_units = world * n_units * steps
@@ -625,19 +705,6 @@ def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=
                 'phase_ms': {'pack': pack_ns * 1e-6, 'map': map_ns * 1e-6, 'classes': class_ns * 1e-6,
                              'em': state['em']['em_ns'] * 1e-6},
             },
-            'roofline': {
-                'kernel': 'map_units_kernel', 'bound': 'hbm',
-                'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': achieved / HBM_PEAK_GBS,
-                'traffic': traffic,
-                'traffic_source': traffic_source,
-                'algorithmic_bytes_per_launch': algorithmic,
-                # the probes are dependent random 16-B reads: the relevant ceiling is the chip's
-                # random-gather rate (52 G/s over a 2 GiB table, profiles/r01_gather_ceiling.log)
-                'l2_miss_rate_vs_random_gather_ceiling': (miss_rate / 52.3e9) if miss_rate else None,
-                'bytes_per_unit': algorithmic / n_units,
-                'launch_ms': map_ns * 1e-6,
-            },
         }
         if em_steps_check:
             line['config']['em_steps_over_ranks'] = em_steps_check
@@ -647,6 +714,74 @@ def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=
             if world == 1:
                 line['config']['bootstrap_em_steps'] = state['boot_iters'] // steps
             line['config']['phase_ms']['bootstraps'] = 1e3 * state['boot_s'] / steps
+    if not full:
+        del result
+        _native.check(hip.skm_device_free(device, d_bases))
+        _native.check(hip.skm_device_free(device, d_offsets))
+        return line
+
+    # ---------------- roofline of the dominant kernel (--full)
+    parity = {}
+    production = table_digest(result)      # the last timed step's table (bucket layout, production kernel)
+    result.set_stats(True)                 # counting build, untimed: access counts per launch
+    result.reset()
+    result.map_resident(d_bases, d_offsets, n_units, paired, read_len)
+    st = result.access_stats()
+    result.set_stats(False)
+    counting = table_digest(result)        # the same units through the reference's table layout
+    parity['counting_vs_production'] = {
+        'units': n_units, 'sizes': list(production[0]), 'digest': production[1],
+        'identical': production == counting,
+        'what': 'sizes() and sha256 of export() of the counting build\'s launch (reference table layout, the '
+                'launch whose access counters are the roofline\'s algorithmic bytes) == the production launch\'s'}
+    if bootstraps and world > 1:
+        # (rank 0's table then holds the other ranks' merged in: not the launch's own any more)
+        parity['counting_vs_production']['identical'] = None
+    elif production != counting:
+        raise SystemExit('parity check failed: counting build %s != production build %s' % (counting, production))
+    algorithmic = (st['read_bases'] + 16 * st['slots'] + 48 * st['contig_reads']
+                   + 8 * (st['targets_copied'] + st['targets_merged']) + 8 * st['seq_fetches']
+                   + 4 * st['tuple_ids'])
+    achieved = algorithmic / map_ns if map_ns else 0.0          # bytes/ns = GB/s
+    sizes = result.sizes()                 # (the counting launch's own table: see the -b note above)
+    em_bytes = int(sizes[1] * 28 + sizes[0] * 12 + n_tx * 40)
+    # HBM traffic of the map launch: NOT measured by this run (a rocprofv3 --pmc pass is not
+    # something a benchmark can do to itself) -- quoted from the PMC passes of the same build over
+    # the same workload (FETCH_SIZE + WRITE_SIZE, separate --pmc runs, summary committed in
+    # profiles/), and only when this run IS that workload
+    traffic, traffic_source, miss_rate = None, None, None
+    try:
+        with open(os.path.join(ROOT, PMC_SUMMARY)) as f:
+            pmc = json.load(f)
+        if pmc.get('source_hash') != map_source_hash():
+            traffic_source = 'null: %s was collected from other kernel sources than this tree\'s' % PMC_SUMMARY
+        elif config == 1 and args.genes == 20000 and n_units == 10_000_000 and read_len == 100:
+            traffic = pmc['derived']['hbm_traffic_bytes']
+            traffic_source = 'quoted from %s (rocprofv3 --pmc passes of this build on this workload), ' \
+                             'not measured by this run; below the algorithmic bytes where the product ' \
+                             'proves k-mers absent without the bucket reads the reference\'s probe makes ' \
+                             '(signatures by minimizer, DESIGN.md 4)' % PMC_SUMMARY
+            miss_rate = pmc['per_launch']['TCC_MISS_sum'] / (map_ns * 1e-9)
+    except (OSError, KeyError, ValueError):
+        pass
+
+    if rank == 0:
+        line['config'].update({'classes': sizes[0], 'class_map_rows': sizes[1], 'em_bytes_per_step': em_bytes,
+                               'em_algorithmic_GBps': em_bytes * state['em']['iterations']
+                               / max(state['em']['em_ns'], 1.0)})
+        line['roofline'] = {
+            'kernel': 'map_units_kernel', 'bound': 'hbm',
+            'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': achieved / HBM_PEAK_GBS,
+            'traffic': traffic,
+            'traffic_source': traffic_source,
+            'algorithmic_bytes_per_launch': algorithmic,
+            # the probes are dependent random 16-B reads: the relevant ceiling is the chip's
+            # random-gather rate (52 G/s over a 2 GiB table, profiles/r01_gather_ceiling.log)
+            'l2_miss_rate_vs_random_gather_ceiling': (miss_rate / 52.3e9) if miss_rate else None,
+            'bytes_per_unit': algorithmic / n_units,
+            'launch_ms': map_ns * 1e-6,
+        }
         if with_cpu and world == 1:
             def gpu_table(sample_bases, sample_offsets, sample_units):
                 from seekmer_amd import common
@@ -673,11 +808,25 @@ def measure(args, ctx, config, steps, warmup, n_units=0, read_len=0, bootstraps=
     return line
 
 
+def _count(minimum):
+    def parse(text):
+        value = int(text)
+        if value < minimum:
+            raise argparse.ArgumentTypeError('must be at least %d' % minimum)
+        return value
+    return parse
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=5)
-    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--steps', type=_count(1), default=5, help='timed steps')
+    ap.add_argument('--warmup', type=_count(0), default=1, help='untimed steps before them')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline (a counting launch), the parity checks, cpu_baseline and, on the '
+                         'default configuration, e2e and other_configs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed to DIR/<name>.npy (float64)')
     ap.add_argument('--config', type=int, default=1, choices=(1, 3, 4), help='BASELINE.json configs[] index')
     ap.add_argument('--genes', type=int, default=20000, help='synthetic genes (20000 -> ~190k tx)')
     ap.add_argument('--pairs', type=int, default=0, help='units per GPU per step (default: the config\'s size)')
@@ -685,23 +834,26 @@ def main():
     ap.add_argument('--bootstraps', type=int, default=-1, help='-b N inside the step (default: 100 for --config 4)')
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--cpu-sample', type=int, default=1_000_000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-e2e', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip cpu_baseline')
+    ap.add_argument('--no-e2e', action='store_true', help='(--full) skip e2e')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the short legs of configs[3] and configs[4] that follow a default run')
+                    help='(--full) skip the short legs of configs[3] and configs[4] that follow a default run')
     ap.add_argument('--other-steps', type=int, default=3)
     ap.add_argument('--e2e-batches', type=int, default=10, help='pieces per stream of the host-array leg')
     ap.add_argument('--e2e-fastq-batches', type=int, default=40,
                     help='batches of the two-pass ASCII comparison leg')
     ap.add_argument('--parse-threads', type=int, default=14)
     ap.add_argument('--e2e-chunk-mb', type=int, default=8, help='text range one parser thread takes at a time')
-    ap.add_argument('--index-cache', default='', help='load/save the index here instead of building it')
+    ap.add_argument('--index-cache', default='',
+                    help='load/save the index here instead of building it (default: .bench_cache/, named by '
+                         'seed, genes and a digest of the sources that build it)')
     ap.add_argument('--cold-child', nargs=3, metavar=('INDEX', 'R1', 'R2'), default=None,
                     help='(internal) one FASTQ -> TPM pass in this fresh process; prints its times as JSON')
     args = ap.parse_args()
     if args.cold_child:
         return cold_child(args)
     args.read_len = args.read_len or SHAPES[args.config][1]
+    args.index_cache = args.index_cache or index_cache_path(args.seed, args.genes)
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -717,7 +869,7 @@ def main():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('gloo', rank=rank, world_size=world)   # rendezvous / barrier / host-side exchanges
 
-    from seekmer_amd import _native, index_builder, parallel, synth
+    from seekmer_amd import _native, parallel, synth
     hip = _native.hip()
     device = local_rank
     if os.environ.get('SKM_BENCH_ONE_DEVICE') == '1':      # rehearsal of the N > 1 path on a 1-GPU box
@@ -728,10 +880,8 @@ def main():
     # ---------------- setup (untimed): transcriptome, index -> HBM, communicator
     t0 = time.perf_counter()
     ids, pool, tx_offsets = synth.transcriptome(args.seed, args.genes)
-    # one rank builds the index, the others map the container it wrote (2.2 GB, memory-mapped)
-    index = parallel.shared_index(lambda: index_builder.build_pooled(ids, pool, tx_offsets), rank, world,
-                                  barrier=(dist.barrier if dist is not None else None),
-                                  cache=args.index_cache or None)
+    # one rank builds the index (or finds it cached), the others map the container (2.2 GB, memory-mapped)
+    index = bench_index(ids, pool, tx_offsets, args.index_cache, rank, world, dist)
     n_tx = len(ids)
     log('rank %d: %d transcripts, %d k-mer slots, index ready in %.1fs'
         % (rank, n_tx, index.kmers.size, time.perf_counter() - t0))
@@ -759,8 +909,8 @@ def main():
     default_run = world == 1 and args.config == 1 and not args.pairs
     line = measure(args, ctx, args.config, args.steps, args.warmup, n_units=args.pairs, read_len=args.read_len,
                    bootstraps=args.bootstraps, with_cpu=not args.no_cpu_baseline,
-                   with_e2e=default_run and not args.no_e2e)
-    if default_run and not args.no_other_configs:
+                   with_e2e=default_run and not args.no_e2e, full=args.full, dump=args.dump_outputs or None)
+    if args.full and default_run and not args.no_other_configs:
         # the other single-GPU configurations of BASELINE.json, a few steps each on the same index
         # (parity at these sizes: tests/test_gpu_parity.py::test_baseline_config{3,4}_properties)
         line['other_configs'] = {}

@@ -7,6 +7,6 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT --output-format csv -- \
-    python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+    python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 find $OUT -name "*kernel_stats.csv" -exec cp {} $ROOT/gpurun_out/prof_${TAG}_kernel_stats.csv \;
 find $OUT -name "*kernel_trace.csv" -exec cp {} $ROOT/gpurun_out/prof_${TAG}_kernel_trace.csv \;

@@ -120,3 +120,63 @@ def test_round4_line_checks_its_own_parity_and_times_the_north_star_size():
     cold = line['e2e']['fastq_inclusive']['cold_process']
     assert cold['unit'] == 'pairs/s' and cold['without_prefault']['value'] <= cold['value'] < line['e2e']['fastq_inclusive']['parse_only']
     assert line['e2e']['fastq_inclusive']['first_pass'] <= line['e2e']['fastq_inclusive']['value']
+
+
+def test_bench_options_for_a_plain_run():
+    """A plain run times exactly --steps steps and can write its outputs; the rest is behind --full."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True,
+                         check=True).stdout
+    for option in ('--steps', '--warmup', '--full', '--dump-outputs'):
+        assert option in out, option
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True)
+    assert bad.returncode == 2
+
+
+def test_dump_outputs_float64_seeded_sample_and_bounded(tmp_path):
+    import numpy as np
+    import bench
+    big = np.arange(3 * bench.DUMP_LIMIT, dtype=np.int64)
+    arrays = {'big': big, 'tpm': np.linspace(0.0, 1.0, 1000), 'steps': [7]}
+    bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    total = 0
+    for name in arrays:
+        a, b = np.load(tmp_path / 'a' / (name + '.npy')), np.load(tmp_path / 'b' / (name + '.npy'))
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        total += a.nbytes
+    sample = np.load(tmp_path / 'a' / 'big.npy')
+    assert sample.size == bench.DUMP_LIMIT and np.all(np.diff(sample) > 0) and np.isin(sample, big).all()
+    assert np.array_equal(np.load(tmp_path / 'a' / 'tpm.npy'), arrays['tpm'])
+    assert total <= 64 << 20
+
+
+def test_bench_index_cache_round_trip(native_libs, tmp_path, monkeypatch):
+    """The cached index is the built one, a stale sibling of the same (seed, genes) in the cache folder
+    goes (and nothing beside a path given by hand), and a cache that belongs to another transcriptome
+    is refused."""
+    import numpy as np
+    import bench
+    from seekmer_amd import index_builder, synth
+    assert bench.index_cache_path(1, 20000) != bench.index_cache_path(2, 20000)
+    assert bench.index_cache_path(1, 20000) != bench.index_cache_path(1, 20001)
+    monkeypatch.setattr(bench, 'CACHE_DIR', str(tmp_path / 'cache'))
+    (tmp_path / 'cache').mkdir()
+    ids, pool, tx_offsets = synth.transcriptome(3, 12)
+    path = str(tmp_path / 'cache' / 'index_s3_g12_new.npz')
+    stale = tmp_path / 'cache' / 'index_s3_g12_old.npz'
+    stale.write_bytes(b'')
+    built = index_builder.build_pooled(ids, pool, tx_offsets)
+    for _ in range(2):                     # built and stored, then loaded
+        index = bench.bench_index(ids, pool, tx_offsets, path, 0, 1, None)
+        for name in ('kmers', 'contigs', 'sequences', 'targets'):
+            assert np.array_equal(getattr(index, name), getattr(built, name)), name
+        assert os.path.exists(path) and not stale.exists()
+    neighbour = tmp_path / 'skm_other.npz'
+    neighbour.write_bytes(b'')
+    bench.bench_index(ids, pool, tx_offsets, str(tmp_path / 'skm_idx.npz'), 0, 1, None)
+    assert neighbour.exists() and (tmp_path / 'skm_idx.npz').exists()
+    other = synth.transcriptome(4, 12)
+    with pytest.raises(SystemExit):
+        bench.bench_index(*other, path, 0, 1, None)
