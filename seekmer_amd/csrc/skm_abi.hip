@@ -23,6 +23,7 @@
 #include <thread>
 #include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace skm;
@@ -66,11 +67,22 @@ int fail(int code, const char *fmt, ...)
         if (rc_ != SKM_OK) return rc_; \
     } while (0)
 
-// device buffer that only ever grows
+// device buffer that only ever grows; its block goes back to the pool with it (a block that a
+// stream may still use: drain that stream before the buffer goes)
 template <class T>
 struct DBuf {
     T *p = nullptr;
     size_t cap = 0;      // elements
+    DBuf() = default;
+    DBuf(const DBuf &) = delete;
+    DBuf &operator=(const DBuf &) = delete;
+    DBuf(DBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DBuf &operator=(DBuf &&o) noexcept
+    {
+        if (this != &o) { pool_free(p); p = std::exchange(o.p, nullptr); cap = std::exchange(o.cap, 0); }
+        return *this;
+    }
+    ~DBuf() { pool_free(p); }
     int ensure(size_t n, bool keep = false, hipStream_t stream = nullptr)
     {
         if (n <= cap) return SKM_OK;
@@ -87,14 +99,39 @@ struct DBuf {
         cap = want;
         return SKM_OK;
     }
-    void release()
-    {
-        pool_free(p);
-        p = nullptr;
-        cap = 0;
-    }
-    size_t bytes() const { return cap * sizeof(T); }
 };
+
+// One HIP resource of another kind -- a stream, an event, a pinned block, hipMalloc'd memory --
+// handed back by `Free` (to the pool or to the runtime) when its owner goes.  Reads as the handle.
+template <class H, auto Free>
+class Own {
+public:
+    Own() = default;
+    explicit Own(H h) : h_(h) {}
+    Own(const Own &) = delete;
+    Own &operator=(const Own &) = delete;
+    ~Own() { reset(); }
+    operator H() const { return h_; }
+    H get() const { return h_; }
+    H operator->() const { return h_; }
+    H *out() { reset(); return &h_; }          // for the call that acquires a new one
+    void reset(H h = nullptr) { if (h_) (void)Free(h_); h_ = h; }
+
+private:
+    H h_ = nullptr;
+};
+
+void pool_event_release_plain(hipEvent_t e) { pool_event_release(e, false); }
+void pool_event_release_timing(hipEvent_t e) { pool_event_release(e, true); }
+
+using PoolStream = Own<hipStream_t, pool_stream_release>;
+using PoolEvent = Own<hipEvent_t, pool_event_release_plain>;
+using PoolTimingEvent = Own<hipEvent_t, pool_event_release_timing>;
+using PoolPinned = Own<unsigned long long *, pool_pinned_release>;
+using Stream = Own<hipStream_t, hipStreamDestroy>;
+using Event = Own<hipEvent_t, hipEventDestroy>;
+using HostPinned = Own<unsigned long long *, hipHostFree>;
+using DevMem = Own<void *, hipFree>;
 
 // runs a clean-up on every exit of the enclosing scope unless dismissed (the HIP_TRY / SKM_TRY
 // macros return from the middle of a function)
@@ -107,6 +144,9 @@ struct ScopeGuard {
     void dismiss() { armed = false; }
 };
 template <class F> ScopeGuard<F> on_exit(F f) { return ScopeGuard<F>(f); }
+// (scratch that kernels on a stream use goes back to the pool, where another stream may get it at
+// once, only after that stream has drained: a function declares its scratch BEFORE the guard that
+// synchronises the stream on an early return -- destroyed in reverse order, the guard runs first)
 
 int set_device(int device)
 {
@@ -117,10 +157,10 @@ int set_device(int device)
 }  // namespace
 
 struct skm_index {
+    ~skm_index() { (void)hipSetDevice(device); }     // (then the members free the device copy)
     int device = 0;
     DevIndex d{};
-    void *kmers = nullptr, *contigs = nullptr, *seq2 = nullptr, *targets = nullptr, *buckets = nullptr;
-    void *edge_kmers = nullptr, *signatures = nullptr;
+    DevMem kmers, contigs, seq2, buckets, edge_kmers, signatures;
     int64_t n_slots = 0, bytes = 0;
     int64_t layout[8] = {0};          // skm_index_layout
     int cu_count = 256;
@@ -131,9 +171,11 @@ struct skm_index {
 };
 
 struct skm_mapper {
-    skm_index *ix = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit skm_mapper(skm_index *index) : ix(index) { index->holders.fetch_add(1); }
+    ~skm_mapper();
+    Own<skm_index *, skm_index_destroy> ix;   // a hold on the index (declared first: given up last)
+    PoolStream stream;
+    Event ev[4];
     std::mutex mu;
     // class table
     ClassTable t{};
@@ -151,12 +193,13 @@ struct skm_mapper {
     DBuf<Coord> unit_anchor;
     DBuf<int64_t> unit_slot;
     DBuf<unsigned long long> rec_tuple;
-    unsigned long long *pinned = nullptr;   // host-pinned readback words
+    HostPinned pinned;                      // host-pinned readback words
     DBuf<uint64_t> rec_key;
     bool keep_spans = false, last_spans = false;   // spans wanted / written by the last batch
     DBuf<int32_t> unit_entries;
     DBuf<unsigned long long> batch_ctl;  // [0]=ids_cursor [8..2007]=fld [2048..2063]=stats
     int grid_blocks = 0;
+    // (both under mu)
     int64_t expected_units = 0;       // skm_mapper_expect_units: the sample's size, announced before its reads
     bool packed_sized = false;        // the batch buffers hold a run of PACKED_MAX_UNITS already
     int64_t units_done = 0;
@@ -180,7 +223,7 @@ struct skm_mapper {
     struct Lane {
         DBuf<uint8_t> bases;
         DBuf<int64_t> offsets;
-        hipStream_t stream = nullptr;
+        Stream stream;
         bool busy = false;
     };
     static constexpr int N_LANES = 3;
@@ -213,7 +256,7 @@ struct skm_mapper {
         bool in_job = false;
     };
     std::deque<Piece> pending[2];
-    hipStream_t packed_stream = nullptr;
+    Stream packed_stream;
     int packed_paired = -1;                   // -1 until the first piece
     int packed_flush = 0;                     // callers waiting for everything mappable to be mapped
     int packed_waiters = 0;                   // pushers held back by the byte limit: whatever run there is gets mapped
@@ -232,11 +275,16 @@ struct skm_mapper {
 };
 
 struct skm_quant {
+    ~skm_quant()                              // (the buffers go once the stream has drained)
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipEvent_t chunk_ev[2] = {nullptr, nullptr};
-    unsigned long long *pinned = nullptr;     // host-pinned readback of the control block
+    PoolStream stream;
+    PoolTimingEvent ev[2];
+    PoolEvent chunk_ev[2];
+    PoolPinned pinned;                        // host-pinned readback of the control block
     std::mutex mu;
     int64_t n_tx = 0, n_classes = 0, n_ids = 0, n_rows = 0;
     DBuf<int64_t> cls_offset, row_start, tx_row;
@@ -451,25 +499,23 @@ extern "C" int skm_device_gather_ceiling(int device, int64_t table_bytes, int bl
             || per_lane < 4)
         return fail(SKM_ERR_ARG, "bad argument");
     SKM_TRY(set_device(device));
-    void *table = nullptr;
-    unsigned long long *sink = nullptr;
-    HIP_TRY(hipMalloc(&table, (size_t)table_bytes));
-    HIP_TRY(hipMalloc((void **)&sink, 8));
+    DevMem table, sink;
+    HIP_TRY(hipMalloc(table.out(), (size_t)table_bytes));
+    HIP_TRY(hipMalloc(sink.out(), 8));
     HIP_TRY(hipMemset(table, 0, (size_t)table_bytes));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, sink, nullptr);   // warm-up
+    Event e0, e1;
+    HIP_TRY(hipEventCreate(e0.out()));
+    HIP_TRY(hipEventCreate(e1.out()));
+    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, (unsigned long long *)sink.get(),
+                        nullptr);   // warm-up
     HIP_TRY(hipEventRecord(e0, nullptr));
-    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, sink, nullptr);
+    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, (unsigned long long *)sink.get(),
+                        nullptr);
     HIP_TRY(hipEventRecord(e1, nullptr));
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     *gathers_per_second = (double)blocks * 256.0 * per_lane / (ms * 1e-3);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(hipFree(table));
-    HIP_TRY(hipFree(sink));
     return SKM_OK;
 }
 
@@ -575,20 +621,16 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
     }
     if (empty == 0) return fail(SKM_ERR_ARG, "k-mer table has no empty slot");
 
-    skm_index *ix = new skm_index();
+    std::unique_ptr<skm_index> ix(new skm_index());  // (any early return below: nothing is left behind)
     ix->device = device;
-    char *d_ascii = nullptr;
-    auto undo = on_exit([&]() {                 // any early return below: nothing is left behind
-        (void)hipFree(d_ascii);
-        skm_index_destroy(ix);
-    });
+    DevMem d_ascii;
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     ix->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const int64_t n_words = (n_bases + 31) / 32 + 1;
-    HIP_TRY(hipMalloc(&ix->kmers, (size_t)n_slots * sizeof(IndexEntry)));
-    HIP_TRY(hipMalloc(&ix->seq2, (size_t)n_words * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void **)&d_ascii, (size_t)n_bases));
+    HIP_TRY(hipMalloc(ix->kmers.out(), (size_t)n_slots * sizeof(IndexEntry)));
+    HIP_TRY(hipMalloc(ix->seq2.out(), (size_t)n_words * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(d_ascii.out(), (size_t)n_bases));
     HIP_TRY(hipMemcpy(ix->kmers, kmers, (size_t)n_slots * sizeof(IndexEntry), hipMemcpyHostToDevice));
     int64_t n_overflow = 0;
     {   // contig records (skm_device.h: DevContig) and, behind them in the same allocation, the target
@@ -625,29 +667,28 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
         }
         n_overflow = (int64_t)overflow.size();
         const size_t row_bytes = (size_t)n_contigs * sizeof(DevContig);
-        HIP_TRY(hipMalloc(&ix->contigs, row_bytes + (size_t)(n_overflow + 16) * sizeof(int32_t)));
+        HIP_TRY(hipMalloc(ix->contigs.out(), row_bytes + (size_t)(n_overflow + 16) * sizeof(int32_t)));
         HIP_TRY(hipMemcpy(ix->contigs, rows.data(), row_bytes, hipMemcpyHostToDevice));
         if (n_overflow)
-            HIP_TRY(hipMemcpy((char *)ix->contigs + row_bytes, overflow.data(), (size_t)n_overflow * sizeof(int32_t),
+            HIP_TRY(hipMemcpy((char *)ix->contigs.get() + row_bytes, overflow.data(), (size_t)n_overflow * sizeof(int32_t),
                               hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&ix->edge_kmers, (edges.size() + 2) * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc(ix->edge_kmers.out(), (edges.size() + 2) * sizeof(uint64_t)));
         HIP_TRY(hipMemcpy(ix->edge_kmers, edges.data(), edges.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(d_ascii, sequences, (size_t)n_bases, hipMemcpyHostToDevice));
-    launch_pack_sequences(d_ascii, n_bases, (uint64_t *)ix->seq2, n_words, nullptr);
+    launch_pack_sequences((const char *)d_ascii.get(), n_bases, (uint64_t *)ix->seq2.get(), n_words, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(d_ascii));
-    d_ascii = nullptr;
+    d_ascii.reset();
     ix->n_slots = n_slots;
-    ix->d.kmers = (const IndexEntry *)ix->kmers;
+    ix->d.kmers = (const IndexEntry *)ix->kmers.get();
     ix->d.slot_mask = (uint32_t)(n_slots - 1);
-    ix->d.contigs = (const DevContig *)ix->contigs;
+    ix->d.contigs = (const DevContig *)ix->contigs.get();
     ix->d.n_contigs = n_contigs;
-    ix->d.seq2 = (const uint64_t *)ix->seq2;
+    ix->d.seq2 = (const uint64_t *)ix->seq2.get();
     ix->d.n_bases = n_bases;
-    ix->d.targets = (const int32_t *)ix->contigs;       // (rows and overflow slices as one int32 array)
-    ix->d.edge_kmers = (const uint64_t *)ix->edge_kmers;
+    ix->d.targets = (const int32_t *)ix->contigs.get();       // (rows and overflow slices as one int32 array)
+    ix->d.edge_kmers = (const uint64_t *)ix->edge_kmers.get();
     ix->d.n_targets = n_targets;
     ix->d.max_target_count = (int32_t)std::max<int64_t>(max_tc, 1);
     ix->d.edge_windows = edge_windows ? 1 : 0;
@@ -660,16 +701,15 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
         while ((int64_t)n_buckets < occupied) n_buckets <<= 1;
         int log2_buckets = 0;
         while ((1ULL << log2_buckets) < n_buckets) ++log2_buckets;
-        unsigned long long *d_report = nullptr;
         unsigned long long report[4] = {0, 0, 0, 0};
         const char *off = getenv("SKM_NO_BUCKETS");          // tuning aid: probe the reference's layout
         if (!(off && off[0] == '1') && n_buckets <= (1ULL << 31)) {
-            auto undo_report = on_exit([&]() { (void)hipFree(d_report); });
-            HIP_TRY(hipMalloc(&ix->buckets, (size_t)n_buckets * sizeof(DevBucket)));
-            HIP_TRY(hipMalloc((void **)&d_report, sizeof(report)));
+            DevMem d_report;
+            HIP_TRY(hipMalloc(ix->buckets.out(), (size_t)n_buckets * sizeof(DevBucket)));
+            HIP_TRY(hipMalloc(d_report.out(), sizeof(report)));
             HIP_TRY(hipMemset(d_report, 0, sizeof(report)));
-            launch_bucket_build(ix->d, (uint64_t)n_slots, (DevBucket *)ix->buckets, (uint32_t)(n_buckets - 1),
-                                (uint32_t)(32 - log2_buckets), d_report, nullptr);
+            launch_bucket_build(ix->d, (uint64_t)n_slots, (DevBucket *)ix->buckets.get(), (uint32_t)(n_buckets - 1),
+                                (uint32_t)(32 - log2_buckets), (unsigned long long *)d_report.get(), nullptr);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(report, d_report, sizeof(report), hipMemcpyDeviceToHost));
             ix->layout[1] = (int64_t)n_buckets;
@@ -678,7 +718,7 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
             ix->layout[4] = (int64_t)report[2];
             ix->layout[5] = (int64_t)report[3];
             if ((int64_t)report[0] == occupied && report[2] == 0 && report[3] == 0) {
-                ix->d.buckets = (const DevBucket *)ix->buckets;
+                ix->d.buckets = (const DevBucket *)ix->buckets.get();
                 ix->d.bucket_mask = (uint32_t)(n_buckets - 1);
                 ix->d.bucket_shift = (uint32_t)(32 - log2_buckets);
                 ix->bytes += (int64_t)n_buckets * (int64_t)sizeof(DevBucket);
@@ -688,13 +728,15 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
                 int sig_bits = 10;
                 while (sig_bits < 30 && (4LL << sig_bits) < occupied) ++sig_bits;
                 const size_t sig_bytes = 2 * sizeof(uint64_t) << sig_bits;
-                if (!(no_sig && no_sig[0] == '1') && hipMalloc(&ix->signatures, sig_bytes) != hipSuccess) {
+                void *sig = nullptr;
+                if (!(no_sig && no_sig[0] == '1') && hipMalloc(&sig, sig_bytes) != hipSuccess) {
                     (void)hipGetLastError();                   // (no room: the roll asks the buckets, as without them)
-                    ix->signatures = nullptr;
+                    sig = nullptr;
                 }
+                ix->signatures.reset(sig);
                 if (ix->signatures) {
                     HIP_TRY(hipMemset(ix->signatures, 0, sig_bytes));
-                    launch_signature_build((const DevBucket *)ix->buckets, n_buckets, (uint64_t *)ix->signatures,
+                    launch_signature_build((const DevBucket *)ix->buckets.get(), n_buckets, (uint64_t *)ix->signatures.get(),
                                            (uint32_t)(32 - sig_bits), nullptr);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipDeviceSynchronize());
@@ -710,7 +752,7 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
                                 "%.1f %% in use, %lld full\n", sig_bits, head.size() / 2, 2.0 * (double)bits / (double)head.size(),
                                 200.0 * (double)used / (double)head.size(), (long long)full);
                     }
-                    ix->d.signatures = (const uint64_t *)ix->signatures;
+                    ix->d.signatures = (const uint64_t *)ix->signatures.get();
                     ix->d.signature_shift = (uint32_t)(32 - sig_bits);
                     ix->bytes += (int64_t)sig_bytes;
                     ix->layout[7] = (int64_t)1 << sig_bits;
@@ -721,7 +763,7 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
                     // lookup the kernels would do.  SKM_TEST_SUCC_LOOKUP=1 (test hook) marks them all
                     // "look it up", so that every hop takes the fall-back a real index hardly ever needs.
                     const char *force = getenv("SKM_TEST_SUCC_LOOKUP");
-                    launch_successor_build(ix->d, (DevContig *)ix->contigs, n_contigs, force && force[0] == '1',
+                    launch_successor_build(ix->d, (DevContig *)ix->contigs.get(), n_contigs, force && force[0] == '1',
                                            nullptr);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipDeviceSynchronize());
@@ -729,24 +771,18 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
                     ix->layout[6] = 1;
                 }
             } else {                 // not a set the reference's probe reaches everywhere: its layout decides
-                HIP_TRY(hipFree(ix->buckets));
-                ix->buckets = nullptr;
+                ix->buckets.reset();
             }
         }
     }
-    undo.dismiss();
-    *out = ix;
+    *out = ix.release();                                  // (the caller's handle from here on)
     return SKM_OK;
 }
 
 extern "C" int skm_index_destroy(skm_index *ix)
 {
     if (!ix) return SKM_OK;
-    if (ix->holders.fetch_sub(1) > 1) return SKM_OK;      // a mapper still maps against it
-    (void)hipSetDevice(ix->device);
-    (void)hipFree(ix->kmers); (void)hipFree(ix->contigs); (void)hipFree(ix->targets); (void)hipFree(ix->seq2);
-    (void)hipFree(ix->buckets); (void)hipFree(ix->edge_kmers); (void)hipFree(ix->signatures);
-    delete ix;
+    if (ix->holders.fetch_sub(1) == 1) delete ix;         // (else a mapper still maps against it)
     return SKM_OK;
 }
 
@@ -830,7 +866,7 @@ int table_grow(skm_mapper *m, uint64_t want_slots, int64_t units_in_flight)
     if (need == n_slots) return SKM_OK;
     DBuf<ClassSlot> new_slots;
     DBuf<int64_t> forward;
-    auto undo = on_exit([&]() { new_slots.release(); forward.release(); });
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
     SKM_TRY(new_slots.ensure(need));
     SKM_TRY(forward.ensure(n_slots));
     ClassTable to = m->t;
@@ -845,10 +881,8 @@ int table_grow(skm_mapper *m, uint64_t want_slots, int64_t units_in_flight)
     launch_slot_remap(m->unit_slot.p, units_in_flight, forward.p, m->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m->stream));
-    m->slots.release();
-    forward.release();
-    m->slots = new_slots;
-    undo.dismiss();
+    drain.dismiss();
+    m->slots = std::move(new_slots);
     bind_table(m, need);
     return SKM_OK;
 }
@@ -1080,57 +1114,42 @@ extern "C" int skm_mapper_create(skm_index *ix, skm_mapper **out)
 {
     if (!ix || !out) return fail(SKM_ERR_ARG, "NULL argument");
     SKM_TRY(set_device(ix->device));
-    skm_mapper *m = new skm_mapper();
-    m->ix = ix;
-    ix->holders.fetch_add(1);
-    HIP_TRY(pool_stream_acquire(&m->stream));
-    for (auto &e : m->ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipHostMalloc((void **)&m->pinned, 64 * sizeof(unsigned long long)));
+    std::unique_ptr<skm_mapper> m(new skm_mapper(ix));     // (any early return below: nothing is left behind)
+    HIP_TRY(pool_stream_acquire(m->stream.out()));
+    for (auto &e : m->ev) HIP_TRY(hipEventCreate(e.out()));
+    HIP_TRY(hipHostMalloc((void **)m->pinned.out(), 64 * sizeof(unsigned long long)));
     if (const char *v = getenv("SKM_MAP_STATS")) m->want_stats = v[0] == '2' ? 2 : 1;
     if (const char *v = getenv("SKM_TEST_PACKED_MAX_PENDING"))      // test hook: the pushers' byte limit
         if (atoll(v) > 0) m->packed_max_pending = atoll(v);
     if (const char *v = getenv("SKM_MAP_VOTE"))          // tuning aid: "start,lookup,merge,left,right,emit,scan"
         sscanf(v, "%d,%d,%d,%d,%d,%d,%d", &m->vote[0], &m->vote[1], &m->vote[2], &m->vote[3], &m->vote[4],
                &m->vote[5], &m->vote[6]);
-    HIP_TRY(hipStreamCreateWithFlags(&m->packed_stream, hipStreamNonBlocking));   // (10 ms: not at the first piece's push)
-    int rc = table_reset(m, 1 << 16);
-    if (rc != SKM_OK) { delete m; ix->holders.fetch_sub(1); return rc; }
+    HIP_TRY(hipStreamCreateWithFlags(m->packed_stream.out(), hipStreamNonBlocking));   // (10 ms: not at the first piece's push)
+    SKM_TRY(table_reset(m.get(), 1 << 16));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    *out = m;
+    *out = m.release();                                     // (the caller's handle from here on)
     return SKM_OK;
+}
+
+skm_mapper::~skm_mapper()
+{
+    (void)hipSetDevice(ix->device);
+    if (worker_started) {
+        { std::lock_guard<std::mutex> hold(q_mu); stop = true; }
+        q_cv.notify_all();
+        worker.join();                     // (finishes what is queued)
+    }
+    // every stream drains before the members -- buffers, pieces, streams, events -- free themselves
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto &lane : lanes)
+        if (lane.stream) (void)hipStreamSynchronize(lane.stream);
+    if (packed_stream) (void)hipStreamSynchronize(packed_stream);
 }
 
 extern "C" int skm_mapper_destroy(skm_mapper *m)
 {
-    if (!m) return SKM_OK;
-    (void)hipSetDevice(m->ix->device);
-    if (m->worker_started) {
-        { std::lock_guard<std::mutex> hold(m->q_mu); m->stop = true; }
-        m->q_cv.notify_all();
-        m->worker.join();                     // (finishes what is queued)
-    }
-    (void)hipStreamSynchronize(m->stream);
-    for (auto &lane : m->lanes) {
-        if (lane.stream) { (void)hipStreamSynchronize(lane.stream); (void)hipStreamDestroy(lane.stream); }
-        lane.bases.release();
-        lane.offsets.release();
-    }
-    for (auto &list : m->pending) list.clear();
-    if (m->packed_stream) { (void)hipStreamSynchronize(m->packed_stream); (void)hipStreamDestroy(m->packed_stream); }
-    m->scan_out.release();
-    m->view_start.release(); m->view_len.release(); m->view_count.release(); m->view_first_seen.release();
-    m->slots.release(); m->arena.release(); m->class_list.release();
-    m->counters.release();
-    m->error.release(); m->bases.release(); m->offsets.release(); m->records.release();
-    m->workspace.release(); m->unit_begin.release(); m->unit_end.release();
-    m->rec_unit.release(); m->unit_anchor.release(); m->rec_tuple.release();
-    m->unit_slot.release(); m->rec_key.release(); m->unit_entries.release(); m->batch_ctl.release();
-    for (auto &e : m->ev) (void)hipEventDestroy(e);
-    if (m->pinned) (void)hipHostFree(m->pinned);
-    pool_stream_release(m->stream);
-    skm_index *const ix = m->ix;
     delete m;
-    return skm_index_destroy(ix);                          // (the mapper's hold on the index)
+    return SKM_OK;
 }
 
 namespace {
@@ -1439,7 +1458,7 @@ int submit_batch(skm_mapper *m, const char *bases, const int64_t *offsets, int64
         { std::lock_guard<std::mutex> hold(m->q_mu); lane.busy = false; }
         m->done_cv.notify_all();
     });
-    if (!lane.stream) HIP_TRY(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+    if (!lane.stream) HIP_TRY(hipStreamCreateWithFlags(lane.stream.out(), hipStreamNonBlocking));
     SKM_TRY(lane.bases.ensure((size_t)n_bytes + 64));
     SKM_TRY(lane.offsets.ensure((size_t)n_reads + 1));
     // pinned sources go over the link at full rate and asynchronously; pageable ones are staged
@@ -1483,7 +1502,7 @@ extern "C" int skm_mapper_map_batch_uniform_async(skm_mapper *m, const char *bas
 extern "C" int skm_mapper_expect_units(skm_mapper *m, int64_t n_units)
 {
     if (!m || n_units < 0) return fail(SKM_ERR_ARG, "bad argument");
-    std::lock_guard<std::mutex> hold(m->q_mu);
+    std::lock_guard<std::mutex> lock(m->mu);          // (run_packed_job reads them under it)
     m->expected_units = n_units;
     m->packed_sized = false;
     return SKM_OK;
@@ -1561,7 +1580,7 @@ int packed_stage(skm_mapper *m, const skm_packed_reads *piece, int paired, skm_m
         if (m->packed_paired >= 0 && m->packed_paired != (paired ? 1 : 0) && (!m->pending[0].empty() || !m->pending[1].empty() || m->packed_busy))
             return fail(SKM_ERR_STATE, "paired and single-ended pieces in one run");
         m->packed_paired = paired ? 1 : 0;
-        if (!m->packed_stream) HIP_TRY(hipStreamCreateWithFlags(&m->packed_stream, hipStreamNonBlocking));
+        if (!m->packed_stream) HIP_TRY(hipStreamCreateWithFlags(m->packed_stream.out(), hipStreamNonBlocking));
     }
     // one HBM block: codes | lengths | exception reads | exception bit planes
     const bool uniform = piece->uniform_len >= 0;
@@ -1830,7 +1849,7 @@ extern "C" int skm_mapper_export(skm_mapper *m, int64_t *class_offsets, int32_t 
     if (class_offsets) class_offsets[0] = 0;
     if (C == 0) return SKM_OK;
     DBuf<int64_t> d_off, d_len; DBuf<double> d_cnt; DBuf<unsigned long long> d_fs;
-    auto undo = on_exit([&]() { d_off.release(); d_len.release(); d_cnt.release(); d_fs.release(); });
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
     SKM_TRY(d_off.ensure(C)); SKM_TRY(d_len.ensure(C)); SKM_TRY(d_cnt.ensure(C)); SKM_TRY(d_fs.ensure(C));
     launch_class_compact(m->t, C, d_off.p, d_len.p, d_cnt.p, d_fs.p, m->stream);
     HIP_TRY(hipGetLastError());
@@ -1844,6 +1863,7 @@ extern "C" int skm_mapper_export(skm_mapper *m, int64_t *class_offsets, int32_t 
     HIP_TRY(hipMemcpyAsync(fs.data(), d_fs.p, C * 8, hipMemcpyDeviceToHost, m->stream));
     if (M) HIP_TRY(hipMemcpyAsync(arena.data(), m->arena.p, (size_t)M * 4, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
+    drain.dismiss();
     // Counter insertion order under -j1 = ascending first-seen unit (mapper.py:88)
     std::vector<int64_t> order(C);
     std::iota(order.begin(), order.end(), 0);
@@ -1889,7 +1909,7 @@ extern "C" int skm_mapper_merge(skm_mapper *m, int64_t n_classes, const int64_t 
         SKM_TRY(m->arena.ensure((size_t)(m->host_arena_used + M + 1024), true, m->stream));
         bind_table(m, m->t.slot_mask + 1);
         DBuf<int64_t> d_off, d_cnt, d_fs; DBuf<int32_t> d_ids;
-        auto undo = on_exit([&]() { d_off.release(); d_cnt.release(); d_fs.release(); d_ids.release(); });
+        auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
         SKM_TRY(d_off.ensure(n_classes + 1)); SKM_TRY(d_cnt.ensure(n_classes));
         SKM_TRY(d_fs.ensure(n_classes)); SKM_TRY(d_ids.ensure(std::max<int64_t>(M, 1)));
         HIP_TRY(hipMemcpy(d_off.p, class_offsets, (n_classes + 1) * 8, hipMemcpyHostToDevice));
@@ -1901,6 +1921,7 @@ extern "C" int skm_mapper_merge(skm_mapper *m, int64_t n_classes, const int64_t 
         unsigned long long ctr[8];
         HIP_TRY(hipMemcpyAsync(ctr, m->counters.p, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
         SKM_TRY(read_error(m));
+        drain.dismiss();                      // (read_error has synchronised the stream)
         m->host_arena_used = (int64_t)ctr[CTR_ARENA];
         m->host_classes = (int64_t)ctr[CTR_CLASSES];
     }
@@ -2068,13 +2089,14 @@ extern "C" int skm_effective_lengths(int device, const int64_t *fld, const doubl
     SKM_TRY(set_device(device));
     if (n_tx == 0) return SKM_OK;
     DBuf<unsigned long long> d_fld; DBuf<double> d_len, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
     SKM_TRY(d_fld.ensure(MAX_FRAGMENT_LENGTH)); SKM_TRY(d_len.ensure(n_tx)); SKM_TRY(d_out.ensure(n_tx));
     HIP_TRY(hipMemcpy(d_fld.p, fld, MAX_FRAGMENT_LENGTH * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_len.p, lengths, n_tx * 8, hipMemcpyHostToDevice));
     launch_effective_lengths(d_fld.p, d_len.p, n_tx, d_out.p, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, d_out.p, n_tx * 8, hipMemcpyDeviceToHost));
-    d_fld.release(); d_len.release(); d_out.release();
+    drain.dismiss();                          // (the copy home has waited for the kernel)
     return SKM_OK;
 }
 
@@ -2087,10 +2109,10 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
     q->n_tx = n_tx;
     q->n_classes = n_classes;
     q->n_ids = n_ids;
-    HIP_TRY(pool_stream_acquire(&q->stream));
-    for (auto &e : q->ev) HIP_TRY(pool_event_acquire(&e, true));
-    for (auto &e : q->chunk_ev) HIP_TRY(pool_event_acquire(&e, false));
-    HIP_TRY(pool_pinned_acquire((void **)&q->pinned));
+    HIP_TRY(pool_stream_acquire(q->stream.out()));
+    for (auto &e : q->ev) HIP_TRY(pool_event_acquire(e.out(), true));
+    for (auto &e : q->chunk_ev) HIP_TRY(pool_event_acquire(e.out(), false));
+    HIP_TRY(pool_pinned_acquire((void **)q->pinned.out()));
     const size_t C = (size_t)std::max<int64_t>(n_classes, 1), M = (size_t)std::max<int64_t>(n_ids, 1);
     const size_t T = (size_t)std::max<int64_t>(n_tx, 1);
     const size_t R = (size_t)quant_rows_upper_bound(n_tx, n_ids);
@@ -2362,9 +2384,8 @@ extern "C" int skm_quant_create(int device, int64_t n_tx, int64_t n_classes,
         if (t < 0 || t >= n_tx) return fail(SKM_ERR_ARG, "class target %d outside [0, n_tx)", t);
     }
     SKM_TRY(set_device(device));
-    skm_quant *q = new skm_quant();
-    int rc = quant_alloc(q, device, n_tx, n_classes, M);
-    if (rc != SKM_OK) { delete q; return rc; }
+    std::unique_ptr<skm_quant> q(new skm_quant());     // (any early return below: nothing is left behind)
+    SKM_TRY(quant_alloc(q.get(), device, n_tx, n_classes, M));
     std::vector<int64_t> rebased(n_classes + 1, 0);
     for (int64_t c = 0; c <= n_classes && n_classes; ++c) rebased[c] = class_offsets[c] - class_offsets[0];
     HIP_TRY(hipMemcpy(q->cls_offset.p, rebased.data(), (n_classes + 1) * 8, hipMemcpyHostToDevice));
@@ -2373,9 +2394,8 @@ extern "C" int skm_quant_create(int device, int64_t n_tx, int64_t n_classes,
         if (M) HIP_TRY(hipMemcpy(q->ids.p, class_targets + class_offsets[0], M * 4, hipMemcpyHostToDevice));
     }
     q->n_total = total;
-    rc = quant_finish_setup(q, nullptr);
-    if (rc != SKM_OK) { skm_quant_destroy(q); return rc; }
-    *out = q;
+    SKM_TRY(quant_finish_setup(q.get(), nullptr));
+    *out = q.release();                                 // (the caller's handle from here on)
     return SKM_OK;
 }
 
@@ -2386,15 +2406,13 @@ extern "C" int skm_quant_create_from_mapper(skm_mapper *m, int64_t n_tx, skm_qua
     std::lock_guard<std::mutex> lock(m->mu);
     SKM_TRY(set_device(m->ix->device));
     const int64_t C = m->host_classes, M = m->host_arena_used;
-    skm_quant *q = new skm_quant();
-    int rc = quant_alloc(q, m->ix->device, n_tx, C, M);
-    if (rc != SKM_OK) { delete q; return rc; }
+    std::unique_ptr<skm_quant> q(new skm_quant());     // (any early return below: nothing is left behind)
+    SKM_TRY(quant_alloc(q.get(), m->ix->device, n_tx, C, M));
     unsigned long long ctr[4];
     HIP_TRY(hipMemcpy(ctr, m->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));
     q->n_total = (double)(ctr[CTR_UNITS] - ctr[CTR_UNALIGNED]);
-    rc = quant_finish_setup(q, &m->t, m->first_seen_bound);
-    if (rc != SKM_OK) { skm_quant_destroy(q); return rc; }
-    *out = q;
+    SKM_TRY(quant_finish_setup(q.get(), &m->t, m->first_seen_bound));
+    *out = q.release();                                 // (the caller's handle from here on)
     return SKM_OK;
 }
 
@@ -2423,111 +2441,91 @@ extern "C" int skm_quant_infer(skm_mapper *m, skm_comm *comm, const double *leng
                 std::chrono::duration<double, std::micro>(now - t_last).count());
         t_last = now;
     };
-    skm_quant *q = new skm_quant();
-    int rc = quant_alloc(q, m->ix->device, n_tx, C, M);
-    if (rc != SKM_OK) { delete q; return rc; }
-    if (comm) { q->comm = comm->comm; q->rank = comm->rank; q->world = comm->world; }
-    lap("alloc");
+    // (the scratch is declared before the handle: the handle's destructor drains the stream first)
     DBuf<unsigned long long> fld;
     DBuf<double> sums;
+    std::unique_ptr<skm_quant> q(new skm_quant());
+    SKM_TRY(quant_alloc(q.get(), m->ix->device, n_tx, C, M));
+    if (comm) { q->comm = comm->comm; q->rank = comm->rank; q->world = comm->world; }
+    lap("alloc");
     const int64_t n_blocks = (n_tx + 8191) / 8192;
-    auto body = [&]() -> int {
-        SKM_TRY(fld.ensure(MAX_FRAGMENT_LENGTH + 1));
-        SKM_TRY(sums.ensure(n_blocks + 2));
-        double *const total = sums.p + n_blocks;          // [0] sum, [1] sum / divisor
-        unsigned long long ctr[4] = {0, 0, m->host_unaligned, m->host_units};
-        if (!m->host_totals_valid)
-            HIP_TRY(hipMemcpy(ctr, m->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));   // (mapper stream is idle)
-        unsigned long long aligned = ctr[CTR_UNITS] - ctr[CTR_UNALIGNED];
-        HIP_TRY(hipMemcpyAsync(fld.p, m->counters.p + CTR_FLD, MAX_FRAGMENT_LENGTH * 8,
-                               hipMemcpyDeviceToDevice, q->stream));
-        if (q->comm) {
-            // merge_fragment_lengths over the ranks, and with it (word 2000 of the same
-            // collective) n = class_count.sum() of infer.py:152 over ALL ranks.  Whether there
-            // is anything to quantify (infer.py:106-107 tests the merged table) must be decided
-            // on the global sum: a rank whose shard produced no class still has to take part
-            // in every collective of the EM below, with empty class views.
-            q->pinned[32] = aligned;
-            HIP_TRY(hipMemcpyAsync(fld.p + MAX_FRAGMENT_LENGTH, q->pinned + 32, 8, hipMemcpyHostToDevice, q->stream));
-            NCCL_TRY(g_rccl.AllReduce(fld.p, fld.p, MAX_FRAGMENT_LENGTH + 1, NCCL_UINT64, NCCL_SUM, q->comm,
-                                      q->stream));
-            HIP_TRY(hipMemcpyAsync(q->pinned + 32, fld.p + MAX_FRAGMENT_LENGTH, 8, hipMemcpyDeviceToHost, q->stream));
-            HIP_TRY(hipStreamSynchronize(q->stream));
-            aligned = q->pinned[32];
-            q->n_total_reduced = true;
-            // test hook: "the other ranks aligned this many units" -- a rank whose own shard produced no
-            // class (C == 0) then goes through the set-up and every collective of the EM with empty
-            // class views, a state one rank cannot reach by itself (tests/test_gpu_parity.py)
-            if (const char *v = getenv("SKM_TEST_ALIGNED_GLOBAL")) aligned += strtoull(v, nullptr, 10);
-        }
-        q->n_total = (double)aligned;
-        HIP_TRY(hipMemcpyAsync(q->x1.p, lengths, n_tx * 8, hipMemcpyHostToDevice, q->stream));
-        launch_effective_lengths(fld.p, q->x1.p, n_tx, q->eff_len.p, q->stream);
-        // (the effective lengths go home at the end, with the TPM: a copy to pageable memory holds the
-        // host up, and the kernels that follow are not launched meanwhile)
-        // quantify(): no class -> zeros (infer.py:106-107); over several ranks "no class anywhere"
-        // is "no aligned unit anywhere" (every aligned unit belongs to a class)
-        if (q->comm ? aligned == 0 : C == 0) {
-            if (effective_lengths)
-                HIP_TRY(hipMemcpyAsync(effective_lengths, q->eff_len.p, n_tx * 8, hipMemcpyDeviceToHost, q->stream));
-            HIP_TRY(hipStreamSynchronize(q->stream));
-            if (tpm) memset(tpm, 0, (size_t)n_tx * 8);
-            if (iters) *iters = 0;
-            return SKM_OK;
-        }
-        launch_reciprocal(q->eff_len.p, n_tx, q->x0.p, q->stream);
-        launch_np_sum(q->x0.p, n_tx, 1.0, sums.p, total, q->stream);
-        launch_divide(q->x0.p, n_tx, total, false, 0.0, q->stream);
-        lap("start vector");
-        SKM_TRY(quant_finish_setup(q, &m->t, m->first_seen_bound));
-        lap("setup");
-        if (trace) fprintf(stderr, "[skm_quant_infer] %lld classes, %lld transcripts, %lld rows\n", (long long)C, (long long)n_tx,
-                           (long long)q->n_rows);
-        int64_t it = 0;
-        SKM_TRY(em_run(q, rel_tol, x_floor, max_iters, 0, &it));
-        lap("em");
-        m->t_em_ns += q->t_em_ns;
-        m->em_iters += (double)it;
-        double *const x = (it & 1) ? q->x1.p : q->x0.p;
-        launch_np_sum(x, n_tx, 1000000.0, sums.p, total, q->stream);
-        launch_divide(x, n_tx, total + 1, true, 0.001, q->stream);
-        launch_np_sum(x, n_tx, 1000000.0, sums.p, total, q->stream);
-        launch_divide(x, n_tx, total + 1, false, 0.0, q->stream);
-        HIP_TRY(hipGetLastError());
-        if (tpm) HIP_TRY(hipMemcpyAsync(tpm, x, n_tx * 8, hipMemcpyDeviceToHost, q->stream));
+    SKM_TRY(fld.ensure(MAX_FRAGMENT_LENGTH + 1));
+    SKM_TRY(sums.ensure(n_blocks + 2));
+    double *const total = sums.p + n_blocks;          // [0] sum, [1] sum / divisor
+    unsigned long long ctr[4] = {0, 0, m->host_unaligned, m->host_units};
+    if (!m->host_totals_valid)
+        HIP_TRY(hipMemcpy(ctr, m->counters.p, sizeof(ctr), hipMemcpyDeviceToHost));   // (mapper stream is idle)
+    unsigned long long aligned = ctr[CTR_UNITS] - ctr[CTR_UNALIGNED];
+    HIP_TRY(hipMemcpyAsync(fld.p, m->counters.p + CTR_FLD, MAX_FRAGMENT_LENGTH * 8,
+                           hipMemcpyDeviceToDevice, q->stream));
+    if (q->comm) {
+        // merge_fragment_lengths over the ranks, and with it (word 2000 of the same
+        // collective) n = class_count.sum() of infer.py:152 over ALL ranks.  Whether there
+        // is anything to quantify (infer.py:106-107 tests the merged table) must be decided
+        // on the global sum: a rank whose shard produced no class still has to take part
+        // in every collective of the EM below, with empty class views.
+        q->pinned[32] = aligned;
+        HIP_TRY(hipMemcpyAsync(fld.p + MAX_FRAGMENT_LENGTH, q->pinned + 32, 8, hipMemcpyHostToDevice, q->stream));
+        NCCL_TRY(g_rccl.AllReduce(fld.p, fld.p, MAX_FRAGMENT_LENGTH + 1, NCCL_UINT64, NCCL_SUM, q->comm,
+                                  q->stream));
+        HIP_TRY(hipMemcpyAsync(q->pinned + 32, fld.p + MAX_FRAGMENT_LENGTH, 8, hipMemcpyDeviceToHost, q->stream));
+        HIP_TRY(hipStreamSynchronize(q->stream));
+        aligned = q->pinned[32];
+        q->n_total_reduced = true;
+        // test hook: "the other ranks aligned this many units" -- a rank whose own shard produced no
+        // class (C == 0) then goes through the set-up and every collective of the EM with empty
+        // class views, a state one rank cannot reach by itself (tests/test_gpu_parity.py)
+        if (const char *v = getenv("SKM_TEST_ALIGNED_GLOBAL")) aligned += strtoull(v, nullptr, 10);
+    }
+    q->n_total = (double)aligned;
+    HIP_TRY(hipMemcpyAsync(q->x1.p, lengths, n_tx * 8, hipMemcpyHostToDevice, q->stream));
+    launch_effective_lengths(fld.p, q->x1.p, n_tx, q->eff_len.p, q->stream);
+    // (the effective lengths go home at the end, with the TPM: a copy to pageable memory holds the
+    // host up, and the kernels that follow are not launched meanwhile)
+    // quantify(): no class -> zeros (infer.py:106-107); over several ranks "no class anywhere"
+    // is "no aligned unit anywhere" (every aligned unit belongs to a class)
+    if (q->comm ? aligned == 0 : C == 0) {
         if (effective_lengths)
             HIP_TRY(hipMemcpyAsync(effective_lengths, q->eff_len.p, n_tx * 8, hipMemcpyDeviceToHost, q->stream));
         HIP_TRY(hipStreamSynchronize(q->stream));
-        lap("tpm");
-        if (iters) *iters = it;
+        if (tpm) memset(tpm, 0, (size_t)n_tx * 8);
+        if (iters) *iters = 0;
         return SKM_OK;
-    };
-    rc = body();
-    fld.release();
-    sums.release();
-    skm_quant_destroy(q);
+    }
+    launch_reciprocal(q->eff_len.p, n_tx, q->x0.p, q->stream);
+    launch_np_sum(q->x0.p, n_tx, 1.0, sums.p, total, q->stream);
+    launch_divide(q->x0.p, n_tx, total, false, 0.0, q->stream);
+    lap("start vector");
+    SKM_TRY(quant_finish_setup(q.get(), &m->t, m->first_seen_bound));
+    lap("setup");
+    if (trace) fprintf(stderr, "[skm_quant_infer] %lld classes, %lld transcripts, %lld rows\n", (long long)C, (long long)n_tx,
+                       (long long)q->n_rows);
+    int64_t it = 0;
+    SKM_TRY(em_run(q.get(), rel_tol, x_floor, max_iters, 0, &it));
+    lap("em");
+    m->t_em_ns += q->t_em_ns;
+    m->em_iters += (double)it;
+    double *const x = (it & 1) ? q->x1.p : q->x0.p;
+    launch_np_sum(x, n_tx, 1000000.0, sums.p, total, q->stream);
+    launch_divide(x, n_tx, total + 1, true, 0.001, q->stream);
+    launch_np_sum(x, n_tx, 1000000.0, sums.p, total, q->stream);
+    launch_divide(x, n_tx, total + 1, false, 0.0, q->stream);
+    HIP_TRY(hipGetLastError());
+    if (tpm) HIP_TRY(hipMemcpyAsync(tpm, x, n_tx * 8, hipMemcpyDeviceToHost, q->stream));
+    if (effective_lengths)
+        HIP_TRY(hipMemcpyAsync(effective_lengths, q->eff_len.p, n_tx * 8, hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    lap("tpm");
+    if (iters) *iters = it;
+    q.reset();
     lap("destroy");
-    return rc;
+    return SKM_OK;
 }
 
 extern "C" int skm_quant_destroy(skm_quant *q)
 {
     if (!q) return SKM_OK;
     STALE_CHECK("quant_destroy entry");
-    (void)hipSetDevice(q->device);
-    (void)hipStreamSynchronize(q->stream);
-    q->cls_offset.release(); q->row_start.release(); q->tx_row.release(); q->ids.release();
-    q->tx_cls.release(); q->row_tx.release(); q->perm.release(); q->cls_count.release(); q->cls_count_saved.release();
-    q->inner.release(); q->row_sum.release(); q->eff_len.release(); q->x0.release(); q->x1.release();
-    q->acc.release(); q->part_max.release(); q->part_flags.release(); q->arrivals.release(); q->ctl.release();
-    q->cum.release(); q->tile_total.release(); q->x_start.release(); q->boot_out.release();
-    q->batch.cls_count.release(); q->batch.inner.release(); q->batch.row_sum.release(); q->batch.x0.release();
-    q->batch.x1.release(); q->batch.part_max.release(); q->batch.part_flags.release(); q->batch.ctl.release();
-    q->batch.mgr.release(); q->batch.counts_all.release(); q->batch.iters.release();
-    for (auto &e : q->ev) pool_event_release(e, true);
-    for (auto &e : q->chunk_ev) pool_event_release(e, false);
-    pool_pinned_release(q->pinned);
-    pool_stream_release(q->stream);
     delete q;
     STALE_CHECK("quant_destroy exit");
     return SKM_OK;
@@ -2609,6 +2607,7 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
     const double saved_total = q->n_total;
     const int64_t n_draws = (int64_t)run;            // n = class_count.sum(), infer.py:109
     int rc = SKM_OK;
+    DBuf<double> sums;                               // (before `restore`: freed after the stream has drained)
     auto restore = on_exit([&]() {                   // every exit: the handle holds the observed counts again
         (void)hipMemcpyAsync(q->cls_count.p, q->cls_count_saved.p, C * 8, hipMemcpyDeviceToDevice, q->stream);
         (void)hipStreamSynchronize(q->stream);
@@ -2636,8 +2635,6 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
         if (iters_out) iters_out[b] = *it_out;
         return SKM_OK;
     };
-    DBuf<double> sums;
-    auto drop_sums = on_exit([&]() { sums.release(); });
     // infer.py:127-129 on `count` results in HBM (TPM scaling with numpy's sums), when TPM is asked for
     auto scale = [&](double *results, int64_t count) -> int {
         if (!tpm || count <= 0) return SKM_OK;
@@ -2868,17 +2865,13 @@ extern "C" int skm_mapper_exchange_tables(skm_mapper *send, int send_to, skm_map
     SKM_TRY(set_device(comm->device));
     skm_device_table out{};
     if (send) SKM_TRY(skm_mapper_device_table(send, &out));            // (waits for what the mapper has queued)
-    hipStream_t stream = nullptr;
-    HIP_TRY(pool_stream_acquire(&stream));
+    PoolStream stream;
+    HIP_TRY(pool_stream_acquire(stream.out()));
     DBuf<unsigned long long> header, fld, first_seen;
     DBuf<int64_t> start, len;
     DBuf<double> count;
     DBuf<int32_t> ids;
-    auto undo = on_exit([&]() {
-        (void)hipStreamSynchronize(stream);
-        header.release(); fld.release(); first_seen.release(); start.release(); len.release(); count.release(); ids.release();
-        pool_stream_release(stream);
-    });
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (every exit: before they go)
     SKM_TRY(header.ensure(16));
     unsigned long long words[16] = {(unsigned long long)out.n_classes, (unsigned long long)out.n_ids,
                                     (unsigned long long)out.unaligned, (unsigned long long)out.units,

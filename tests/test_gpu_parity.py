@@ -1786,6 +1786,61 @@ def test_tables_merge_on_the_device(oracle, native_libs, chr21, chr21_oracle_ind
 
 
 
+def test_handles_go_in_any_order_with_work_still_queued(oracle, native_libs, chr21, chr21_oracle_index, pairs21):
+    """Handles free themselves whatever the order they go in: an index destroyed before its mapper
+    (the mapper's hold keeps the device copy until the mapper goes), a mapper destroyed with host
+    batches still queued and packed pieces pushed that nobody synced, a quantification handle made
+    from that mapper's table that outlives it, a mapper destroyed before its index.  Fresh handles
+    afterwards map the 21 pairs to the oracle's table, and their quantification handle runs the
+    same EM as the one that outlived its mapper, bit for bit."""
+    from seekmer_amd import common, infer, mapper
+    hip = native_libs.hip()
+    bases, offsets = oracle.pack_reads(pairs21)
+    fld = np.zeros(2000, dtype=np.int64)
+    expected = oracle.map_batch(chr21_oracle_index, bases, offsets, 21, True, fld)
+    n_tx = chr21_oracle_index.lengths.size
+    lengths = np.asarray(chr21_oracle_index.lengths, dtype='f8')
+    x0 = (1.0 / lengths) / np.sum(1.0 / lengths)
+    reps = 3000                           # (the 21 pairs over and over: batches that take a while to map)
+    big_offsets = np.concatenate([[0], np.cumsum(np.tile(np.diff(offsets), reps))]).astype(np.int64)
+    big_bases = np.tile(np.ascontiguousarray(bases[:offsets[-1]]), reps)
+
+    def destroy(result):
+        hip.skm_mapper_destroy(result._handle)
+        result._handle = None
+
+    index = make_product_index(chr21_oracle_index, chr21[0])
+    busy = mapper.MapResult(index)
+    rm = mapper.ReadMapper(index, busy)
+    rm.map_batch(common.ReadBatch(21, bases, offsets, True))
+    _compare_tables(oracle, expected, fld, busy)
+    outliving = infer._QuantHandle.from_map_result(busy, n_tx)
+    for k in range(4):
+        rm.map_batch_async(common.ReadBatch(21 * reps, big_bases, big_offsets, True, first_unit=21 + k * 21 * reps))
+    for piece in _streams_of(common, bases, offsets, 21, True):
+        rm.push_packed(piece)
+    index.release()                       # the index first ...
+    destroy(busy)                         # ... then its mapper, its queue and its pieces never synced
+    kept, kept_iters = outliving.em(x0, lengths)
+    outliving.close()
+
+    index = make_product_index(chr21_oracle_index, chr21[0])
+    early = mapper.MapResult(index)
+    mapper.ReadMapper(index, early).map_batch(common.ReadBatch(21, bases, offsets, True))
+    destroy(early)                        # a mapper before its index
+    index.release()
+
+    index = make_product_index(chr21_oracle_index, chr21[0])
+    fresh = mapper.MapResult(index)
+    mapper.ReadMapper(index, fresh).map_batch(common.ReadBatch(21, bases, offsets, True))
+    _compare_tables(oracle, expected, fld, fresh)
+    quant = infer._QuantHandle.from_map_result(fresh, n_tx)
+    x, iters = quant.em(x0, lengths)
+    quant.close()
+    np.testing.assert_array_equal(x, kept)
+    assert iters == kept_iters
+
+
 def test_table_hand_over_through_rccl(native_libs):
     """skm_mapper_exchange_tables: a mapper's table sent as it lies in HBM (ncclSend / ncclRecv) and
     merged by key on the receiving side -- on one GPU a rank sends to itself, which drives the
