@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import make_product_index
+from quant_reference import check_multinomial_dispersion as _check_multinomial_dispersion
 
 pytestmark = pytest.mark.gpu
 
@@ -700,39 +701,6 @@ def test_em_skewed_and_degenerate_tables(oracle, native_libs):
     x_perm, _ = infer.em(x0, l, class_map[:, perm], class_count, fixed_iters=2, return_iters=True)
     x_ref2, _ = oracle.em(x0, l, class_map[:, np.sort(perm, kind='stable')], class_count, fixed_iters=2)
     np.testing.assert_allclose(x_perm, x_ref2, rtol=1e-9, atol=1e-300)
-
-
-def _check_multinomial_dispersion(counts, class_count):
-    """Second moments of B draws of multinomial(n, p = class_count / n) (mean AND
-    variance): per class the sample variance over the replicates against n p (1 - p), and
-    Pearson's statistic sum_c (x_c - n p_c)^2 / (n p_c) of every replicate, which is
-    chi-square with C' - 1 degrees of freedom (C' = classes with p > 0).  Bounds are 6 sigma of
-    the respective sampling distributions, so a correct generator fails with p < 1e-8."""
-    counts = np.asarray(counts, dtype='f8')
-    n_boot = counts.shape[0]
-    n = class_count.sum()
-    p = class_count / n
-    live = p > 0
-    assert (counts[:, ~live] == 0).all()
-    var = counts[:, live].var(axis=0, ddof=1)
-    expect = n * p[live] * (1 - p[live])
-    big = expect > 25                                  # near-normal cells: var * (B-1) / expect ~ chi2(B-1)
-    ratio = var[big] / expect[big]
-    tol = 6 * np.sqrt(2.0 / (n_boot - 1))
-    assert big.sum() > 0 and (np.abs(ratio - 1) < tol + 0.05).all(), (ratio.min(), ratio.max(), tol)
-    # pooled: the mean of the ratios is far tighter than any single one
-    assert abs(ratio.mean() - 1) < 6 * np.sqrt(2.0 / (n_boot - 1) / big.sum()) + 0.01
-    cells = n * p >= 5                                 # chi-square approximation holds cell by cell
-    dof = int(cells.sum()) - (1 if cells.all() else 0)
-    pearson = (((counts[:, cells] - n * p[cells]) ** 2) / (n * p[cells])).sum(axis=1)
-    if dof > 30:
-        assert (np.abs(pearson - dof) < 6 * np.sqrt(2.0 * dof)).all(), (pearson.min(), pearson.max(), dof)
-        assert abs(pearson.mean() - dof) < 6 * np.sqrt(2.0 * dof / n_boot) + 0.002 * dof
-    # negative covariance between classes (-n p_i p_j): the two largest classes
-    i, j = np.argsort(p)[-2:]
-    cov = np.cov(counts[:, i], counts[:, j])[0, 1]
-    sd = np.sqrt(n * p[i] * (1 - p[i]) * n * p[j] * (1 - p[j]) / n_boot)
-    assert abs(cov + n * p[i] * p[j]) < 6 * sd * np.sqrt(2)
 
 
 def test_bootstrap_draw_and_em(oracle, native_libs, monkeypatch):
