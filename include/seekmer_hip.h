@@ -217,6 +217,21 @@ int skm_mapper_last_batch(skm_mapper *mapper, int32_t *begin, int32_t *end,
                           int32_t *counts, int32_t *entries,
                           int64_t cap_entries, int64_t *n_entries);
 int skm_mapper_keep_spans(skm_mapper *mapper, int enable);
+/* Strand-specific libraries (kallisto's --fr-stranded / --rf-stranded).  Every target entry of a
+ * unit is signed: e >= 0 means mate 1 (or the single read) lies in transcript e's own orientation,
+ * e < 0 that it lies antisense to transcript ~e.  SKM_STRAND_FR keeps a unit's entries with
+ * e >= 0, SKM_STRAND_RF those with e < 0, in their order; the class is the tuple of their unsigned
+ * ids, and a unit with no entry left is unaligned.  SKM_STRAND_NONE (the default) keeps all.  The
+ * fragment-length histogram and the spans are those of the unfiltered unit; skm_mapper_last_batch
+ * returns the kept (still signed) entries.  The mode applies to every batch the handle maps, not to
+ * tables merged in (skm_mapper_merge*, skm_mapper_exchange_tables).  It survives skm_mapper_reset
+ * and skm_mapper_clear, and can only change while the handle holds no units and has nothing queued
+ * (a new handle, or after skm_mapper_reset / skm_mapper_clear): SKM_ERR_STATE otherwise,
+ * SKM_ERR_ARG for an unknown mode. */
+#define SKM_STRAND_NONE 0
+#define SKM_STRAND_FR 1
+#define SKM_STRAND_RF 2
+int skm_mapper_set_strand(skm_mapper *mapper, int mode);
 /* Counter sizes (MapResult.summarize, seekmer/mapper.py:77-104):
  * summary[0]=C classes [1]=M (class,target) rows [2]=unaligned [3]=total units */
 int skm_mapper_summary(skm_mapper *mapper, int64_t summary[4]);

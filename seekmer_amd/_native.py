@@ -21,6 +21,10 @@ SKM_ERR_IO = 6
 SKM_ERR_UNDEFINED = 7
 SKM_ERR_COMM = 8
 
+SKM_STRAND_NONE = 0
+SKM_STRAND_FR = 1
+SKM_STRAND_RF = 2
+
 c_void_pp = ctypes.POINTER(ctypes.c_void_p)
 c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -86,6 +90,7 @@ HIP_SYMBOLS = {
     'skm_mapper_last_batch': (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p,
                                              c_i32p, c_i32p, c_i64, c_i64p]),
     'skm_mapper_keep_spans': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_mapper_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_summary': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_mapper_export': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i64p, c_i64p, c_i64p]),
     'skm_mapper_merge': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,

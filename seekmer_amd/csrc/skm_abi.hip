@@ -196,6 +196,7 @@ struct skm_mapper {
     HostPinned pinned;                      // host-pinned readback words
     DBuf<uint64_t> rec_key;
     bool keep_spans = false, last_spans = false;   // spans wanted / written by the last batch
+    int strand = SKM_STRAND_NONE;                  // skm_mapper_set_strand (under mu)
     DBuf<int32_t> unit_entries;
     DBuf<unsigned long long> batch_ctl;  // [0]=ids_cursor [8..2007]=fld [2048..2063]=stats
     int grid_blocks = 0;
@@ -1027,6 +1028,12 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
         HIP_TRY(hipMemcpy(st, b.stats, sizeof(st), hipMemcpyDeviceToHost));
         for (int i = 0; i < 48; ++i) m->stats_total[i] += st[i];
     }
+    // strand-specific library: the records keep the entries of its orientation (nothing is
+    // launched unstranded)
+    if (m->strand != SKM_STRAND_NONE) {
+        launch_strand_filter(b, m->strand, m->stream);
+        HIP_TRY(hipGetLastError());
+    }
 
     // class counting
     SKM_TRY(table_reserve(m, n_units));
@@ -1817,6 +1824,25 @@ extern "C" int skm_mapper_keep_spans(skm_mapper *m, int enable)
     (void)wait_jobs(m, 0, false);
     std::lock_guard<std::mutex> lock(m->mu);
     m->keep_spans = enable != 0;
+    return SKM_OK;
+}
+
+extern "C" int skm_mapper_set_strand(skm_mapper *m, int mode)
+{
+    if (!m) return fail(SKM_ERR_ARG, "NULL mapper");
+    if (mode != SKM_STRAND_NONE && mode != SKM_STRAND_FR && mode != SKM_STRAND_RF)
+        return fail(SKM_ERR_ARG, "unknown strand mode %d", mode);
+    (void)wait_jobs(m, 0, false);
+    bool queued;
+    {
+        std::lock_guard<std::mutex> hold(m->q_mu);
+        queued = !m->jobs.empty() || m->packed_busy || !m->pending[0].empty() || !m->pending[1].empty();
+    }
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (queued || m->units_done != 0)
+        return fail(SKM_ERR_STATE, "the strand mode can only change on an empty mapper (new, or after "
+                                   "skm_mapper_reset / skm_mapper_clear)");
+    m->strand = mode;
     return SKM_OK;
 }
 

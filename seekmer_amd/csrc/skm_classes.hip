@@ -401,12 +401,8 @@ class_merge_kernel(ClassTable t, int64_t n_classes, const int64_t *class_offsets
          c += (int64_t)gridDim.x * blockDim.x) {
         const int64_t off = class_offsets[c];
         const int n = (int)(class_len ? class_len[c] : class_offsets[c + 1] - off);
-        unsigned long long key = 0x243F6A8885A308D3ULL ^ (unsigned long long)n;
-        for (int i = 0; i < n; ++i) {
-            key ^= (uint32_t)class_targets[off + i];
-            key *= 0x9E3779B97F4A7C15ULL;
-            key ^= key >> 32;
-        }
+        unsigned long long key = tuple_key_seed(n);
+        for (int i = 0; i < n; ++i) key = tuple_key_step(key, (uint32_t)class_targets[off + i]);
         if (key == 0) key = 1;
         bool claimed;
         const uint64_t slot = probe_claim(t, key, claimed, ~0ULL);

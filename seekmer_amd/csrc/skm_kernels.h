@@ -80,6 +80,10 @@ void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, in
                       hipStream_t stream);
 void launch_pack_sequences(const char *bases, int64_t n_bases, uint64_t *seq2, int64_t n_words,
                            hipStream_t stream);
+// strand filter (skm_strand.hip), between the map kernel and class counting: every record of `b`
+// keeps the entries of its unit that lie in the library's orientation (mode SKM_STRAND_FR: e >= 0,
+// SKM_STRAND_RF: e < 0), compacted in place in the entry arena; its key and tuple length follow
+void launch_strand_filter(const MapBatch &b, int mode, hipStream_t stream);
 
 void launch_gather_probe(const void *table, uint64_t n_slots, int blocks, int per_lane, int chain,
                          unsigned long long *sink, hipStream_t stream);
@@ -92,6 +96,18 @@ struct alignas(32) ClassSlot {    // 32 B; key and first_seen side by side: one 
     long long tuple;              // -1 until the tuple has been committed to the arena, then
                                   // arena offset (bits 0-39) | tuple length (bits 40-62)
 };
+// 64-bit key of a class tuple (unsigned ids in list order): tuple_key_seed(n), then one
+// tuple_key_step per id.  The map kernel, the strand filter and the merge of foreign tables
+// all key with these two, so equal tuples meet in one slot.  A result of 0 is stored as 1
+// (0 marks an empty table slot).  Full tuples are compared later; this is only the tag.
+__host__ __device__ __forceinline__ uint64_t tuple_key_seed(int n) { return 0x243F6A8885A308D3ULL ^ (uint64_t)n; }
+__host__ __device__ __forceinline__ uint64_t tuple_key_step(uint64_t h, uint32_t id)
+{
+    h ^= id;
+    h *= 0x9E3779B97F4A7C15ULL;
+    h ^= h >> 32;
+    return h;
+}
 __host__ __device__ inline long long tuple_pack(long long offset, int n) { return offset | ((long long)n << 40); }
 __host__ __device__ inline long long tuple_offset(long long t) { return t & ((1LL << 40) - 1); }
 __host__ __device__ inline int tuple_len(long long t) { return (int)(t >> 40); }

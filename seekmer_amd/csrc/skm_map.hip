@@ -780,16 +780,6 @@ __device__ __forceinline__ bool intersect(const DevIndex &ix, TSet &a, Span &s1,
     return true;
 }
 
-// 64-bit key of a class tuple (unsigned ids in list order).  Never 0 (0 marks
-// an empty table slot).  Full tuples are compared later; this is only the tag.
-__device__ __forceinline__ uint64_t tuple_key_step(uint64_t h, uint32_t id)
-{
-    h ^= id;
-    h *= 0x9E3779B97F4A7C15ULL;
-    h ^= h >> 32;
-    return h;
-}
-
 // The reference maps a read with nested loops (map_read -> _find_first_kmer /
 // _filter_targets_to_left / _filter_targets_to_right, _mapper.pyx:151-343).
 // On a 64-wide wave that shape is ruinous (measured: the kernel is VALU-issue
@@ -1505,7 +1495,7 @@ map_units_kernel(DevIndex ix, MapBatch b)
                 phase(3);
                 if (valid) {
                     const int64_t off = chunk_pos + scan - n_out;
-                    uint64_t key = 0x243F6A8885A308D3ULL ^ (uint64_t)n_out;
+                    uint64_t key = tuple_key_seed(n_out);
                     const bool fits = off + n_out <= b.ids_capacity;
                     int i = 0;
                     int words = n_out ? set.words() : 0;

@@ -26,11 +26,12 @@ _LOG = logging.getLogger(__name__)
 
 
 def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, power,
-        device=0, seed=None, **__):
+        device=0, seed=None, strand=None, **__):
     """The entrypoint of the imputation module (seekmer/impute.py:54-125).
     `seed` fixes the 2-means split of the weights (the reference leaves it to
-    numpy's global generator)."""
+    numpy's global generator).  strand: None, 'fr' or 'rf' for every cell (mapper.MapResult)."""
     import pandas
+    mapper.strand_mode(strand)
     for path in fastq_paths:
         if not pathlib.Path(path).exists():
             raise ValueError(f'invalid FastQ file: {path}')
@@ -49,7 +50,7 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
                if common.PackedReadFeeder.eligible(group) else common.NativeReadFeeder(list(group), paired=not single_ended)
                for group in groups]
     map_results = mapper.map_multiple_samples(index, feeders, job_count=job_count, debug=debug,
-                                              device=device)
+                                              device=device, strand=strand)
     _LOG.info('Mapped all reads.')
     pool_fragment_lengths(map_results)
     summaries = [result.summarize() for result in map_results]
@@ -189,3 +190,4 @@ def add_subcommand_parser(subparsers):
     parser.add_argument('--device', type=int, default=0, help='GPU ordinal (default 0)')
     parser.add_argument('--seed', type=int, default=None,
                         help='seed of the 2-means split of the cell weights (default: random)')
+    infer.add_strand_arguments(parser)

@@ -26,7 +26,7 @@ X_FLOOR = 1e-8          # seekmer/infer.py:160
 
 
 def run(index_path, output_path, fastq_paths, job_count, save_readmap,
-        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, **__):
+        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, **__):
     """The entrypoint of the inference module (seekmer/infer.py:27-85).
 
     Started as one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m
@@ -35,21 +35,25 @@ def run(index_path, output_path, fastq_paths, job_count, save_readmap,
     index, the EM runs over the rank-local class tables with one RCCL all-reduce per step, rank 0
     merges the ranks' tables on its GPU, the `-b N` replicates are shared out over the ranks again
     (the merged table on every rank, no collective while they run), and rank 0 writes the outputs
-    of the whole sample.  A rank that fails ends the job (parallel.Ranks.fail)."""
+    of the whole sample.  A rank that fails ends the job (parallel.Ranks.fail).
+
+    strand: None, 'fr' (--fr-stranded) or 'rf' (--rf-stranded): every rank's mapper keeps only the
+    targets that lie in the library's orientation (mapper.MapResult)."""
     from . import parallel
     start_time = datetime.datetime.utcnow()
     ranks = parallel.Ranks.from_env()
     try:
         _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-             bootstrap, debug, device, seed, parse_threads)
+             bootstrap, debug, device, seed, parse_threads, strand=strand)
     except BaseException as error:          # noqa: B902 -- one rank: re-raised as it is
         ranks.fail(error)
     ranks.close()
 
 
 def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-         bootstrap, debug, device, seed, parse_threads):
+         bootstrap, debug, device, seed, parse_threads, strand=None):
     from . import parallel
+    mapper.strand_mode(strand)              # (an unknown mode fails before any file is touched)
     if ranks.world > 1:
         device = ranks.local_rank
         if save_readmap:
@@ -77,7 +81,7 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         index.device_handle(device)
         _LOG.info('Mapping all reads')
         map_result = mapper.map_reads(index, read_feeder, job_count=job_count,
-                                      readmap=readmap, debug=debug, device=device)
+                                      readmap=readmap, debug=debug, device=device, strand=strand)
     finally:
         ahead.finish()
     _LOG.info('Mapped all reads')
@@ -536,3 +540,13 @@ def add_subcommand_parser(subparsers):
     parser.add_argument('--parse-threads', type=int, dest='parse_threads', default=None, metavar='N',
                         help='parse plain FASTQ files with N threads (default: up to 8; 0: one thread, '
                              'the batches of the reference)')
+    add_strand_arguments(parser)
+
+
+def add_strand_arguments(parser):
+    """--fr-stranded / --rf-stranded (kallisto's flags), one at most: dest 'strand'."""
+    group = parser.add_mutually_exclusive_group()
+    group.add_argument('--fr-stranded', action='store_const', const='fr', dest='strand', default=None,
+                       help='strand-specific reads: mate 1 (or the single read) in the transcript\'s orientation')
+    group.add_argument('--rf-stranded', action='store_const', const='rf', dest='strand', default=None,
+                       help='strand-specific reads: mate 1 (or the single read) antisense to the transcript')

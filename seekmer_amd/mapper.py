@@ -26,6 +26,15 @@ MAX_FRAGMENT_LENGTH = 2000          # seekmer/_mapper.pyx:18-20
 
 EPS = numpy.finfo('f4').eps
 
+STRAND_MODES = {None: _native.SKM_STRAND_NONE, 'fr': _native.SKM_STRAND_FR, 'rf': _native.SKM_STRAND_RF}
+
+
+def strand_mode(strand):
+    """None | 'fr' | 'rf' -> SKM_STRAND_* (include/seekmer_hip.h, skm_mapper_set_strand)"""
+    if strand not in STRAND_MODES:
+        raise ValueError('strand must be None, \'fr\' or \'rf\', not %r' % (strand,))
+    return STRAND_MODES[strand]
+
 
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
@@ -51,9 +60,13 @@ class SummarizedResult:
 class MapResult:
     """A mapping result collection with a lock (seekmer/mapper.py:40-145)."""
 
-    def __init__(self, index, readmap=None, device=0, keep_spans=False):
+    def __init__(self, index, readmap=None, device=0, keep_spans=False, strand=None):
         """keep_spans: also store every unit's MappedSpan (begin, end, anchor) for
-        ReadMapper.last_batch -- parity tests and diagnostics; inference does not read them."""
+        ReadMapper.last_batch -- parity tests and diagnostics; inference does not read them.
+        strand: None (unstranded), 'fr' (--fr-stranded: mate 1 in the transcript's orientation) or
+        'rf' (--rf-stranded: mate 1 antisense); every mapped unit keeps only the targets of that
+        orientation (skm_mapper_set_strand)."""
+        mode = strand_mode(strand)
         self.lock = threading.Lock()
         self.index = index
         self.readmap = readmap
@@ -65,6 +78,9 @@ class MapResult:
         self.keep_spans = bool(keep_spans)
         if keep_spans:
             _native.check(_native.hip().skm_mapper_keep_spans(self._handle, 1))
+        self.strand = strand
+        if mode != _native.SKM_STRAND_NONE:
+            _native.check(_native.hip().skm_mapper_set_strand(self._handle, mode))
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
@@ -404,11 +420,11 @@ def _drain_worker(mapper, reads_queue, errors):
             pass
 
 
-def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0):
+def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0, strand=None):
     """Map reads (seekmer/mapper.py:148-193).  Unlike the reference's CPU workers the device
     calls can fail; a worker's exception is re-raised here once every thread has stopped,
-    instead of being lost with its thread."""
-    map_result = MapResult(index, readmap, device=device)
+    instead of being lost with its thread.  strand: None, 'fr' or 'rf' (MapResult)."""
+    map_result = _new_result(index, strand, readmap=readmap, device=device)
     try:
         if debug or job_count <= 1 or isinstance(read_feeder, PackedReadFeeder):
             # (a packed feeder parses with its own threads and is drained natively: the GIL is not held)
@@ -440,19 +456,21 @@ def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device
     return map_result
 
 
-def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0):
-    """Map reads for multiple samples (seekmer/mapper.py:196-234); a failed sample raises."""
+def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0, strand=None):
+    """Map reads for multiple samples (seekmer/mapper.py:196-234); a failed sample raises.
+    strand: None, 'fr' or 'rf' for every sample (MapResult)."""
+    strand_mode(strand)
     map_results = []
     if debug:
         for read_feeder in read_feeders:
-            result = MapResult(index, device=device)
+            result = _new_result(index, strand, device=device)
             map_results.append(result)
             ReadMapper(index, result)(read_feeder)
     else:
         pool = multiprocessing.pool.ThreadPool(job_count)
         pending = []
         for read_feeder in read_feeders:
-            result = MapResult(index, device=device)
+            result = _new_result(index, strand, device=device)
             map_results.append(result)
             pending.append(pool.apply_async(_map, args=(index, result, read_feeder)))
         pool.close()
@@ -460,6 +478,13 @@ def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0
         for job in pending:
             job.get()                     # re-raises what the worker raised
     return map_results
+
+
+def _new_result(index, strand, **kwargs):
+    """MapResult(index, **kwargs, strand=strand); unstranded, the call is the one of before."""
+    if strand is not None:
+        kwargs['strand'] = strand
+    return MapResult(index, **kwargs)
 
 
 def _map(index, map_result, read_feeder):
