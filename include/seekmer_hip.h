@@ -337,6 +337,14 @@ int skm_quant_bootstrap_share_tpm(skm_quant *quant, int64_t n_boot, int64_t firs
                                   int64_t *iters_out);
 /* EM with externally supplied class counts (parity of the bootstrap EM leg). */
 int skm_quant_set_counts(skm_quant *quant, const double *class_counts);
+/* The connected components of the (class, transcript) graph and the tiles the one-GPU EM steps them in
+ * (diagnostics, tests).  info[0] = tiles were built, [1] = tiles, [2] = components above the tile capacity
+ * (any: the EM steps the whole table as one problem), [3] = the EM of this handle runs on the tiles,
+ * [4..6] = tile capacity in pairs, classes, transcripts.  Optional arrays: tx_label[n_tx] = smallest
+ * transcript id of the transcript's component, tx_tile[n_tx] = its tile (n_tx: none), class_tile
+ * [n_classes] = tile of every class in the caller's class order. */
+int skm_quant_components(skm_quant *quant, int64_t info[8], int32_t *tx_label, int32_t *tx_tile,
+                         int32_t *class_tile);
 /* timing[0]=EM kernel ns total [1]=iterations [2]=launches */
 int skm_quant_timing(skm_quant *quant, double timing[4]);
 

@@ -120,6 +120,7 @@ HIP_SYMBOLS = {
                                                      c_f64p, c_i64p]),
     'skm_quant_set_counts': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_quant_timing': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
+    'skm_quant_components': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i32p, c_i32p]),
     'skm_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_comm_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        c_void_pp]),

@@ -304,6 +304,24 @@ struct skm_quant {
         DBuf<double> counts_all;              // [group][C] pre-drawn class counts of a group of replicates
         DBuf<int64_t> iters;                  // [group] their step counts
     } batch;
+    // the component tiles of the class table (EmTiles, skm_kernels.h): built with the class views
+    struct Tiles {
+        DBuf<int64_t> tile_tx, tile_cls, cls_pair, tx_pair;
+        DBuf<int32_t> tx_list, cls_list, tx_label, tx_tile, cls_tile;
+        DBuf<uint16_t> cls_tx, tx_cls;
+        DBuf<double> x2, step_max;            // x2: third abundance vector (a chunk's input outlives the chunk after it)
+        DBuf<unsigned int> step_flags;
+        // the components above the capacity as an EM problem beside the tiles (QuantResidual)
+        struct Residual {
+            int64_t n_classes = 0, n_ids = 0, n_rows = 0;
+            DBuf<int64_t> cls_offset, row_start, tx_row;
+            DBuf<int32_t> ids, cls_src, row_tx, tx_cls;
+            DBuf<double> cls_count, inner, row_sum;
+            bool built = false;
+        } residual;
+        bool built = false;                   // the set-up has run
+        int64_t n_tiles = 0, n_oversize = 0;  // n_oversize: components above the tile capacity (then the tiles are not used)
+    } tiles;
     double n_total = 0;
     bool n_total_reduced = false;             // n_total already is the sum over all ranks
     // RCCL communicator (borrowed from an skm_comm), loaded lazily
@@ -2128,7 +2146,20 @@ extern "C" int skm_effective_lengths(int device, const int64_t *fld, const doubl
 
 namespace {
 
-int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64_t n_ids)
+// SKM_EM_NO_COMPONENTS (tuning aid, looked up at every use so that one process can compare both forms):
+// no component tiles are built, and an EM run steps the whole table with two launches per step
+bool em_components_enabled() { return getenv("SKM_EM_NO_COMPONENTS") == nullptr; }
+// what an EM run needs besides the handle's own state to step tiles: one rank (the all-reduce of several
+// sits inside every step) and the fused rows + finalize launch (the unfused finalize walks every transcript)
+bool em_tiles_possible(bool several_ranks)
+{
+    static const bool unfused = getenv("SKM_EM_UNFUSED") != nullptr;
+    return !several_ranks && !unfused && em_components_enabled();
+}
+
+// several_ranks: the handle gets a communicator right after this call; the tiles, which only a one-rank EM
+// can use, are then neither given room here nor built by quant_finish_setup
+int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64_t n_ids, bool several_ranks = false)
 {
     STALE_CHECK("quant_alloc entry");
     q->device = device;
@@ -2161,6 +2192,15 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
     SKM_TRY(q->part_flags.ensure(EM_FINAL_BLOCKS));
     SKM_TRY(q->arrivals.ensure(T));
     HIP_TRY(hipMemsetAsync(q->arrivals.p, 0, T * sizeof(unsigned int), q->stream));
+    if (em_tiles_possible(several_ranks)) {
+        auto &t = q->tiles;
+        SKM_TRY(t.tile_tx.ensure(T + 2)); SKM_TRY(t.tile_cls.ensure(T + 2));
+        SKM_TRY(t.cls_pair.ensure(C + 1)); SKM_TRY(t.tx_pair.ensure(T + 1));
+        SKM_TRY(t.tx_list.ensure(T)); SKM_TRY(t.cls_list.ensure(C));
+        SKM_TRY(t.tx_label.ensure(T)); SKM_TRY(t.tx_tile.ensure(T)); SKM_TRY(t.cls_tile.ensure(C));
+        SKM_TRY(t.cls_tx.ensure(M)); SKM_TRY(t.tx_cls.ensure(M));
+        SKM_TRY(t.x2.ensure(T));
+    }
     STALE_CHECK("quant_alloc exit");
     return SKM_OK;
 }
@@ -2179,6 +2219,14 @@ QuantBuild quant_build_view(skm_quant *q)
     b.row_start = q->row_start.p;
     b.row_tx = q->row_tx.p;
     b.n_rows_cap = (int64_t)q->row_tx.cap;
+    if (q->tiles.x2.p) {                       // (quant_alloc made room for the tiles)
+        auto &t = q->tiles;
+        b.tile_tx = t.tile_tx.p; b.tile_cls = t.tile_cls.p;
+        b.tx_list = t.tx_list.p; b.cls_list = t.cls_list.p;
+        b.cls_pair = t.cls_pair.p; b.tx_pair = t.tx_pair.p;
+        b.tile_cls_tx = t.cls_tx.p; b.tile_tx_cls = t.tx_cls.p;
+        b.tx_label = t.tx_label.p; b.tx_tile = t.tx_tile.p; b.cls_tile = t.cls_tile.p;
+    }
     return b;
 }
 
@@ -2190,6 +2238,38 @@ int quant_finish_setup(skm_quant *q, const ClassTable *table, int64_t units_seen
     const int64_t rows = quant_setup(table, b, q->perm.p, q->stream);
     if (rows < 0) return fail(SKM_ERR_HIP, "building the class views failed (%lld): %s", (long long)rows, quant_setup_failure());
     q->n_rows = rows;
+    if (b.tile_tx) {
+        q->tiles.built = true;
+        q->tiles.n_tiles = b.tile_info[0];
+        q->tiles.n_oversize = b.tile_info[1];
+        if (q->tiles.n_tiles > 0) {
+            SKM_TRY(q->tiles.step_max.ensure((size_t)(EM_CHUNK_MAX * q->tiles.n_tiles)));
+            SKM_TRY(q->tiles.step_flags.ensure((size_t)(EM_CHUNK_MAX * q->tiles.n_tiles)));
+        }
+        if (q->tiles.n_oversize > 0 && q->tiles.n_tiles > 0) {
+            // tiles AND components above the capacity: those become the residual problem (a table that
+            // is one such component has no tiles and keeps the whole-table EM as it is)
+            auto &r = q->tiles.residual;
+            int64_t counts[3] = {0, 0, 0};
+            if (quant_residual_count(b, counts, q->stream))
+                return fail(SKM_ERR_HIP, "sizing the residual EM problem failed: %s", quant_setup_failure());
+            r.n_classes = counts[0]; r.n_ids = counts[1]; r.n_rows = counts[2];
+            SKM_TRY(r.cls_offset.ensure((size_t)r.n_classes + 1)); SKM_TRY(r.ids.ensure((size_t)std::max<int64_t>(r.n_ids, 1)));
+            SKM_TRY(r.cls_src.ensure((size_t)std::max<int64_t>(r.n_classes, 1)));
+            SKM_TRY(r.row_start.ensure((size_t)r.n_rows + 1)); SKM_TRY(r.row_tx.ensure((size_t)std::max<int64_t>(r.n_rows, 1)));
+            SKM_TRY(r.tx_cls.ensure((size_t)std::max<int64_t>(r.n_ids, 1))); SKM_TRY(r.tx_row.ensure((size_t)q->n_tx + 1));
+            SKM_TRY(r.cls_count.ensure((size_t)std::max<int64_t>(r.n_classes, 1)));
+            SKM_TRY(r.inner.ensure((size_t)std::max<int64_t>(r.n_classes, 1)));
+            SKM_TRY(r.row_sum.ensure((size_t)std::max<int64_t>(r.n_rows, 1)));
+            QuantResidual out{};
+            out.n_classes = r.n_classes; out.n_ids = r.n_ids; out.n_rows = r.n_rows;
+            out.cls_offset = r.cls_offset.p; out.ids = r.ids.p; out.cls_src = r.cls_src.p;
+            out.row_start = r.row_start.p; out.row_tx = r.row_tx.p; out.tx_cls = r.tx_cls.p; out.tx_row = r.tx_row.p;
+            if (quant_residual_build(b, out, q->stream))
+                return fail(SKM_ERR_HIP, "building the residual EM problem failed: %s", quant_setup_failure());
+            r.built = true;
+        }
+    }
     return SKM_OK;
 }
 
@@ -2278,6 +2358,108 @@ EmProblem em_problem(skm_quant *q, double rel_tol, double x_floor, int64_t max_i
     return p;
 }
 
+// one rank, every component within the tile capacity: the EM runs tile by tile in LDS (em_run_tiles)
+bool em_uses_tiles(const skm_quant *q)
+{
+    return em_tiles_possible(q->comm != nullptr) && q->tiles.built && q->tiles.n_tiles > 0 &&
+           (q->tiles.n_oversize == 0 || q->tiles.residual.built);
+}
+
+// The component form of em_run's loop (after its preamble: control block cleared, ev[0] recorded).  Every
+// chunk is ONE launch that steps all the tiles `chunk` times in LDS, from abundance vector i % 3 to
+// (i + 1) % 3 of three, plus the one-block launch that judges the chunk's steps in order.  The host
+// stays one chunk ahead as before.  The tiles of the chunk in which the EM stops (at step K) have run
+// to the chunk's end, so that chunk is replayed from its input -- still there: the chunk after it wrote
+// the third vector -- for exactly K - first steps into x[K & 1], where the callers look for the result.
+constexpr int CTL_WORD_TILE_FAULT = 4;        // control block word em_local_chunk_kernel raises (skm_em.hip: CTL_TILE_FAULT)
+int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters_out)
+{
+    auto &t = q->tiles;
+    EmTiles tl{};
+    tl.n_tiles = t.n_tiles;
+    tl.tile_tx = t.tile_tx.p; tl.tile_cls = t.tile_cls.p;
+    tl.tx_list = t.tx_list.p; tl.cls_list = t.cls_list.p;
+    tl.cls_pair = t.cls_pair.p; tl.tx_pair = t.tx_pair.p;
+    tl.cls_tx = t.cls_tx.p; tl.tx_cls = t.tx_cls.p;
+    tl.step_max = t.step_max.p; tl.step_flags = t.step_flags.p;
+    double *const x[3] = {q->x0.p, q->x1.p, t.x2.p};
+    // With components above the capacity the residual problem runs beside the tiles, step by step with
+    // the whole-table kernels on its own classes and rows (its transcripts' entries of x0 / x1; the
+    // tiles' entries are the tiles' alone), and ITS judge takes the tiles' partials of the step along.
+    const bool mixed = t.n_oversize > 0;
+    EmProblem pr = p;
+    if (mixed) {
+        auto &r = t.residual;
+        pr.n_classes = r.n_classes; pr.n_rows = r.n_rows;
+        pr.cls_offset = r.cls_offset.p; pr.ids = r.ids.p; pr.cls_count = r.cls_count.p; pr.inner = r.inner.p;
+        pr.row_start = r.row_start.p; pr.row_tx = r.row_tx.p; pr.tx_cls = r.tx_cls.p; pr.tx_row = r.tx_row.p;
+        pr.row_sum = r.row_sum.p;
+        pr.fused = 1;
+        pr.extra_max = t.step_max.p; pr.extra_flags = t.step_flags.p; pr.n_extra = t.n_tiles;
+        launch_permute_f64(q->cls_count.p, r.cls_src.p, r.n_classes, r.cls_count.p, false, q->stream);   // (set_counts may have changed them)
+    }
+    int64_t queued = 0;
+    auto enqueue_chunk = [&](int slot) -> int {
+        launch_em_local_chunk(p, tl, x[queued % 3], x[(queued + 1) % 3], (int)chunk, true, q->stream);
+        if (mixed) {
+            pr.extra_first = queued * chunk;
+            for (int64_t i = 0, k = queued * chunk; i < chunk; ++i, ++k) {
+                launch_em_inner(pr, (int)(k & 1), i > 0, k, q->stream);
+                launch_em_rows_finalize(pr, (int)(k & 1), q->stream);
+            }
+            launch_em_decide(pr, (queued + 1) * chunk, q->stream);
+            q->launches += 2 * chunk + 2;
+        } else {
+            launch_em_local_decide(p, tl, queued * chunk, (int)chunk, q->stream);
+            q->launches += 2;
+        }
+        ++queued;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(q->pinned + 8 * slot, q->ctl.p, 8 * sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, q->stream));
+        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
+        return SKM_OK;
+    };
+    unsigned long long ctl[8] = {0};
+    SKM_TRY(enqueue_chunk(0));
+    int64_t last = 0;                                     // the chunk whose verdict has been read
+    for (int slot = 0;; slot ^= 1, ++last) {
+        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
+        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
+        memcpy(ctl, q->pinned + 8 * slot, sizeof(ctl));
+        if (ctl[0]) break;
+    }
+    // (a tile above the capacity cannot come out of the set-up; the kernel that meets one leaves it alone,
+    // says so here and stops the run rather than going on with abundances nobody stepped)
+    if (ctl[CTL_WORD_TILE_FAULT]) {
+        HIP_TRY(hipStreamSynchronize(q->stream));
+        return fail(SKM_ERR_STATE, "a component tile exceeds the tile capacity: the class views of this handle are damaged");
+    }
+    const int64_t steps = (int64_t)ctl[1], into = steps - last * chunk;      // 1 .. chunk steps into chunk `last`
+    double *const result = (steps & 1) ? q->x1.p : q->x0.p;
+    // (beside a residual the last chunk is replayed also when the EM stopped on its last step and
+    // x[(last + 1) % 3] holds the tiles' result already: a whole-vector copy would overwrite the residual's
+    // entries, and a copy of the tiles' entries alone is a kernel this path does not have yet -- up to
+    // `chunk` steps of tile work, once per run, on such tables)
+    if (into == chunk && !mixed) {
+        if (x[(last + 1) % 3] != result)
+            HIP_TRY(hipMemcpyAsync(result, x[(last + 1) % 3], q->n_tx * 8, hipMemcpyDeviceToDevice, q->stream));
+    } else {
+        launch_em_local_chunk(p, tl, x[last % 3], result, (int)into, false, q->stream);
+        q->launches += 1;
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(q->ev[1], q->stream));
+    HIP_TRY(hipEventSynchronize(q->ev[1]));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
+    q->t_em_ns += ms * 1e6;
+    q->iters_total += (double)steps;
+    if (iters_out) *iters_out = steps;
+    if (ctl[3]) return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
+    return SKM_OK;
+}
+
 // runs the EM from the abundance already in q->x0; result left in x[iters & 1]
 int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int64_t fixed_iters,
            int64_t *iters_out, int64_t chunk_steps = 16)
@@ -2296,6 +2478,7 @@ int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int6
     int64_t k = 0;
     const int64_t chunk = fixed_iters > 0 ? std::min<int64_t>(fixed_iters, chunk_steps) : chunk_steps;
     HIP_TRY(hipEventRecord(q->ev[0], q->stream));
+    if (em_uses_tiles(q) && chunk <= EM_CHUNK_MAX) return em_run_tiles(q, p, chunk, iters_out);
     // Steps are enqueued in chunks; after each chunk the control block is copied to pinned
     // memory and an event recorded.  The host stays one chunk ahead: chunk i+1 is already
     // queued when it waits for chunk i's verdict, so the GPU never idles at a check-point
@@ -2471,7 +2654,7 @@ extern "C" int skm_quant_infer(skm_mapper *m, skm_comm *comm, const double *leng
     DBuf<unsigned long long> fld;
     DBuf<double> sums;
     std::unique_ptr<skm_quant> q(new skm_quant());
-    SKM_TRY(quant_alloc(q.get(), m->ix->device, n_tx, C, M));
+    SKM_TRY(quant_alloc(q.get(), m->ix->device, n_tx, C, M, comm != nullptr));
     if (comm) { q->comm = comm->comm; q->rank = comm->rank; q->world = comm->world; }
     lap("alloc");
     const int64_t n_blocks = (n_tx + 8191) / 8192;
@@ -2569,6 +2752,35 @@ extern "C" int skm_quant_em(skm_quant *q, double *x, const double *l, double rel
     SKM_TRY(em_run(q, rel_tol, x_floor, max_iters, fixed_iters, &it));
     HIP_TRY(hipMemcpy(x, (it & 1) ? q->x1.p : q->x0.p, q->n_tx * 8, hipMemcpyDeviceToHost));
     if (iters) *iters = it;
+    return SKM_OK;
+}
+
+extern "C" int skm_quant_components(skm_quant *q, int64_t info[8], int32_t *tx_label, int32_t *tx_tile,
+                                    int32_t *class_tile)
+{
+    if (!q || !info) return fail(SKM_ERR_ARG, "NULL argument");
+    std::lock_guard<std::mutex> lock(q->mu);
+    SKM_TRY(set_device(q->device));
+    const auto &t = q->tiles;
+    info[0] = t.built ? 1 : 0;
+    info[1] = t.n_tiles;
+    info[2] = t.n_oversize;
+    info[3] = em_uses_tiles(q) ? 1 : 0;
+    info[4] = EM_TILE_PAIRS; info[5] = EM_TILE_CLASSES; info[6] = EM_TILE_TX; info[7] = 0;
+    if (!t.built) {
+        if (tx_label || tx_tile || class_tile) return fail(SKM_ERR_ARG, "no component tiles were built for this handle");
+        return SKM_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    if (tx_label) HIP_TRY(hipMemcpy(tx_label, t.tx_label.p, q->n_tx * 4, hipMemcpyDeviceToHost));
+    if (tx_tile) HIP_TRY(hipMemcpy(tx_tile, t.tx_tile.p, q->n_tx * 4, hipMemcpyDeviceToHost));
+    if (class_tile && q->n_classes) {
+        // internal (locality) order -> the caller's class order
+        std::vector<int32_t> tile(q->n_classes), perm(q->n_classes);
+        HIP_TRY(hipMemcpy(tile.data(), t.cls_tile.p, q->n_classes * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(perm.data(), q->perm.p, q->n_classes * 4, hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < q->n_classes; ++k) class_tile[perm[k]] = tile[k];
+    }
     return SKM_OK;
 }
 

@@ -25,7 +25,7 @@
 
 namespace skm {
 
-enum { CTL_DONE = 0, CTL_ITERS = 1, CTL_UNDEFINED = 3 };
+enum { CTL_DONE = 0, CTL_ITERS = 1, CTL_UNDEFINED = 3, CTL_TILE_FAULT = 4 };
 
 __device__ bool em_evaluate(const EmProblem &p, int n_parts, int64_t steps_done, bool publish);
 
@@ -288,6 +288,14 @@ __device__ bool em_evaluate(const EmProblem &p, int n_parts, int64_t steps_done,
         m = o > m ? o : m;
         f |= p.part_flags[b];
     }
+    if (p.n_extra > 0) {                        // (the tiles' partials of this step: max and or, any order)
+        const int64_t first = (steps_done - 1 - p.extra_first) * p.n_extra;
+        for (int64_t b = threadIdx.x; b < p.n_extra; b += blockDim.x) {
+            const double o = p.extra_max[first + b];
+            m = o > m ? o : m;
+            f |= p.extra_flags[first + b];
+        }
+    }
     for (int d = 32; d > 0; d >>= 1) {
         const double o = __shfl_xor(m, d, 64);
         m = o > m ? o : m;
@@ -324,6 +332,186 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 {
     if (p.ctl[CTL_DONE]) return;
     em_evaluate(p, n_parts, steps_done, true);
+}
+
+// ---- the EM of independent components, a chunk of steps per launch (EmTiles, skm_kernels.h)
+// One workgroup per tile.  The tile's pairs in both views (16-bit tile-local indices), the class counts,
+// `inner`, the effective lengths and both abundance vectors live in LDS for the whole chunk; a step is
+//   class phase  one lane per class: S_c over the tuple in tuple order, inner_c = S_c / count_c
+//                (the arithmetic of em_inner_kernel)
+//   row phase    eight lanes per transcript, its rows of <= EM_ROW_CAP entries one after the other: lane
+//                `sub` adds x_t / inner_c for entries begin + sub + 8 k in ascending k, the xor 4, 2, 1
+//                butterfly, the row sums added in row order from 0.0, then x'_t = a / l_t / n, NaN -> 0
+//                and the relative change (the arithmetic of em_rows_finalize_kernel, association for
+//                association)
+// with two workgroup barriers and nothing that crosses workgroups.  Each step's partials of the stopping
+// rule go to step_max / step_flags [step][tile]; em_local_decide_kernel judges the steps in order.
+__global__ void __launch_bounds__(256)
+em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out, int n_steps, int check_done)
+{
+    static_assert(EM_TILE_TX <= 8 * 32, "a lane group of the row phase takes at most eight transcripts");
+    if (check_done && p.ctl[CTL_DONE]) return;
+    __shared__ double s_x[2][EM_TILE_TX];
+    __shared__ double s_eff[EM_TILE_TX];
+    __shared__ double s_inner[EM_TILE_CLASSES];
+    __shared__ double s_count[EM_TILE_CLASSES];
+    __shared__ double s_max[EM_CHUNK_MAX][4];
+    __shared__ unsigned int s_flags[EM_CHUNK_MAX][4];
+    __shared__ int32_t s_tx[EM_TILE_TX];
+    __shared__ uint16_t s_cls_tx[EM_TILE_PAIRS], s_tx_cls[EM_TILE_PAIRS];
+    __shared__ uint16_t s_cls_off[EM_TILE_CLASSES + 1], s_tx_off[EM_TILE_TX + 1];
+    const int64_t tile = blockIdx.x;
+    const int64_t tx0 = tl.tile_tx[tile], cls0 = tl.tile_cls[tile];
+    const int n_tx = (int)(tl.tile_tx[tile + 1] - tx0), n_cls = (int)(tl.tile_cls[tile + 1] - cls0);
+    const int64_t cp0 = tl.cls_pair[cls0], tp0 = tl.tx_pair[tx0];
+    const int n_pairs = (int)(tl.cls_pair[cls0 + n_cls] - cp0);
+    // The set-up keeps every tile within the capacities.  One that is not would overrun the arrays above:
+    // it is left alone, and the run is stopped with the fault word set, which the host turns into an error.
+    if (n_tx > EM_TILE_TX || n_cls > EM_TILE_CLASSES || n_pairs > EM_TILE_PAIRS || n_tx < 0 || n_cls < 0 || n_pairs < 0) {
+        if (threadIdx.x == 0) { p.ctl[CTL_TILE_FAULT] = 1; p.ctl[CTL_DONE] = 1; }
+        return;
+    }
+    const int tid = threadIdx.x;
+    for (int j = tid; j < n_pairs; j += 256) {
+        s_cls_tx[j] = tl.cls_tx[cp0 + j];
+        s_tx_cls[j] = tl.tx_cls[tp0 + j];
+    }
+    for (int k = tid; k <= n_cls; k += 256) {
+        s_cls_off[k] = (uint16_t)(tl.cls_pair[cls0 + k] - cp0);
+        if (k < n_cls) s_count[k] = p.cls_count[tl.cls_list[cls0 + k]];
+    }
+    for (int i = tid; i <= n_tx; i += 256) {
+        s_tx_off[i] = (uint16_t)(tl.tx_pair[tx0 + i] - tp0);
+        if (i < n_tx) {
+            const int32_t t = tl.tx_list[tx0 + i];
+            s_tx[i] = t;
+            s_x[0][i] = x_in[t];
+            s_eff[i] = p.eff_len[t];
+        }
+    }
+    __syncthreads();
+    const int sub = tid & 7, wave = tid >> 6;
+    for (int step = 0; step < n_steps; ++step) {
+        const double *x = s_x[step & 1];
+        double *x_new = s_x[(step & 1) ^ 1];
+        for (int k = tid; k < n_cls; k += 256) {
+            const int end = s_cls_off[k + 1];
+            double s = 0.0;
+            for (int j = s_cls_off[k]; j < end; ++j) s += x[s_cls_tx[j]];
+            s_inner[k] = s / s_count[k];
+        }
+        __syncthreads();
+        double local_max = 0.0;
+        unsigned int flags = 0;
+        // (all eight lanes of a group hold a row's sum after the butterfly: lane `sub` keeps the
+        // numerator of the group's transcript number `sub` and finalizes it after the loop, so that the
+        // three divisions of the finalize run once per wave, not once per transcript of a group)
+        double my_a = 0.0, my_xt = 0.0;
+        int my_i = -1, turn = 0;
+        for (int i = tid >> 3; i < n_tx; i += 32, ++turn) {
+            const double xt = x[i];
+            const int end = s_tx_off[i + 1];
+            int begin = s_tx_off[i];
+            double a = 0.0;
+            do {                                    // (a transcript in no class has one empty row)
+                const int row_end = min(begin + EM_ROW_CAP, end);
+                double s = 0.0;
+                for (int e = begin + sub; e < row_end; e += 8) s += xt / s_inner[s_tx_cls[e]];
+                s += __shfl_xor(s, 4, 8);
+                s += __shfl_xor(s, 2, 8);
+                s += __shfl_xor(s, 1, 8);
+                a += s;
+                begin = row_end;
+            } while (begin < end);
+            if (turn == sub) { my_a = a; my_xt = xt; my_i = i; }
+        }
+        if (my_i >= 0) {
+            double v = my_a / s_eff[my_i] / p.n_total;                    // infer.py:158
+            if (v != v) v = 0.0;                                          // infer.py:159
+            x_new[my_i] = v;
+            if (v > p.x_floor) {                                          // infer.py:160
+                const double change = fabs(v - my_xt) / v;
+                if (change != change) flags |= 2u;
+                else if (change > local_max) local_max = change;
+                flags |= 1u;
+            }
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+            const double o = __shfl_xor(local_max, d, 64);
+            local_max = o > local_max ? o : local_max;
+            flags |= __shfl_xor(flags, d, 64);
+        }
+        if ((tid & 63) == 0) { s_max[step][wave] = local_max; s_flags[step][wave] = flags; }
+        __syncthreads();
+    }
+    const double *x = s_x[n_steps & 1];
+    for (int i = tid; i < n_tx; i += 256) x_out[s_tx[i]] = x[i];
+    if (tid < n_steps) {
+        double m = s_max[tid][0];
+        unsigned int f = s_flags[tid][0];
+        for (int w = 1; w < 4; ++w) { m = s_max[tid][w] > m ? s_max[tid][w] : m; f |= s_flags[tid][w]; }
+        tl.step_max[tid * tl.n_tiles + tile] = m;
+        tl.step_flags[tid * tl.n_tiles + tile] = f;
+    }
+}
+
+// The stopping rule (em_evaluate) for the n_steps steps of a chunk, in order: wave s takes the maximum and
+// the flags of step s over the tiles (max and or: the order does not matter), lane 0 then walks the steps
+// and latches the first that stops.
+__global__ void __launch_bounds__(64 * EM_CHUNK_MAX)
+em_local_decide_kernel(EmProblem p, EmTiles tl, int64_t first_step, int n_steps)
+{
+    if (p.ctl[CTL_DONE]) return;
+    __shared__ double s_max[EM_CHUNK_MAX];
+    __shared__ unsigned int s_flags[EM_CHUNK_MAX];
+    const int step = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (step < n_steps) {
+        double m = 0.0;
+        unsigned int f = 0;
+        const double *__restrict__ step_max = tl.step_max + step * tl.n_tiles;
+        const unsigned int *__restrict__ step_flags = tl.step_flags + step * tl.n_tiles;
+        int64_t b = lane;
+        for (; b + 7 * 64 < tl.n_tiles; b += 8 * 64) {       // (eight loads of each in flight)
+            double o[8];
+            unsigned int g[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { o[k] = step_max[b + 64 * k]; g[k] = step_flags[b + 64 * k]; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { m = o[k] > m ? o[k] : m; f |= g[k]; }
+        }
+        for (; b < tl.n_tiles; b += 64) {
+            const double o = step_max[b];
+            m = o > m ? o : m;
+            f |= step_flags[b];
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+            const double o = __shfl_xor(m, d, 64);
+            m = o > m ? o : m;
+            f |= __shfl_xor(f, d, 64);
+        }
+        if (lane == 0) { s_max[step] = m; s_flags[step] = f; }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int s = 0; s < n_steps; ++s) {
+        const int64_t steps_done = first_step + s + 1;
+        const double m = s_max[s];
+        const unsigned int f = s_flags[s];
+        bool done, undefined = false;
+        if (p.fixed_iters > 0) {
+            done = steps_done >= p.fixed_iters;
+        } else if (!(f & 1u)) {
+            undefined = true;                 // numpy raises on max() of an empty selection
+            done = true;
+        } else {
+            done = (f & 2u) || !(m > p.rel_tol);                 // NaN propagates through max()
+            if (p.max_iters > 0 && steps_done >= p.max_iters) done = true;
+        }
+        if (undefined) p.ctl[CTL_UNDEFINED] = 1;
+        p.ctl[CTL_ITERS] = (unsigned long long)steps_done;
+        p.ctl[CTL_DONE] = done ? 1ULL : 0ULL;
+        if (done) break;
+    }
 }
 
 // MapResult.effective_lengths, mapper.py:134-141: p = fld / fld.sum();
@@ -653,6 +841,20 @@ void launch_em_rows_acc(const EmProblem &p, int parity, hipStream_t stream)
     EmProblem fused = p;
     fused.fused = 1;                            // (the grid of the fused form)
     hipLaunchKernelGGL(em_rows_finalize_kernel<true>, dim3((unsigned)em_final_blocks(fused)), dim3(256), 0, stream, p, parity);
+}
+
+void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, double *x_out, int n_steps,
+                           bool check_done, hipStream_t stream)
+{
+    if (tiles.n_tiles <= 0 || n_steps <= 0) return;
+    hipLaunchKernelGGL(em_local_chunk_kernel, dim3((unsigned)tiles.n_tiles), dim3(256), 0, stream, p, tiles, x_in, x_out,
+                       std::min(n_steps, EM_CHUNK_MAX), check_done ? 1 : 0);
+}
+
+void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream)
+{
+    hipLaunchKernelGGL(em_local_decide_kernel, dim3(1), dim3(64 * EM_CHUNK_MAX), 0, stream, p, tiles, first_step,
+                       std::min(n_steps, EM_CHUNK_MAX));
 }
 
 void launch_em_rows_to_acc(const EmProblem &p, hipStream_t stream)

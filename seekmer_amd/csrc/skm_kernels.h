@@ -184,6 +184,12 @@ struct EmProblem {
     // rows of a many-row transcript that have been summed in the current step (zero between steps)
     int fused;
     unsigned int *arrivals;
+    // further partials of the stopping rule, judged together with part_max / part_flags: those of the
+    // component tiles (EmTiles::step_max, step_flags) when this problem is the residual beside them --
+    // n_extra per step, the chunk's first step being number extra_first (0: none)
+    const double *extra_max;
+    const unsigned int *extra_flags;
+    int64_t n_extra, extra_first;
 };
 #ifndef SKM_EM_FINAL_BLOCKS
 #define SKM_EM_FINAL_BLOCKS 2048
@@ -200,6 +206,35 @@ void launch_em_finalize(const EmProblem &p, int parity, bool from_acc, hipStream
 // out = the result of an EM that latched after ctl[1] steps (x0 if even, x1 if odd)
 void launch_em_result(const unsigned long long *ctl, const double *x0, const double *x1, int64_t n, double *out,
                       hipStream_t stream);
+
+// ---- the EM of independent components in LDS (skm_em.hip: em_local_chunk_kernel).  One EM step couples a
+// transcript only with the transcripts it shares a class with, so the connected components of the
+// (class, transcript) graph can be stepped independently.  Consecutive components (by their smallest
+// transcript id) are packed into TILES of at most EM_TILE_PAIRS pairs, EM_TILE_CLASSES classes and
+// EM_TILE_TX transcripts; one workgroup keeps a tile's two views, `inner` and both abundance vectors in
+// LDS and runs a whole chunk of steps with workgroup barriers only.
+constexpr int EM_TILE_PAIRS = 2048, EM_TILE_CLASSES = 512, EM_TILE_TX = 128;
+constexpr int EM_TILE_SEGMENT = 128;     // tiles are packed within runs of this many transcript ids (set-up)
+constexpr int EM_CHUNK_MAX = 16;         // steps of one launch at most
+struct EmTiles {
+    int64_t n_tiles;
+    const int64_t *tile_tx;       // [n_tiles + 1] first place of tile i in tx_list
+    const int64_t *tile_cls;      // [n_tiles + 1] first place of tile i in cls_list
+    const int32_t *tx_list;       // [T] transcript ids, tile by tile (inside a tile: those of many pairs first)
+    const int32_t *cls_list;      // [C] internal class indices, tile by tile, ascending inside a tile
+    const int64_t *cls_pair;      // [C + 1] by place in cls_list: first pair of the class in cls_tx
+    const int64_t *tx_pair;       // [T + 1] by place in tx_list: first pair of the transcript in tx_cls
+    const uint16_t *cls_tx;       // [M] tile-local transcript of every pair, class-major, tuple order
+    const uint16_t *tx_cls;       // [M] tile-local class of every pair, transcript-major, internal class order
+    double *step_max;             // [EM_CHUNK_MAX][n_tiles] the tiles' partials of the stopping rule, per step
+    unsigned int *step_flags;     // [EM_CHUNK_MAX][n_tiles] bit0 = any, bit1 = nan
+};
+// n_steps (<= EM_CHUNK_MAX) steps of every tile from x_in to x_out (x_in == x_out is allowed: a tile reads
+// and writes its own transcripts only); check_done: a no-op once the control block says stopped
+void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, double *x_out, int n_steps,
+                           bool check_done, hipStream_t stream);
+// the stopping rule for steps first_step + 1 .. first_step + n_steps in order: latches the first that stops
+void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream);
 
 // ---- the EM for EM_BATCH problems of one class structure side by side (skm_em_batch.hip):
 // the bootstrap replicates.  Arrays with a replicate dimension are [item][EM_BATCH].
@@ -259,12 +294,36 @@ struct QuantBuild {
     int32_t *row_tx;              // [R]   out
     int64_t n_rows_cap;
     int64_t first_seen_bound;     // every first-seen value of the table is below this (0: unknown)
+    // the component tiles (EmTiles), built when tile_tx is given; tile_info[0] = tiles, [1] = components
+    // above the tile capacity (then the tiles are not used), both read by the host with the row count
+    int64_t *tile_tx, *tile_cls;  // [T + 2], [T + 2] out
+    int32_t *tx_list, *cls_list;  // [T], [C] out
+    int64_t *cls_pair, *tx_pair;  // [C + 1], [T + 1] out
+    uint16_t *tile_cls_tx, *tile_tx_cls;   // [M], [M] out
+    int32_t *tx_label, *tx_tile, *cls_tile;   // [T], [T], [C] out: component (smallest id), tile of each
+    int64_t tile_info[2];
 };
 // One asynchronous pipeline: classes (from a mapper's table when `table` is given, the caller's
 // order being first-seen order) in (smallest transcript id, caller's index) order for gather
 // locality, perm[k] = caller's index of internal class k -> transcript-major rows.  Returns the
 // number of rows, or < 0.
 int64_t quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipStream_t stream);
+// The components above the tile capacity as an EM problem of their own (the "residual"): their classes
+// (internal order kept, renumbered) and the rows of their transcripts, in the form em_inner_kernel and
+// em_rows_finalize_kernel take; tx_row stays indexed by transcript id (no rows for a transcript of a tile).
+// _count: counts[0] classes, [1] pairs, [2] rows (synchronises); _build: fills arrays of those sizes.
+struct QuantResidual {
+    int64_t n_classes, n_ids, n_rows;
+    int64_t *cls_offset;          // [n_classes + 1] out
+    int32_t *ids;                 // [n_ids] out
+    int32_t *cls_src;             // [n_classes] out: internal class index (where the count comes from)
+    int64_t *row_start;           // [n_rows + 1] out
+    int32_t *row_tx;              // [n_rows] out
+    int32_t *tx_cls;              // [n_ids] out: residual class index
+    int64_t *tx_row;              // [T + 1] out
+};
+int quant_residual_count(const QuantBuild &q, int64_t counts[3], hipStream_t stream);
+int quant_residual_build(const QuantBuild &q, QuantResidual &r, hipStream_t stream);
 // y[k] = x[perm[k]] (gather) or y[perm[k]] = x[k] (scatter), n doubles
 void launch_permute_f64(const double *x, const int32_t *perm, int64_t n, double *y, bool scatter,
                         hipStream_t stream);

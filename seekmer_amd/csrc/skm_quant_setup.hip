@@ -723,6 +723,316 @@ int transpose(Scratch &scratch, QuantBuild &q)
     return 0;
 }
 
+// ---- connected components of the (class, transcript) graph and their tiles (EmTiles, skm_kernels.h)
+// Union-find over the transcripts with the smaller id as the parent, so that a component's root -- its
+// label -- is its smallest transcript id whatever the order of the hooks.  A hook is one compare-and-swap
+// on a ROOT (a word that still points to itself); the walks read with plain loads: what they may miss
+// of another workgroup's hooks only costs a failed swap, which returns the current parent.
+__device__ __forceinline__ int32_t cc_root(const int32_t *parent, int32_t v)
+{
+    int32_t p;
+    while ((p = parent[v]) != v) v = p;
+    return v;
+}
+
+// The same walk while the hooks are being made, halving the path it walks: a node two or more steps
+// from the top is re-pointed to its grandparent with an atomic minimum.  Parents only ever get smaller
+// and only ever name an ancestor, so the minimum keeps both; it never touches a root (a root has no
+// grandparent), so the hooks' compare-and-swap still sees every root as it is.  Without it a table whose
+// classes form one long chain walked O(transcripts) per hook.
+__device__ __forceinline__ int32_t cc_root_halving(int32_t *parent, int32_t v)
+{
+    int32_t p = parent[v];
+    while (p != v) {
+        const int32_t g = parent[p];
+        if (g != p) atomicMin(&parent[v], g);
+        v = p;
+        p = g;
+    }
+    return v;
+}
+
+// (one lane per class; several lanes per class put more swaps in flight on the same few roots and were
+// slower: DESIGN.md, "The EM of independent components")
+__global__ void __launch_bounds__(256)
+cc_hook_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, int32_t *parent)
+{
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t begin = cls_offset[c], end = cls_offset[c + 1];
+        if (begin == end) continue;
+        int32_t b = cc_root_halving(parent, ids[begin]);
+        for (int64_t j = begin + 1; j < end; ++j) {
+            int32_t a = cc_root_halving(parent, ids[j]);
+            while (a != b) {                        // (a or b gets smaller every turn)
+                if (a < b) { const int32_t s = a; a = b; b = s; }
+                const int32_t old = atomicCAS(&parent[a], a, b);
+                if (old == a) break;
+                a = cc_root_halving(parent, old);
+            }
+            b = a < b ? a : b;
+        }
+    }
+}
+
+// label of every transcript; comp[3 r .. 3 r + 2] of root r: transcripts, pairs (classes: cc_classes_kernel).
+// The walks go on halving the paths (a chain of classes hooked root to root leaves paths as long as the
+// chain), and a wave adds once per root it meets, not once per transcript: on a table that is one
+// component every transcript would otherwise add to the same two words.
+__global__ void __launch_bounds__(256)
+cc_label_kernel(int32_t *parent, const int64_t *tx_row, const int64_t *row_start, int64_t n_tx,
+                int32_t *label, int32_t *comp)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; t0 < n_tx; t0 += stride) {
+        const int64_t t = t0 + lane;
+        int32_t r = -1, degree = 0;
+        if (t < n_tx) {
+            r = cc_root_halving(parent, (int32_t)t);
+            label[t] = r;
+            degree = (int32_t)(row_start[tx_row[t + 1]] - row_start[tx_row[t]]);
+        }
+        unsigned long long todo = __ballot(r >= 0);
+        while (todo) {                              // (wave-uniform: one turn per distinct root among the lanes)
+            const int leader = __ffsll((long long)todo) - 1;
+            const int32_t r0 = __shfl(r, leader, 64);
+            const bool mine = r == r0;
+            const unsigned long long same = __ballot(mine);
+            int sum = mine ? degree : 0;
+            for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+            if (lane == leader) {
+                atomicAdd(&comp[3 * (int64_t)r0], (int)__popcll(same));
+                atomicAdd(&comp[3 * (int64_t)r0 + 1], sum);
+            }
+            todo &= ~same;
+        }
+    }
+}
+
+// (a class without transcripts belongs nowhere; it is counted, and later listed, with transcript 0)
+__global__ void __launch_bounds__(256)
+cc_classes_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, const int32_t *label,
+                  int32_t *comp)
+{
+    // (classes are kept by smallest transcript id, so neighbouring lanes mostly name one component: a run
+    // of lanes with the same root adds its length once)
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; c0 < n_classes; c0 += stride) {
+        const int64_t c = c0 + lane;
+        int32_t r = -1;
+        if (c < n_classes) {
+            const int64_t begin = cls_offset[c];
+            r = label[begin < cls_offset[c + 1] ? ids[begin] : 0];
+        }
+        const int32_t before = __shfl_up(r, 1, 64);
+        const unsigned long long heads = __ballot(lane == 0 || before != r);
+        if (r >= 0 && ((heads >> lane) & 1ULL)) {
+            const unsigned long long later = lane == 63 ? 0ULL : heads >> (lane + 1);
+            const int run = later ? __ffsll((long long)later) : 64 - lane;
+            atomicAdd(&comp[3 * (int64_t)r + 2], run);
+        }
+    }
+}
+
+// One lane per run of EM_TILE_SEGMENT transcript ids: the components rooted there, in label order, go
+// into the run's tiles one after the other, a new tile whenever the next component would exceed a
+// capacity.  root_tile[r] = tile within the run, -1: not a root, -2: above the capacity by itself.
+__global__ void __launch_bounds__(256)
+tile_pack_kernel(const int32_t *__restrict__ comp, int64_t n_tx, int64_t n_segments, int32_t *__restrict__ root_tile,
+                 int64_t *__restrict__ seg_tiles, unsigned long long *__restrict__ oversize)
+{
+    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < n_segments;
+         g += (int64_t)gridDim.x * blockDim.x) {
+        int tx = 0, pairs = 0, classes = 0, n = 0;
+        const int64_t last = min(n_tx, (g + 1) * EM_TILE_SEGMENT);
+        // (the walk is serial; the sizes of eight transcripts at a time are fetched ahead of it)
+        for (int64_t t0 = g * EM_TILE_SEGMENT; t0 < last; t0 += 8) {
+            int size[24];
+#pragma unroll
+            for (int k = 0; k < 24; ++k) size[k] = 3 * t0 + k < 3 * n_tx ? comp[3 * t0 + k] : 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int64_t t = t0 + k;
+                if (t >= last) break;
+                const int c_tx = size[3 * k], c_pairs = size[3 * k + 1], c_classes = size[3 * k + 2];
+                if (c_tx == 0) { root_tile[t] = -1; continue; }
+                if (c_tx > EM_TILE_TX || c_pairs > EM_TILE_PAIRS || c_classes > EM_TILE_CLASSES) {
+                    root_tile[t] = -2;
+                    atomicAdd(oversize, 1ULL);
+                    continue;
+                }
+                if (n == 0 || tx + c_tx > EM_TILE_TX || pairs + c_pairs > EM_TILE_PAIRS ||
+                    classes + c_classes > EM_TILE_CLASSES) {
+                    ++n;
+                    tx = pairs = classes = 0;
+                }
+                tx += c_tx; pairs += c_pairs; classes += c_classes;
+                root_tile[t] = n - 1;
+            }
+        }
+        seg_tiles[g] = n;
+    }
+}
+
+// tile of every transcript (n_tx: a component above the capacity -- sorts behind every tile), and the key
+// its place in the tile's list is sorted by: the tile, then (degree_bits > 0) transcripts of many pairs
+// first -- the row phase of em_local_chunk_kernel gives a wave eight neighbours of the list at a time and
+// loops as long as the longest of them, so neighbours should be of a length; the EM's arithmetic does
+// not depend on the order of a tile's transcripts
+__global__ void __launch_bounds__(256)
+tx_tile_kernel(const int32_t *label, const int32_t *root_tile, const int64_t *seg_base, int64_t n_tx,
+               const int64_t *tx_row, const int64_t *row_start, int degree_bits, int32_t *tx_tile, int32_t *key)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tx;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t r = label[t], at = root_tile[r];
+        const int32_t tile = at < 0 ? (int32_t)n_tx : (int32_t)(seg_base[r / EM_TILE_SEGMENT] + at);
+        tx_tile[t] = tile;
+        const int64_t turns = (row_start[tx_row[t + 1]] - row_start[tx_row[t]] + 7) >> 3;     // (of an 8-lane group)
+        const int32_t longest = (1 << degree_bits) - 1;
+        key[t] = (tile << degree_bits) | (longest - (int32_t)min(turns, (int64_t)longest));
+    }
+}
+
+__global__ void __launch_bounds__(256)
+cls_tile_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, const int32_t *tx_tile,
+                int32_t *cls_tile)
+{
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t begin = cls_offset[c];
+        cls_tile[c] = tx_tile[begin < cls_offset[c + 1] ? ids[begin] : 0];
+    }
+}
+
+// first[i] = first place of tile i in a list sorted by tile, for i = 0 .. *n_tiles (whatever lies in no
+// tile -- key n_tx -- sorts last and starts at first[*n_tiles]); a tile may be empty (one of transcripts
+// that are in no class has no classes)
+__global__ void __launch_bounds__(256)
+tile_starts_kernel(const int32_t *sorted_tile, int shift, int64_t n, const int64_t *n_tiles, int64_t *first)
+{
+    const int64_t tiles = *n_tiles;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j <= n;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t lo = j == 0 ? -1 : min((int64_t)(sorted_tile[j - 1] >> shift), tiles);
+        const int64_t hi = j == n ? tiles : min((int64_t)(sorted_tile[j] >> shift), tiles);
+        for (int64_t t = lo + 1; t <= hi; ++t) first[t] = j;
+    }
+}
+
+// item list[i] sits at place i - first[tile] of its tile; len[i] = its number of pairs
+__global__ void __launch_bounds__(256)
+tile_local_tx_kernel(const int32_t *list, const int32_t *tile_sorted, int shift, const int64_t *first, const int64_t *n_tiles, int64_t n,
+                     const int64_t *tx_row, const int64_t *row_start, int32_t *local, int64_t *len)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t t = list[i];
+        local[t] = (int32_t)(i - first[min((int64_t)(tile_sorted[i] >> shift), *n_tiles)]);
+        len[i] = row_start[tx_row[t + 1]] - row_start[tx_row[t]];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+tile_local_cls_kernel(const int32_t *list, const int32_t *tile_sorted, const int64_t *first, const int64_t *n_tiles, int64_t n,
+                      const int64_t *cls_offset, int32_t *local, int64_t *len)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t c = list[k];
+        local[c] = (int32_t)(k - first[min((int64_t)tile_sorted[k], *n_tiles)]);
+        len[k] = cls_offset[c + 1] - cls_offset[c];
+    }
+}
+
+// the pairs of listed item i, from src[src_first(i) ...], renamed by `local`, to dst[dst_pair[i] ...];
+// nothing for what lies in no tile (tile == residual_tile: a local index need not fit 16 bits there)
+__global__ void __launch_bounds__(256)
+tile_fill_cls_kernel(const int32_t *cls_list, int64_t n_classes, const int64_t *cls_offset, const int32_t *ids,
+                     const int32_t *tx_local, const int64_t *cls_pair, const int32_t *cls_tile, int32_t residual_tile,
+                     uint16_t *out)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_classes;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t c = cls_list[k];
+        if (cls_tile[c] == residual_tile) continue;
+        const int64_t src = cls_offset[c], n = cls_offset[c + 1] - src, dst = cls_pair[k];
+        for (int64_t j = 0; j < n; ++j) out[dst + j] = (uint16_t)tx_local[ids[src + j]];
+    }
+}
+
+// (eight lanes per transcript: a transcript has 22 pairs on average)
+__global__ void __launch_bounds__(256)
+tile_fill_tx_kernel(const int32_t *tx_list, int64_t n_tx, const int64_t *tx_row, const int64_t *row_start,
+                    const int32_t *tx_cls, const int32_t *cls_local, const int64_t *tx_pair, const int32_t *tx_tile,
+                    uint16_t *out)
+{
+    const int sub = threadIdx.x & 7;
+    for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; i < n_tx;
+         i += ((int64_t)gridDim.x * blockDim.x) >> 3) {
+        const int32_t t = tx_list[i];
+        if (tx_tile[t] == (int32_t)n_tx) continue;
+        const int64_t src = row_start[tx_row[t]], n = row_start[tx_row[t + 1]] - src, dst = tx_pair[i];
+        for (int64_t j = sub; j < n; j += 8) out[dst + j] = (uint16_t)cls_local[tx_cls[src + j]];
+    }
+}
+
+int build_tiles(Scratch &scratch, QuantBuild &q)
+{
+    hipStream_t stream = scratch.stream;
+    const int64_t C = q.n_classes, M = q.n_ids, T = q.n_tx;
+    if (M >= (1LL << 31) || C >= (1LL << 31) || T >= (1LL << 31) - 2) return -2;
+    const int64_t n_segments = (T + EM_TILE_SEGMENT - 1) / EM_TILE_SEGMENT;
+    QB_ALLOC(parent, int32_t, T); QB_ALLOC(comp, int32_t, 3 * T); QB_ALLOC(root_tile, int32_t, T);
+    QB_ALLOC(seg_tiles, int64_t, n_segments); QB_ALLOC(seg_base, int64_t, n_segments + 1);
+    QB_ALLOC(oversize, unsigned long long, 1);
+    QB_ALLOC(iota, int32_t, std::max(T, C)); QB_ALLOC(sorted_tile, int32_t, std::max(T, C));
+    QB_ALLOC(tx_local, int32_t, T); QB_ALLOC(cls_local, int32_t, C);
+    QB_ALLOC(len, int64_t, std::max(T, C));
+    QB_TRY(hipMemsetAsync(comp, 0, 3 * T * sizeof(int32_t), stream));
+    QB_TRY(hipMemsetAsync(oversize, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, T);
+    hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, parent);
+    hipLaunchKernelGGL(cc_label_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, q.tx_row, q.row_start, T,
+                       q.tx_label, comp);
+    hipLaunchKernelGGL(cc_classes_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C,
+                       q.tx_label, comp);
+    hipLaunchKernelGGL(tile_pack_kernel, dim3(blocks_for(n_segments)), dim3(256), 0, stream, comp, T, n_segments,
+                       root_tile, seg_tiles, oversize);
+    if (exclusive_scan_with_total(scratch, seg_tiles, seg_base, n_segments)) return -1;
+    int end_bit = 1;
+    while ((1LL << end_bit) < T + 1 && end_bit < 31) ++end_bit;
+    const int degree_bits = end_bit + 5 <= 31 ? 5 : 0;
+    QB_ALLOC(tx_key, int32_t, T);
+    hipLaunchKernelGGL(tx_tile_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_label, root_tile, seg_base, T,
+                       q.tx_row, q.row_start, degree_bits, q.tx_tile, tx_key);
+    // transcripts by tile (stable: ascending ids inside a tile), then the classes the same way
+    hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(std::max(T, C))), dim3(256), 0, stream, iota, std::max(T, C));
+    if (sort_pairs(scratch, tx_key, sorted_tile, iota, q.tx_list, T, end_bit + degree_bits)) return -1;
+    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(T + 1)), dim3(256), 0, stream, sorted_tile, degree_bits, T,
+                       seg_base + n_segments, q.tile_tx);
+    hipLaunchKernelGGL(tile_local_tx_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_list, sorted_tile, degree_bits,
+                       q.tile_tx, seg_base + n_segments, T, q.tx_row, q.row_start, tx_local, len);
+    if (exclusive_scan_with_total(scratch, len, q.tx_pair, T)) return -1;
+    hipLaunchKernelGGL(cls_tile_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, q.tx_tile,
+                       q.cls_tile);
+    if (sort_pairs(scratch, q.cls_tile, sorted_tile, iota, q.cls_list, C, end_bit)) return -1;
+    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(C + 1)), dim3(256), 0, stream, sorted_tile, 0, C,
+                       seg_base + n_segments, q.tile_cls);
+    hipLaunchKernelGGL(tile_local_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, sorted_tile,
+                       q.tile_cls, seg_base + n_segments, C, q.cls_offset, cls_local, len);
+    if (exclusive_scan_with_total(scratch, len, q.cls_pair, C)) return -1;
+    hipLaunchKernelGGL(tile_fill_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, C, q.cls_offset,
+                       q.ids, tx_local, q.cls_pair, q.cls_tile, (int32_t)T, q.tile_cls_tx);
+    hipLaunchKernelGGL(tile_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_list, T, q.tx_row,
+                       q.row_start, q.tx_cls, cls_local, q.tx_pair, q.tx_tile, q.tile_tx_cls);
+    QB_TRY(hipMemcpyAsync(&q.tile_info[0], seg_base + n_segments, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    QB_TRY(hipMemcpyAsync(&q.tile_info[1], oversize, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    return 0;
+}
+
 }  // namespace
 
 // The whole setup as one asynchronous pipeline on `stream`: classes from the mapper's table (when
@@ -745,6 +1055,7 @@ int64_t quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipSt
                 if (localize(scratch, q, perm)) return -1;
             }
             if (transpose(scratch, q)) return -1;
+            if (q.tile_tx && build_tiles(scratch, q)) return -1;
             QB_TRY(hipGetLastError());
             QB_TRY(hipMemcpyAsync(&n_rows, q.tx_row + q.n_tx, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
         }                              // ~Scratch: the synchronisation
@@ -752,6 +1063,120 @@ int64_t quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipSt
         return n_rows;
     }
     return -1;
+}
+
+// ---- the residual: the components above the tile capacity as an EM problem of their own ---------
+namespace {
+
+// counts[0] classes, [1] pairs, [2] rows of the components above the capacity (tile == n_tx)
+__global__ void __launch_bounds__(256)
+residual_count_kernel(const int32_t *cls_tile, const int64_t *cls_offset, int64_t n_classes, const int32_t *tx_tile,
+                      const int64_t *tx_row, int64_t n_tx, unsigned long long *counts)
+{
+    unsigned long long classes = 0, pairs = 0, rows = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < max(n_classes, n_tx);
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < n_classes && cls_tile[i] == (int32_t)n_tx) { ++classes; pairs += cls_offset[i + 1] - cls_offset[i]; }
+        if (i < n_tx && tx_tile[i] == (int32_t)n_tx) rows += tx_row[i + 1] - tx_row[i];
+    }
+    if (classes) atomicAdd(&counts[0], classes);
+    if (pairs) atomicAdd(&counts[1], pairs);
+    if (rows) atomicAdd(&counts[2], rows);
+}
+
+// keep[c] = class c is residual; len[c] = its pairs if so
+__global__ void __launch_bounds__(256)
+residual_class_sizes_kernel(const int32_t *cls_tile, const int64_t *cls_offset, int64_t n_classes, int32_t residual_tile,
+                            int64_t *keep, int64_t *len)
+{
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        const bool mine = cls_tile[c] == residual_tile;
+        keep[c] = mine ? 1 : 0;
+        len[c] = mine ? cls_offset[c + 1] - cls_offset[c] : 0;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+residual_tx_sizes_kernel(const int32_t *tx_tile, const int64_t *tx_row, const int64_t *row_start, int64_t n_tx,
+                         int64_t *rows, int64_t *len)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tx;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const bool mine = tx_tile[t] == (int32_t)n_tx;
+        rows[t] = mine ? tx_row[t + 1] - tx_row[t] : 0;
+        len[t] = mine ? row_start[tx_row[t + 1]] - row_start[tx_row[t]] : 0;
+    }
+}
+
+// residual class rank[c] <- class c: its tuple and where its count comes from
+__global__ void __launch_bounds__(256)
+residual_fill_cls_kernel(const int32_t *cls_tile, int64_t n_classes, int32_t residual_tile, const int64_t *rank,
+                         const int64_t *cls_offset, const int32_t *ids, const int64_t *new_offset,
+                         int64_t *out_offset, int32_t *out_ids, int32_t *out_src, int64_t n_residual)
+{
+    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
+         c += (int64_t)gridDim.x * blockDim.x) {
+        if (cls_tile[c] != residual_tile) continue;
+        const int64_t k = rank[c], src = cls_offset[c], n = cls_offset[c + 1] - src, dst = new_offset[c];
+        out_offset[k] = dst;
+        if (k == n_residual - 1) out_offset[n_residual] = dst + n;
+        out_src[k] = (int32_t)c;
+        for (int64_t j = 0; j < n; ++j) out_ids[dst + j] = ids[src + j];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+residual_fill_tx_kernel(const int32_t *tx_tile, int64_t n_tx, const int64_t *tx_row, const int64_t *row_start,
+                        const int32_t *tx_cls, const int64_t *rank, const int64_t *new_pair, int32_t *out)
+{
+    const int sub = threadIdx.x & 7;
+    for (int64_t t = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; t < n_tx;
+         t += ((int64_t)gridDim.x * blockDim.x) >> 3) {
+        if (tx_tile[t] != (int32_t)n_tx) continue;
+        const int64_t src = row_start[tx_row[t]], n = row_start[tx_row[t + 1]] - src, dst = new_pair[t];
+        for (int64_t j = sub; j < n; j += 8) out[dst + j] = (int32_t)rank[tx_cls[src + j]];
+    }
+}
+
+}  // namespace
+
+int quant_residual_count(const QuantBuild &q, int64_t counts[3], hipStream_t stream)
+{
+    Scratch scratch(stream);
+    QB_ALLOC(sums, unsigned long long, 3);
+    QB_TRY(hipMemsetAsync(sums, 0, 3 * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(residual_count_kernel, dim3(blocks_for(std::max(q.n_classes, q.n_tx))), dim3(256), 0, stream,
+                       q.cls_tile, q.cls_offset, q.n_classes, q.tx_tile, q.tx_row, q.n_tx, sums);
+    QB_TRY(hipGetLastError());
+    QB_TRY(hipMemcpyAsync(counts, sums, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    QB_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int quant_residual_build(const QuantBuild &q, QuantResidual &r, hipStream_t stream)
+{
+    Scratch scratch(stream);
+    const int64_t C = q.n_classes, T = q.n_tx;
+    QB_ALLOC(keep, int64_t, C); QB_ALLOC(rank, int64_t, C + 1);
+    QB_ALLOC(len, int64_t, std::max(C, T)); QB_ALLOC(new_offset, int64_t, C + 1);
+    QB_ALLOC(rows, int64_t, T); QB_ALLOC(new_pair, int64_t, T + 1);
+    hipLaunchKernelGGL(residual_class_sizes_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_tile, q.cls_offset, C,
+                       (int32_t)T, keep, len);
+    if (exclusive_scan_with_total(scratch, keep, rank, C)) return -1;
+    if (exclusive_scan_with_total(scratch, len, new_offset, C)) return -1;
+    hipLaunchKernelGGL(residual_fill_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_tile, C, (int32_t)T, rank,
+                       q.cls_offset, q.ids, new_offset, r.cls_offset, r.ids, r.cls_src, r.n_classes);
+    hipLaunchKernelGGL(residual_tx_sizes_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_tile, q.tx_row,
+                       q.row_start, T, rows, len);
+    if (exclusive_scan_with_total(scratch, rows, r.tx_row, T)) return -1;
+    if (exclusive_scan_with_total(scratch, len, new_pair, T)) return -1;
+    hipLaunchKernelGGL(row_fill_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, new_pair, r.tx_row, T, r.n_ids,
+                       r.row_start, r.row_tx);
+    hipLaunchKernelGGL(residual_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_tile, T, q.tx_row,
+                       q.row_start, q.tx_cls, rank, new_pair, r.tx_cls);
+    QB_TRY(hipGetLastError());
+    return 0;
 }
 
 const char *quant_setup_failure() { return g_setup_failure; }

@@ -212,14 +212,32 @@ class _QuantHandle:
             map_result._handle, n_tx, ctypes.byref(out)))
         return cls(out, n_tx, map_result.sizes()[0])
 
-    def em(self, x, l, fixed_iters=0, max_iters=0):
+    def em(self, x, l, fixed_iters=0, max_iters=0, rel_tol=REL_TOL, x_floor=X_FLOOR):
         x = numpy.array(x, dtype='f8', copy=True, order='C')
         l = numpy.ascontiguousarray(l, dtype='f8')
         iters = ctypes.c_int64()
         _native.check(_native.hip().skm_quant_em(
             self.handle, _native.ptr(x, _native.c_f64p), _native.ptr(l, _native.c_f64p),
-            REL_TOL, X_FLOOR, max_iters, fixed_iters, ctypes.byref(iters)))
+            rel_tol, x_floor, max_iters, fixed_iters, ctypes.byref(iters)))
         return x, iters.value
+
+    def components(self, arrays=True):
+        """The connected components of the class table and the tiles the one-GPU EM steps them in:
+        (info, tx_label, tx_tile, class_tile); info as skm_quant_components documents it."""
+        raw = numpy.zeros(8, dtype=numpy.int64)
+        _native.check(_native.hip().skm_quant_components(self.handle, _native.ptr(raw, _native.c_i64p),
+                                                         None, None, None))
+        info = {'built': bool(raw[0]), 'tiles': int(raw[1]), 'oversize': int(raw[2]), 'em_uses_tiles': bool(raw[3]),
+                'capacity': (int(raw[4]), int(raw[5]), int(raw[6]))}
+        if not arrays or not info['built']:
+            return info, None, None, None
+        label = numpy.zeros(self.n_tx, dtype=numpy.int32)
+        tile = numpy.zeros(self.n_tx, dtype=numpy.int32)
+        class_tile = numpy.zeros(max(self.n_classes, 1), dtype=numpy.int32)
+        _native.check(_native.hip().skm_quant_components(
+            self.handle, _native.ptr(raw, _native.c_i64p), _native.ptr(label, _native.c_i32p),
+            _native.ptr(tile, _native.c_i32p), _native.ptr(class_tile, _native.c_i32p)))
+        return info, label, tile, class_tile[:self.n_classes]
 
     def set_counts(self, counts):
         counts = numpy.ascontiguousarray(counts, dtype='f8')
