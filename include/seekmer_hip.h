@@ -337,6 +337,29 @@ int skm_quant_bootstrap_share_tpm(skm_quant *quant, int64_t n_boot, int64_t firs
                                   int64_t *iters_out);
 /* EM with externally supplied class counts (parity of the bootstrap EM leg). */
 int skm_quant_set_counts(skm_quant *quant, const double *class_counts);
+/* K EM problems on the handle's class structure that differ in their class counts only: counts[K][C]
+ * (host, the caller's class order), the common start vector x0[n_tx] and effective lengths l[n_tx];
+ * out[K][n_tx] = the raw EM results, or with tpm != 0 the vectors quantify() makes of them
+ * (seekmer/infer.py:127-129); iters_out[K] (optional) the steps of each.  Eight problems run side by
+ * side and a place is refilled when its problem stops; every result and step count is bit for bit what
+ * skm_quant_set_counts + skm_quant_em give for that count vector, whatever its neighbours are.  The
+ * handle holds its own counts again afterwards.  SKM_ERR_UNDEFINED when a problem leaves no abundance
+ * above x_floor; SKM_ERR_STATE with a communicator of several ranks attached (with one of one rank the
+ * problems run one by one); n_sets == 0 does nothing. */
+int skm_quant_em_many(skm_quant *quant, int64_t n_sets, const double *counts, const double *x0,
+                      const double *l, double rel_tol, double x_floor, int tpm, double *out,
+                      int64_t *iters_out);
+/* The second round of impute (seekmer/impute.py:101-108, 229-252) as such a set of problems: the
+ * handle holds the concatenation of all cells' classes with their OWN counts; class_cell[C] = the cell
+ * a class came from, weight[n_cells][n_cells] row-major, cell_total[n_cells] = each cell's own count
+ * sum.  Problem i = the table blended for cell i: class k counts ((own[k] * weight[i][class_cell[k]])
+ * * cell_total[i]) / cell_total[class_cell[k]], made on the device.  counts_out (optional,
+ * [n_cells][C], the caller's class order) returns the blended counts.  SKM_ERR_ARG also for a
+ * class_cell value outside [0, n_cells).  Otherwise as skm_quant_em_many. */
+int skm_quant_em_blend(skm_quant *quant, int64_t n_cells, const int32_t *class_cell,
+                       const double *weight, const double *cell_total, const double *x0,
+                       const double *l, double rel_tol, double x_floor, int tpm, double *out,
+                       int64_t *iters_out, double *counts_out);
 /* The connected components of the (class, transcript) graph and the tiles the one-GPU EM steps them in
  * (diagnostics, tests).  info[0] = tiles were built, [1] = tiles, [2] = components above the tile capacity
  * (any: the EM steps the whole table as one problem), [3] = the EM of this handle runs on the tiles,

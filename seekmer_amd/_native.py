@@ -119,6 +119,10 @@ HIP_SYMBOLS = {
                                                      c_f64p, ctypes.c_double, ctypes.c_double, c_i64,
                                                      c_f64p, c_i64p]),
     'skm_quant_set_counts': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
+    'skm_quant_em_many': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_f64p, c_f64p, c_f64p, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_int, c_f64p, c_i64p]),
+    'skm_quant_em_blend': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, c_f64p, c_i64p, c_f64p]),
     'skm_quant_timing': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_quant_components': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i32p, c_i32p]),
     'skm_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),

@@ -296,12 +296,13 @@ struct skm_quant {
     DBuf<unsigned long long> ctl, cum;
     DBuf<unsigned int> tile_total;            // scratch of the tiled multinomial draw
     DBuf<double> x_start, boot_out;           // bootstrap: the common start vector, the replicates' results
-    // working set of the batched EM (skm_em_batch.hip): eight bootstrap replicates side by side
+    // working set of the batched EM (skm_em_batch.hip): eight problems of this class structure side by side
     struct Batch {
         DBuf<double> cls_count, inner, row_sum, x0, x1, part_max;
         DBuf<unsigned int> part_flags;
         DBuf<unsigned long long> ctl, mgr;
-        DBuf<double> counts_all;              // [group][C] pre-drawn class counts of a group of replicates
+        DBuf<double> counts_all;              // [group][C] class counts of a group of problems (internal class order)
+        DBuf<double> totals;                  // [group][2] their sums (pairs, as launch_np_sum_many leaves them)
         DBuf<int64_t> iters;                  // [group] their step counts
     } batch;
     // the component tiles of the class table (EmTiles, skm_kernels.h): built with the class views
@@ -2803,71 +2804,58 @@ extern "C" int skm_quant_set_counts(skm_quant *q, const double *class_counts)
 }
 
 namespace {
-// Replicate b of the call (b = 0 .. n_boot - 1) is replicate number rep_first + b * rep_step of the
-// `-b N` run: its draw depends on (seed, that number) alone, so a rank's share of the replicates
-// gives the same results as the one-GPU loop, replicate by replicate.
-int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0,
-                   const double *l, double rel_tol, double x_floor, int64_t max_iters,
-                   double *out, int64_t *counts_out, int64_t *iters_out, bool tpm,
-                   int64_t rep_first = 0, int64_t rep_step = 1)
+
+// ---- many EM problems on ONE class structure: the group loop that `-b N` (bootstrap_impl), K count
+// vectors of the caller's (skm_quant_em_many) and the second round of `impute` (skm_quant_em_blend)
+// share.  The callers differ in where a problem's class counts come from, and say so with
+//     fill(first, n, rows, totals): queue on the handle's stream whatever leaves rows[i][C] (device,
+//     INTERNAL class order) = the class counts of problems first + i, i < n, and totals[2 i] (device;
+//     pairs, as launch_np_sum_many leaves them) = their sums as numpy adds them up in the caller's order.
+// Problem b starts from x0, runs the EM of seekmer/infer.py:133-168 to its stopping rule and leaves
+// out[b][T]: the raw result, or with `tpm` what quantify() makes of it (infer.py:127-129).  The caller
+// holds q->mu, has set the device and has checked its arguments; C > 0.  On every exit the handle
+// holds the class counts and the total it came with.
+//   batched: EM_BATCH problems side by side with the device refilling the places (skm_em_batch.hip);
+//   otherwise (resampled counts wanted, a step cap set, a communicator attached: its collectives
+//   must stay matched) one problem after the other through the single-problem EM.
+//   slot_cap > 0 (tests): at most that many problems per group.
+template <class Fill>
+int em_group_run(skm_quant *q, int64_t n_problems, Fill &&fill, bool batched, int64_t slot_cap, const double *x0,
+                 const double *l, double rel_tol, double x_floor, int64_t max_iters, double *out, int64_t *iters_out,
+                 bool tpm)
 {
-    if (!q || !x0 || !l || !out || n_boot < 0 || rep_first < 0 || rep_step < 1) return fail(SKM_ERR_ARG, "bad argument");
-    std::lock_guard<std::mutex> lock(q->mu);
-    SKM_TRY(set_device(q->device));
-    // (seekmer/infer.py:108-111 resamples the table of the WHOLE sample: a handle that holds one
-    // rank's share of the classes -- a communicator of several ranks attached -- cannot)
-    if (q->comm && q->world > 1)
-        return fail(SKM_ERR_STATE, "bootstraps resample the merged class table: detach the communicator "
-                                   "(skm_quant_set_comm(quant, NULL)) and give every rank the merged table");
-    auto number = [&](int64_t b) { return (uint64_t)(rep_first + b * rep_step); };
-    const int64_t C = q->n_classes;
-    if (C == 0) return fail(SKM_ERR_STATE, "no classes to resample");
-    // integer cumulative counts of the observed table
+    const int64_t C = q->n_classes, T = q->n_tx;
+    skm_quant::Batch &w = q->batch;
+    // the problems' results stay in HBM and come back in groups (one copy per group, not one per problem)
+    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(n_problems, (int64_t)(1LL << 28) / T));
+    const int64_t by_counts = std::max<int64_t>(1, (int64_t)((1LL << 31) / (8 * std::max<int64_t>(C, 1))));
+    int64_t slots = batched ? std::max<int64_t>(1, std::min(group, by_counts)) : 1;
+    if (slot_cap > 0) slots = std::min(slots, slot_cap);
     SKM_TRY(q->cls_count_saved.ensure(C));
-    SKM_TRY(q->cum.ensure(C));
-    SKM_TRY(q->tile_total.ensure(4096));
-    HIP_TRY(hipMemcpyAsync(q->cls_count_saved.p, q->cls_count.p, C * 8, hipMemcpyDeviceToDevice, q->stream));
-    std::vector<double> cnt(C);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), q->cls_count.p, C * 8, hipMemcpyDeviceToHost, q->stream));
-    HIP_TRY(hipStreamSynchronize(q->stream));
-    std::vector<unsigned long long> cum(C);
-    unsigned long long run = 0;
-    for (int64_t c = 0; c < C; ++c) { run += (unsigned long long)cnt[c]; cum[c] = run; }
-    if (run >= (1ULL << 32)) return fail(SKM_ERR_STATE, "more than 2^32 - 1 units to resample");
-    const int64_t T = q->n_tx;
-    // the replicates' results stay in HBM and come back in groups (one copy per group, not one per replicate)
-    const int64_t group = std::max<int64_t>(1, std::min<int64_t>(n_boot, (int64_t)(1LL << 28) / T));
     SKM_TRY(q->x_start.ensure(T));
-    SKM_TRY(q->boot_out.ensure((size_t)(group * T)));
-    HIP_TRY(hipMemcpyAsync(q->cum.p, cum.data(), C * 8, hipMemcpyHostToDevice, q->stream));
+    SKM_TRY(q->boot_out.ensure((size_t)(slots * T)));
+    SKM_TRY(w.totals.ensure((size_t)(2 * slots)));
+    HIP_TRY(hipMemcpyAsync(q->cls_count_saved.p, q->cls_count.p, C * 8, hipMemcpyDeviceToDevice, q->stream));
     HIP_TRY(hipMemcpyAsync(q->eff_len.p, l, T * 8, hipMemcpyHostToDevice, q->stream));
     HIP_TRY(hipMemcpyAsync(q->x_start.p, x0, T * 8, hipMemcpyHostToDevice, q->stream));
     const double saved_total = q->n_total;
-    const int64_t n_draws = (int64_t)run;            // n = class_count.sum(), infer.py:109
     int rc = SKM_OK;
     DBuf<double> sums;                               // (before `restore`: freed after the stream has drained)
-    auto restore = on_exit([&]() {                   // every exit: the handle holds the observed counts again
+    auto restore = on_exit([&]() {                   // every exit: the handle holds its own counts again
         (void)hipMemcpyAsync(q->cls_count.p, q->cls_count_saved.p, C * 8, hipMemcpyDeviceToDevice, q->stream);
         (void)hipStreamSynchronize(q->stream);
         q->n_total = saved_total;
     });
-    // One replicate the careful way (host-checked chunks of the single-problem EM): draw, EM from
-    // x_start, result to `dst` (HBM).
-    auto replicate_checked = [&](int64_t b, int64_t *it_out, double *dst) -> int {
-        if (!launch_multinomial(q->cum.p, C, n_draws, seed, number(b), q->tile_total.p, q->cls_count.p, 1, q->stream))
-            return fail(SKM_ERR_STATE, "class table too large to resample (%lld classes)", (long long)C);
+    // One problem the careful way (host-checked chunks of the single-problem EM): its counts straight
+    // into the handle's, EM from x_start, result to `dst` (HBM).
+    auto problem_checked = [&](int64_t b, int64_t *it_out, double *dst) -> int {
+        SKM_TRY(fill(b, (int64_t)1, q->cls_count.p, w.totals.p));
         HIP_TRY(hipGetLastError());
-        if (counts_out) {
-            // internal (locality) class order -> caller's order; the counts fit a double exactly
-            SKM_TRY(q->inner.ensure(C));
-            launch_permute_f64(q->cls_count.p, q->perm.p, C, q->inner.p, true, q->stream);
-            std::vector<double> as_double(C);
-            HIP_TRY(hipMemcpyAsync(as_double.data(), q->inner.p, C * 8, hipMemcpyDeviceToHost, q->stream));
-            HIP_TRY(hipStreamSynchronize(q->stream));
-            for (int64_t c = 0; c < C; ++c) counts_out[b * C + c] = (int64_t)as_double[c];
-        }
+        double total = 0.0;
+        HIP_TRY(hipMemcpyAsync(&total, w.totals.p, 8, hipMemcpyDeviceToHost, q->stream));
         HIP_TRY(hipMemcpyAsync(q->x0.p, q->x_start.p, T * 8, hipMemcpyDeviceToDevice, q->stream));
-        q->n_total = (double)n_draws;
+        HIP_TRY(hipStreamSynchronize(q->stream));
+        q->n_total = total;
         SKM_TRY(em_run(q, rel_tol, x_floor, max_iters, 0, it_out, 8));
         HIP_TRY(hipMemcpyAsync(dst, (*it_out & 1) ? q->x1.p : q->x0.p, T * 8, hipMemcpyDeviceToDevice, q->stream));
         if (iters_out) iters_out[b] = *it_out;
@@ -2878,7 +2866,7 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
         if (!tpm || count <= 0) return SKM_OK;
         const int64_t n_blocks = (T + 8191) / 8192;
         SKM_TRY(sums.ensure((size_t)(count * (n_blocks + 2))));
-        double *const totals = sums.p + count * n_blocks;            // (sum, sum / 1e6) per replicate
+        double *const totals = sums.p + count * n_blocks;            // (sum, sum / 1e6) per problem
         launch_np_sum_many(results, T, count, T, 1000000.0, sums.p, totals, q->stream);
         launch_divide_many(results, T, count, T, totals + 1, true, 0.001, q->stream);
         launch_np_sum_many(results, T, count, T, 1000000.0, sums.p, totals, q->stream);
@@ -2886,51 +2874,38 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
         HIP_TRY(hipGetLastError());
         return SKM_OK;
     };
-    auto send_home = [&](int64_t first, int64_t count) -> int {     // boot_out[0 .. count) = replicates first ..
+    auto send_home = [&](int64_t first, int64_t count) -> int {     // boot_out[0 .. count) = problems first ..
         if (count <= 0) return SKM_OK;
         SKM_TRY(scale(q->boot_out.p, count));
         HIP_TRY(hipMemcpyAsync(out + first * T, q->boot_out.p, (size_t)count * T * 8, hipMemcpyDeviceToHost, q->stream));
         HIP_TRY(hipStreamSynchronize(q->stream));
         return SKM_OK;
     };
-    // With the resampled counts wanted, a step cap set or a communicator attached (its collectives
-    // must stay matched) every replicate goes the careful way.  Otherwise EM_BATCH replicates sit side
-    // by side in the batched EM (skm_em_batch.hip) and the working set is kept full: steps are queued
-    // in short chunks; after each chunk the host reads which replicates have latched their stopping
-    // rule, takes their results, and puts the next replicates (fresh draw, the common start vector)
-    // in their places -- the others run on undisturbed.  Step counts have a long tail (most
-    // replicates of the 20 M-pair table stop near 30 steps, one in six needs 60-90): replicates
-    // that wait for the slowest of a fixed group of eight waste half the working set's steps.
-    // Every replicate still runs the single-problem EM's steps bit for bit, whoever its neighbours are.
-    const bool batched = !counts_out && !q->comm && max_iters <= 0;
     if (!batched) {
-        for (int64_t b = 0; b < n_boot; ++b) {
+        for (int64_t b = 0; b < n_problems; ++b) {
             int64_t it = 0;
-            SKM_TRY(replicate_checked(b, &it, q->boot_out.p));
+            SKM_TRY(problem_checked(b, &it, q->boot_out.p));
             SKM_TRY(send_home(b, 1));
         }
         return rc;
     }
-    // EM_BATCH replicates sit side by side in the batched EM (skm_em_batch.hip) and THE DEVICE keeps the
-    // working set full: the class counts of a whole group of replicates are drawn first (HBM has the
-    // room: 8 MB per replicate at a million classes), and after every step two small launches take
-    // the results of the replicates that have latched their stopping rule and put the next ones in
+    // EM_BATCH problems sit side by side in the batched EM (skm_em_batch.hip) and THE DEVICE keeps the
+    // working set full: the class counts of a whole group of problems are made first (HBM has the
+    // room: 8 MB per problem at a million classes), and after every step two small launches take
+    // the results of the problems that have latched their stopping rule and put the next ones in
     // their places (launch_em_batch_manage) -- no host look between steps; the host queues steps
-    // and reads now and then how many replicates have finished.  (Through round 3's first half the
+    // and reads now and then how many problems have finished.  (Through round 3's first half the
     // host looked every four steps and refilled: ~100 looks and a fifth of the phase's wall time in
     // gaps.)  Step counts have a long tail (most replicates of the 20 M-pair table stop near 30
-    // steps, one in six needs 60-90); every replicate still runs the single-problem EM's steps bit
+    // steps, one in six needs 60-90): problems that wait for the slowest of a fixed group of eight
+    // waste half the working set's steps.  Every problem still runs the single-problem EM's steps bit
     // for bit, whoever its neighbours are and whenever it starts.
-    const int64_t by_counts = std::max<int64_t>(1, (int64_t)((1LL << 31) / (8 * std::max<int64_t>(C, 1))));
-    const int64_t slots = std::max<int64_t>(1, std::min(group, by_counts));
-    SKM_TRY(q->boot_out.ensure((size_t)(slots * T)));
-    skm_quant::Batch &w = q->batch;
     SKM_TRY(w.cls_count.ensure((size_t)C * EM_BATCH)); SKM_TRY(w.inner.ensure((size_t)C * EM_BATCH));
     SKM_TRY(w.row_sum.ensure((size_t)std::max<int64_t>(q->n_rows, 1) * EM_BATCH));
     SKM_TRY(w.x0.ensure((size_t)T * EM_BATCH)); SKM_TRY(w.x1.ensure((size_t)T * EM_BATCH));
     SKM_TRY(w.part_max.ensure((size_t)EM_FINAL_BLOCKS * EM_BATCH));
     SKM_TRY(w.part_flags.ensure((size_t)EM_FINAL_BLOCKS * EM_BATCH));
-    SKM_TRY(w.ctl.ensure(32));
+    SKM_TRY(w.ctl.ensure(32 + EM_BATCH));                        // (the places' totals lie behind the control block)
     SKM_TRY(w.mgr.ensure(64));
     SKM_TRY(w.counts_all.ensure((size_t)slots * C));
     SKM_TRY(w.iters.ensure((size_t)slots));
@@ -2940,7 +2915,8 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
     p.tx_cls = q->tx_cls.p; p.tx_row = q->tx_row.p; p.eff_len = q->eff_len.p;
     p.cls_count = w.cls_count.p; p.inner = w.inner.p; p.row_sum = w.row_sum.p;
     p.x[0] = w.x0.p; p.x[1] = w.x1.p;
-    p.n_total = (double)n_draws; p.rel_tol = rel_tol; p.x_floor = x_floor;
+    p.place_total = reinterpret_cast<double *>(w.ctl.p + 32);
+    p.rel_tol = rel_tol; p.x_floor = x_floor;
     p.ctl = w.ctl.p; p.part_max = w.part_max.p; p.part_flags = w.part_flags.p;
     p.managed = 1;
     p.mgr = w.mgr.p;
@@ -2951,23 +2927,25 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
     if (const char *e = getenv("SKM_BOOTSTRAP_CHUNK")) chunk = std::max<int64_t>(1, atoll(e));   // (tests)
     unsigned long long *const look = q->pinned + 64;             // 64 + 8 words of the pinned block
     std::vector<int64_t> iters_host((size_t)slots);
-    for (int64_t w0 = 0; w0 < n_boot; w0 += slots) {
-        const int64_t n = std::min(n_boot, w0 + slots) - w0;
-        for (int64_t i = 0; i < n; ++i)
-            if (!launch_multinomial(q->cum.p, C, n_draws, seed, number(w0 + i), q->tile_total.p,
-                                    w.counts_all.p + (size_t)i * C, 1, q->stream))
-                return fail(SKM_ERR_STATE, "class table too large to resample (%lld classes)", (long long)C);
-        launch_em_batch_manage_init(p, w.mgr.p, look, n, w.counts_all.p, q->x_start.p, q->boot_out.p, q->stream);
+    std::vector<double> totals_host((size_t)(2 * slots));        // (what the tail hands to the single-problem EM)
+    for (int64_t w0 = 0; w0 < n_problems; w0 += slots) {
+        const int64_t n = std::min(n_problems, w0 + slots) - w0;
+        SKM_TRY(fill(w0, n, w.counts_all.p, w.totals.p));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(totals_host.data(), w.totals.p, (size_t)(2 * n) * 8, hipMemcpyDeviceToHost, q->stream));
+        launch_em_batch_manage_init(p, w.mgr.p, look, n, w.counts_all.p, w.totals.p, q->x_start.p, q->boot_out.p, q->stream);
         HIP_TRY(hipGetLastError());
         for (int64_t k = 0;;) {
             for (int64_t i = 0; i < chunk; ++i, ++k) {
                 launch_em_batch_step(p, k, q->stream);        // (its first kernel also plans for what has stopped)
-                launch_em_batch_manage(p, w.mgr.p, w.counts_all.p, q->x_start.p, q->boot_out.p, w.iters.p, k, true, q->stream);
+                launch_em_batch_manage(p, w.mgr.p, w.counts_all.p, w.totals.p, q->x_start.p, q->boot_out.p, w.iters.p, k, true,
+                                       q->stream);
             }
             // before the host looks, the last pass is judged too (otherwise only the next step's first
             // kernel would) and what it stops is taken: a place that is still occupied then is running
             launch_em_batch_decide(p, k, q->stream);
-            launch_em_batch_manage(p, w.mgr.p, w.counts_all.p, q->x_start.p, q->boot_out.p, w.iters.p, k - 1, false, q->stream);
+            launch_em_batch_manage(p, w.mgr.p, w.counts_all.p, w.totals.p, q->x_start.p, q->boot_out.p, w.iters.p, k - 1, false,
+                                   q->stream);
             q->launches += 4 * chunk + 3;
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(look, w.mgr.p, 24 * 8, hipMemcpyDeviceToHost, q->stream));
@@ -2975,9 +2953,9 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
             HIP_TRY(hipStreamSynchronize(q->stream));
             if (look[3])
                 return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
-            if (look[24]) break;                                 // every replicate of the group has finished
-            if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the bootstrap EM does not stop");
-            // The tail: nothing left to put in, a few replicates still running.  A step of the
+            if (look[24]) break;                                 // every problem of the group has finished
+            if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the batched EM does not stop");
+            // The tail: nothing left to put in, a few problems still running.  A step of the
             // working set costs the same however many places are live (~5 single-problem steps), so
             // the last three or fewer go on one by one in the single-problem EM, from where they are.
             int live = 0;
@@ -2989,7 +2967,7 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
                     launch_em_batch_take(p.x[k & 1], T, r, q->x0.p, q->stream);
                     launch_em_batch_take(w.cls_count.p, C, r, q->cls_count.p, q->stream);
                     HIP_TRY(hipGetLastError());
-                    q->n_total = (double)n_draws;
+                    q->n_total = totals_host[(size_t)(2 * rep)];
                     int64_t more = 0;
                     SKM_TRY(em_run(q, rel_tol, x_floor, max_iters, 0, &more, 8));
                     HIP_TRY(hipMemcpyAsync(q->boot_out.p + rep * T, (more & 1) ? q->x1.p : q->x0.p, (size_t)T * 8,
@@ -3013,7 +2991,193 @@ int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0
     return rc;
 }
 
+// Replicate b of the call (b = 0 .. n_boot - 1) is replicate number rep_first + b * rep_step of the
+// `-b N` run: its draw depends on (seed, that number) alone, so a rank's share of the replicates
+// gives the same results as the one-GPU loop, replicate by replicate.
+int bootstrap_impl(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0,
+                   const double *l, double rel_tol, double x_floor, int64_t max_iters,
+                   double *out, int64_t *counts_out, int64_t *iters_out, bool tpm,
+                   int64_t rep_first = 0, int64_t rep_step = 1)
+{
+    if (!q || !x0 || !l || !out || n_boot < 0 || rep_first < 0 || rep_step < 1) return fail(SKM_ERR_ARG, "bad argument");
+    std::lock_guard<std::mutex> lock(q->mu);
+    SKM_TRY(set_device(q->device));
+    // (seekmer/infer.py:108-111 resamples the table of the WHOLE sample: a handle that holds one
+    // rank's share of the classes -- a communicator of several ranks attached -- cannot)
+    if (q->comm && q->world > 1)
+        return fail(SKM_ERR_STATE, "bootstraps resample the merged class table: detach the communicator "
+                                   "(skm_quant_set_comm(quant, NULL)) and give every rank the merged table");
+    auto number = [&](int64_t b) { return (uint64_t)(rep_first + b * rep_step); };
+    const int64_t C = q->n_classes;
+    if (C == 0) return fail(SKM_ERR_STATE, "no classes to resample");
+    // integer cumulative counts of the observed table
+    SKM_TRY(q->cum.ensure(C));
+    SKM_TRY(q->tile_total.ensure(4096));
+    SKM_TRY(q->inner.ensure(C));
+    std::vector<double> cnt(C);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), q->cls_count.p, C * 8, hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    std::vector<unsigned long long> cum(C);
+    unsigned long long run = 0;
+    for (int64_t c = 0; c < C; ++c) { run += (unsigned long long)cnt[c]; cum[c] = run; }
+    if (run >= (1ULL << 32)) return fail(SKM_ERR_STATE, "more than 2^32 - 1 units to resample");
+    HIP_TRY(hipMemcpyAsync(q->cum.p, cum.data(), C * 8, hipMemcpyHostToDevice, q->stream));
+    const int64_t n_draws = (int64_t)run;            // n = class_count.sum(), infer.py:109
+    // (a resample keeps the total: the same for every replicate; filled once, never changed while the
+    // call runs, so the copies out of it need no synchronisation of their own)
+    const std::vector<double> totals((size_t)(2 * std::max<int64_t>(n_boot, 1)), (double)n_draws);
+    // a group's counts: one multinomial draw per replicate, straight into its row
+    auto draw = [&](int64_t first, int64_t n, double *rows, double *totals_dev) -> int {
+        for (int64_t i = 0; i < n; ++i)
+            if (!launch_multinomial(q->cum.p, C, n_draws, seed, number(first + i), q->tile_total.p, rows + (size_t)i * C, 1,
+                                    q->stream))
+                return fail(SKM_ERR_STATE, "class table too large to resample (%lld classes)", (long long)C);
+        HIP_TRY(hipGetLastError());
+        for (int64_t i = 0; i < n && counts_out; ++i) {
+            // internal (locality) class order -> caller's order; the counts fit a double exactly
+            launch_permute_f64(rows + (size_t)i * C, q->perm.p, C, q->inner.p, true, q->stream);
+            std::vector<double> as_double(C);
+            HIP_TRY(hipMemcpyAsync(as_double.data(), q->inner.p, C * 8, hipMemcpyDeviceToHost, q->stream));
+            HIP_TRY(hipStreamSynchronize(q->stream));
+            for (int64_t c = 0; c < C; ++c) counts_out[(first + i) * C + c] = (int64_t)as_double[c];
+        }
+        HIP_TRY(hipMemcpyAsync(totals_dev, totals.data(), (size_t)(2 * n) * 8, hipMemcpyHostToDevice, q->stream));
+        return SKM_OK;
+    };
+    // With the resampled counts wanted, a step cap set or a communicator attached (its collectives
+    // must stay matched) every replicate goes the careful way.
+    const bool batched = !counts_out && !q->comm && max_iters <= 0;
+    return em_group_run(q, n_boot, draw, batched, 0, x0, l, rel_tol, x_floor, max_iters, out, iters_out, tpm);
+}
+
+// Rows of class counts in the caller's order, `produce`d piece by piece into a staging buffer, on their
+// way into a group of em_group_run: the sum of each row as numpy adds it up (what skm_quant_set_counts
+// computes on the host), then the row in the internal (locality) class order.  A piece is at most
+// 256 MB, so neither side holds a second copy of a whole group and the caller's rows need not be
+// page-locked.  The staging buffers belong to the call (ManyStage: sized before anything is queued, given
+// back to the pool when the call ends), not to the handle, which may live long (infer._quant_for).
+int64_t many_piece(int64_t n_classes, int64_t n_rows)
+{
+    return std::max<int64_t>(1, std::min<int64_t>(n_rows, (int64_t)(1LL << 25) / std::max<int64_t>(n_classes, 1)));
+}
+
+struct ManyStage {
+    DBuf<double> rows, sums;
+    int reserve(int64_t n_classes, int64_t n_rows)
+    {
+        const int64_t piece = many_piece(n_classes, n_rows);
+        SKM_TRY(rows.ensure((size_t)(piece * n_classes)));
+        SKM_TRY(sums.ensure((size_t)(piece * ((n_classes + 8191) / 8192))));
+        return SKM_OK;
+    }
+};
+
+template <class Produce>
+int many_rows_in(skm_quant *q, ManyStage &stage, int64_t first, int64_t n, double *rows, double *totals,
+                 int64_t n_rows_of_call, Produce &&produce)
+{
+    const int64_t C = q->n_classes, piece = many_piece(C, n_rows_of_call);
+    for (int64_t i0 = 0; i0 < n; i0 += piece) {
+        const int64_t m = std::min(piece, n - i0);
+        SKM_TRY(produce(first + i0, m, stage.rows.p));
+        launch_np_sum_many(stage.rows.p, C, m, C, 1.0, stage.sums.p, totals + 2 * i0, q->stream);
+        launch_permute_rows_f64(stage.rows.p, q->perm.p, C, m, rows + (size_t)i0 * C, q->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return SKM_OK;
+}
+
+// what the two entry points below check alike, before the handle is touched
+int many_check(const skm_quant *q, int64_t n_sets, const double *x0, const double *l, const double *out, bool sources)
+{
+    if (!q || n_sets < 0) return fail(SKM_ERR_ARG, "bad argument");
+    if (n_sets > 0 && (!x0 || !l || !out || !sources)) return fail(SKM_ERR_ARG, "NULL argument");
+    return SKM_OK;
+}
+
+int many_state_check(const skm_quant *q)
+{
+    // (one rank's share of the classes is not the table the caller's counts belong to)
+    if (q->comm && q->world > 1)
+        return fail(SKM_ERR_STATE, "bootstraps resample the merged class table: detach the communicator "
+                                   "(skm_quant_set_comm(quant, NULL)) and give every rank the merged table");
+    if (q->n_classes == 0) return fail(SKM_ERR_STATE, "no classes to quantify");
+    return SKM_OK;
+}
+
+int64_t many_slot_cap()
+{
+    const char *e = getenv("SKM_EM_MANY_SLOTS");                  // (tests: several groups from a few problems)
+    return e ? std::max<int64_t>(1, atoll(e)) : 0;
+}
+
 }  // namespace
+
+extern "C" int skm_quant_em_many(skm_quant *q, int64_t n_sets, const double *counts, const double *x0, const double *l,
+                                 double rel_tol, double x_floor, int tpm, double *out, int64_t *iters_out)
+{
+    SKM_TRY(many_check(q, n_sets, x0, l, out, counts != nullptr));
+    if (n_sets == 0) return SKM_OK;                               // (nothing to do, with or without a GPU)
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    std::lock_guard<std::mutex> lock(q->mu);
+    SKM_TRY(set_device(q->device));
+    SKM_TRY(many_state_check(q));
+    const int64_t C = q->n_classes;
+    ManyStage stage;                                              // (before the guard: freed after the stream has drained)
+    SKM_TRY(stage.reserve(C, n_sets));
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(q->stream); });
+    auto upload = [&](int64_t first, int64_t m, double *stage) -> int {
+        HIP_TRY(hipMemcpyAsync(stage, counts + (size_t)first * C, (size_t)m * C * 8, hipMemcpyHostToDevice, q->stream));
+        return SKM_OK;
+    };
+    auto fill = [&](int64_t first, int64_t n, double *rows, double *totals) -> int {
+        return many_rows_in(q, stage, first, n, rows, totals, n_sets, upload);
+    };
+    return em_group_run(q, n_sets, fill, !q->comm, many_slot_cap(), x0, l, rel_tol, x_floor, 0, out, iters_out, tpm != 0);
+}
+
+extern "C" int skm_quant_em_blend(skm_quant *q, int64_t n_cells, const int32_t *class_cell, const double *weight,
+                                  const double *cell_total, const double *x0, const double *l, double rel_tol,
+                                  double x_floor, int tpm, double *out, int64_t *iters_out, double *counts_out)
+{
+    SKM_TRY(many_check(q, n_cells, x0, l, out, class_cell && weight && cell_total));
+    if (n_cells == 0) return SKM_OK;                              // (nothing to do, with or without a GPU)
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    std::lock_guard<std::mutex> lock(q->mu);
+    SKM_TRY(set_device(q->device));
+    SKM_TRY(many_state_check(q));
+    const int64_t C = q->n_classes;
+    for (int64_t k = 0; k < C; ++k)
+        if (class_cell[k] < 0 || class_cell[k] >= n_cells)
+            return fail(SKM_ERR_ARG, "class_cell[%lld] = %d outside [0, n_cells)", (long long)k, (int)class_cell[k]);
+    ManyStage stage;
+    SKM_TRY(stage.reserve(C, n_cells));
+    // what the kernel reads: the handle's own counts in the caller's class order, the class -> cell map,
+    // the weights and the cells' totals (declared before the guard: freed after the stream has drained)
+    DBuf<double> own, weight_dev, total_dev;
+    DBuf<int32_t> cell_dev;
+    SKM_TRY(own.ensure(C)); SKM_TRY(cell_dev.ensure(C));
+    SKM_TRY(weight_dev.ensure((size_t)(n_cells * n_cells))); SKM_TRY(total_dev.ensure((size_t)n_cells));
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(q->stream); });
+    launch_permute_f64(q->cls_count.p, q->perm.p, C, own.p, true, q->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cell_dev.p, class_cell, C * 4, hipMemcpyHostToDevice, q->stream));
+    HIP_TRY(hipMemcpyAsync(weight_dev.p, weight, (size_t)(n_cells * n_cells) * 8, hipMemcpyHostToDevice, q->stream));
+    HIP_TRY(hipMemcpyAsync(total_dev.p, cell_total, (size_t)n_cells * 8, hipMemcpyHostToDevice, q->stream));
+    auto blend = [&](int64_t first, int64_t m, double *stage) -> int {
+        launch_blend_counts(own.p, cell_dev.p, weight_dev.p, total_dev.p, n_cells, first, m, C, stage, q->stream);
+        HIP_TRY(hipGetLastError());
+        if (counts_out)
+            HIP_TRY(hipMemcpyAsync(counts_out + (size_t)first * C, stage, (size_t)m * C * 8, hipMemcpyDeviceToHost, q->stream));
+        return SKM_OK;
+    };
+    auto fill = [&](int64_t first, int64_t n, double *rows, double *totals) -> int {
+        return many_rows_in(q, stage, first, n, rows, totals, n_cells, blend);
+    };
+    return em_group_run(q, n_cells, fill, !q->comm, many_slot_cap(), x0, l, rel_tol, x_floor, 0, out, iters_out, tpm != 0);
+}
 
 extern "C" int skm_quant_bootstrap(skm_quant *q, int64_t n_boot, uint64_t seed, const double *x0,
                                    const double *l, double rel_tol, double x_floor, int64_t max_iters,

@@ -1,7 +1,13 @@
 // The EM of /root/reference/seekmer/infer.py:133-168 for EM_BATCH problems at once that share
-// their class structure and differ only in the class counts and the abundance vector: the
-// bootstrap replicates of `-b N` (infer.py:79-82, 108-111 -- every replicate resamples the
-// counts of the SAME class table and starts from the same estimate).
+// their class structure and differ only in the class counts (and with them the total) and the
+// abundance vector.  Three callers have problems of that shape (skm_abi.hip: em_group_run):
+//   - the bootstrap replicates of `-b N` (infer.py:79-82, 108-111 -- every replicate resamples the
+//     counts of the SAME class table and starts from the same estimate; all totals are equal),
+//   - K count vectors of the caller's on one class table (skm_quant_em_many),
+//   - the second round of `impute` (impute.py:229-252: the concatenation of all cells' classes,
+//     blended for each cell in turn -- skm_quant_em_blend; blend_counts_kernel below makes the
+//     counts where they are used).
+// "Replicate" below means any such problem.
 //
 // A single problem's step is three launches of 5-13 us that move 8 useful bytes per 64-byte
 // sector they gather (x[t] per (class, transcript) pair, inner[c] per pair the other way round),
@@ -11,10 +17,11 @@
 // eight, and there is one launch where there were eight.
 //
 // Every replicate still runs ITS OWN iteration: the additions are the single-problem kernels'
-// additions in the same order (skm_em.hip), the stopping rule (infer.py:160) is judged per
-// replicate, and a replicate that has stopped is frozen (its x is carried from buffer to buffer
-// unchanged) while the others go on, so its result and its step count are exactly what the
-// one-by-one run gives -- bit for bit (tests/test_gpu_parity.py::test_bootstrap_draw_and_em).
+// additions in the same order (skm_em.hip), its total divides its own numerators (place_total),
+// the stopping rule (infer.py:160) is judged per replicate, and a replicate that has stopped is
+// frozen (its x is carried from buffer to buffer unchanged) while the others go on, so its result
+// and its step count are exactly what the one-by-one run gives -- bit for bit
+// (tests/test_gpu_parity.py::test_bootstrap_draw_and_em, tests/test_gpu_em_many.py).
 #include "skm_kernels.h"
 
 #include <algorithm>
@@ -206,6 +213,7 @@ em_finalize_batch_kernel(EmBatchProblem p, int parity)
     double *__restrict__ x_new = p.x[parity ^ 1];
     const int r = threadIdx.x & (R - 1);
     const bool stopped = p.ctl[BCTL_DONE + r] != 0;           // this lane's replicate is frozen
+    const double n_total = p.place_total[r];                  // ... and this is the sum of its class counts
     double local_max = 0.0;
     unsigned int flags = 0;
     for (int64_t t = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / R; t < p.n_tx;
@@ -213,7 +221,7 @@ em_finalize_batch_kernel(EmBatchProblem p, int parity)
         double a = 0.0;
         for (int64_t row = p.tx_row[t]; row < p.tx_row[t + 1]; ++row) a += p.row_sum[row * R + r];
         const double before = x_old[t * R + r];
-        double v = a / p.eff_len[t] / p.n_total;                 // infer.py:158
+        double v = a / p.eff_len[t] / n_total;                   // infer.py:158
         if (v != v) v = 0.0;                                     // infer.py:159
         if (stopped) {
             x_new[t * R + r] = before;                           // a stopped replicate keeps its result
@@ -263,6 +271,7 @@ em_rows_finalize_batch_kernel(EmBatchProblem p, int parity)
     double *__restrict__ x_new = p.x[parity ^ 1];
     const int sub = threadIdx.x & 7;
     const bool stopped = p.ctl[BCTL_DONE + sub] != 0;          // this lane's replicate (r = sub) is frozen
+    const double n_total = p.place_total[sub];                 // ... and this is the sum of its class counts
     double local_max = 0.0;
     unsigned int flags = 0;
     for (int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; row < p.n_rows;
@@ -307,7 +316,7 @@ em_rows_finalize_batch_kernel(EmBatchProblem p, int parity)
                                                                        __HIP_MEMORY_SCOPE_AGENT));
             if (sub == 0) atomicExch(&p.arrivals[t], 0u);         // (for the next step)
         }
-        double v = a / eff / p.n_total;                           // infer.py:158
+        double v = a / eff / n_total;                             // infer.py:158
         if (v != v) v = 0.0;                                      // infer.py:159
         if (stopped) {
             x_new[(int64_t)t * R + sub] = before;                 // a stopped replicate keeps its result
@@ -373,11 +382,11 @@ __global__ void em_batch_assign_kernel(EmBatchProblem p, unsigned long long *mgr
 }
 
 // the plan carried out; `into` = the abundance buffer the NEXT step reads (a stopped replicate's
-// result is carried there by the finalize pass of this step)
+// result is carried there by the finalize pass of this step).  A place's total comes in with its counts.
 __global__ void __launch_bounds__(256)
 em_batch_refill_kernel(EmBatchProblem p, const unsigned long long *__restrict__ mgr, const double *__restrict__ counts_all,
-                       const double *__restrict__ x_start, double *__restrict__ out_all, double *__restrict__ into,
-                       int64_t step)
+                       const double *__restrict__ totals, const double *__restrict__ x_start, double *__restrict__ out_all,
+                       double *__restrict__ into, int64_t step)
 {
     __shared__ unsigned long long plan[2 * R];
     if (threadIdx.x < 2 * R) plan[threadIdx.x] = mgr[MGR_TAKE + threadIdx.x];     // (TAKE and PUT are adjacent)
@@ -407,6 +416,7 @@ em_batch_refill_kernel(EmBatchProblem p, const unsigned long long *__restrict__ 
             const double *counts = counts_all + (int64_t)(put - 1) * p.n_classes;
             for (int64_t c = first; c < p.n_classes; c += stride) cls_count[c * R + r] = counts[c];
             if (first < EM_FINAL_BLOCKS) { p.part_max[first * R + r] = 1e300; p.part_flags[first * R + r] = 1u; }
+            if (first == 0) p.place_total[r] = totals[2 * (put - 1)];        // (pairs: as launch_np_sum_many leaves them)
         }
     }
 }
@@ -416,6 +426,40 @@ __global__ void em_batch_ctl_kernel(unsigned long long *ctl, unsigned int idle)
 {
     const int i = threadIdx.x;
     if (i < 32) ctl[i] = (i >= BCTL_DONE && i < BCTL_DONE + R && ((idle >> (i - BCTL_DONE)) & 1u)) ? 1ULL : 0ULL;
+}
+
+// ---- the counts of a group of problems on their way into counts_all (skm_quant_em_many, _em_blend)
+//
+// The blended class counts of seekmer/impute.py:248-252 for the cells first .. first +
+// n_rows - 1, in the caller's class order: rows[i][k] = ((own[k] * weight[first + i][cell_of[k]]) *
+// total[first + i]) / total[cell_of[k]] -- numpy's `c * w * total / c.sum()` operation by operation
+// (multiply, multiply, IEEE divide; there is no addition, so nothing to contract, and the library is
+// built without fast-math).  A lane keeps its class; the rows of the group go by in blockIdx.y.
+__global__ void __launch_bounds__(256)
+blend_counts_kernel(const double *__restrict__ own, const int32_t *__restrict__ class_cell, const double *__restrict__ weight,
+                    const double *__restrict__ cell_total, int64_t n_cells, int64_t first, int64_t n_rows, int64_t n_classes,
+                    double *__restrict__ rows)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_classes; k += (int64_t)gridDim.x * blockDim.x) {
+        const double c = own[k];
+        const int32_t from = class_cell[k];
+        const double from_total = cell_total[from];
+        for (int64_t i = blockIdx.y; i < n_rows; i += gridDim.y) {
+            const double w = weight[(first + i) * n_cells + from];
+            rows[i * n_classes + k] = ((c * w) * cell_total[first + i]) / from_total;
+        }
+    }
+}
+
+// y[i][k] = x[i][perm[k]]: `n_rows` count vectors from the caller's class order to the internal one
+__global__ void __launch_bounds__(256)
+permute_rows_kernel(const double *__restrict__ x, const int32_t *__restrict__ perm, int64_t n, int64_t n_rows,
+                    double *__restrict__ y)
+{
+    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t from = perm[k];
+        for (int64_t i = blockIdx.y; i < n_rows; i += gridDim.y) y[i * n + k] = x[i * n + from];
+    }
 }
 
 inline unsigned grid_of(int64_t items, int per_block, int64_t cap = 256 * 8)
@@ -455,7 +499,8 @@ void launch_em_batch_step(const EmBatchProblem &p, int64_t step, hipStream_t str
 // the device-managed working set: set up for `n_reps` replicates (places 0 .. min(n_reps, 8) - 1 filled
 // from counts_all[0 ..]), then after every step em_batch_manage
 void launch_em_batch_manage_init(const EmBatchProblem &p, unsigned long long *mgr, unsigned long long *host, int64_t n_reps,
-                                 const double *counts_all, const double *x_start, double *out_all, hipStream_t stream)
+                                 const double *counts_all, const double *totals, const double *x_start, double *out_all,
+                                 hipStream_t stream)
 {
     for (int i = 0; i < 64; ++i) host[i] = 0;          // (64 words of page-locked memory of the caller's)
     const int filled = (int)std::min<int64_t>(n_reps, EM_BATCH);
@@ -468,18 +513,19 @@ void launch_em_batch_manage_init(const EmBatchProblem &p, unsigned long long *mg
     }
     (void)hipMemcpyAsync(mgr, host, 64 * sizeof(unsigned long long), hipMemcpyHostToDevice, stream);
     hipLaunchKernelGGL(em_batch_ctl_kernel, dim3(1), dim3(64), 0, stream, p.ctl, idle);
-    hipLaunchKernelGGL(em_batch_refill_kernel, dim3(1024), dim3(256), 0, stream, p, mgr, counts_all, x_start, out_all, p.x[0],
-                       (int64_t)-1);
+    hipLaunchKernelGGL(em_batch_refill_kernel, dim3(1024), dim3(256), 0, stream, p, mgr, counts_all, totals, x_start, out_all,
+                       p.x[0], (int64_t)-1);
 }
 
 // behind a step whose em_inner_batch has planned (p.mgr set): the refill alone; `planned` false (a
 // look between chunks, behind em_batch_decide): the plan first, as a launch of its own
-void launch_em_batch_manage(const EmBatchProblem &p, unsigned long long *mgr, const double *counts_all, const double *x_start,
-                            double *out_all, int64_t *iters_out, int64_t step, bool planned, hipStream_t stream)
+void launch_em_batch_manage(const EmBatchProblem &p, unsigned long long *mgr, const double *counts_all, const double *totals,
+                            const double *x_start, double *out_all, int64_t *iters_out, int64_t step, bool planned,
+                            hipStream_t stream)
 {
     if (!planned) hipLaunchKernelGGL(em_batch_assign_kernel, dim3(1), dim3(64), 0, stream, p, mgr, iters_out, step);
-    hipLaunchKernelGGL(em_batch_refill_kernel, dim3(1024), dim3(256), 0, stream, p, mgr, counts_all, x_start, out_all,
-                       p.x[(step + 1) & 1], step);
+    hipLaunchKernelGGL(em_batch_refill_kernel, dim3(1024), dim3(256), 0, stream, p, mgr, counts_all, totals, x_start,
+                       out_all, p.x[(step + 1) & 1], step);
 }
 
 void launch_em_batch_decide(const EmBatchProblem &p, int64_t steps_done, hipStream_t stream)
@@ -495,6 +541,21 @@ void launch_em_batch_take(const double *x, int64_t n_tx, int r, double *out, hip
 void launch_em_batch_ctl(unsigned long long *ctl, unsigned int idle, hipStream_t stream)
 {
     hipLaunchKernelGGL(em_batch_ctl_kernel, dim3(1), dim3(64), 0, stream, ctl, idle);
+}
+
+void launch_blend_counts(const double *own, const int32_t *class_cell, const double *weight, const double *cell_total,
+                         int64_t n_cells, int64_t first, int64_t n_rows, int64_t n_classes, double *rows, hipStream_t stream)
+{
+    if (n_rows <= 0 || n_classes <= 0) return;
+    hipLaunchKernelGGL(blend_counts_kernel, dim3(grid_of(n_classes, 256, 1024), (unsigned)std::min<int64_t>(n_rows, 64)),
+                       dim3(256), 0, stream, own, class_cell, weight, cell_total, n_cells, first, n_rows, n_classes, rows);
+}
+
+void launch_permute_rows_f64(const double *x, const int32_t *perm, int64_t n, int64_t n_rows, double *y, hipStream_t stream)
+{
+    if (n_rows <= 0 || n <= 0) return;
+    hipLaunchKernelGGL(permute_rows_kernel, dim3(grid_of(n, 256, 1024), (unsigned)std::min<int64_t>(n_rows, 64)), dim3(256), 0,
+                       stream, x, perm, n, n_rows, y);
 }
 
 // (skm_index_create loads every code object of the library before the first sample needs it: the first

@@ -237,7 +237,8 @@ void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const doubl
 void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream);
 
 // ---- the EM for EM_BATCH problems of one class structure side by side (skm_em_batch.hip):
-// the bootstrap replicates.  Arrays with a replicate dimension are [item][EM_BATCH].
+// the bootstrap replicates, count vectors of the caller's, the blended tables of the second round of `impute`.
+// Arrays with a replicate dimension are [item][EM_BATCH].
 constexpr int EM_BATCH = 8;
 struct EmBatchProblem {
     int64_t n_tx, n_classes, n_rows;
@@ -252,7 +253,7 @@ struct EmBatchProblem {
     double *inner;                // [C][EM_BATCH]
     double *row_sum;              // [R][EM_BATCH]
     double *x[2];                 // [T][EM_BATCH] ping-pong
-    double n_total;               // the same for every replicate (a resample keeps the total)
+    double *place_total;          // [EM_BATCH] sum of the class counts of the problem in each place (the refill writes it)
     double rel_tol, x_floor;
     // control block (32 words): [0] all stopped [1] step at which the last one stopped,
     // [8 + r] replicate r stopped, [16 + r] its step count, [24 + r] undefined (no x above x_floor)
@@ -265,16 +266,17 @@ struct EmBatchProblem {
     int fused;                    // rows and finalize are one launch (em_rows_finalize_batch_kernel)
     unsigned int *arrivals;       // [T] rows of a many-row transcript summed so far in this step (zero between steps)
 };
-// The working set kept full by the device: `mgr` is 64 words of HBM; counts_all[i][C] the pre-drawn
-// class counts of replicate i of the group, out_all[i][T] its result, iters_out[i] its step count
-// (device memory).  _init fills the first places; _manage after EVERY step takes what has stopped and
+// The working set kept full by the device: `mgr` is 64 words of HBM; counts_all[i][C] the class counts
+// of replicate i of the group (internal class order), totals[2 i] their sum (pairs, as launch_np_sum_many
+// leaves them), out_all[i][T] its result, iters_out[i] its step count (device memory).  _init fills the first places; _manage after EVERY step takes what has stopped and
 // puts the next replicates in.  ctl[0] is set once every replicate of the group has finished; mgr[2]
 // counts the finished ones, mgr[3] != 0: a replicate had no abundance above x_floor.
 void launch_em_batch_manage_init(const EmBatchProblem &p, unsigned long long *mgr, unsigned long long *host_pinned64,
-                                 int64_t n_reps, const double *counts_all, const double *x_start, double *out_all,
-                                 hipStream_t stream);
-void launch_em_batch_manage(const EmBatchProblem &p, unsigned long long *mgr, const double *counts_all, const double *x_start,
-                            double *out_all, int64_t *iters_out, int64_t step, bool planned, hipStream_t stream);
+                                 int64_t n_reps, const double *counts_all, const double *totals, const double *x_start,
+                                 double *out_all, hipStream_t stream);
+void launch_em_batch_manage(const EmBatchProblem &p, unsigned long long *mgr, const double *counts_all, const double *totals,
+                            const double *x_start, double *out_all, int64_t *iters_out, int64_t step, bool planned,
+                            hipStream_t stream);
 // one step (inner, rows, finalize); step > 0 first judges the step before it
 void launch_em_batch_step(const EmBatchProblem &p, int64_t step, hipStream_t stream);
 void launch_em_batch_decide(const EmBatchProblem &p, int64_t steps_done, hipStream_t stream);
@@ -282,6 +284,12 @@ void launch_em_batch_decide(const EmBatchProblem &p, int64_t steps_done, hipStre
 void launch_em_batch_take(const double *x, int64_t n_tx, int r, double *out, hipStream_t stream);
 // fresh control block; bit r of `idle`: place r holds no replicate and counts as stopped
 void launch_em_batch_ctl(unsigned long long *ctl, unsigned int idle, hipStream_t stream);
+// rows[i][k] (i < n_rows, caller's class order) = the blended count of class k for cell first + i:
+// ((own[k] * weight[first + i][class_cell[k]]) * cell_total[first + i]) / cell_total[class_cell[k]]
+void launch_blend_counts(const double *own, const int32_t *class_cell, const double *weight, const double *cell_total,
+                         int64_t n_cells, int64_t first, int64_t n_rows, int64_t n_classes, double *rows, hipStream_t stream);
+// y[i][k] = x[i][perm[k]] for n_rows vectors of n doubles
+void launch_permute_rows_f64(const double *x, const int32_t *perm, int64_t n, int64_t n_rows, double *y, hipStream_t stream);
 // device-side construction of the two CSR views (skm_quant_setup.hip)
 struct QuantBuild {
     int64_t n_tx, n_classes, n_ids;

@@ -8,10 +8,16 @@ cell is quantified again on the weighted blend of all cells' class tables.
 What the engine changes: the blended problem has ONE class structure (the
 concatenation of all cells' classes, impute.py:243-247) and only the class
 counts differ from cell to cell (:248-252), so its two CSR views are built on
-the GPU once and each cell's second round is `set_counts` + the EM kernels.
+the GPU once.  The second round is then many EM problems on one structure:
+the cells' blended counts are made on the device and eight cells at a time run
+side by side in the batched EM (`_QuantHandle.em_blend`), each with the steps
+and the bits of `set_counts` + the EM kernels for that cell alone -- the loop
+that SKM_IMPUTE_SERIAL=1 still selects.  The first round stays one cell at a
+time: the cells' own tables have different structures.
 The arithmetic that decides results is the reference's, cited per function.
 """
 import logging
+import os
 import pathlib
 
 import numpy
@@ -125,6 +131,16 @@ def cell_weights(index, tpm_matrix, output_path=None, seed=None):
     return weights
 
 
+def blend_structure(summaries):
+    """(offsets, targets) of the blended problem: all cells' classes one after the other."""
+    sizes = [numpy.bincount(s.class_map[0].astype(numpy.int64), minlength=s.class_count.size)
+             for s in summaries]
+    offsets = numpy.zeros(sum(s.size for s in sizes) + 1, dtype=numpy.int64)
+    numpy.cumsum(numpy.concatenate(sizes), out=offsets[1:])
+    targets = numpy.concatenate([s.class_map[1] for s in summaries]).astype(numpy.int32)
+    return offsets, targets
+
+
 def blend(summaries, weight):
     """The blended problem of seekmer/impute.py:229-252 in CSR form: (offsets,
     targets) = all cells' classes one after the other; counts[i] = for cell i
@@ -133,11 +149,7 @@ def blend(summaries, weight):
     for summary in summaries:
         if summary.class_count.size == 0:
             raise ValueError('a cell without aligned reads cannot be blended')   # max() of nothing, :241
-    sizes = [numpy.bincount(s.class_map[0].astype(numpy.int64), minlength=s.class_count.size)
-             for s in summaries]
-    offsets = numpy.zeros(sum(s.size for s in sizes) + 1, dtype=numpy.int64)
-    numpy.cumsum(numpy.concatenate(sizes), out=offsets[1:])
-    targets = numpy.concatenate([s.class_map[1] for s in summaries]).astype(numpy.int32)
+    offsets, targets = blend_structure(summaries)
     own = [s.class_count for s in summaries]
     counts = []
     for i, summary in enumerate(summaries):
@@ -146,10 +158,62 @@ def blend(summaries, weight):
     return offsets, targets, counts
 
 
+def blend_sources(summaries):
+    """What the device needs to make blend()'s counts itself: (own, class_cell, cell_total) = all
+    cells' own class counts one after the other, the cell every class of the concatenation came
+    from, and each cell's own count sum (c.sum() of blend()).  counts[i][k] of blend() is
+    ((own[k] * weight[i, class_cell[k]]) * cell_total[i]) / cell_total[class_cell[k]]."""
+    own = numpy.concatenate([s.class_count for s in summaries]).astype('f8')
+    class_cell = numpy.repeat(numpy.arange(len(summaries), dtype=numpy.int32),
+                              [s.class_count.size for s in summaries])
+    cell_total = numpy.asarray([s.class_count.sum() for s in summaries], dtype='f8')
+    return own, class_cell, cell_total
+
+
+# Where the second round takes the batched EM: the regime in which it was measured ahead of the loop over
+# the cells (DESIGN.md, "Many count vectors on one class table"; profiles/impute_many_ab.log).  Below
+# eight cells -- one full working set -- four cells took 6.9 ms batched against 6.0 ms one by one (a
+# working-set step costs about five single-problem steps and half the places are empty), eight took 10 ms
+# against 41.  The other two bounds are the largest blended structure and transcript count measured (64
+# cells x 50 k pairs on 190 402 transcripts, 2.63 M blended classes: 7.65 ms per cell against 16.5): the
+# batched EM steps the whole table, the loop's single-problem EM runs in component tiles where it can, and
+# how the two compare on larger tables is not known.
+BATCH_MIN_CELLS = 8
+BATCH_MAX_CLASSES = 3_000_000
+BATCH_MAX_TRANSCRIPTS = 200_000
+
+
 def requantify_blend(summaries, weight, device=0):
-    """quantify() of every cell's blended table (seekmer/impute.py:101-108):
-    one quantification handle for the shared class structure, the cell's counts
-    swapped in for each run."""
+    """quantify() of every cell's blended table (seekmer/impute.py:101-108): one quantification
+    handle for the shared class structure; the cells' blended counts are made on the device and the
+    cells run eight at a time in the batched EM (_QuantHandle.em_blend), bit for bit what the loop
+    over the cells gives.  That loop remains for SKM_IMPUTE_SERIAL=1, for cells whose effective
+    lengths differ (they do not after pool_fragment_lengths) and outside the regime in which the batched
+    form was measured ahead (BATCH_MIN_CELLS, BATCH_MAX_CLASSES, BATCH_MAX_TRANSCRIPTS)."""
+    lengths = [summary.effective_lengths.astype('f8') for summary in summaries]
+    if os.environ.get('SKM_IMPUTE_SERIAL') == '1' or len(summaries) < BATCH_MIN_CELLS \
+            or sum(summary.class_count.size for summary in summaries) > BATCH_MAX_CLASSES \
+            or lengths[0].size > BATCH_MAX_TRANSCRIPTS \
+            or any(not numpy.array_equal(lengths[0], other) for other in lengths[1:]):
+        return _requantify_blend_serial(summaries, weight, device)
+    for summary in summaries:
+        if summary.class_count.size == 0:
+            raise ValueError('a cell without aligned reads cannot be blended')   # max() of nothing, :241
+    offsets, targets = blend_structure(summaries)
+    own, class_cell, cell_total = blend_sources(summaries)
+    n_tx = lengths[0].size
+    x = numpy.ones(n_tx, dtype='f8') / lengths[0]                       # infer.py:116-119
+    x /= x.sum()
+    handle = infer._QuantHandle.from_csr(n_tx, offsets, targets, own, device)
+    try:
+        columns, _, _ = handle.em_blend(class_cell, numpy.asarray(weight, dtype='f8'), cell_total, x, lengths[0], tpm=True)
+    finally:
+        handle.close()
+    return list(columns)
+
+
+def _requantify_blend_serial(summaries, weight, device=0):
+    """The second round one cell at a time: the cell's counts swapped in for each run."""
     offsets, targets, counts = blend(summaries, weight)
     n_tx = summaries[0].effective_lengths.size
     handle = infer._QuantHandle.from_csr(n_tx, offsets, targets, counts[0], device)

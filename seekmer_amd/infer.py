@@ -17,7 +17,8 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'quantify', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify', 'bootstrap_ranks']
+__all__ = ['run', 'quantify', 'quantify_many', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+           'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
 
@@ -267,6 +268,47 @@ class _QuantHandle:
             _native.ptr(iters, _native.c_i64p)))
         return out, counts, iters[:n_boot]
 
+    def em_many(self, counts, x0, l, tpm=False):
+        """The EM on this handle's class structure for every row of counts [K, C] (the caller's class
+        order), all from x0: (results [K, n_tx], EM steps per row) -- what set_counts(row) + em(x0, l)
+        give, row by row and bit for bit, with eight rows side by side on the device; tpm: the results
+        already scaled as quantify() scales them (seekmer/infer.py:127-129).  The handle keeps its own counts."""
+        counts = numpy.ascontiguousarray(counts, dtype='f8')
+        if counts.ndim != 2 or counts.shape[1] != self.n_classes:
+            raise ValueError('counts must be [K, %d]' % self.n_classes)
+        x0 = numpy.ascontiguousarray(x0, dtype='f8')
+        l = numpy.ascontiguousarray(l, dtype='f8')
+        n = counts.shape[0]
+        out = numpy.zeros((n, self.n_tx), dtype='f8')
+        iters = numpy.zeros(max(n, 1), dtype=numpy.int64)
+        _native.check(_native.hip().skm_quant_em_many(
+            self.handle, n, _native.ptr(counts, _native.c_f64p), _native.ptr(x0, _native.c_f64p),
+            _native.ptr(l, _native.c_f64p), REL_TOL, X_FLOOR, int(bool(tpm)), _native.ptr(out, _native.c_f64p),
+            _native.ptr(iters, _native.c_i64p)))
+        return out, iters[:n]
+
+    def em_blend(self, class_cell, weight, cell_total, x0, l, tpm=False, want_counts=False):
+        """The second round of impute on a handle that holds all cells' classes with their own counts:
+        problem i is the table blended for cell i (skm_quant_em_blend; the counts are made on the device).
+        (results [n, n_tx], EM steps per cell, blended counts [n, C] or None)."""
+        class_cell = numpy.ascontiguousarray(class_cell, dtype=numpy.int32)
+        weight = numpy.ascontiguousarray(weight, dtype='f8')
+        cell_total = numpy.ascontiguousarray(cell_total, dtype='f8')
+        n = cell_total.size
+        if weight.shape != (n, n) or class_cell.size != self.n_classes:
+            raise ValueError('weight must be [n, n] and class_cell [C] for n = len(cell_total) cells')
+        x0 = numpy.ascontiguousarray(x0, dtype='f8')
+        l = numpy.ascontiguousarray(l, dtype='f8')
+        out = numpy.zeros((n, self.n_tx), dtype='f8')
+        iters = numpy.zeros(max(n, 1), dtype=numpy.int64)
+        counts = numpy.zeros((n, max(self.n_classes, 1)), dtype='f8') if want_counts else None
+        _native.check(_native.hip().skm_quant_em_blend(
+            self.handle, n, _native.ptr(class_cell, _native.c_i32p), _native.ptr(weight, _native.c_f64p),
+            _native.ptr(cell_total, _native.c_f64p), _native.ptr(x0, _native.c_f64p), _native.ptr(l, _native.c_f64p),
+            REL_TOL, X_FLOOR, int(bool(tpm)), _native.ptr(out, _native.c_f64p), _native.ptr(iters, _native.c_i64p),
+            _native.ptr(counts, _native.c_f64p) if want_counts else None))
+        return out, iters[:n], (counts[:, :self.n_classes] if want_counts else None)
+
     def timing(self):
         out = (ctypes.c_double * 4)()
         _native.check(_native.hip().skm_quant_timing(self.handle, out))
@@ -342,6 +384,31 @@ def quantify(results, x0=None, bootstrap=False, seed=None, fixed_iters=0, return
             quant.close()
     x = _tpm(x)
     return (x, iters) if return_iters else x
+
+
+def quantify_many(results, class_counts, device=0, return_iters=False):
+    """quantify() for K count vectors on ONE class table: `results` supplies the class structure and
+    the effective lengths, class_counts is [K, C] in the order of results.class_count.  Returns the K
+    TPM vectors ([K, n_tx]) that quantify() gives for a table with those counts -- every problem starts
+    from 1 / effective length as quantify() does (seekmer/infer.py:116-119) --, with the EM steps of each
+    when return_iters is set.  The problems run eight at a time on the device (skm_quant_em_many)."""
+    transcript_length = results.effective_lengths.astype('f8')
+    class_counts = numpy.asarray(class_counts, dtype='f8')
+    if class_counts.ndim != 2:
+        raise ValueError('class_counts must be [K, C]')
+    n = class_counts.shape[0]
+    if results.class_map.size == 0:
+        zeros = numpy.zeros((n, transcript_length.size), dtype='f8')
+        return (zeros, numpy.zeros(n, dtype=numpy.int64)) if return_iters else zeros
+    x = numpy.ones(transcript_length.size, dtype='f8') / transcript_length
+    x /= x.sum()
+    quant, owned = _quant_for(results, device)
+    try:
+        out, iters = quant.em_many(class_counts, x, transcript_length, tpm=True)
+    finally:
+        if owned:
+            quant.close()
+    return (out, iters) if return_iters else out
 
 
 def quantify_resident(map_result, comm=None, return_iters=False, return_effective_lengths=False):
