@@ -11,7 +11,8 @@
  *
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
- *                          skm_mapper_*, skm_quant_*, skm_comm_*, skm_device_*)
+ *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_comm_*,
+ *                          skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
  *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_synth_*)
  */
@@ -287,6 +288,85 @@ int skm_mapper_timing(skm_mapper *mapper, double stats[8]);
  * paths with the census and cycle sums (a profiling aid; its access counters undercount). */
 int skm_mapper_set_stats(skm_mapper *mapper, int enable);
 int skm_mapper_access_stats(skm_mapper *mapper, int64_t out[48]);
+
+/* ------------------------------------------------------------- sample sets
+ * map_multiple_samples (seekmer/mapper.py:196-234) for MANY SMALL samples -- the cells of `impute`:
+ * one handle maps the units of all its samples in shared launches into one class table in which a
+ * class is the pair (sample, target tuple), and hands back one class table per sample.
+ *
+ * Contract: every per-sample table -- classes in first-seen order, class_offsets, class_targets,
+ * counts, first-seen unit numbers counted inside the sample, the unaligned and total unit counts --
+ * is bit for bit what a skm_mapper of its own gives for that sample's reads, however the samples'
+ * segments are interleaved, cut into launches, or spread over adding threads.  Two samples that
+ * hold the same tuple keep separate classes: a record's 64-bit class key is that of (sample, tuple),
+ * and two different tuples that meet in one slot fail the call with SKM_ERR_COLLISION as they do in a
+ * mapper; counts are exact or the call fails.
+ * The FRAGMENT-LENGTH HISTOGRAM is one for the whole set: the sum over all its samples, which is
+ * what impute.pool_fragment_lengths gives every cell before anything reads it
+ * (seekmer/impute.py:128-146).  There is no per-sample histogram.
+ * The strand mode (skm_mapper_set_strand) applies to the whole set.  Read names (-m) are not kept.
+ *
+ * Samples are numbered 0, 1, ... by the caller (below 2^24); the set holds the samples 0 .. the
+ * largest number an add call has named.  A sample's reads arrive as one or more SEGMENTS, runs of
+ * consecutive units, each beginning at the unit (`first_unit`) where the sample's units added so
+ * far end: SKM_ERR_STATE otherwise.  Segments of different samples may be added in any order and
+ * from any threads; the calling thread copies the segment to HBM (the call returns when the arrays
+ * are free again) and one worker maps what is queued, at most 2^21 units a launch
+ * (SKM_SAMPLE_SET_MAX_UNITS in the environment at create: fewer, for tests), a short queue waiting
+ * for 2^15 units or for a call that reads the tables.  A segment of no units just makes the sample
+ * exist.  After a failed launch the set stays failed: every later call returns that error.
+ * A call that reads the tables (_summary with room for samples, _export) waits until every segment
+ * added before it has been mapped and keeps adders waiting while it reads, so what it returns is
+ * whole: the tables of exactly the segments added so far.  It may run while other threads add. */
+typedef struct skm_sample_set skm_sample_set;
+int skm_sample_set_create(skm_index *index, int paired, skm_sample_set **out);
+int skm_sample_set_destroy(skm_sample_set *set);
+/* only while the set holds no units (SKM_ERR_STATE otherwise) */
+int skm_sample_set_set_strand(skm_sample_set *set, int mode);
+/* Units [first_unit, first_unit + n) of `sample` as packed reads (skm_packed_reads): unit
+ * first_unit + r = read r of mate1 (+ read r of mate2 in a paired set; NULL in a single-ended one).
+ * n = mate1->n_reads = mate2->n_reads; the pieces' `stream` and `first_read` are not looked at. */
+int skm_sample_set_add_packed(skm_sample_set *set, int64_t sample, int64_t first_unit,
+                              const skm_packed_reads *mate1, const skm_packed_reads *mate2);
+/* The same for reads as text: the layout of skm_mapper_map_batch (paired: reads 2u, 2u + 1 are the
+ * mates of unit first_unit + u). */
+int skm_sample_set_add_batch(skm_sample_set *set, int64_t sample, int64_t first_unit,
+                             const char *bases, const int64_t *offsets, int64_t n_units);
+/* waits for everything added to be mapped; the set's failure, if there is one */
+int skm_sample_set_sync(skm_sample_set *set);
+/* *n_samples = samples of the set; summary[4 i .. 4 i + 3] for the samples i < min(cap_samples,
+ * *n_samples) = skm_mapper_summary of sample i: C classes, M (class, target) rows, unaligned (the
+ * sample's units minus the sum of its class counts), total units.  With cap_samples = 0 (summary
+ * may be NULL) the call only counts the samples named so far and waits for nothing. */
+int skm_sample_set_summary(skm_sample_set *set, int64_t cap_samples, int64_t *n_samples,
+                           int64_t *summary);
+/* All samples' tables one after the other: sample i owns the classes sample_class_offsets[i] ..
+ * sample_class_offsets[i + 1] (array of n_samples + 1) of class_offsets[C + 1] (one CSR over all C
+ * classes of the set), class_targets[M], class_counts[C], first_seen[C] -- the arrays of
+ * skm_mapper_export with first_seen counted inside the sample.  Any pointer may be NULL. */
+int skm_sample_set_export(skm_sample_set *set, int64_t *sample_class_offsets,
+                          int64_t *class_offsets, int32_t *class_targets, int64_t *class_counts,
+                          int64_t *first_seen);
+/* fld[2000]: the set's one histogram, summed over its samples */
+int skm_sample_set_histogram(skm_sample_set *set, int64_t *fld);
+/* DIAGNOSTICS, with no promise of stability: the set's bookkeeping on the host alone (no GPU is
+ * touched), for tests.  They run the cutting, the log and the ordering by (sample, local first
+ * seen) that the set itself runs; _split bisects the log on the host where the set does it in a
+ * kernel (sample_assign_kernel).  Not part of the interface a caller should build on.  _plan: segments
+ * (sample[i], n_units[i]) queued in this order before the first launch, cut into launches of at most
+ * max_units units as the worker cuts them -> the log the export reads: entry e says that the set's
+ * units from entry_global[e] (ascending, from 0) up to the next entry's are the units from
+ * entry_local[e] on of sample entry_sample[e].  *n_entries = entries; the arrays are filled when
+ * cap_entries holds them.  _split: such a log against the global first-seen units of C classes ->
+ * class_sample[C], class_local[C] (first seen, counted inside the sample), order[C] (the classes by
+ * sample, then by class_local: the export's order) and sample_class_offsets[n_samples + 1]. */
+int skm_sample_set_plan(int64_t n_segments, const int32_t *sample, const int64_t *n_units,
+                        int64_t max_units, int64_t cap_entries, int64_t *n_entries,
+                        int64_t *entry_global, int64_t *entry_local, int32_t *entry_sample);
+int skm_sample_set_split(int64_t n_entries, const int64_t *entry_global, const int64_t *entry_local,
+                         const int32_t *entry_sample, int64_t n_samples, int64_t n_classes,
+                         const int64_t *first_seen, int32_t *class_sample, int64_t *class_local,
+                         int64_t *order, int64_t *sample_class_offsets);
 
 /* ------------------------------------------------------------ quantification
  * MapResult.effective_lengths (seekmer/mapper.py:134-141). */

@@ -103,6 +103,19 @@ HIP_SYMBOLS = {
     'skm_mapper_set_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_access_stats': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_effective_lengths': (ctypes.c_int, [ctypes.c_int, c_i64p, c_f64p, c_i64, c_f64p]),
+    'skm_sample_set_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp]),
+    'skm_sample_set_destroy': (ctypes.c_int, [ctypes.c_void_p]),
+    'skm_sample_set_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_add_packed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(PackedReads),
+                                                 ctypes.POINTER(PackedReads)]),
+    'skm_sample_set_add_batch': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_void_p, c_i64p, c_i64]),
+    'skm_sample_set_sync': (ctypes.c_int, [ctypes.c_void_p]),
+    'skm_sample_set_summary': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p, c_i64p]),
+    'skm_sample_set_export': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i32p, c_i64p, c_i64p]),
+    'skm_sample_set_histogram': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),
+    'skm_sample_set_split': (ctypes.c_int, [c_i64, c_i64p, c_i64p, c_i32p, c_i64, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
+                                            c_i64p]),
     'skm_quant_create': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64p, c_i32p, c_f64p,
                                         c_void_pp]),
     'skm_quant_create_from_mapper': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_void_pp]),

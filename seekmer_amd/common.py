@@ -522,6 +522,10 @@ class PackedReads:
         raw.uniform_len = -1
         return cls(raw, paired=paired)
 
+    def held(self):
+        """This piece if its arrays are kept alive with it, a copy() if they belong to a reader."""
+        return self if isinstance(self._keep, tuple) or self.is_cut else self.copy()
+
     def copy(self):
         """The same piece over arrays of its own."""
         if self.is_cut:

@@ -953,10 +953,12 @@ int read_error(skm_mapper *m)
 // to continue after the units mapped so far
 // fill_records: what makes the read records of the batch (records, words per read, u32 words per
 // record); nullptr = pack_reads_kernel over ASCII bases + offsets
+// salt: the batch is a launch of a sample set -- the segments whose samples go into the records' keys
+// before class counting (skm_samples.hip); nullptr = one sample, keys as the map kernel made them
 typedef std::function<int(uint32_t *, int, int)> RecordStage;
 int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_offsets,
                        int64_t n_units, int paired, int max_len, int64_t first_unit = -1,
-                       const RecordStage *fill_records = nullptr)
+                       const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr)
 {
     const int64_t unit_base = first_unit >= 0 ? first_unit : m->units_done;
     skm_index *ix = m->ix;
@@ -1051,6 +1053,10 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     // launched unstranded)
     if (m->strand != SKM_STRAND_NONE) {
         launch_strand_filter(b, m->strand, m->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (salt) {
+        launch_sample_salt(b, *salt, m->error.p, m->stream);
         HIP_TRY(hipGetLastError());
     }
 
@@ -1283,6 +1289,35 @@ struct PackedSegment {               // part of one piece inside a run
     int64_t exc_base;                // index (relative to the piece as pushed) of the segment's first read
 };
 
+// the parts of a stream's pieces that lie in units [lo, hi), as segments of a launch
+void packed_segments(std::deque<skm_mapper::Piece> &pieces, int mate, int64_t lo, int64_t hi, bool mark_in_job,
+                     std::vector<PackedSegment> *segments, int *max_cw)
+{
+    for (auto &piece : pieces) {
+        const int64_t from = std::max(lo, piece.first), to = std::min(hi, piece.first + piece.n);
+        if (from >= to) continue;
+        if (mark_in_job) piece.in_job = true;
+        PackedSegment seg{};
+        seg.mate = mate;
+        seg.first = from;
+        seg.n = to - from;
+        const int64_t skip = from - piece.origin;
+        seg.codes = piece.codes + skip * piece.cw;
+        seg.lengths = piece.lengths ? piece.lengths + skip : nullptr;
+        seg.cw = piece.cw;
+        seg.uniform_len = (uint32_t)std::max<int64_t>(piece.uniform_len, 0);
+        const auto e0 = std::lower_bound(piece.exc_reads.begin(), piece.exc_reads.end(), (uint32_t)skip);
+        const auto e1 = std::lower_bound(piece.exc_reads.begin(), piece.exc_reads.end(), (uint32_t)(skip + seg.n));
+        seg.n_exc = e1 - e0;
+        const int64_t at = e0 - piece.exc_reads.begin();
+        seg.exc_reads = piece.exc_reads_dev + at;
+        seg.exc_masks = piece.exc_masks + at * piece.cw;
+        seg.exc_base = skip;
+        *max_cw = std::max(*max_cw, piece.cw);
+        segments->push_back(seg);
+    }
+}
+
 int run_packed_job(skm_mapper *m, int64_t lo, int64_t hi, int paired, const std::vector<PackedSegment> &segments,
                    int max_cw)
 {
@@ -1352,29 +1387,7 @@ void worker_main(skm_mapper *m)
             } else {
                 paired = m->packed_paired == 1;
                 for (int s = 0; s < (paired ? 2 : 1); ++s)
-                    for (auto &piece : m->pending[s]) {
-                        const int64_t from = std::max(lo, piece.first), to = std::min(hi, piece.first + piece.n);
-                        if (from >= to) continue;
-                        piece.in_job = true;
-                        PackedSegment seg{};
-                        seg.mate = s;
-                        seg.first = from;
-                        seg.n = to - from;
-                        const int64_t skip = from - piece.origin;
-                        seg.codes = piece.codes + skip * piece.cw;
-                        seg.lengths = piece.lengths ? piece.lengths + skip : nullptr;
-                        seg.cw = piece.cw;
-                        seg.uniform_len = (uint32_t)std::max<int64_t>(piece.uniform_len, 0);
-                        const auto e0 = std::lower_bound(piece.exc_reads.begin(), piece.exc_reads.end(), (uint32_t)skip);
-                        const auto e1 = std::lower_bound(piece.exc_reads.begin(), piece.exc_reads.end(), (uint32_t)(skip + seg.n));
-                        seg.n_exc = e1 - e0;
-                        const int64_t at = e0 - piece.exc_reads.begin();
-                        seg.exc_reads = piece.exc_reads_dev + at;
-                        seg.exc_masks = piece.exc_masks + at * piece.cw;
-                        seg.exc_base = skip;
-                        max_cw = std::max(max_cw, piece.cw);
-                        segments.push_back(seg);
-                    }
+                    packed_segments(m->pending[s], s, lo, hi, true, &segments, &max_cw);
                 m->packed_busy = true;
             }
         }
@@ -1563,6 +1576,70 @@ extern "C" int skm_mapper_push_packed(skm_mapper *m, const skm_packed_reads *pie
 
 namespace {
 
+// the arrays of a piece that holds reads
+int packed_check_arrays(const skm_packed_reads *piece)
+{
+    const int64_t n = piece->n_reads;
+    const int cw = piece->code_words;
+    if (cw < 1 || cw > (1 << 15) || piece->read_stride < cw || !piece->codes) return fail(SKM_ERR_ARG, "bad code words");
+    if (piece->uniform_len < 0 && !piece->lengths) return fail(SKM_ERR_ARG, "lengths is NULL");
+    if (piece->uniform_len > 32LL * cw) return fail(SKM_ERR_ARG, "reads of %lld bases in %d code words", (long long)piece->uniform_len, cw);
+    const int64_t n_exc = piece->n_exceptions;
+    if (n_exc < 0 || n_exc > n || (n_exc > 0 && (!piece->exception_reads || !piece->exception_masks)))
+        return fail(SKM_ERR_ARG, "bad exception list");
+    for (int64_t e = 0; e < n_exc; ++e)
+        if (piece->exception_reads[e] >= (uint64_t)n || (e && piece->exception_reads[e] <= piece->exception_reads[e - 1]))
+            return fail(SKM_ERR_ARG, "exception reads must ascend and lie inside the piece");
+    return SKM_OK;
+}
+
+// A piece's one HBM block: codes | lengths | exception reads | exception bit planes
+size_t packed_round(size_t b) { return (b + 255) & ~(size_t)255; }
+int64_t packed_block_bytes(const skm_packed_reads *piece)
+{
+    const size_t n = (size_t)piece->n_reads, cw = (size_t)piece->code_words, n_exc = (size_t)piece->n_exceptions;
+    return (int64_t)(packed_round(n * cw * 8) + (piece->uniform_len >= 0 ? 0 : packed_round(n * 4)) + packed_round(n_exc * 4)
+                     + packed_round(n_exc * cw * 4) + 256);
+}
+
+// take the block (counted in *counter while it lives) and QUEUE the copies of the piece's arrays on `stream`
+int packed_upload(const skm_packed_reads *piece, const std::shared_ptr<std::atomic<int64_t>> &counter, hipStream_t stream,
+                  skm_mapper::Piece *out)
+{
+    const int64_t n = piece->n_reads, n_exc = piece->n_exceptions;
+    const int cw = piece->code_words;
+    const bool uniform = piece->uniform_len >= 0;
+    const size_t codes_bytes = packed_round((size_t)n * cw * 8);
+    const size_t len_bytes = uniform ? 0 : packed_round((size_t)n * 4);
+    const size_t exc_bytes = packed_round((size_t)n_exc * 4);
+    const int64_t block_bytes = packed_block_bytes(piece);
+    char *raw = nullptr;
+    HIP_TRY(pool_alloc((void **)&raw, (size_t)block_bytes));
+    skm_mapper::Piece &held = *out;
+    counter->fetch_add(block_bytes);       // (the counter outlives its owner if a block does)
+    held.block = std::shared_ptr<char>(raw, [counter, block_bytes](char *q) { pool_free(q); counter->fetch_sub(block_bytes); });
+    held.first = held.origin = piece->first_read;
+    held.n = n;
+    held.cw = cw;
+    held.uniform_len = uniform ? piece->uniform_len : -1;
+    held.codes = (uint64_t *)raw;
+    held.lengths = uniform ? nullptr : (uint32_t *)(raw + codes_bytes);
+    held.exc_reads_dev = (uint32_t *)(raw + codes_bytes + len_bytes);
+    held.exc_masks = (uint32_t *)(raw + codes_bytes + len_bytes + exc_bytes);
+    if (n_exc) held.exc_reads.assign(piece->exception_reads, piece->exception_reads + n_exc);
+    if (piece->read_stride == cw)
+        HIP_TRY(hipMemcpyAsync(held.codes, piece->codes, (size_t)n * cw * 8, hipMemcpyHostToDevice, stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(held.codes, (size_t)cw * 8, piece->codes, (size_t)piece->read_stride * 8, (size_t)cw * 8,
+                                 (size_t)n, hipMemcpyHostToDevice, stream));
+    if (!uniform) HIP_TRY(hipMemcpyAsync(held.lengths, piece->lengths, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+    if (n_exc) {
+        HIP_TRY(hipMemcpyAsync(held.exc_reads_dev, piece->exception_reads, (size_t)n_exc * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(held.exc_masks, piece->exception_masks, (size_t)n_exc * cw * 4, hipMemcpyHostToDevice, stream));
+    }
+    return SKM_OK;
+}
+
 int packed_stage(skm_mapper *m, const skm_packed_reads *piece, int paired, skm_mapper::Piece *out, bool *staged)
 {
     *staged = false;
@@ -1591,15 +1668,7 @@ int packed_stage(skm_mapper *m, const skm_packed_reads *piece, int paired, skm_m
         return SKM_OK;
     }
     if (n == 0) return SKM_OK;
-    if (cw < 1 || cw > (1 << 15) || piece->read_stride < cw || !piece->codes) return fail(SKM_ERR_ARG, "bad code words");
-    if (piece->uniform_len < 0 && !piece->lengths) return fail(SKM_ERR_ARG, "lengths is NULL");
-    if (piece->uniform_len > 32LL * cw) return fail(SKM_ERR_ARG, "reads of %lld bases in %d code words", (long long)piece->uniform_len, cw);
-    const int64_t n_exc = piece->n_exceptions;
-    if (n_exc < 0 || n_exc > n || (n_exc > 0 && (!piece->exception_reads || !piece->exception_masks)))
-        return fail(SKM_ERR_ARG, "bad exception list");
-    for (int64_t e = 0; e < n_exc; ++e)
-        if (piece->exception_reads[e] >= (uint64_t)n || (e && piece->exception_reads[e] <= piece->exception_reads[e - 1]))
-            return fail(SKM_ERR_ARG, "exception reads must ascend and lie inside the piece");
+    SKM_TRY(packed_check_arrays(piece));
     SKM_TRY(set_device(m->ix->device));
     {
         std::lock_guard<std::mutex> hold(m->q_mu);
@@ -1608,13 +1677,7 @@ int packed_stage(skm_mapper *m, const skm_packed_reads *piece, int paired, skm_m
         m->packed_paired = paired ? 1 : 0;
         if (!m->packed_stream) HIP_TRY(hipStreamCreateWithFlags(m->packed_stream.out(), hipStreamNonBlocking));
     }
-    // one HBM block: codes | lengths | exception reads | exception bit planes
-    const bool uniform = piece->uniform_len >= 0;
-    auto round = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t codes_bytes = round((size_t)n * cw * 8);
-    const size_t len_bytes = uniform ? 0 : round((size_t)n * 4);
-    const size_t exc_bytes = round((size_t)n_exc * 4), mask_bytes = round((size_t)n_exc * cw * 4);
-    const int64_t block_bytes = (int64_t)(codes_bytes + len_bytes + exc_bytes + mask_bytes + 256);
+    const int64_t block_bytes = packed_block_bytes(piece);
     {
         std::unique_lock<std::mutex> hold(m->q_mu);
         auto may_go = [&] {
@@ -1629,34 +1692,7 @@ int packed_stage(skm_mapper *m, const skm_packed_reads *piece, int paired, skm_m
             m->packed_waiters--;
         }
     }
-    char *raw = nullptr;
-    HIP_TRY(pool_alloc((void **)&raw, (size_t)block_bytes));
-    skm_mapper::Piece &held = *out;
-    {
-        std::shared_ptr<std::atomic<int64_t>> counter = m->packed_bytes;   // (outlives the mapper if a block does)
-        counter->fetch_add(block_bytes);
-        held.block = std::shared_ptr<char>(raw, [counter, block_bytes](char *q) { pool_free(q); counter->fetch_sub(block_bytes); });
-    }
-    held.first = held.origin = piece->first_read;
-    held.n = n;
-    held.cw = cw;
-    held.uniform_len = uniform ? piece->uniform_len : -1;
-    held.codes = (uint64_t *)raw;
-    held.lengths = uniform ? nullptr : (uint32_t *)(raw + codes_bytes);
-    held.exc_reads_dev = (uint32_t *)(raw + codes_bytes + len_bytes);
-    held.exc_masks = (uint32_t *)(raw + codes_bytes + len_bytes + exc_bytes);
-    if (n_exc) held.exc_reads.assign(piece->exception_reads, piece->exception_reads + n_exc);
-    hipStream_t stream = m->packed_stream;
-    if (piece->read_stride == cw)
-        HIP_TRY(hipMemcpyAsync(held.codes, piece->codes, (size_t)n * cw * 8, hipMemcpyHostToDevice, stream));
-    else
-        HIP_TRY(hipMemcpy2DAsync(held.codes, (size_t)cw * 8, piece->codes, (size_t)piece->read_stride * 8, (size_t)cw * 8,
-                                 (size_t)n, hipMemcpyHostToDevice, stream));
-    if (!uniform) HIP_TRY(hipMemcpyAsync(held.lengths, piece->lengths, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-    if (n_exc) {
-        HIP_TRY(hipMemcpyAsync(held.exc_reads_dev, piece->exception_reads, (size_t)n_exc * 4, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(held.exc_masks, piece->exception_masks, (size_t)n_exc * cw * 4, hipMemcpyHostToDevice, stream));
-    }
+    SKM_TRY(packed_upload(piece, m->packed_bytes, m->packed_stream, out));
     *staged = true;
     return SKM_OK;
 }
@@ -2120,6 +2156,524 @@ extern "C" int skm_mapper_set_stats(skm_mapper *m, int enable)
     std::lock_guard<std::mutex> lock(m->mu);
     m->want_stats = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
     for (auto &v : m->stats_total) v = 0;
+    return SKM_OK;
+}
+
+// ------------------------------------------------------------------ sample sets
+// Many small samples through ONE mapper: their units share launches and the class table, in which a
+// class is (sample, tuple) -- skm_samples.hip.  The set owns a mapper (its table, batch buffers, stream)
+// and drives map_batch_resident itself: added segments wait in HBM in a queue, one worker cuts the
+// front of the queue into launches and logs which units of which sample every launch held.
+namespace {
+
+struct SetChunk {                        // the reads of one added segment where they lie in HBM
+    std::deque<skm_mapper::Piece> pieces[2];   // packed form: one piece per mate, numbered by the sample's units
+    std::shared_ptr<char> ascii;         // ASCII form: one block, offsets | bases
+    const uint8_t *bases = nullptr;      // biased: read r of the segment = bases[offsets[r] .. offsets[r + 1])
+    const int64_t *offsets = nullptr;    // [reads + 1], as the caller gave them
+    int64_t origin = 0;                  // the sample's unit of the segment's first read
+    int max_len = 0;
+};
+struct SetQueued { int32_t sample; int64_t first, n; std::shared_ptr<SetChunk> data; };   // what is left of a segment
+struct SetPart { int32_t sample; int64_t first, n, at; std::shared_ptr<SetChunk> data; }; // units [first, first + n) of
+                                                                                         // the sample at place `at` of a launch
+
+// the next launch: whole segments from the front of the queue, the last one cut where the launch is full
+int64_t set_cut_launch(std::deque<SetQueued> &queue, int64_t max_units, std::vector<SetPart> *parts)
+{
+    int64_t n_units = 0;
+    parts->clear();
+    while (!queue.empty() && n_units < max_units && (int)parts->size() < SAMPLE_LAUNCH_SEGMENTS) {
+        SetQueued &front = queue.front();
+        const int64_t take = std::min(front.n, max_units - n_units);
+        parts->push_back(SetPart{front.sample, front.first, take, n_units, front.data});
+        n_units += take;
+        if (take == front.n) queue.pop_front();
+        else { front.first += take; front.n -= take; }
+    }
+    return n_units;
+}
+
+// which units of which sample the set's unit numbers are: one entry per part of every launch, in launch
+// order, so `global` ascends and the entries tile [0, units)
+struct SetLog {
+    std::vector<int64_t> global, local;
+    std::vector<int32_t> sample;
+    int64_t units = 0;
+    void append(const std::vector<SetPart> &parts)
+    {
+        for (const SetPart &part : parts) {
+            global.push_back(units + part.at);
+            local.push_back(part.first);
+            sample.push_back(part.sample);
+        }
+        if (!parts.empty()) units += parts.back().at + parts.back().n;
+    }
+};
+
+// classes by (sample, first-seen unit inside the sample): order[k] = the class in place k,
+// sample_class_offsets[i] = place of sample i's first class
+void set_split_order(int64_t n_samples, int64_t n_classes, const int32_t *class_sample, const int64_t *class_local,
+                     int64_t *order, int64_t *sample_class_offsets)
+{
+    std::iota(order, order + n_classes, (int64_t)0);
+    std::sort(order, order + n_classes, [&](int64_t a, int64_t b) {
+        return class_sample[a] != class_sample[b] ? class_sample[a] < class_sample[b] : class_local[a] < class_local[b];
+    });
+    std::fill(sample_class_offsets, sample_class_offsets + n_samples + 1, (int64_t)0);
+    for (int64_t k = 0; k < n_classes; ++k) sample_class_offsets[class_sample[k] + 1]++;
+    for (int64_t i = 0; i < n_samples; ++i) sample_class_offsets[i + 1] += sample_class_offsets[i];
+}
+
+constexpr int64_t SET_MAX_SAMPLES = 1 << 24;
+constexpr int64_t SET_MAX_QUEUED = 4 * PACKED_MAX_UNITS;     // units that may wait in HBM before an adder waits
+
+}  // namespace
+
+struct skm_sample_set {
+    skm_sample_set(skm_mapper *mapper, int paired_) : m(mapper), paired(paired_) {}
+    ~skm_sample_set();
+    Own<skm_mapper *, skm_mapper_destroy> m;      // (declared first: given up last)
+    const int paired;
+    int64_t max_units = PACKED_MAX_UNITS;         // of one launch (SKM_SAMPLE_SET_MAX_UNITS)
+    std::mutex copy_mu;                           // one adder copies at a time
+    Stream copy_stream;
+    std::shared_ptr<std::atomic<int64_t>> bytes = std::make_shared<std::atomic<int64_t>>(0);
+    DBuf<int32_t> seg_table;                      // the segments of the launch under way: first units | samples
+    // ---- under mu
+    std::mutex mu;
+    std::condition_variable work_cv, done_cv;
+    std::deque<SetQueued> queue;
+    int64_t queued_units = 0;
+    std::vector<int64_t> sample_units;            // units added per sample = where its next segment must begin
+    SetLog log;
+    bool busy = false, stop = false, worker_started = false;
+    int flush = 0;
+    int error = SKM_OK;                           // the first failed launch: the set stays failed
+    std::string error_msg;
+    std::thread worker;
+    // the tables by sample, made by the first reader after the last launch
+    struct View {
+        bool valid = false;
+        std::vector<int64_t> start, len, count, local, order, sample_class_offsets, sample_rows, sample_aligned;
+        std::vector<int64_t> units;               // sample_units as the view was made: all of them mapped
+        std::vector<int32_t> arena;
+    } view;
+};
+
+namespace {
+
+int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_units, int64_t global_first)
+{
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    const int mates = s->paired ? 2 : 1;
+    const int n_parts = (int)parts.size();
+    if (n_parts > SAMPLE_LAUNCH_SEGMENTS) return fail(SKM_ERR_STATE, "%d segments in one launch", n_parts);
+    std::vector<int32_t> table(2 * (size_t)n_parts);
+    std::vector<PackedSegment> segments;          // `first` = place in the launch
+    int max_cw = 0, max_len = 0;
+    for (int i = 0; i < n_parts; ++i) {
+        const SetPart &part = parts[i];
+        table[i] = (int32_t)part.at;
+        table[n_parts + i] = part.sample;
+        if (part.data->ascii) { max_len = std::max(max_len, part.data->max_len); continue; }
+        for (int mate = 0; mate < mates; ++mate) {
+            const size_t from = segments.size();
+            packed_segments(part.data->pieces[mate], mate, part.first, part.first + part.n, false, &segments, &max_cw);
+            for (size_t k = from; k < segments.size(); ++k) segments[k].first += part.at - part.first;
+        }
+    }
+    max_len = std::max(max_len, max_cw * 32);
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (`table` is read by a queued copy)
+    SKM_TRY(s->seg_table.ensure(2 * SAMPLE_LAUNCH_SEGMENTS));
+    HIP_TRY(hipMemcpyAsync(s->seg_table.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    const SampleSalt salt{s->seg_table.p, s->seg_table.p + n_parts, n_parts};
+    const RecordStage fill = [&](uint32_t *records, int words, int record_words) -> int {
+        for (const PackedSegment &seg : segments) {
+            uint32_t *dst = records + (seg.first * mates + seg.mate) * (int64_t)record_words;
+            launch_unpack_reads(seg.codes, seg.cw, seg.cw, seg.lengths, seg.uniform_len, seg.n, words, dst,
+                                (int64_t)mates * record_words, m->error.p, m->stream);
+            if (seg.n_exc)
+                launch_unpack_exceptions(seg.exc_reads, seg.exc_masks, seg.n_exc, seg.cw, seg.exc_base, words, dst,
+                                         (int64_t)mates * record_words, m->stream);
+        }
+        for (const SetPart &part : parts) {
+            if (!part.data->ascii) continue;
+            launch_pack_reads(part.data->bases, part.data->offsets + (part.first - part.data->origin) * mates, part.n * mates,
+                              words, record_words, records + part.at * mates * (int64_t)record_words, m->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        return SKM_OK;
+    };
+    return map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt);
+}
+
+void set_worker(skm_sample_set *s)
+{
+    for (;;) {
+        std::vector<SetPart> parts;
+        int64_t n_units = 0, global_first = 0;
+        {
+            std::unique_lock<std::mutex> hold(s->mu);
+            s->work_cv.wait(hold, [&] {
+                return s->stop || (!s->queue.empty()
+                                   && (s->error != SKM_OK || s->flush || s->queued_units >= std::min(PACKED_MIN_UNITS, s->max_units)));
+            });
+            if (s->stop || s->error != SKM_OK) {          // nothing more is mapped: what waits goes
+                s->queue.clear();
+                s->queued_units = 0;
+                s->done_cv.notify_all();
+                if (s->stop) return;
+                continue;
+            }
+            n_units = set_cut_launch(s->queue, s->max_units, &parts);
+            s->queued_units -= n_units;
+            global_first = s->log.units;
+            s->log.append(parts);
+            s->view.valid = false;
+            s->busy = true;
+        }
+        const int rc = set_launch(s, parts, n_units, global_first);
+        const std::string message = rc != SKM_OK ? g_error : std::string();
+        if (rc != SKM_OK) (void)hipStreamSynchronize(s->m->stream);   // (before the parts' blocks go back to the pool)
+        parts.clear();
+        {
+            std::lock_guard<std::mutex> hold(s->mu);
+            if (rc != SKM_OK) { s->error = rc; s->error_msg = message; }
+            s->busy = false;
+        }
+        s->done_cv.notify_all();
+    }
+}
+
+// wait until everything added has been mapped; the set's failure, if it has one
+int set_wait(skm_sample_set *s)
+{
+    std::unique_lock<std::mutex> hold(s->mu);
+    s->flush++;
+    s->work_cv.notify_all();
+    s->done_cv.wait(hold, [&] { return !s->busy && s->queue.empty(); });
+    s->flush--;
+    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    return SKM_OK;
+}
+
+// (before the copy) the caller's arguments, and room in the queue
+int set_admit(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n_units)
+{
+    if (sample < 0 || sample >= SET_MAX_SAMPLES) return fail(SKM_ERR_ARG, "sample %lld outside [0, 2^24)", (long long)sample);
+    if (first_unit < 0 || n_units < 0 || n_units >= (1LL << 31)) return fail(SKM_ERR_ARG, "bad unit range");
+    SKM_TRY(set_device(s->m->ix->device));
+    std::unique_lock<std::mutex> hold(s->mu);
+    s->done_cv.wait(hold, [&] { return s->error != SKM_OK || s->queued_units <= SET_MAX_QUEUED; });
+    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    return SKM_OK;
+}
+
+// (after the copy) the segment joins the queue if it begins where the sample's units so far end
+int set_enqueue(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n_units, std::shared_ptr<SetChunk> data)
+{
+    {
+        std::lock_guard<std::mutex> hold(s->mu);
+        if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+        if ((int64_t)s->sample_units.size() <= sample) s->sample_units.resize((size_t)sample + 1, 0);
+        if (first_unit != s->sample_units[sample])
+            return fail(SKM_ERR_STATE, "sample %lld: a segment from unit %lld after %lld units (segments are added in order)",
+                        (long long)sample, (long long)first_unit, (long long)s->sample_units[sample]);
+        s->sample_units[sample] += n_units;
+        s->view.valid = false;
+        if (n_units == 0) return SKM_OK;
+        s->queue.push_back(SetQueued{(int32_t)sample, first_unit, n_units, std::move(data)});
+        s->queued_units += n_units;
+        if (!s->worker_started) {
+            s->worker = std::thread(set_worker, s);
+            s->worker_started = true;
+        }
+    }
+    s->work_cv.notify_all();
+    return SKM_OK;
+}
+
+// the tables by sample (s->view), made once after the last launch.  `hold` (s->mu) is taken here and stays
+// taken for the caller's reading: from the moment everything added has been mapped no segment joins the queue
+// (an adder waits in set_enqueue), so the view, the log and the units per sample describe the same units.
+int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
+{
+    hold = std::unique_lock<std::mutex>(s->mu);
+    s->flush++;
+    s->work_cv.notify_all();
+    s->done_cv.wait(hold, [&] { return !s->busy && s->queue.empty(); });
+    s->flush--;
+    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    if (s->view.valid) return SKM_OK;
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    const int64_t C = m->host_classes, M = m->host_arena_used, n_samples = (int64_t)s->sample_units.size();
+    const int64_t n_log = (int64_t)s->log.global.size();
+    skm_sample_set::View &v = s->view;
+    v.start.assign(C, 0); v.len.assign(C, 0); v.count.assign(C, 0); v.local.assign(C, 0); v.order.assign(C, 0);
+    v.arena.assign((size_t)std::max<int64_t>(M, 1), 0);
+    v.sample_class_offsets.assign(n_samples + 1, 0);
+    v.sample_rows.assign(n_samples, 0); v.sample_aligned.assign(n_samples, 0);
+    v.units = s->sample_units;
+    std::vector<int32_t> cls_sample(C);
+    if (C) {
+        if (n_log == 0) return fail(SKM_ERR_STATE, "classes without a launch");
+        DBuf<int64_t> d_off, d_len, d_local, d_log; DBuf<double> d_cnt; DBuf<unsigned long long> d_fs; DBuf<int32_t> d_sample, d_log_sample;
+        auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
+        SKM_TRY(d_off.ensure(C)); SKM_TRY(d_len.ensure(C)); SKM_TRY(d_cnt.ensure(C)); SKM_TRY(d_fs.ensure(C));
+        SKM_TRY(d_sample.ensure(C)); SKM_TRY(d_local.ensure(C)); SKM_TRY(d_log.ensure(2 * n_log)); SKM_TRY(d_log_sample.ensure(n_log));
+        HIP_TRY(hipMemcpyAsync(d_log.p, s->log.global.data(), n_log * 8, hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(d_log.p + n_log, s->log.local.data(), n_log * 8, hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(d_log_sample.p, s->log.sample.data(), n_log * 4, hipMemcpyHostToDevice, m->stream));
+        launch_class_compact(m->t, C, d_off.p, d_len.p, d_cnt.p, d_fs.p, m->stream);
+        launch_sample_assign(d_log.p, d_log.p + n_log, d_log_sample.p, n_log, d_fs.p, C, d_sample.p, d_local.p, m->stream);
+        HIP_TRY(hipGetLastError());
+        std::vector<double> cnt(C);
+        HIP_TRY(hipMemcpyAsync(v.start.data(), d_off.p, C * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipMemcpyAsync(v.len.data(), d_len.p, C * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt.p, C * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipMemcpyAsync(cls_sample.data(), d_sample.p, C * 4, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipMemcpyAsync(v.local.data(), d_local.p, C * 8, hipMemcpyDeviceToHost, m->stream));
+        if (M) HIP_TRY(hipMemcpyAsync(v.arena.data(), m->arena.p, (size_t)M * 4, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        drain.dismiss();
+        for (int64_t k = 0; k < C; ++k) {
+            if (cls_sample[k] < 0 || cls_sample[k] >= n_samples || v.start[k] < 0)
+                return fail(SKM_ERR_STATE, "class %lld of the shared table belongs to no sample", (long long)k);
+            v.count[k] = (int64_t)cnt[k];
+            v.sample_rows[cls_sample[k]] += v.len[k];
+            v.sample_aligned[cls_sample[k]] += v.count[k];
+        }
+    }
+    set_split_order(n_samples, C, cls_sample.data(), v.local.data(), v.order.data(), v.sample_class_offsets.data());
+    // (units_s - aligned_s is each sample's unaligned count; their sum is what the table counted)
+    int64_t unaligned = 0;
+    for (int64_t i = 0; i < n_samples; ++i) {
+        if (v.sample_aligned[i] > s->sample_units[i]) return fail(SKM_ERR_STATE, "sample %lld counts more units than it has", (long long)i);
+        unaligned += s->sample_units[i] - v.sample_aligned[i];
+    }
+    if (m->host_totals_valid && unaligned != (int64_t)m->host_unaligned)
+        return fail(SKM_ERR_STATE, "the samples' unaligned units (%lld) are not the table's (%llu)", (long long)unaligned, m->host_unaligned);
+    v.valid = true;
+    return SKM_OK;
+}
+
+}  // namespace
+
+skm_sample_set::~skm_sample_set()
+{
+    (void)hipSetDevice(m->ix->device);
+    if (worker_started) {
+        { std::lock_guard<std::mutex> hold(mu); stop = true; }
+        work_cv.notify_all();
+        worker.join();                     // (finishes the launch under way; what waits is dropped)
+    }
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+}
+
+extern "C" int skm_sample_set_create(skm_index *ix, int paired, skm_sample_set **out)
+{
+    if (!ix || !out) return fail(SKM_ERR_ARG, "NULL argument");
+    skm_mapper *mapper = nullptr;
+    SKM_TRY(skm_mapper_create(ix, &mapper));
+    std::unique_ptr<skm_sample_set> s(new skm_sample_set(mapper, paired ? 1 : 0));
+    HIP_TRY(hipStreamCreateWithFlags(s->copy_stream.out(), hipStreamNonBlocking));
+    if (const char *v = getenv("SKM_SAMPLE_SET_MAX_UNITS"))
+        if (atoll(v) > 0) s->max_units = std::min<int64_t>(atoll(v), PACKED_MAX_UNITS);
+    *out = s.release();
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_destroy(skm_sample_set *s)
+{
+    delete s;
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_set_strand(skm_sample_set *s, int mode)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    {
+        std::lock_guard<std::mutex> hold(s->mu);
+        for (const int64_t units : s->sample_units)
+            if (units) return fail(SKM_ERR_STATE, "the strand mode can only change on an empty sample set");
+    }
+    return skm_mapper_set_strand(s->m, mode);
+}
+
+extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit,
+                                         const skm_packed_reads *mate1, const skm_packed_reads *mate2)
+{
+    if (!s || !mate1) return fail(SKM_ERR_ARG, "NULL argument");
+    if ((mate2 != nullptr) != (s->paired != 0)) return fail(SKM_ERR_ARG, "a %s set takes %s", s->paired ? "paired" : "single-ended",
+                                                           s->paired ? "both mates" : "mate 1 alone");
+    const int64_t n = mate1->n_reads;
+    if (mate2 && mate2->n_reads != n) return fail(SKM_ERR_ARG, "%lld reads of mate 1, %lld of mate 2", (long long)n, (long long)mate2->n_reads);
+    SKM_TRY(set_admit(s, sample, first_unit, n));
+    auto data = std::make_shared<SetChunk>();
+    if (n) {
+        const skm_packed_reads *mates[2] = {mate1, mate2};
+        for (int k = 0; k < (s->paired ? 2 : 1); ++k) SKM_TRY(packed_check_arrays(mates[k]));
+        std::lock_guard<std::mutex> copying(s->copy_mu);
+        auto drain = on_exit([&]() { (void)hipStreamSynchronize(s->copy_stream); });   // (the caller's arrays, the blocks)
+        for (int k = 0; k < (s->paired ? 2 : 1); ++k) {
+            skm_packed_reads piece = *mates[k];
+            piece.first_read = first_unit;             // (numbered by the sample's units)
+            skm_mapper::Piece held;
+            SKM_TRY(packed_upload(&piece, s->bytes, s->copy_stream, &held));
+            data->pieces[k].push_back(std::move(held));
+        }
+        drain.dismiss();
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    }
+    return set_enqueue(s, sample, first_unit, n, std::move(data));
+}
+
+extern "C" int skm_sample_set_add_batch(skm_sample_set *s, int64_t sample, int64_t first_unit, const char *bases,
+                                        const int64_t *offsets, int64_t n_units)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    if (n_units > 0 && (!bases || !offsets)) return fail(SKM_ERR_ARG, "NULL reads");
+    SKM_TRY(set_admit(s, sample, first_unit, n_units));
+    auto data = std::make_shared<SetChunk>();
+    if (n_units) {
+        const int64_t n_reads = s->paired ? 2 * n_units : n_units;
+        int64_t longest = 0;
+        for (int64_t r = 0; r < n_reads; ++r) {
+            if (offsets[r + 1] < offsets[r]) return fail(SKM_ERR_ARG, "offsets are not monotone");
+            longest = std::max(longest, offsets[r + 1] - offsets[r]);
+        }
+        if (longest > (1 << 20)) return fail(SKM_ERR_ARG, "read longer than 2^20 bases");
+        const int64_t n_bytes = offsets[n_reads] - offsets[0];
+        const size_t offsets_bytes = packed_round((size_t)(n_reads + 1) * 8);
+        const int64_t block_bytes = (int64_t)(offsets_bytes + (size_t)n_bytes + 64);     // (the pack kernel reads 32 bytes at a time)
+        char *raw = nullptr;
+        HIP_TRY(pool_alloc((void **)&raw, (size_t)block_bytes));
+        std::shared_ptr<std::atomic<int64_t>> counter = s->bytes;
+        counter->fetch_add(block_bytes);
+        data->ascii = std::shared_ptr<char>(raw, [counter, block_bytes](char *q) { pool_free(q); counter->fetch_sub(block_bytes); });
+        data->offsets = (const int64_t *)raw;
+        data->bases = (const uint8_t *)raw + offsets_bytes - offsets[0];
+        data->origin = first_unit;
+        data->max_len = (int)longest;
+        std::lock_guard<std::mutex> copying(s->copy_mu);
+        auto drain = on_exit([&]() { (void)hipStreamSynchronize(s->copy_stream); });
+        HIP_TRY(hipMemcpyAsync(raw, offsets, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, s->copy_stream));
+        if (n_bytes)
+            HIP_TRY(hipMemcpyAsync(raw + offsets_bytes, bases + offsets[0], (size_t)n_bytes, hipMemcpyHostToDevice, s->copy_stream));
+        drain.dismiss();
+        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    }
+    return set_enqueue(s, sample, first_unit, n_units, std::move(data));
+}
+
+extern "C" int skm_sample_set_sync(skm_sample_set *s)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    return set_wait(s);
+}
+
+extern "C" int skm_sample_set_summary(skm_sample_set *s, int64_t cap_samples, int64_t *n_samples, int64_t *summary)
+{
+    if (!s || !n_samples || cap_samples < 0 || (cap_samples && !summary)) return fail(SKM_ERR_ARG, "bad argument");
+    if (cap_samples == 0) {                               // (the number alone: nothing is waited for)
+        std::lock_guard<std::mutex> counting(s->mu);
+        *n_samples = (int64_t)s->sample_units.size();
+        return SKM_OK;
+    }
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    const skm_sample_set::View &v = s->view;
+    *n_samples = (int64_t)v.units.size();
+    for (int64_t i = 0; i < std::min(cap_samples, *n_samples); ++i) {
+        summary[4 * i + 0] = v.sample_class_offsets[i + 1] - v.sample_class_offsets[i];
+        summary[4 * i + 1] = v.sample_rows[i];
+        summary[4 * i + 2] = v.units[i] - v.sample_aligned[i];
+        summary[4 * i + 3] = v.units[i];
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_export(skm_sample_set *s, int64_t *sample_class_offsets, int64_t *class_offsets,
+                                     int32_t *class_targets, int64_t *class_counts, int64_t *first_seen)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    const skm_sample_set::View &v = s->view;
+    if (sample_class_offsets) std::copy(v.sample_class_offsets.begin(), v.sample_class_offsets.end(), sample_class_offsets);
+    if (class_offsets) class_offsets[0] = 0;
+    int64_t pos = 0;
+    for (size_t k = 0; k < v.order.size(); ++k) {
+        const int64_t c = v.order[k];
+        if (class_targets) memcpy(class_targets + pos, v.arena.data() + v.start[c], (size_t)v.len[c] * 4);
+        pos += v.len[c];
+        if (class_offsets) class_offsets[k + 1] = pos;
+        if (class_counts) class_counts[k] = v.count[c];
+        if (first_seen) first_seen[k] = v.local[c];
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_histogram(skm_sample_set *s, int64_t *fld)
+{
+    if (!s || !fld) return fail(SKM_ERR_ARG, "NULL argument");
+    SKM_TRY(set_wait(s));
+    return skm_mapper_export(s->m, nullptr, nullptr, nullptr, nullptr, fld);
+}
+
+extern "C" int skm_sample_set_plan(int64_t n_segments, const int32_t *sample, const int64_t *n_units, int64_t max_units,
+                                   int64_t cap_entries, int64_t *n_entries, int64_t *entry_global, int64_t *entry_local,
+                                   int32_t *entry_sample)
+{
+    if (n_segments < 0 || max_units < 1 || cap_entries < 0 || !n_entries || (n_segments && (!sample || !n_units)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    std::deque<SetQueued> queue;
+    std::unordered_map<int32_t, int64_t> next;
+    for (int64_t i = 0; i < n_segments; ++i) {
+        if (sample[i] < 0 || n_units[i] < 0) return fail(SKM_ERR_ARG, "bad segment %lld", (long long)i);
+        if (n_units[i]) queue.push_back(SetQueued{sample[i], next[sample[i]], n_units[i], nullptr});
+        next[sample[i]] += n_units[i];
+    }
+    SetLog log;
+    std::vector<SetPart> parts;
+    while (!queue.empty()) {
+        set_cut_launch(queue, max_units, &parts);
+        log.append(parts);
+    }
+    *n_entries = (int64_t)log.global.size();
+    if (*n_entries > cap_entries) return SKM_OK;       // (the caller sizes its arrays and asks again)
+    if (*n_entries && (!entry_global || !entry_local || !entry_sample)) return fail(SKM_ERR_ARG, "NULL entry arrays");
+    std::copy(log.global.begin(), log.global.end(), entry_global);
+    std::copy(log.local.begin(), log.local.end(), entry_local);
+    std::copy(log.sample.begin(), log.sample.end(), entry_sample);
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_split(int64_t n_entries, const int64_t *entry_global, const int64_t *entry_local,
+                                    const int32_t *entry_sample, int64_t n_samples, int64_t n_classes,
+                                    const int64_t *first_seen, int32_t *class_sample, int64_t *class_local, int64_t *order,
+                                    int64_t *sample_class_offsets)
+{
+    if (n_entries < 0 || n_samples < 0 || n_classes < 0 || !sample_class_offsets
+            || (n_entries && (!entry_global || !entry_local || !entry_sample))
+            || (n_classes && (!first_seen || !class_sample || !class_local || !order)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    if (n_classes && (n_entries == 0 || entry_global[0] != 0)) return fail(SKM_ERR_ARG, "the log does not start at unit 0");
+    for (int64_t i = 0; i < n_entries; ++i)
+        if (entry_sample[i] < 0 || entry_sample[i] >= n_samples || (i && entry_global[i] <= entry_global[i - 1]))
+            return fail(SKM_ERR_ARG, "bad log entry %lld", (long long)i);
+    for (int64_t k = 0; k < n_classes; ++k) {
+        if (first_seen[k] < 0) return fail(SKM_ERR_ARG, "negative first-seen unit");
+        const int64_t e = segment_find(entry_global, n_entries, first_seen[k]);
+        class_sample[k] = entry_sample[e];
+        class_local[k] = entry_local[e] + (first_seen[k] - entry_global[e]);
+    }
+    set_split_order(n_samples, n_classes, class_sample, class_local, order, sample_class_offsets);
     return SKM_OK;
 }
 

@@ -85,6 +85,39 @@ void launch_pack_sequences(const char *bases, int64_t n_bases, uint64_t *seq2, i
 // SKM_STRAND_RF: e < 0), compacted in place in the entry arena; its key and tuple length follow
 void launch_strand_filter(const MapBatch &b, int mode, hipStream_t stream);
 
+// ---- sample sets (skm_samples.hip): many samples' units in shared launches, one class table whose
+// classes are (sample, tuple).  A SEGMENT is a run of consecutive units of one sample; the segments of
+// a launch, and of the whole set in launch order, ascend by their first unit.
+// index of the segment that holds `unit`: the last i with first[i] <= unit (first[0] <= unit)
+template <class T>
+__host__ __device__ __forceinline__ int64_t segment_find(const T *first, int64_t n, int64_t unit)
+{
+    int64_t lo = 0, hi = n;                       // first[lo] <= unit < first[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)first[mid] <= unit) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the key of class (sample, tuple) from the tuple's key: for a fixed tuple key distinct samples give
+// distinct keys (the constant is odd), so two samples' copies of one tuple never meet in a slot
+constexpr uint64_t SAMPLE_KEY_STEP = 0xD6E8FEB86659FD93ULL;
+__host__ __device__ __forceinline__ uint64_t sample_key(uint64_t key, uint32_t sample) { return key + sample * SAMPLE_KEY_STEP; }
+constexpr int SAMPLE_LAUNCH_SEGMENTS = 2048;      // segments of one launch at most (their table lives in LDS)
+struct SampleSalt {                               // the segments of one launch (device arrays)
+    const int32_t *seg_first;                     // [n_segments] first unit of the segment inside the launch, ascending from 0
+    const int32_t *seg_sample;                    // [n_segments]
+    int32_t n_segments;
+};
+// between the strand filter and class counting: every record with a key takes the key of (its unit's
+// sample, its tuple); a key that comes out as 0 raises SKM_ERR_COLLISION in *error (never "unaligned")
+void launch_sample_salt(const MapBatch &b, const SampleSalt &salt, int *error, hipStream_t stream);
+// the set's segment log against the classes' global first-seen units: cls_sample[k], cls_local[k] =
+// the sample of class k and its first-seen unit counted inside that sample
+void launch_sample_assign(const int64_t *log_global, const int64_t *log_local, const int32_t *log_sample,
+                          int64_t n_segments, const unsigned long long *cls_first_seen, int64_t n_classes,
+                          int32_t *cls_sample, int64_t *cls_local, hipStream_t stream);
+
 void launch_gather_probe(const void *table, uint64_t n_slots, int blocks, int per_lane, int chain,
                          unsigned long long *sink, hipStream_t stream);
 

@@ -1,6 +1,8 @@
 """Single-cell imputation -- the `seekmer.impute` surface (reference:
-seekmer/impute.py:1-252) over the MI355X engine.  Every cell is mapped into its
-own device-resident class table (`mapper.map_multiple_samples`), the cells'
+seekmer/impute.py:1-252) over the MI355X engine.  All cells are mapped in shared
+launches into one device-resident class table that keeps their classes apart
+(`mapper.map_sample_set`; one table per cell, `mapper.map_multiple_samples`,
+outside the regime of SAMPLE_SET_* and with SKM_IMPUTE_PER_CELL=1), the cells'
 fragment-length histograms are pooled, every cell is quantified once, a
 cell-by-cell weight matrix is derived from the gene-level abundances, and every
 cell is quantified again on the weighted blend of all cells' class tables.
@@ -55,11 +57,18 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
     feeders = [common.PackedReadFeeder(list(group), paired=not single_ended)
                if common.PackedReadFeeder.eligible(group) else common.NativeReadFeeder(list(group), paired=not single_ended)
                for group in groups]
-    map_results = mapper.map_multiple_samples(index, feeders, job_count=job_count, debug=debug,
-                                              device=device, strand=strand)
-    _LOG.info('Mapped all reads.')
-    pool_fragment_lengths(map_results)
-    summaries = [result.summarize() for result in map_results]
+    if use_sample_set(groups):
+        # (the set's one histogram IS the pooled one: every summary carries it)
+        sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count),
+                                           device=device, strand=strand)
+        _LOG.info('Mapped all reads.')
+        summaries = sample_set.summarize()
+    else:
+        map_results = mapper.map_multiple_samples(index, feeders, job_count=job_count, debug=debug,
+                                                  device=device, strand=strand)
+        _LOG.info('Mapped all reads.')
+        pool_fragment_lengths(map_results)
+        summaries = [result.summarize() for result in map_results]
     _LOG.info('First round quantification...')
     base = numpy.asarray([infer.quantify(summary) for summary in summaries])
     if power is not None:
@@ -76,6 +85,42 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
     _LOG.info('Writing results to %s...', output_path)
     table.to_csv(output_path / 'tpm.csv')
     return table
+
+
+# Where the cells are mapped through one sample set (mapper.map_sample_set) instead of a mapper per cell.
+# Measured ("Sample sets"; profiles/sample_set_ab.log: the mapping stage alone, packed reads in
+# host memory to exported tables, against the parent commit's map_multiple_samples on the same GPU): the set
+# is 7 x ahead at 64 and at 512 cells of 20 k pairs, 2.1 x at 8 cells, 1.7 x at 4, 1.3 x at 64 cells of 50 k
+# pairs on the 190 k-transcript index, 1.2 x at 4 and at 2 cells of 2 M pairs; at 2 cells of 20 k pairs and at
+# 4 cells of 8 M pairs the two are level within their spread.  No shape was found at which the mapper per
+# cell is ahead, so the bounds are not a crossover.  One cell has nothing to share.  The size bound is where
+# the gain was last seen (2 M pairs a cell): the set parses a cell completely before it adds it, so a cell's
+# packed reads must fit in host memory, which the mapper per cell, fed piece by piece, does not ask for --
+# and what the set buys, filled launches, a cell of that size has by itself.  Reading and parsing the files
+# is outside what was measured.  SKM_IMPUTE_PER_CELL=1 (exactly that value, looked up at every call)
+# selects the mapper per cell whatever the shape.
+SAMPLE_SET_MIN_CELLS = 2
+SAMPLE_SET_MAX_CELL_BYTES = 640 << 20     # the files of the largest cell: what 2 M pairs of 2 x 75 bases with short names come to
+SAMPLE_SET_COMPRESSED_RATIO = 4           # a compressed file counts this many times its size (an estimate of its text; not measured)
+
+
+def cell_text_bytes(group):
+    """What the rule takes for the FASTQ text of one cell (its tuple of paths): the sizes of plain files,
+    SAMPLE_SET_COMPRESSED_RATIO times those of compressed ones.  A path that is no file counts nothing
+    (the reader says what is wrong with it)."""
+    total = 0
+    for path in map(pathlib.Path, group):
+        if path.is_file():
+            plain = common.PackedReadFeeder.eligible([path])
+            total += path.stat().st_size * (1 if plain else SAMPLE_SET_COMPRESSED_RATIO)
+    return total
+
+
+def use_sample_set(groups):
+    """The rule of run(): groups = every cell's tuple of FASTQ paths."""
+    if os.environ.get('SKM_IMPUTE_PER_CELL') == '1' or len(groups) < SAMPLE_SET_MIN_CELLS:
+        return False
+    return max(cell_text_bytes(group) for group in groups) <= SAMPLE_SET_MAX_CELL_BYTES
 
 
 def pool_fragment_lengths(map_results):

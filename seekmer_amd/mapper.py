@@ -7,6 +7,11 @@ are materialised as ``collections.Counter`` / ``numpy`` objects only when the
 attributes are read.  ``ReadMapper(index, map_result)(reads_iterator)`` packs
 each batch and hands it to ``skm_mapper_map_batch``; there is no CPU mapping
 path.
+
+``SampleSet`` (``map_sample_set``) is the form for many small samples -- the
+cells of ``impute``: one handle maps all samples' units in shared launches
+into one table whose classes are (sample, tuple) and hands back every
+sample's own table, bit for bit what a ``MapResult`` per sample gives.
 """
 import collections
 import ctypes
@@ -19,8 +24,8 @@ import numpy
 from . import _native
 from .common import PackedReadFeeder, PackedReads, ReadBatch
 
-__all__ = ('MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SummarizedResult',
-           'map_reads', 'map_multiple_samples')
+__all__ = ('MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet', 'SummarizedResult',
+           'map_reads', 'map_multiple_samples', 'map_sample_set')
 
 MAX_FRAGMENT_LENGTH = 2000          # seekmer/_mapper.pyx:18-20
 
@@ -490,3 +495,249 @@ def _new_result(index, strand, **kwargs):
 def _map(index, map_result, read_feeder):
     ReadMapper(index, map_result)(read_feeder)
     return None
+
+
+# ---- many small samples in shared launches (include/seekmer_hip.h, skm_sample_set_*) -------------------
+
+def _slice_piece(piece, begin, end):
+    """Reads [begin, end) of a PackedReads piece as a piece of its own (arrays copied)."""
+    reads, masks = piece.exceptions
+    inside = (reads >= begin) & (reads < end)
+    return PackedReads.from_arrays(piece.stream, piece.first_read + begin, numpy.array(piece.codes[begin:end]),
+                                   numpy.array(piece.lengths[begin:end]), reads[inside] - numpy.uint32(begin),
+                                   numpy.array(masks[inside]), paired=piece.paired)
+
+
+def sample_segments(pieces, paired):
+    """The pieces of ONE sample as a packed reader hands them out (common.PackedReadFeeder: one stream
+    single-ended, two streams paired, each numbered by unit; a piece that begins below what its stream
+    holds replaces the reads from there on, and so does a cut, by nothing) -> the sample's units as
+    in-order segments [(first_unit, mate1, mate2 or None), ...] over arrays of their own.  A pair of
+    files counts min(records) units, zip(file1, file2) (seekmer/common.py:180-197): reads of one
+    stream that the other never matches are in no segment."""
+    streams = ([], [])
+    for piece in pieces:
+        if piece.stream not in ((0, 1) if paired else (0,)):
+            raise ValueError('stream %d of a %s sample' % (piece.stream, 'paired' if paired else 'single-ended'))
+        if not piece.is_cut and piece.n_reads == 0:
+            continue
+        held = streams[piece.stream]
+        first = piece.first_read
+        while held and held[-1].first_read >= first:
+            held.pop()
+        if held and held[-1].first_read + held[-1].n_reads > first:
+            held[-1] = _slice_piece(held[-1], 0, first - held[-1].first_read)
+        if piece.is_cut:
+            continue
+        if held and held[-1].first_read + held[-1].n_reads != first:
+            raise ValueError('the reads of stream %d do not follow each other (unit %d after %d)'
+                             % (piece.stream, first, held[-1].first_read + held[-1].n_reads))
+        held.append(piece.held())
+    if not paired:
+        return [(piece.first_read, piece, None) for piece in streams[0]]
+    segments = []
+    i = j = 0
+    while i < len(streams[0]) and j < len(streams[1]):
+        a, b = streams[0][i], streams[1][j]
+        begin = max(a.first_read, b.first_read)
+        end = min(a.first_read + a.n_reads, b.first_read + b.n_reads)
+        if begin < end:
+            segments.append((begin,) + tuple(
+                piece if (piece.first_read, piece.n_reads) == (begin, end - begin)
+                else _slice_piece(piece, begin - piece.first_read, end - piece.first_read) for piece in (a, b)))
+        if a.first_read + a.n_reads <= b.first_read + b.n_reads:
+            i += 1
+        else:
+            j += 1
+    return segments
+
+
+def _effective_lengths(lengths, fld, device):
+    """MapResult.effective_lengths (seekmer/mapper.py:134-141) for a histogram, on the GPU."""
+    out = numpy.zeros(lengths.shape, dtype='f8')
+    _native.check(_native.hip().skm_effective_lengths(
+        device, _native.ptr(numpy.ascontiguousarray(fld, dtype=numpy.int64), _native.c_i64p),
+        _native.ptr(lengths, _native.c_f64p), lengths.size, _native.ptr(out, _native.c_f64p)))
+    return out
+
+
+class SampleSet:
+    """Many small samples on one device handle (skm_sample_set): their units share launches and one
+    class table whose classes are (sample, target tuple).  Every sample's table -- class order,
+    offsets, targets, counts, first-seen units counted inside the sample, unaligned and total units --
+    is bit for bit that of a MapResult fed the sample's reads alone, however the samples are
+    interleaved, cut into launches or spread over feeding threads.
+
+    The set keeps ONE fragment-length histogram, the sum over its samples: what
+    impute.pool_fragment_lengths gives every cell (seekmer/impute.py:128-146).  There is no per-sample
+    histogram, and no readmap.  ``strand`` (None, 'fr', 'rf') applies to every sample.
+
+    Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
+    where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
+
+    def __init__(self, index, paired, device=0, strand=None):
+        mode = strand_mode(strand)
+        self.index = index
+        self.paired = bool(paired)
+        self.device = device
+        self.strand = strand
+        self._handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_sample_set_create(index.device_handle(device), int(self.paired),
+                                                          ctypes.byref(self._handle)))
+        if mode != _native.SKM_STRAND_NONE:
+            _native.check(_native.hip().skm_sample_set_set_strand(self._handle, mode))
+
+    def __del__(self):
+        handle = getattr(self, '_handle', None)
+        if handle:
+            try:
+                _native.hip().skm_sample_set_destroy(handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    def add_packed(self, sample, first_unit, mate1, mate2=None):
+        """Units [first_unit, first_unit + n) of `sample` as common.PackedReads (mate2: paired sets)."""
+        if (mate2 is not None) != self.paired:
+            raise ValueError('a %s set takes %s' % (('paired', 'both mates') if self.paired else ('single-ended', 'mate 1 alone')))
+        _native.check(_native.hip().skm_sample_set_add_packed(
+            self._handle, int(sample), int(first_unit), ctypes.byref(mate1.raw),
+            ctypes.byref(mate2.raw) if mate2 is not None else None))
+
+    def add_batch(self, sample, first_unit, batch):
+        """The same for a common.ReadBatch (text: bases back to back + offsets)."""
+        if batch.count and bool(batch.paired) != self.paired:
+            raise ValueError('a %s batch for a %s set' % ('paired' if batch.paired else 'single-ended',
+                                                          'paired' if self.paired else 'single-ended'))
+        _native.check(_native.hip().skm_sample_set_add_batch(
+            self._handle, int(sample), int(first_unit), batch.bases.ctypes.data,
+            _native.ptr(batch.offsets, _native.c_i64p), batch.count))
+
+    def add_sample(self, sample, read_feeder):
+        """All reads of `sample` from a feeder of its own: a common.PackedReadFeeder (parsed completely
+        by this thread, then added as in-order segments) or an iterable of ReadBatch / (count, names,
+        reads) items.  Returns the sample's units."""
+        units = 0
+        pieces = []
+        for item in read_feeder:
+            if isinstance(item, PackedReads):
+                pieces.append(item.held())            # (a reader's piece is valid until its next one)
+                continue
+            if pieces:
+                raise ValueError('packed and text reads in one sample')
+            batch = item if isinstance(item, ReadBatch) else ReadBatch.from_lists(*item)
+            self.add_batch(sample, units, batch)
+            units += batch.count
+        for first_unit, mate1, mate2 in sample_segments(pieces, self.paired):
+            if first_unit != units:
+                raise ValueError('sample %d: its reads begin at unit %d, not %d' % (sample, first_unit, units))
+            self.add_packed(sample, first_unit, mate1, mate2)
+            units = first_unit + mate1.n_reads
+        if units == 0:
+            self.add_batch(sample, 0, ReadBatch(0, numpy.zeros(0, dtype=numpy.uint8), numpy.zeros(1, dtype=numpy.int64),
+                                                self.paired))
+        return units
+
+    def sync(self):
+        """Wait for everything added to be mapped; raises the set's failure."""
+        _native.check(_native.hip().skm_sample_set_sync(self._handle))
+
+    def __bool__(self):
+        return True                   # (a handle, not a container: its truth waits for nothing)
+
+    def __len__(self):
+        """The samples added so far (nothing is waited for)."""
+        n = ctypes.c_int64()
+        _native.check(_native.hip().skm_sample_set_summary(self._handle, 0, ctypes.byref(n), None))
+        return n.value
+
+    def sizes(self):
+        """int64[n_samples, 4]: per sample (classes, class_map rows, unaligned, total units) -- MapResult.sizes()."""
+        n = ctypes.c_int64(len(self))
+        out = numpy.zeros((n.value, 4), dtype=numpy.int64)
+        _native.check(_native.hip().skm_sample_set_summary(self._handle, n.value, ctypes.byref(n),
+                                                           _native.ptr(out, _native.c_i64p) if out.size else None))
+        return out
+
+    @property
+    def fragment_length_counts(self):
+        """The set's one histogram: the sum over all its samples."""
+        fld = numpy.zeros(MAX_FRAGMENT_LENGTH, dtype=numpy.int64)
+        _native.check(_native.hip().skm_sample_set_histogram(self._handle, _native.ptr(fld, _native.c_i64p)))
+        return fld
+
+    def export(self):
+        """[(class_offsets, class_targets, class_counts, first_seen), ...] per sample, each as
+        MapResult.export() gives them for the sample alone (first_seen counted inside the sample)."""
+        sizes = self.sizes()
+        n_classes, n_rows = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
+        bounds = numpy.zeros(len(sizes) + 1, dtype=numpy.int64)
+        offsets = numpy.zeros(n_classes + 1, dtype=numpy.int64)
+        targets = numpy.zeros(max(n_rows, 1), dtype=numpy.int32)
+        counts = numpy.zeros(max(n_classes, 1), dtype=numpy.int64)
+        first = numpy.zeros(max(n_classes, 1), dtype=numpy.int64)
+        _native.check(_native.hip().skm_sample_set_export(
+            self._handle, _native.ptr(bounds, _native.c_i64p), _native.ptr(offsets, _native.c_i64p),
+            _native.ptr(targets, _native.c_i32p), _native.ptr(counts, _native.c_i64p), _native.ptr(first, _native.c_i64p)))
+        tables = []
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            rows = offsets[lo:hi + 1]
+            tables.append((rows - rows[0], targets[rows[0]:rows[-1]].copy(), counts[lo:hi].copy(), first[lo:hi].copy()))
+        return tables
+
+    def summarize(self):
+        """[SummarizedResult, ...] per sample, as MapResult.summarize() (seekmer/mapper.py:77-104); every
+        item carries the POOLED histogram and the effective lengths that follow from it (one shared,
+        read-only pair of arrays), i.e. what the samples' MapResults hold after impute.pool_fragment_lengths."""
+        sizes = self.sizes()
+        tables = self.export()
+        fld = self.fragment_length_counts
+        lengths = numpy.ascontiguousarray(self.index.transcripts['length'], dtype='f8')
+        effective = _effective_lengths(lengths, fld, self.device)
+        fld.setflags(write=False)
+        effective.setflags(write=False)
+        summaries = []
+        for (offsets, targets, counts, _), (_, _, unaligned, _) in zip(tables, sizes):
+            if targets.size:
+                class_ids = numpy.repeat(numpy.arange(counts.size, dtype=numpy.int64), numpy.diff(offsets))
+                class_map = numpy.vstack([class_ids, targets.astype(numpy.int64)])
+            else:
+                class_map = numpy.asarray([]).T
+            class_count = counts.astype('f8')
+            aligned = class_count.sum()
+            summaries.append(SummarizedResult(
+                aligned=int(aligned), unaligned=int(unaligned), total=int(aligned + unaligned), class_map=class_map,
+                class_count=class_count, fragment_length_frequencies=fld, effective_lengths=effective,
+                class_offsets=offsets, class_targets=targets))
+        return summaries
+
+
+def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None):
+    """map_multiple_samples for many small samples (single cells): sample i = read_feeders[i], all of
+    them mapped through ONE SampleSet in shared launches.  Each of `job_count` threads takes a sample
+    at a time, parses its files completely and adds it; results do not depend on the thread count.
+    The feeders must agree on paired / single-ended.  strand: None, 'fr' or 'rf' for every sample.
+    A failed sample raises."""
+    strand_mode(strand)
+    read_feeders = list(read_feeders)
+    if job_count < 1:
+        raise ValueError('job_count must be at least 1, not %r' % (job_count,))
+    if not read_feeders:
+        raise ValueError('no samples')
+    layouts = {bool(feeder.paired) for feeder in read_feeders}     # (every feeder of common says which it is)
+    if len(layouts) != 1:
+        raise ValueError('paired and single-ended samples in one set')
+    sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand)
+    if job_count == 1:
+        for sample, read_feeder in enumerate(read_feeders):
+            sample_set.add_sample(sample, read_feeder)
+    else:
+        pool = multiprocessing.pool.ThreadPool(job_count)
+        pending = [pool.apply_async(sample_set.add_sample, args=(sample, read_feeder))
+                   for sample, read_feeder in enumerate(read_feeders)]
+        pool.close()
+        pool.join()
+        for job in pending:
+            job.get()                     # re-raises what the worker raised
+    sample_set.sync()
+    return sample_set
