@@ -310,7 +310,7 @@ struct skm_quant {
         DBuf<int64_t> tile_tx, tile_cls, cls_pair, tx_pair;
         DBuf<int32_t> tx_list, cls_list, tx_label, tx_tile, cls_tile;
         DBuf<uint16_t> cls_tx, tx_cls;
-        DBuf<double> x2, step_max;            // x2: third abundance vector (a chunk's input outlives the chunk after it)
+        DBuf<double> snap, step_max;          // snap: [EM_CHUNK_MAX][T] every step's abundances of the chunk in flight
         DBuf<unsigned int> step_flags;
         // the components above the capacity as an EM problem beside the tiles (QuantResidual)
         struct Residual {
@@ -2754,7 +2754,6 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
         SKM_TRY(t.tx_list.ensure(T)); SKM_TRY(t.cls_list.ensure(C));
         SKM_TRY(t.tx_label.ensure(T)); SKM_TRY(t.tx_tile.ensure(T)); SKM_TRY(t.cls_tile.ensure(C));
         SKM_TRY(t.cls_tx.ensure(M)); SKM_TRY(t.tx_cls.ensure(M));
-        SKM_TRY(t.x2.ensure(T));
     }
     STALE_CHECK("quant_alloc exit");
     return SKM_OK;
@@ -2774,7 +2773,7 @@ QuantBuild quant_build_view(skm_quant *q)
     b.row_start = q->row_start.p;
     b.row_tx = q->row_tx.p;
     b.n_rows_cap = (int64_t)q->row_tx.cap;
-    if (q->tiles.x2.p) {                       // (quant_alloc made room for the tiles)
+    if (q->tiles.tile_tx.p) {                      // (quant_alloc made room for the tiles)
         auto &t = q->tiles;
         b.tile_tx = t.tile_tx.p; b.tile_cls = t.tile_cls.p;
         b.tx_list = t.tx_list.p; b.cls_list = t.cls_list.p;
@@ -2800,6 +2799,7 @@ int quant_finish_setup(skm_quant *q, const ClassTable *table, int64_t units_seen
         if (q->tiles.n_tiles > 0) {
             SKM_TRY(q->tiles.step_max.ensure((size_t)(EM_CHUNK_MAX * q->tiles.n_tiles)));
             SKM_TRY(q->tiles.step_flags.ensure((size_t)(EM_CHUNK_MAX * q->tiles.n_tiles)));
+            SKM_TRY(q->tiles.snap.ensure((size_t)EM_CHUNK_MAX * (size_t)q->n_tx));
         }
         if (q->tiles.n_oversize > 0 && q->tiles.n_tiles > 0) {
             // tiles AND components above the capacity: those become the residual problem (a table that
@@ -2921,11 +2921,11 @@ bool em_uses_tiles(const skm_quant *q)
 }
 
 // The component form of em_run's loop (after its preamble: control block cleared, ev[0] recorded).  Every
-// chunk is ONE launch that steps all the tiles `chunk` times in LDS, from abundance vector i % 3 to
-// (i + 1) % 3 of three, plus the one-block launch that judges the chunk's steps in order.  The host
-// stays one chunk ahead as before.  The tiles of the chunk in which the EM stops (at step K) have run
-// to the chunk's end, so that chunk is replayed from its input -- still there: the chunk after it wrote
-// the third vector -- for exactly K - first steps into x[K & 1], where the callers look for the result.
+// chunk is ONE launch that steps all the tiles `chunk` times in LDS and leaves every step's abundances in
+// the snapshot buffer -- the next chunk starts from the last of them -- plus the one-block launch that
+// judges the chunk's steps in order.  The host stays one chunk ahead as before; the look-ahead chunk that
+// finds the EM stopped (at step K) copies the tiles' entries of step K from the snapshots to x[K & 1],
+// where the callers look for the result: no step runs twice and the stop costs no launch of its own.
 constexpr int CTL_WORD_TILE_FAULT = 4;        // control block word em_local_chunk_kernel raises (skm_em.hip: CTL_TILE_FAULT)
 int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters_out)
 {
@@ -2937,7 +2937,7 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
     tl.cls_pair = t.cls_pair.p; tl.tx_pair = t.tx_pair.p;
     tl.cls_tx = t.cls_tx.p; tl.tx_cls = t.tx_cls.p;
     tl.step_max = t.step_max.p; tl.step_flags = t.step_flags.p;
-    double *const x[3] = {q->x0.p, q->x1.p, t.x2.p};
+    tl.snap = t.snap.p;
     // With components above the capacity the residual problem runs beside the tiles, step by step with
     // the whole-table kernels on its own classes and rows (its transcripts' entries of x0 / x1; the
     // tiles' entries are the tiles' alone), and ITS judge takes the tiles' partials of the step along.
@@ -2955,7 +2955,7 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
     }
     int64_t queued = 0;
     auto enqueue_chunk = [&](int slot) -> int {
-        launch_em_local_chunk(p, tl, x[queued % 3], x[(queued + 1) % 3], (int)chunk, true, q->stream);
+        launch_em_local_chunk(p, tl, queued == 0 ? q->x0.p : t.snap.p + (chunk - 1) * q->n_tx, (int)chunk, queued * chunk, q->stream);
         if (mixed) {
             pr.extra_first = queued * chunk;
             for (int64_t i = 0, k = queued * chunk; i < chunk; ++i, ++k) {
@@ -2977,8 +2977,7 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
     };
     unsigned long long ctl[8] = {0};
     SKM_TRY(enqueue_chunk(0));
-    int64_t last = 0;                                     // the chunk whose verdict has been read
-    for (int slot = 0;; slot ^= 1, ++last) {
+    for (int slot = 0;; slot ^= 1) {
         SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
         HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
         memcpy(ctl, q->pinned + 8 * slot, sizeof(ctl));
@@ -2990,20 +2989,8 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
         HIP_TRY(hipStreamSynchronize(q->stream));
         return fail(SKM_ERR_STATE, "a component tile exceeds the tile capacity: the class views of this handle are damaged");
     }
-    const int64_t steps = (int64_t)ctl[1], into = steps - last * chunk;      // 1 .. chunk steps into chunk `last`
-    double *const result = (steps & 1) ? q->x1.p : q->x0.p;
-    // (beside a residual the last chunk is replayed also when the EM stopped on its last step and
-    // x[(last + 1) % 3] holds the tiles' result already: a whole-vector copy would overwrite the residual's
-    // entries, and a copy of the tiles' entries alone is a kernel this path does not have yet -- up to
-    // `chunk` steps of tile work, once per run, on such tables)
-    if (into == chunk && !mixed) {
-        if (x[(last + 1) % 3] != result)
-            HIP_TRY(hipMemcpyAsync(result, x[(last + 1) % 3], q->n_tx * 8, hipMemcpyDeviceToDevice, q->stream));
-    } else {
-        launch_em_local_chunk(p, tl, x[last % 3], result, (int)into, false, q->stream);
-        q->launches += 1;
-        HIP_TRY(hipGetLastError());
-    }
+    // (the look-ahead chunk, queued above, is the copy of step `steps` of the tiles to x[steps & 1])
+    const int64_t steps = (int64_t)ctl[1];
     HIP_TRY(hipEventRecord(q->ev[1], q->stream));
     HIP_TRY(hipEventSynchronize(q->ev[1]));
     float ms = 0;

@@ -338,7 +338,11 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 // One workgroup per tile.  The tile's pairs in both views (16-bit tile-local indices), the class counts,
 // `inner`, the effective lengths and both abundance vectors live in LDS for the whole chunk; a step is
 //   class phase  one lane per class: S_c over the tuple in tuple order, inner_c = S_c / count_c
-//                (the arithmetic of em_inner_kernel)
+//                (the arithmetic of em_inner_kernel).  A lane takes EM_CLASS_BATCH entries at a time: the
+//                indices, then the abundances -- all of them in flight at once -- and adds them one after
+//                the other in tuple order; an entry past the tuple's end is not added (a select: adding
+//                +0.0 would turn a sum of -0.0 into +0.0).  The set-up lists a tile's classes by the
+//                number of such batches, so the 64 classes of a wave take like numbers of turns.
 //   row phase    eight lanes per transcript, its rows of <= EM_ROW_CAP entries one after the other: lane
 //                `sub` adds x_t / inner_c for entries begin + sub + 8 k in ascending k, the xor 4, 2, 1
 //                butterfly, the row sums added in row order from 0.0, then x'_t = a / l_t / n, NaN -> 0
@@ -346,11 +350,28 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 //                association)
 // with two workgroup barriers and nothing that crosses workgroups.  Each step's partials of the stopping
 // rule go to step_max / step_flags [step][tile]; em_local_decide_kernel judges the steps in order.
+// Every step's abundances also go to tl.snap[step][transcript]: the next chunk starts from the last of
+// them, and the launch that finds the EM stopped -- the look-ahead chunk, which would otherwise do
+// nothing -- copies its tile's entries of the step the rule was met at to p.x[steps & 1], where the
+// callers look for the result.  No step is run twice, and the copy names the tile's transcripts only,
+// so it serves beside a residual problem that keeps its own entries of p.x.
+//
+// Timing experiments only (scripts/build_variant.sh; the results of these builds are wrong):
+// 1 = no class phase (inner is left as loaded: garbage), 2 = no row phase (x is never stepped).
+#ifndef SKM_EM_TILE_EXPERIMENT
+#define SKM_EM_TILE_EXPERIMENT 0
+#endif
+// entries of a class tuple fetched together (1: one after the other, the form this kernel began with)
+#ifndef SKM_EM_CLASS_BATCH
+#define SKM_EM_CLASS_BATCH 4
+#endif
+constexpr int EM_CLASS_BATCH = SKM_EM_CLASS_BATCH;
+static_assert(EM_CLASS_BATCH == EM_TILE_CLASS_BATCH || EM_CLASS_BATCH == 1, "the set-up orders classes by turns of this width");
+
 __global__ void __launch_bounds__(256)
-em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out, int n_steps, int check_done)
+em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, int n_steps, int64_t first_step)
 {
     static_assert(EM_TILE_TX <= 8 * 32, "a lane group of the row phase takes at most eight transcripts");
-    if (check_done && p.ctl[CTL_DONE]) return;
     __shared__ double s_x[2][EM_TILE_TX];
     __shared__ double s_eff[EM_TILE_TX];
     __shared__ double s_inner[EM_TILE_CLASSES];
@@ -372,6 +393,21 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out
         return;
     }
     const int tid = threadIdx.x;
+    if (p.ctl[CTL_DONE]) {                      // (block-uniform)
+        // The EM stopped in the chunk before this one, `at` steps into it: that step's abundances of
+        // this tile's transcripts are the result.  (Nothing is copied after a tile fault -- the run
+        // fails -- and the range check keeps a control block that a faulting tile of this very launch
+        // is writing from naming a step outside the buffer.)
+        const int64_t steps = (int64_t)p.ctl[CTL_ITERS], at = steps - 1 - (first_step - n_steps);
+        if (p.ctl[CTL_TILE_FAULT] || first_step < n_steps || at < 0 || at >= n_steps) return;
+        const double *__restrict__ from = tl.snap + at * p.n_tx;
+        double *__restrict__ to = p.x[steps & 1];
+        for (int i = tid; i < n_tx; i += 256) {
+            const int32_t t = tl.tx_list[tx0 + i];
+            to[t] = from[t];
+        }
+        return;
+    }
     for (int j = tid; j < n_pairs; j += 256) {
         s_cls_tx[j] = tl.cls_tx[cp0 + j];
         s_tx_cls[j] = tl.tx_cls[tp0 + j];
@@ -379,6 +415,7 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out
     for (int k = tid; k <= n_cls; k += 256) {
         s_cls_off[k] = (uint16_t)(tl.cls_pair[cls0 + k] - cp0);
         if (k < n_cls) s_count[k] = p.cls_count[tl.cls_list[cls0 + k]];
+        if ((SKM_EM_TILE_EXPERIMENT & 1) && k < n_cls) s_inner[k] = 1.0;
     }
     for (int i = tid; i <= n_tx; i += 256) {
         s_tx_off[i] = (uint16_t)(tl.tx_pair[tx0 + i] - tp0);
@@ -394,11 +431,31 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out
     for (int step = 0; step < n_steps; ++step) {
         const double *x = s_x[step & 1];
         double *x_new = s_x[(step & 1) ^ 1];
-        for (int k = tid; k < n_cls; k += 256) {
-            const int end = s_cls_off[k + 1];
-            double s = 0.0;
-            for (int j = s_cls_off[k]; j < end; ++j) s += x[s_cls_tx[j]];
-            s_inner[k] = s / s_count[k];
+        if (!(SKM_EM_TILE_EXPERIMENT & 1)) {
+            for (int k = tid; k < n_cls; k += 256) {
+                const int end = s_cls_off[k + 1];
+                double s = 0.0;
+                if (EM_CLASS_BATCH == 1) {
+                    for (int j = s_cls_off[k]; j < end; ++j) s += x[s_cls_tx[j]];
+                } else {
+                    for (int j = s_cls_off[k]; j < end; j += EM_CLASS_BATCH) {
+                        // (an entry past the end re-reads the tuple's last: a valid place, never added)
+                        int t[EM_CLASS_BATCH];
+                        double v[EM_CLASS_BATCH];
+#pragma unroll
+                        for (int b = 0; b < EM_CLASS_BATCH; ++b) t[b] = s_cls_tx[min(j + b, end - 1)];
+#pragma unroll
+                        for (int b = 0; b < EM_CLASS_BATCH; ++b) v[b] = x[t[b]];
+                        s += v[0];
+#pragma unroll
+                        for (int b = 1; b < EM_CLASS_BATCH; ++b) {
+                            const double with = s + v[b];
+                            s = j + b < end ? with : s;
+                        }
+                    }
+                }
+                s_inner[k] = s / s_count[k];
+            }
         }
         __syncthreads();
         double local_max = 0.0;
@@ -408,27 +465,30 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out
         // three divisions of the finalize run once per wave, not once per transcript of a group)
         double my_a = 0.0, my_xt = 0.0;
         int my_i = -1, turn = 0;
-        for (int i = tid >> 3; i < n_tx; i += 32, ++turn) {
-            const double xt = x[i];
-            const int end = s_tx_off[i + 1];
-            int begin = s_tx_off[i];
-            double a = 0.0;
-            do {                                    // (a transcript in no class has one empty row)
-                const int row_end = min(begin + EM_ROW_CAP, end);
-                double s = 0.0;
-                for (int e = begin + sub; e < row_end; e += 8) s += xt / s_inner[s_tx_cls[e]];
-                s += __shfl_xor(s, 4, 8);
-                s += __shfl_xor(s, 2, 8);
-                s += __shfl_xor(s, 1, 8);
-                a += s;
-                begin = row_end;
-            } while (begin < end);
-            if (turn == sub) { my_a = a; my_xt = xt; my_i = i; }
+        if (!(SKM_EM_TILE_EXPERIMENT & 2)) {
+            for (int i = tid >> 3; i < n_tx; i += 32, ++turn) {
+                const double xt = x[i];
+                const int end = s_tx_off[i + 1];
+                int begin = s_tx_off[i];
+                double a = 0.0;
+                do {                                    // (a transcript in no class has one empty row)
+                    const int row_end = min(begin + EM_ROW_CAP, end);
+                    double s = 0.0;
+                    for (int e = begin + sub; e < row_end; e += 8) s += xt / s_inner[s_tx_cls[e]];
+                    s += __shfl_xor(s, 4, 8);
+                    s += __shfl_xor(s, 2, 8);
+                    s += __shfl_xor(s, 1, 8);
+                    a += s;
+                    begin = row_end;
+                } while (begin < end);
+                if (turn == sub) { my_a = a; my_xt = xt; my_i = i; }
+            }
         }
         if (my_i >= 0) {
             double v = my_a / s_eff[my_i] / p.n_total;                    // infer.py:158
             if (v != v) v = 0.0;                                          // infer.py:159
             x_new[my_i] = v;
+            tl.snap[step * p.n_tx + s_tx[my_i]] = v;
             if (v > p.x_floor) {                                          // infer.py:160
                 const double change = fabs(v - my_xt) / v;
                 if (change != change) flags |= 2u;
@@ -444,8 +504,6 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, double *x_out
         if ((tid & 63) == 0) { s_max[step][wave] = local_max; s_flags[step][wave] = flags; }
         __syncthreads();
     }
-    const double *x = s_x[n_steps & 1];
-    for (int i = tid; i < n_tx; i += 256) x_out[s_tx[i]] = x[i];
     if (tid < n_steps) {
         double m = s_max[tid][0];
         unsigned int f = s_flags[tid][0];
@@ -843,12 +901,12 @@ void launch_em_rows_acc(const EmProblem &p, int parity, hipStream_t stream)
     hipLaunchKernelGGL(em_rows_finalize_kernel<true>, dim3((unsigned)em_final_blocks(fused)), dim3(256), 0, stream, p, parity);
 }
 
-void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, double *x_out, int n_steps,
-                           bool check_done, hipStream_t stream)
+void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, int n_steps, int64_t first_step,
+                           hipStream_t stream)
 {
     if (tiles.n_tiles <= 0 || n_steps <= 0) return;
-    hipLaunchKernelGGL(em_local_chunk_kernel, dim3((unsigned)tiles.n_tiles), dim3(256), 0, stream, p, tiles, x_in, x_out,
-                       std::min(n_steps, EM_CHUNK_MAX), check_done ? 1 : 0);
+    hipLaunchKernelGGL(em_local_chunk_kernel, dim3((unsigned)tiles.n_tiles), dim3(256), 0, stream, p, tiles, x_in,
+                       std::min(n_steps, EM_CHUNK_MAX), first_step);
 }
 
 void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream)

@@ -247,25 +247,34 @@ void launch_em_result(const unsigned long long *ctl, const double *x0, const dou
 // EM_TILE_TX transcripts; one workgroup keeps a tile's two views, `inner` and both abundance vectors in
 // LDS and runs a whole chunk of steps with workgroup barriers only.
 constexpr int EM_TILE_PAIRS = 2048, EM_TILE_CLASSES = 512, EM_TILE_TX = 128;
-constexpr int EM_TILE_SEGMENT = 128;     // tiles are packed within runs of this many transcript ids (set-up)
+#ifndef SKM_EM_TILE_SEGMENT              // (a sweep aid, scripts/build_variant.sh: results do not depend on it)
+#define SKM_EM_TILE_SEGMENT 128
+#endif
+constexpr int EM_TILE_SEGMENT = SKM_EM_TILE_SEGMENT;     // tiles are packed within runs of this many transcript ids (set-up)
 constexpr int EM_CHUNK_MAX = 16;         // steps of one launch at most
+constexpr int EM_TILE_CLASS_BATCH = 4;   // tuple entries a lane of the class phase fetches together; the set-up
+                                         // lists a tile's classes by their number of such batches
 struct EmTiles {
     int64_t n_tiles;
     const int64_t *tile_tx;       // [n_tiles + 1] first place of tile i in tx_list
     const int64_t *tile_cls;      // [n_tiles + 1] first place of tile i in cls_list
     const int32_t *tx_list;       // [T] transcript ids, tile by tile (inside a tile: those of many pairs first)
-    const int32_t *cls_list;      // [C] internal class indices, tile by tile, ascending inside a tile
+    const int32_t *cls_list;      // [C] internal class indices, tile by tile (inside a tile: those of many batches
+                                  //     of EM_TILE_CLASS_BATCH entries first, ascending among equals)
     const int64_t *cls_pair;      // [C + 1] by place in cls_list: first pair of the class in cls_tx
     const int64_t *tx_pair;       // [T + 1] by place in tx_list: first pair of the transcript in tx_cls
     const uint16_t *cls_tx;       // [M] tile-local transcript of every pair, class-major, tuple order
     const uint16_t *tx_cls;       // [M] tile-local class of every pair, transcript-major, internal class order
     double *step_max;             // [EM_CHUNK_MAX][n_tiles] the tiles' partials of the stopping rule, per step
     unsigned int *step_flags;     // [EM_CHUNK_MAX][n_tiles] bit0 = any, bit1 = nan
+    double *snap;                 // [EM_CHUNK_MAX][T] the tiles' abundances after every step of the chunk in flight
 };
-// n_steps (<= EM_CHUNK_MAX) steps of every tile from x_in to x_out (x_in == x_out is allowed: a tile reads
-// and writes its own transcripts only); check_done: a no-op once the control block says stopped
-void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, double *x_out, int n_steps,
-                           bool check_done, hipStream_t stream);
+// Steps first_step + 1 .. first_step + n_steps (n_steps <= EM_CHUNK_MAX, the same for every chunk of a run) of
+// every tile, from x_in (a tile reads its own transcripts only) to tiles.snap[0 .. n_steps).  Once the control
+// block says stopped, the launch instead copies the tiles' entries of the step the EM stopped at -- one of the
+// chunk before, still in tiles.snap -- to p.x[steps & 1].
+void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, int n_steps, int64_t first_step,
+                           hipStream_t stream);
 // the stopping rule for steps first_step + 1 .. first_step + n_steps in order: latches the first that stops
 void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream);
 

@@ -896,14 +896,29 @@ tx_tile_kernel(const int32_t *label, const int32_t *root_tile, const int64_t *se
     }
 }
 
+// (tuning aid, scripts/build_variant.sh: 0 lists a tile's classes by ascending index alone, as before the
+// class phase took its tuples in batches; the EM's results are the same either way)
+#ifndef SKM_EM_CLASS_ORDER
+#define SKM_EM_CLASS_ORDER 1
+#endif
+// tile of every class, and the key its place in the tile's list is sorted by: the tile, then
+// (length_bits > 0) classes of many batches first -- a lane of em_local_chunk_kernel's class phase takes
+// its tuple EM_TILE_CLASS_BATCH entries at a time and a wave loops as long as the longest of its 64
+// classes, so neighbours in the list should take like numbers of turns.  A class's place in the list is a
+// label only: the tuple keeps its order and every row of the transcript view keeps its entries' order
+// (tile_fill_tx_kernel), so no sum changes.
 __global__ void __launch_bounds__(256)
 cls_tile_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, const int32_t *tx_tile,
-                int32_t *cls_tile)
+                int length_bits, int32_t *cls_tile, int32_t *key)
 {
     for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
          c += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t begin = cls_offset[c];
-        cls_tile[c] = tx_tile[begin < cls_offset[c + 1] ? ids[begin] : 0];
+        const int64_t begin = cls_offset[c], end = cls_offset[c + 1];
+        const int32_t tile = tx_tile[begin < end ? ids[begin] : 0];
+        cls_tile[c] = tile;
+        const int64_t turns = (end - begin + EM_TILE_CLASS_BATCH - 1) / EM_TILE_CLASS_BATCH;
+        const int32_t longest = (1 << length_bits) - 1;
+        key[c] = (tile << length_bits) | (longest - (int32_t)min(turns, (int64_t)longest));
     }
 }
 
@@ -936,13 +951,13 @@ tile_local_tx_kernel(const int32_t *list, const int32_t *tile_sorted, int shift,
 }
 
 __global__ void __launch_bounds__(256)
-tile_local_cls_kernel(const int32_t *list, const int32_t *tile_sorted, const int64_t *first, const int64_t *n_tiles, int64_t n,
+tile_local_cls_kernel(const int32_t *list, const int32_t *tile_sorted, int shift, const int64_t *first, const int64_t *n_tiles, int64_t n,
                       const int64_t *cls_offset, int32_t *local, int64_t *len)
 {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n;
          k += (int64_t)gridDim.x * blockDim.x) {
         const int32_t c = list[k];
-        local[c] = (int32_t)(k - first[min((int64_t)tile_sorted[k], *n_tiles)]);
+        local[c] = (int32_t)(k - first[min((int64_t)(tile_sorted[k] >> shift), *n_tiles)]);
         len[k] = cls_offset[c + 1] - cls_offset[c];
     }
 }
@@ -1008,7 +1023,8 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
     QB_ALLOC(tx_key, int32_t, T);
     hipLaunchKernelGGL(tx_tile_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_label, root_tile, seg_base, T,
                        q.tx_row, q.row_start, degree_bits, q.tx_tile, tx_key);
-    // transcripts by tile (stable: ascending ids inside a tile), then the classes the same way
+    // transcripts by tile and turns of the row phase (stable: ascending ids among equals), then the classes the
+    // same way by tile and turns of the class phase
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(std::max(T, C))), dim3(256), 0, stream, iota, std::max(T, C));
     if (sort_pairs(scratch, tx_key, sorted_tile, iota, q.tx_list, T, end_bit + degree_bits)) return -1;
     hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(T + 1)), dim3(256), 0, stream, sorted_tile, degree_bits, T,
@@ -1016,12 +1032,14 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
     hipLaunchKernelGGL(tile_local_tx_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_list, sorted_tile, degree_bits,
                        q.tile_tx, seg_base + n_segments, T, q.tx_row, q.row_start, tx_local, len);
     if (exclusive_scan_with_total(scratch, len, q.tx_pair, T)) return -1;
+    const int length_bits = SKM_EM_CLASS_ORDER ? degree_bits : 0;
+    QB_ALLOC(cls_key, int32_t, C);
     hipLaunchKernelGGL(cls_tile_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, q.tx_tile,
-                       q.cls_tile);
-    if (sort_pairs(scratch, q.cls_tile, sorted_tile, iota, q.cls_list, C, end_bit)) return -1;
-    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(C + 1)), dim3(256), 0, stream, sorted_tile, 0, C,
+                       length_bits, q.cls_tile, cls_key);
+    if (sort_pairs(scratch, cls_key, sorted_tile, iota, q.cls_list, C, end_bit + length_bits)) return -1;
+    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(C + 1)), dim3(256), 0, stream, sorted_tile, length_bits, C,
                        seg_base + n_segments, q.tile_cls);
-    hipLaunchKernelGGL(tile_local_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, sorted_tile,
+    hipLaunchKernelGGL(tile_local_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, sorted_tile, length_bits,
                        q.tile_cls, seg_base + n_segments, C, q.cls_offset, cls_local, len);
     if (exclusive_scan_with_total(scratch, len, q.cls_pair, C)) return -1;
     hipLaunchKernelGGL(tile_fill_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, C, q.cls_offset,
