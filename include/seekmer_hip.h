@@ -301,9 +301,10 @@ int skm_mapper_access_stats(skm_mapper *mapper, int64_t out[48]);
  * hold the same tuple keep separate classes: a record's 64-bit class key is that of (sample, tuple),
  * and two different tuples that meet in one slot fail the call with SKM_ERR_COLLISION as they do in a
  * mapper; counts are exact or the call fails.
- * The FRAGMENT-LENGTH HISTOGRAM is one for the whole set: the sum over all its samples, which is
- * what impute.pool_fragment_lengths gives every cell before anything reads it
- * (seekmer/impute.py:128-146).  There is no per-sample histogram.
+ * The FRAGMENT-LENGTH HISTOGRAM of the set is the sum over all its samples, which is what
+ * impute.pool_fragment_lengths gives every cell before anything reads it
+ * (seekmer/impute.py:128-146).  A set asked to (skm_sample_set_keep_histograms, before the first
+ * unit) also keeps one histogram per sample, each that of a mapper fed the sample's reads alone.
  * The strand mode (skm_mapper_set_strand) applies to the whole set.  Read names (-m) are not kept.
  *
  * Samples are numbered 0, 1, ... by the caller (below 2^24); the set holds the samples 0 .. the
@@ -347,8 +348,22 @@ int skm_sample_set_summary(skm_sample_set *set, int64_t cap_samples, int64_t *n_
 int skm_sample_set_export(skm_sample_set *set, int64_t *sample_class_offsets,
                           int64_t *class_offsets, int32_t *class_targets, int64_t *class_counts,
                           int64_t *first_seen);
-/* fld[2000]: the set's one histogram, summed over its samples */
+/* fld[2000]: the set's pooled histogram, summed over its samples (with or without histograms
+ * per sample) */
 int skm_sample_set_histogram(skm_sample_set *set, int64_t *fld);
+/* enable != 0: the set also keeps one fragment-length histogram per sample, in HBM.  Its mapper then
+ * stores every unit's span (skm_mapper_keep_spans: 16 bytes a unit) and a kernel after each launch
+ * counts the spans' lengths by the unit's sample (sample_fld_kernel, skm_samples.hip).  Only while
+ * the set holds no units (SKM_ERR_STATE otherwise).  The histograms are rows of 16 KB indexed by the
+ * sample NUMBER, so such a set numbers its samples below 2^16 (1 GiB of rows): an add call that
+ * names a larger one fails with SKM_ERR_ARG. */
+int skm_sample_set_keep_histograms(skm_sample_set *set, int enable);
+/* fld[n_samples][2000], in sample order: row i is the histogram of a mapper fed sample i alone (all
+ * zero for a sample without units); the rows add up to skm_sample_set_histogram.  Waits for
+ * everything added to be mapped and keeps adders waiting while it reads, as _summary and _export.
+ * SKM_ERR_STATE if the set does not keep them, SKM_ERR_ARG if cap_samples (rows of room in fld) is
+ * below the samples named so far. */
+int skm_sample_set_histograms(skm_sample_set *set, int64_t cap_samples, int64_t *fld);
 /* DIAGNOSTICS, with no promise of stability: the set's bookkeeping on the host alone (no GPU is
  * touched), for tests.  They run the cutting, the log and the ordering by (sample, local first
  * seen) that the set itself runs; _split bisects the log on the host where the set does it in a
@@ -372,6 +387,12 @@ int skm_sample_set_split(int64_t n_entries, const int64_t *entry_global, const i
  * MapResult.effective_lengths (seekmer/mapper.py:134-141). */
 int skm_effective_lengths(int device, const int64_t *fld, const double *lengths,
                           int64_t n_tx, double *out);
+/* The same for n histograms in one call: fld[n][2000] -> out[n][n_tx], row s bit for bit what
+ * skm_effective_lengths gives for fld[s] (NaN for an empty histogram).  The lengths are uploaded
+ * once; the histograms pass through the device in groups whose rows, of `fld` and of `out`, stay
+ * within 256 MB each (SKM_EFF_MANY_GROUP in the environment: rows per group at most, for tests). */
+int skm_effective_lengths_many(int device, int64_t n, const int64_t *fld, const double *lengths,
+                               int64_t n_tx, double *out);
 
 /* Device-resident class table for infer.em / infer.quantify
  * (seekmer/infer.py:88-168).  class_counts are f8 as in

@@ -6,7 +6,9 @@ exported class tables, through one sample set (mapper.map_sample_set) and throug
     python3 scripts/sample_set_rate.py --cells 4 --pairs 2000000 --genes 100
 Generating the reads and packing them to 2-bit codes (what a FASTQ reader hands out) happens before the
 clock starts; the timed region of a form runs from the call that maps to the last exported table.
---only set|per_cell runs one form alone (for a kernel trace); --tree DIR measures the seekmer_amd of another
+--lengths per_sample: the set keeps a fragment-length histogram per sample (spans stored by the map kernel, counted
+by sample after every launch); the timed region then also reads the histograms, and they are compared with the
+per-cell mappers' own.  --only set|per_cell runs one form alone (for a kernel trace); --tree DIR measures the seekmer_amd of another
 checkout -- on one without sample sets only the per-cell form exists, which is how the parent commit is timed.
 On a shared GPU machine run every invocation under a time limit of its own (`timeout -k 10 600 python3 ...`).
 """
@@ -25,6 +27,7 @@ ap.add_argument('--read-len', type=int, default=75)
 ap.add_argument('--jobs', type=int, default=4)
 ap.add_argument('--reps', type=int, default=3)
 ap.add_argument('--only', choices=['set', 'per_cell'], default=None)
+ap.add_argument('--lengths', choices=['pooled', 'per_sample'], default='pooled')
 ap.add_argument('--cache', default='')
 ap.add_argument('--tree', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                 help='the checkout whose seekmer_amd is measured (default: this one)')
@@ -69,11 +72,14 @@ def make_cells():
 
 def through_set(index, cells):
     t0 = time.perf_counter()
-    sample_set = mapper.map_sample_set(index, cells, job_count=args.jobs)
+    per_sample = args.lengths == 'per_sample'
+    sample_set = mapper.map_sample_set(index, cells, job_count=args.jobs, **({'per_sample_lengths': True} if per_sample else {}))
     sizes = sample_set.sizes()
     tables = sample_set.export()
+    flds = sample_set.sample_fragment_length_counts if per_sample else None
     dt = time.perf_counter() - t0
-    return [(tuple(int(v) for v in size), table) for size, table in zip(sizes, tables)], sample_set.fragment_length_counts, dt
+    return ([(tuple(int(v) for v in size), table) for size, table in zip(sizes, tables)],
+            flds if per_sample else sample_set.fragment_length_counts, dt)
 
 
 def per_cell(index, cells):
@@ -81,7 +87,8 @@ def per_cell(index, cells):
     results = mapper.map_multiple_samples(index, cells, job_count=args.jobs)
     tables = [(result.sizes(), result.export()) for result in results]
     dt = time.perf_counter() - t0
-    fld = np.sum([table[4] for _, table in tables], axis=0, dtype=np.int64)
+    flds = np.asarray([table[4] for _, table in tables], dtype=np.int64)
+    fld = flds if args.lengths == 'per_sample' else np.sum(flds, axis=0, dtype=np.int64)
     return [(size, table[:4]) for size, table in tables], fld, dt
 
 
@@ -118,11 +125,12 @@ def main():
             assert size == want_size, 'sizes of cell %d differ' % i
             for a, b in zip(table, want):
                 assert np.array_equal(a, b), 'tables of cell %d differ' % i
-        assert np.array_equal(our_fld, their_fld), 'the pooled histogram differs'
+        assert np.array_equal(our_fld, their_fld), 'the %s differ' % ('histograms by sample' if args.lengths == 'per_sample'
+                                                                      else 'pooled histograms')
         classes = [size[0] for size, _ in ours]
-        print('all %d tables and the pooled histogram agree (classes per cell %d .. %d); per_cell / set = %.2f '
+        print('all %d tables and the %s agree (classes per cell %d .. %d); per_cell / set = %.2f '
               '(best of the later repetitions)'
-              % (args.cells, min(classes), max(classes),
+              % (args.cells, 'histograms by sample' if args.lengths == 'per_sample' else 'pooled histogram', min(classes), max(classes),
                  min(times['per_cell'][1:] or times['per_cell']) / min(times['set'][1:] or times['set'])), flush=True)
 
 

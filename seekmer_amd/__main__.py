@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CLI (reference: seekmer/__main__.py:13-71): `seekmer_amd [--debug] {index,infer,impute} ...`"""
+"""CLI (reference: seekmer/__main__.py:13-71): `seekmer_amd [--debug] {index,infer,infer-many,impute} ...`"""
 import argparse
 import logging
 import sys
@@ -17,6 +17,7 @@ def main(argv=None):
     subparsers = parser.add_subparsers(title='subcommand', dest='subcommand')
     index_builder.add_subcommand_parser(subparsers)
     infer.add_subcommand_parser(subparsers)
+    infer.add_many_subcommand_parser(subparsers)
     impute.add_subcommand_parser(subparsers)
     opts = vars(parser.parse_args(argv))
     logging.basicConfig(level=logging.DEBUG if opts['debug'] else logging.INFO,
@@ -26,6 +27,8 @@ def main(argv=None):
         index_builder.run(**opts)
     elif opts['subcommand'] == 'infer':
         infer.run(**opts)
+    elif opts['subcommand'] == 'infer-many':
+        infer.run_many(**opts)
     elif opts['subcommand'] == 'impute':
         impute.run(**opts)
     else:

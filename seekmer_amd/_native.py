@@ -103,6 +103,7 @@ HIP_SYMBOLS = {
     'skm_mapper_set_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_access_stats': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_effective_lengths': (ctypes.c_int, [ctypes.c_int, c_i64p, c_f64p, c_i64, c_f64p]),
+    'skm_effective_lengths_many': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_f64p, c_i64, c_f64p]),
     'skm_sample_set_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp]),
     'skm_sample_set_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_sample_set_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -113,6 +114,8 @@ HIP_SYMBOLS = {
     'skm_sample_set_summary': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p, c_i64p]),
     'skm_sample_set_export': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i32p, c_i64p, c_i64p]),
     'skm_sample_set_histogram': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_sample_set_keep_histograms': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_histograms': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
     'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),
     'skm_sample_set_split': (ctypes.c_int, [c_i64, c_i64p, c_i64p, c_i32p, c_i64, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
                                             c_i64p]),

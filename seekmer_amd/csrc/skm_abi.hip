@@ -2226,6 +2226,7 @@ void set_split_order(int64_t n_samples, int64_t n_classes, const int32_t *class_
 }
 
 constexpr int64_t SET_MAX_SAMPLES = 1 << 24;
+constexpr int64_t SET_MAX_HIST_SAMPLES = 1 << 16;   // with a histogram per sample: rows of 16 KB by sample NUMBER, 1 GiB at most
 constexpr int64_t SET_MAX_QUEUED = 4 * PACKED_MAX_UNITS;     // units that may wait in HBM before an adder waits
 
 }  // namespace
@@ -2240,6 +2241,10 @@ struct skm_sample_set {
     Stream copy_stream;
     std::shared_ptr<std::atomic<int64_t>> bytes = std::make_shared<std::atomic<int64_t>>(0);
     DBuf<int32_t> seg_table;                      // the segments of the launch under way: first units | samples
+    // one fragment-length histogram per sample (skm_sample_set_keep_histograms): [rows][2000], rows >= the
+    // largest sample a launch has held + 1, every word up to hist.cap counted or zero; touched under m->mu
+    bool keep_hist = false;
+    DBuf<unsigned long long> hist;
     // ---- under mu
     std::mutex mu;
     std::condition_variable work_cv, done_cv;
@@ -2307,7 +2312,23 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
         HIP_TRY(hipGetLastError());
         return SKM_OK;
     };
-    return map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt);
+    if (s->keep_hist) {                           // room for the rows of this launch's samples, the new ones zero
+        int32_t largest = 0;
+        for (const SetPart &part : parts) largest = std::max(largest, part.sample);
+        const size_t held = s->hist.cap;
+        SKM_TRY(s->hist.ensure(((size_t)largest + 1) * MAX_FRAGMENT_LENGTH, true, m->stream));
+        if (s->hist.cap > held)
+            HIP_TRY(hipMemsetAsync(s->hist.p + held, 0, (s->hist.cap - held) * sizeof(unsigned long long), m->stream));
+    }
+    SKM_TRY(map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt));
+    if (s->keep_hist) {
+        // the spans of the attempt that stood (an overflowing entry arena runs the map kernel again), after
+        // the pair rule; they stay until this mapper's next launch, which the set's worker starts after this one
+        if (!m->last_spans) return fail(SKM_ERR_STATE, "a set that keeps histograms mapped without spans");
+        launch_sample_fld(m->unit_begin.p, m->unit_end.p, n_units, salt, s->hist.p, m->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return SKM_OK;
 }
 
 void set_worker(skm_sample_set *s)
@@ -2367,6 +2388,9 @@ int set_admit(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n_u
     if (first_unit < 0 || n_units < 0 || n_units >= (1LL << 31)) return fail(SKM_ERR_ARG, "bad unit range");
     SKM_TRY(set_device(s->m->ix->device));
     std::unique_lock<std::mutex> hold(s->mu);
+    if (s->keep_hist && sample >= SET_MAX_HIST_SAMPLES)
+        return fail(SKM_ERR_ARG, "sample %lld: a set that keeps a histogram per sample numbers its samples below %lld",
+                    (long long)sample, (long long)SET_MAX_HIST_SAMPLES);
     s->done_cv.wait(hold, [&] { return s->error != SKM_OK || s->queued_units <= SET_MAX_QUEUED; });
     if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
     return SKM_OK;
@@ -2396,10 +2420,11 @@ int set_enqueue(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n
     return SKM_OK;
 }
 
-// the tables by sample (s->view), made once after the last launch.  `hold` (s->mu) is taken here and stays
-// taken for the caller's reading: from the moment everything added has been mapped no segment joins the queue
-// (an adder waits in set_enqueue), so the view, the log and the units per sample describe the same units.
-int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
+// `hold` (s->mu) is taken here, when everything added has been mapped, and stays taken for the caller's
+// reading: from that moment no segment joins the queue (an adder waits in set_enqueue), so what the caller
+// reads, the log and the units per sample describe the same units.
+// set_view: the tables by sample (s->view), made once after the last launch.
+int set_hold(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
 {
     hold = std::unique_lock<std::mutex>(s->mu);
     s->flush++;
@@ -2407,6 +2432,12 @@ int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
     s->done_cv.wait(hold, [&] { return !s->busy && s->queue.empty(); });
     s->flush--;
     if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    return SKM_OK;
+}
+
+int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
+{
+    SKM_TRY(set_hold(s, hold));
     if (s->view.valid) return SKM_OK;
     skm_mapper *m = s->m;
     std::lock_guard<std::mutex> lock(m->mu);
@@ -2503,6 +2534,17 @@ extern "C" int skm_sample_set_set_strand(skm_sample_set *s, int mode)
             if (units) return fail(SKM_ERR_STATE, "the strand mode can only change on an empty sample set");
     }
     return skm_mapper_set_strand(s->m, mode);
+}
+
+extern "C" int skm_sample_set_keep_histograms(skm_sample_set *s, int enable)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    std::lock_guard<std::mutex> hold(s->mu);
+    for (const int64_t units : s->sample_units)
+        if (units) return fail(SKM_ERR_STATE, "histograms per sample can only be switched on an empty sample set");
+    SKM_TRY(skm_mapper_keep_spans(s->m, enable));
+    s->keep_hist = enable != 0;
+    return SKM_OK;
 }
 
 extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit,
@@ -2626,6 +2668,29 @@ extern "C" int skm_sample_set_histogram(skm_sample_set *s, int64_t *fld)
     return skm_mapper_export(s->m, nullptr, nullptr, nullptr, nullptr, fld);
 }
 
+extern "C" int skm_sample_set_histograms(skm_sample_set *s, int64_t cap_samples, int64_t *fld)
+{
+    if (!s || cap_samples < 0 || (cap_samples && !fld)) return fail(SKM_ERR_ARG, "bad argument");
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_hold(s, hold));
+    if (!s->keep_hist)
+        return fail(SKM_ERR_STATE, "the set keeps no histogram per sample: call skm_sample_set_keep_histograms(set, 1) before adding");
+    const int64_t n_samples = (int64_t)s->sample_units.size();
+    if (cap_samples < n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)n_samples);
+    if (n_samples == 0) return SKM_OK;
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    // (a sample that no launch has held -- no units -- may lie past the buffer: its row is zero)
+    const int64_t rows = std::min<int64_t>(n_samples, (int64_t)(s->hist.cap / MAX_FRAGMENT_LENGTH));
+    std::fill(fld + rows * MAX_FRAGMENT_LENGTH, fld + n_samples * MAX_FRAGMENT_LENGTH, (int64_t)0);
+    if (rows) {
+        HIP_TRY(hipMemcpyAsync(fld, s->hist.p, (size_t)rows * MAX_FRAGMENT_LENGTH * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    return SKM_OK;
+}
+
 extern "C" int skm_sample_set_plan(int64_t n_segments, const int32_t *sample, const int64_t *n_units, int64_t max_units,
                                    int64_t cap_entries, int64_t *n_entries, int64_t *entry_global, int64_t *entry_local,
                                    int32_t *entry_sample)
@@ -2696,6 +2761,38 @@ extern "C" int skm_effective_lengths(int device, const int64_t *fld, const doubl
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, d_out.p, n_tx * 8, hipMemcpyDeviceToHost));
     drain.dismiss();                          // (the copy home has waited for the kernel)
+    return SKM_OK;
+}
+
+// Groups of histograms, so that the rows staged in HBM, in and out, stay within 256 MB each (as many_rows_in);
+// the lengths go up once.
+extern "C" int skm_effective_lengths_many(int device, int64_t n, const int64_t *fld, const double *lengths,
+                                          int64_t n_tx, double *out)
+{
+    if (n < 0 || n_tx < 0 || (n && (!fld || (n_tx && (!lengths || !out))))) return fail(SKM_ERR_ARG, "bad argument");
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(set_device(device));
+    if (n == 0 || n_tx == 0) return SKM_OK;
+    // rows per group: 256 MB of output rows and of histograms at most (16 777 rows: one launch's gridDim.y holds them);
+    // SKM_EFF_MANY_GROUP (tests): fewer
+    int64_t group = std::min<int64_t>((int64_t)(1LL << 25) / n_tx, (int64_t)(1LL << 25) / MAX_FRAGMENT_LENGTH);
+    if (const char *v = getenv("SKM_EFF_MANY_GROUP"))
+        if (atoll(v) > 0) group = std::min<int64_t>(group, atoll(v));
+    group = std::max<int64_t>(1, std::min(group, n));
+    DBuf<unsigned long long> d_fld; DBuf<double> d_len, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_fld.ensure((size_t)group * MAX_FRAGMENT_LENGTH)); SKM_TRY(d_len.ensure(n_tx)); SKM_TRY(d_out.ensure((size_t)(group * n_tx)));
+    HIP_TRY(hipMemcpy(d_len.p, lengths, n_tx * 8, hipMemcpyHostToDevice));
+    for (int64_t first = 0; first < n; first += group) {
+        const int64_t here = std::min(group, n - first);
+        HIP_TRY(hipMemcpy(d_fld.p, fld + first * MAX_FRAGMENT_LENGTH, (size_t)here * MAX_FRAGMENT_LENGTH * 8, hipMemcpyHostToDevice));
+        launch_effective_lengths_many(d_fld.p, here, d_len.p, n_tx, d_out.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out + first * n_tx, d_out.p, (size_t)(here * n_tx) * 8, hipMemcpyDeviceToHost));
+    }
+    drain.dismiss();                          // (the copies home have waited for the kernels)
     return SKM_OK;
 }
 

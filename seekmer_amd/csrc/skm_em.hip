@@ -575,10 +575,14 @@ em_local_decide_kernel(EmProblem p, EmTiles tl, int64_t first_step, int n_steps)
 // MapResult.effective_lengths, mapper.py:134-141: p = fld / fld.sum();
 // eff_t = sum_i max(len_t - i, 1) * p_i accumulated for i = 0..1999 in order
 // (compiled with -ffp-contract=off: separate multiply and add, as numpy).
+// blockIdx.y is the histogram: row y of fld[gridDim.y][2000] gives row y of out[gridDim.y][n_tx], each by
+// the arithmetic of a launch on that row alone (the lengths are shared).
 __global__ void __launch_bounds__(256)
 effective_lengths_kernel(const unsigned long long *__restrict__ fld,
                          const double *__restrict__ lengths, int64_t n_tx, double *__restrict__ out)
 {
+    fld += (int64_t)blockIdx.y * MAX_FRAGMENT_LENGTH;
+    out += (int64_t)blockIdx.y * n_tx;
     // Only the bins with p_i != 0 are visited: a term max(len - i, 1) * 0.0 is +0.0 and adding
     // +0.0 leaves the running sum as it is, bit for bit (the sum starts at +0.0 and every term
     // is >= 0); a NaN bin (empty histogram: 0 / 0) is not zero and stays in.  A fragment-length
@@ -1146,6 +1150,15 @@ void launch_effective_lengths(const unsigned long long *fld, const double *lengt
 {
     hipLaunchKernelGGL(effective_lengths_kernel, dim3(grid_for(n_tx)), dim3(256), 0, stream, fld,
                        lengths, n_tx, out);
+}
+
+void launch_effective_lengths_many(const unsigned long long *fld, int64_t n, const double *lengths, int64_t n_tx,
+                                   double *out, hipStream_t stream)
+{
+    // n <= 65535 (gridDim.y; the caller's groups are smaller).  Every block packs its histogram first: few
+    // blocks per histogram when there are many of them.
+    const unsigned per_row = std::min<unsigned>(grid_for(n_tx), n >= 64 ? 16u : 256u);
+    hipLaunchKernelGGL(effective_lengths_kernel, dim3(per_row, (unsigned)n), dim3(256), 0, stream, fld, lengths, n_tx, out);
 }
 
 int multinomial_tile(int64_t n_classes)

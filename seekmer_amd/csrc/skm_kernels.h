@@ -112,6 +112,11 @@ struct SampleSalt {                               // the segments of one launch 
 // between the strand filter and class counting: every record with a key takes the key of (its unit's
 // sample, its tuple); a key that comes out as 0 raises SKM_ERR_COLLISION in *error (never "unaligned")
 void launch_sample_salt(const MapBatch &b, const SampleSalt &salt, int *error, hipStream_t stream);
+// after a launch mapped with keep_spans: hist[sample of unit u][fragment length of unit u] += 1 for every
+// unit u < n_units of the launch whose span gives a length (the map kernel's fragment length rule on
+// unit_begin / unit_end); hist holds MAX_FRAGMENT_LENGTH words for every sample the segments name
+void launch_sample_fld(const int32_t *unit_begin, const int32_t *unit_end, int64_t n_units, const SampleSalt &salt,
+                       unsigned long long *hist, hipStream_t stream);
 // the set's segment log against the classes' global first-seen units: cls_sample[k], cls_local[k] =
 // the sample of class k and its first-seen unit counted inside that sample
 void launch_sample_assign(const int64_t *log_global, const int64_t *log_local, const int32_t *log_sample,
@@ -394,6 +399,9 @@ void launch_divide_many(double *x, int64_t n, int64_t count, int64_t stride, con
                         double floor, hipStream_t stream);
 void launch_effective_lengths(const unsigned long long *fld, const double *lengths, int64_t n_tx,
                               double *out, hipStream_t stream);
+// the same for n <= 65535 histograms fld[n][2000] -> out[n][n_tx], row by row what the launch above gives
+void launch_effective_lengths_many(const unsigned long long *fld, int64_t n, const double *lengths, int64_t n_tx,
+                                   double *out, hipStream_t stream);
 // multinomial(n_draws, counts / n_draws) over the classes whose inclusive cumulative counts are
 // `cum`: counts[c * stride] = draws of class c (f8).  tile_total: 4096 unsigned ints of scratch.
 // false = table too large for the tiled draw.

@@ -10,6 +10,10 @@
 // compare as before (SKM_ERR_COLLISION) -- counts are exact or the call fails.  A salted key of 0
 // (2^-64 per record) would read as "unaligned": it raises the same error instead.
 //
+// A set that keeps one fragment-length histogram per sample maps with keep_spans and runs
+// sample_fld_kernel after every launch: the units' final spans, through the map kernel's fragment length
+// rule, counted into the row of the unit's sample.
+//
 // At export, sample_assign_kernel gives every class its sample and its first-seen unit counted inside
 // that sample from the set's segment log (global first unit, sample, local first unit of every
 // segment, in launch order).
@@ -44,6 +48,58 @@ sample_salt_kernel(const int32_t *__restrict__ rec_unit, uint64_t *__restrict__ 
     if (zero) atomicExch(error, SKM_ERR_COLLISION);
 }
 
+// Fragment lengths by sample.  A block takes SAMPLE_FLD_RUN consecutive units, 256 at a time.  A sample's
+// units are consecutive, so most tiles of 256 lie inside one segment: those count the bins below
+// SAMPLE_FLD_WINDOW in an LDS histogram that the block flushes (one 64-bit atomic per occupied bin) when its
+// sample changes and at the end.  A tile that crosses a segment border (many tiny samples) and the rare long
+// fragments add straight to HBM: neighbouring lanes then hit different rows or far bins.  Integer adds:
+// any order gives the same histogram.
+constexpr int SAMPLE_FLD_WINDOW = 512;            // (the map kernel's FLD_WINDOW)
+constexpr int SAMPLE_FLD_RUN = 1024;
+
+__global__ void __launch_bounds__(256)
+sample_fld_kernel(const int32_t *__restrict__ unit_begin, const int32_t *__restrict__ unit_end, int64_t n_units,
+                  const int32_t *__restrict__ seg_first, const int32_t *__restrict__ seg_sample, int n_segments,
+                  unsigned long long *__restrict__ hist)
+{
+    __shared__ int32_t s_first[SAMPLE_LAUNCH_SEGMENTS], s_sample[SAMPLE_LAUNCH_SEGMENTS];
+    __shared__ uint32_t s_hist[SAMPLE_FLD_WINDOW];
+    for (int i = threadIdx.x; i < n_segments; i += blockDim.x) { s_first[i] = seg_first[i]; s_sample[i] = seg_sample[i]; }
+    for (int i = threadIdx.x; i < SAMPLE_FLD_WINDOW; i += blockDim.x) s_hist[i] = 0;
+    __syncthreads();
+    const int64_t run_first = (int64_t)blockIdx.x * SAMPLE_FLD_RUN;
+    const int64_t run_end = run_first + SAMPLE_FLD_RUN < n_units ? run_first + SAMPLE_FLD_RUN : n_units;
+    int64_t held = -1;                            // the sample whose counts s_hist holds (block-uniform)
+    auto flush = [&]() {                          // (called by the whole block)
+        __syncthreads();
+        for (int i = threadIdx.x; i < SAMPLE_FLD_WINDOW; i += blockDim.x)
+            if (s_hist[i]) {
+                atomicAdd(&hist[held * MAX_FRAGMENT_LENGTH + i], (unsigned long long)s_hist[i]);
+                s_hist[i] = 0;
+            }
+        __syncthreads();
+    };
+    for (int64_t tile = run_first; tile < run_end; tile += blockDim.x) {
+        const int64_t tile_last = tile + blockDim.x <= run_end ? tile + blockDim.x - 1 : run_end - 1;
+        const int64_t seg_a = segment_find(s_first, n_segments, tile), seg_b = segment_find(s_first, n_segments, tile_last);
+        const bool one_segment = seg_a == seg_b;  // (block-uniform: both units are the tile's)
+        if (one_segment && held != s_sample[seg_a]) {
+            if (held >= 0) flush();
+            held = s_sample[seg_a];
+        }
+        const int64_t u = tile + threadIdx.x;
+        if (u > tile_last) continue;
+        // fragment length rule, _mapper.pyx:90-94, on the span the map kernel stored for the unit
+        int length = unit_end[u] - unit_begin[u] + K;
+        if (length <= 0) continue;
+        if (length >= MAX_FRAGMENT_LENGTH) length = MAX_FRAGMENT_LENGTH - 1;
+        if (one_segment && length < SAMPLE_FLD_WINDOW) { atomicAdd(&s_hist[length], 1u); continue; }
+        const int64_t sample = one_segment ? held : (int64_t)s_sample[segment_find(s_first, n_segments, u)];
+        atomicAdd(&hist[sample * MAX_FRAGMENT_LENGTH + length], 1ULL);
+    }
+    if (held >= 0) flush();
+}
+
 __global__ void __launch_bounds__(256)
 sample_assign_kernel(const int64_t *__restrict__ log_global, const int64_t *__restrict__ log_local,
                      const int32_t *__restrict__ log_sample, int64_t n_segments,
@@ -66,6 +122,15 @@ void launch_sample_salt(const MapBatch &b, const SampleSalt &salt, int *error, h
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sample_salt_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b.rec_unit, b.rec_key,
                        b.n_units, salt.seg_first, salt.seg_sample, (int)salt.n_segments, error);
+}
+
+void launch_sample_fld(const int32_t *unit_begin, const int32_t *unit_end, int64_t n_units, const SampleSalt &salt,
+                       unsigned long long *hist, hipStream_t stream)
+{
+    if (n_units <= 0 || salt.n_segments <= 0) return;
+    const int64_t blocks = (n_units + SAMPLE_FLD_RUN - 1) / SAMPLE_FLD_RUN;        // (at most 2^21 units a launch)
+    hipLaunchKernelGGL(sample_fld_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, unit_begin, unit_end,
+                       n_units, salt.seg_first, salt.seg_sample, (int)salt.n_segments, hist);
 }
 
 void launch_sample_assign(const int64_t *log_global, const int64_t *log_local, const int32_t *log_sample,

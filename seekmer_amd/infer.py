@@ -7,6 +7,7 @@ import ctypes
 import datetime
 import json
 import logging
+import os
 import pathlib
 import shlex
 import sys
@@ -17,7 +18,7 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'quantify', 'quantify_many', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+__all__ = ['run', 'run_many', 'quantify', 'quantify_many', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
            'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
@@ -104,6 +105,121 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         output_results(output_path, index, start_time, summarized_results,
                        main_result, bootstrapped_results)
         _LOG.info('Wrote results to %s', output_path)
+
+
+def sample_groups(fastq_paths, single_ended):
+    """The samples of infer-many: every two files are one (with single_ended every file), impute's convention --
+    but a file left over (an odd number of files for paired samples) raises ValueError: every file named must
+    end up in a sample's folder."""
+    width = 1 if single_ended else 2
+    if len(fastq_paths) % width:
+        raise ValueError('%d files for paired samples: every two files are one sample (use -s for single-ended reads)'
+                         % len(fastq_paths))
+    return [tuple(fastq_paths[i:i + width]) for i in range(0, len(fastq_paths), width)]
+
+
+def sample_names(groups, names=None):
+    """One name per sample: its first file's name up to the first '.', or the matching entry of `names`
+    (a list, or one string with commas).  A list of the wrong length and names that are not unique (or
+    cannot name a folder) raise ValueError; no file is looked at."""
+    if names is None:
+        names = [pathlib.Path(group[0]).name.split('.')[0] for group in groups]
+    else:
+        names = names.split(',') if isinstance(names, str) else [str(name) for name in names]
+        if len(names) != len(groups):
+            raise ValueError('%d names for %d samples' % (len(names), len(groups)))
+    for name in names:
+        if name in ('', '.', '..') or '/' in name:
+            raise ValueError('%r cannot name a sample\'s output folder' % (name,))
+    repeated = sorted({name for name in names if names.count(name) > 1})
+    if repeated:
+        raise ValueError('sample names are not unique: %s (name them with --names)' % ', '.join(repeated))
+    return names
+
+
+def sample_set_members(sizes, max_bytes, per_sample=None):
+    """The routing rule of run_many as a function of the samples' text sizes (impute.cell_text_bytes):
+    the indices of the samples that go through one sample set -- those of at most `max_bytes`, when
+    there are at least two of them; every other sample is mapped by itself.  per_sample: the
+    switch SKM_INFER_MANY_PER_SAMPLE=1 (None = looked up in the environment now)."""
+    if per_sample is None:
+        per_sample = os.environ.get('SKM_INFER_MANY_PER_SAMPLE') == '1'
+    small = [i for i, size in enumerate(sizes) if size <= max_bytes]
+    return small if len(small) >= 2 and not per_sample else []
+
+
+def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
+             strand=None, names=None, **__):
+    """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
+    the files `infer` writes for that sample alone (same bits but for the start time and the call), and
+    output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
+
+    Small samples (impute.SAMPLE_SET_MAX_CELL_BYTES of text at most, two of them at least) share
+    launches in one mapper.SampleSet that keeps a fragment-length histogram per sample; every other
+    sample is mapped by itself on the same index handle.  SKM_INFER_MANY_PER_SAMPLE=1 maps every
+    sample by itself.  `seed` is used for every sample, so a sample's `-b N` replicates are those of
+    `infer -b N --seed S` on it.  One process, one GPU; no readmap (a set has none)."""
+    from . import impute
+    from . import parallel
+    start_time = datetime.datetime.utcnow()
+    mapper.strand_mode(strand)
+    groups = sample_groups(fastq_paths, single_ended)
+    if not groups:
+        raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
+    names = sample_names(groups, names)
+    ranks = parallel.Ranks.from_env()
+    if ranks.world > 1:
+        ranks.close()
+        raise ValueError('infer-many runs in one process on one GPU: start it without a launcher')
+    for path in fastq_paths:
+        if not pathlib.Path(path).exists():
+            raise ValueError(f'invalid FastQ file: {path}')
+    try:
+        output_path.mkdir(parents=True)
+    except FileExistsError:
+        _LOG.warning('The output folder exists. Overriding...')
+    _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    _native.check(_native.hip().skm_pinned_set_device(device))
+    index = common.KMerIndex.load(index_path)
+    index.device_handle(device)
+    paired = not single_ended
+    in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
+    summaries, means = [None] * len(groups), [None] * len(groups)
+    if in_set:
+        _LOG.info('Mapping %d samples in shared launches', len(in_set))
+        feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
+                   else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
+        sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
+                                           strand=strand, per_sample_lengths=True)
+        for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
+            summaries[i], means[i] = summary, mean
+        del sample_set
+    for i, group in enumerate(groups):
+        if summaries[i] is not None:
+            continue
+        _LOG.info('Mapping sample %s', names[i])
+        map_result = mapper.map_reads(index, _feeder(list(group), paired, None, None, False), job_count=job_count,
+                                      debug=debug, device=device, strand=strand)
+        summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
+        del map_result
+    _LOG.info('Mapped all reads')
+    for name, summary in zip(names, summaries):
+        if summary.total == 0:
+            raise ValueError('sample %s has no reads' % name)
+        if bootstrap > 0 and summary.aligned > RESAMPLE_LIMIT:
+            raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
+                             % (RESAMPLE_LIMIT, name, summary.aligned))
+    for name, summary in zip(names, summaries):
+        _LOG.info('Quantifying sample %s', name)
+        main_result = quantify(summary, device=device)
+        bootstrapped_results = bootstrap_quantify(summary, main_result, bootstrap, seed=seed, device=device)
+        sample_path = output_path / name
+        sample_path.mkdir(exist_ok=True)
+        output_results(sample_path, index, start_time, summary, main_result, bootstrapped_results)
+    with (output_path / 'samples.tsv').open('w') as f:
+        for name, summary, mean in zip(names, summaries, means):
+            f.write('%s\t%d\t%d\t%.2f\n' % (name, summary.total, summary.aligned, mean))
+    _LOG.info('Wrote results to %s', output_path)
 
 
 RESAMPLE_LIMIT = 2 ** 32 - 1        # units one multinomial draw can resample (skm_quant_bootstrap*)
@@ -625,6 +741,33 @@ def add_subcommand_parser(subparsers):
     parser.add_argument('--parse-threads', type=int, dest='parse_threads', default=None, metavar='N',
                         help='parse plain FASTQ files with N threads (default: up to 8; 0: one thread, '
                              'the batches of the reference)')
+    add_strand_arguments(parser)
+
+
+def add_many_subcommand_parser(subparsers):
+    """Add the infer-many command: `infer` for many samples against one resident index."""
+    parser = subparsers.add_parser(
+        'infer-many', help='infer transcript abundance of many samples against one resident index',
+        epilog='List the read files of all samples as arguments: every two files are one sample; with "-s" '
+               '(single-ended reads) every file is one sample.  Sample NAME gets the folder output/NAME with '
+               'the files that "infer" writes for it.')
+    parser.add_argument('index_path', type=pathlib.Path, metavar='index',
+                        help='specify a Seekmer index file')
+    parser.add_argument('output_path', type=pathlib.Path, metavar='output',
+                        help='specify a output folder')
+    parser.add_argument('fastq_paths', type=pathlib.Path, metavar='fastq',
+                        nargs='+', help='specify a FASTQ read file')
+    parser.add_argument('-j', '--jobs', type=int, dest='job_count', metavar='N', default=1,
+                        help='specify the maximum parallel job number')
+    parser.add_argument('-s', '--single-ended', action='store_true', dest='single_ended',
+                        help='specify whether the reads are single-ended')
+    parser.add_argument('-b', '--bootstrap', type=int, dest='bootstrap', default=0,
+                        help='specify the number of bootstrapped estimation')
+    parser.add_argument('--device', type=int, default=0, help='GPU ordinal (default 0)')
+    parser.add_argument('--seed', type=int, default=None,
+                        help='seed of the bootstrap resampling, the same for every sample (default: random)')
+    parser.add_argument('--names', type=str, default=None, metavar='A,B,C',
+                        help='name the samples (default: each sample\'s first file name up to its first ".")')
     add_strand_arguments(parser)
 
 

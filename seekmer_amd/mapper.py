@@ -61,6 +61,12 @@ class SummarizedResult:
         self.class_targets = class_targets
         self._map_result = map_result
 
+    def detach(self):
+        """Let go of the MapResult the summary came from (its table is in the summary): the mapper's
+        handle and its device memory go when nothing else holds them."""
+        self._map_result = None
+        return self
+
 
 class MapResult:
     """A mapping result collection with a lock (seekmer/mapper.py:40-145)."""
@@ -561,6 +567,31 @@ def _effective_lengths(lengths, fld, device):
     return out
 
 
+def _effective_lengths_many(lengths, fld, device):
+    """_effective_lengths for every row of fld[n, 2000] in one native call: f8[n, n_tx]."""
+    fld = numpy.ascontiguousarray(fld, dtype=numpy.int64).reshape(-1, MAX_FRAGMENT_LENGTH)
+    out = numpy.zeros((fld.shape[0], lengths.size), dtype='f8')
+    _native.check(_native.hip().skm_effective_lengths_many(
+        device, fld.shape[0], _native.ptr(fld, _native.c_i64p) if fld.size else None,
+        _native.ptr(lengths, _native.c_f64p), lengths.size, _native.ptr(out, _native.c_f64p) if out.size else None))
+    return out
+
+
+def harmonic_mean_fragment_lengths(counts):
+    """MapResult.harmonic_mean_fragment_length (seekmer/mapper.py:117-132) for every row of
+    counts[n, 2000]: a list of n numbers, 0 for an empty histogram."""
+    means = []
+    for fld in numpy.asarray(counts).reshape(-1, MAX_FRAGMENT_LENGTH):
+        assert fld[0] == 0
+        numerator = fld.sum()
+        if numerator == 0:
+            means.append(0)
+            continue
+        denominator = (fld[1:].astype('f8') / numpy.arange(1, MAX_FRAGMENT_LENGTH)).sum()
+        means.append(numerator / denominator)
+    return means
+
+
 class SampleSet:
     """Many small samples on one device handle (skm_sample_set): their units share launches and one
     class table whose classes are (sample, target tuple).  Every sample's table -- class order,
@@ -568,24 +599,31 @@ class SampleSet:
     is bit for bit that of a MapResult fed the sample's reads alone, however the samples are
     interleaved, cut into launches or spread over feeding threads.
 
-    The set keeps ONE fragment-length histogram, the sum over its samples: what
-    impute.pool_fragment_lengths gives every cell (seekmer/impute.py:128-146).  There is no per-sample
-    histogram, and no readmap.  ``strand`` (None, 'fr', 'rf') applies to every sample.
+    By default the set keeps ONE fragment-length histogram, the sum over its samples: what
+    impute.pool_fragment_lengths gives every cell (seekmer/impute.py:128-146), and every summary carries
+    it.  With ``per_sample_lengths`` it also keeps one histogram per sample, counted on the device after
+    every launch from the units' spans: sample_fragment_length_counts, and every summary then carries
+    its own sample's histogram and effective lengths, those of a MapResult fed the sample alone -- what
+    an ordinary `infer` of the sample needs.  There is no readmap.  ``strand`` (None, 'fr', 'rf')
+    applies to every sample.
 
     Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
     where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
 
-    def __init__(self, index, paired, device=0, strand=None):
+    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False):
         mode = strand_mode(strand)
         self.index = index
         self.paired = bool(paired)
         self.device = device
         self.strand = strand
+        self.per_sample_lengths = bool(per_sample_lengths)
         self._handle = ctypes.c_void_p()
         _native.check(_native.hip().skm_sample_set_create(index.device_handle(device), int(self.paired),
                                                           ctypes.byref(self._handle)))
         if mode != _native.SKM_STRAND_NONE:
             _native.check(_native.hip().skm_sample_set_set_strand(self._handle, mode))
+        if self.per_sample_lengths:
+            _native.check(_native.hip().skm_sample_set_keep_histograms(self._handle, 1))
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
@@ -661,10 +699,30 @@ class SampleSet:
 
     @property
     def fragment_length_counts(self):
-        """The set's one histogram: the sum over all its samples."""
+        """The set's pooled histogram: the sum over all its samples."""
         fld = numpy.zeros(MAX_FRAGMENT_LENGTH, dtype=numpy.int64)
         _native.check(_native.hip().skm_sample_set_histogram(self._handle, _native.ptr(fld, _native.c_i64p)))
         return fld
+
+    @property
+    def sample_fragment_length_counts(self):
+        """int64[n_samples, 2000]: row i is MapResult.fragment_length_counts of sample i mapped alone
+        (a set made with per_sample_lengths; ValueError otherwise)."""
+        if not self.per_sample_lengths:
+            raise ValueError('the set keeps one pooled histogram: make it with per_sample_lengths=True')
+        # (samples may be added meanwhile: the call says when there are more than the rows it was given)
+        while True:
+            fld = numpy.zeros((len(self), MAX_FRAGMENT_LENGTH), dtype=numpy.int64)
+            code = _native.hip().skm_sample_set_histograms(self._handle, fld.shape[0],
+                                                           _native.ptr(fld, _native.c_i64p) if fld.size else None)
+            if code == _native.SKM_ERR_ARG and len(self) > fld.shape[0]:
+                continue
+            _native.check(code)
+            return fld
+
+    def harmonic_mean_fragment_lengths(self):
+        """One number per sample: MapResult.harmonic_mean_fragment_length of the sample mapped alone."""
+        return harmonic_mean_fragment_lengths(self.sample_fragment_length_counts)
 
     def export(self):
         """[(class_offsets, class_targets, class_counts, first_seen), ...] per sample, each as
@@ -686,18 +744,31 @@ class SampleSet:
         return tables
 
     def summarize(self):
-        """[SummarizedResult, ...] per sample, as MapResult.summarize() (seekmer/mapper.py:77-104); every
-        item carries the POOLED histogram and the effective lengths that follow from it (one shared,
-        read-only pair of arrays), i.e. what the samples' MapResults hold after impute.pool_fragment_lengths."""
+        """[SummarizedResult, ...] per sample, as MapResult.summarize() (seekmer/mapper.py:77-104).  By
+        default every item carries the POOLED histogram and the effective lengths that follow from it
+        (one shared, read-only pair of arrays), i.e. what the samples' MapResults hold after
+        impute.pool_fragment_lengths.  With per_sample_lengths item i carries sample i's own histogram
+        and effective lengths: read-only rows of two arrays, the lengths of all samples made in one
+        device call."""
         sizes = self.sizes()
         tables = self.export()
-        fld = self.fragment_length_counts
         lengths = numpy.ascontiguousarray(self.index.transcripts['length'], dtype='f8')
-        effective = _effective_lengths(lengths, fld, self.device)
-        fld.setflags(write=False)
-        effective.setflags(write=False)
+        if self.per_sample_lengths:
+            flds = self.sample_fragment_length_counts[:len(sizes)]
+            if len(flds) != len(sizes):
+                raise RuntimeError('samples were added while the set was summarized')
+            effectives = _effective_lengths_many(lengths, flds, self.device)
+            flds.setflags(write=False)
+            effectives.setflags(write=False)
+        else:
+            fld = self.fragment_length_counts
+            effective = _effective_lengths(lengths, fld, self.device)
+            fld.setflags(write=False)
+            effective.setflags(write=False)
         summaries = []
-        for (offsets, targets, counts, _), (_, _, unaligned, _) in zip(tables, sizes):
+        for i, ((offsets, targets, counts, _), (_, _, unaligned, _)) in enumerate(zip(tables, sizes)):
+            if self.per_sample_lengths:
+                fld, effective = flds[i], effectives[i]
             if targets.size:
                 class_ids = numpy.repeat(numpy.arange(counts.size, dtype=numpy.int64), numpy.diff(offsets))
                 class_map = numpy.vstack([class_ids, targets.astype(numpy.int64)])
@@ -712,11 +783,12 @@ class SampleSet:
         return summaries
 
 
-def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None):
+def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_sample_lengths=False):
     """map_multiple_samples for many small samples (single cells): sample i = read_feeders[i], all of
     them mapped through ONE SampleSet in shared launches.  Each of `job_count` threads takes a sample
     at a time, parses its files completely and adds it; results do not depend on the thread count.
     The feeders must agree on paired / single-ended.  strand: None, 'fr' or 'rf' for every sample.
+    per_sample_lengths: every sample keeps its own fragment-length histogram (SampleSet).
     A failed sample raises."""
     strand_mode(strand)
     read_feeders = list(read_feeders)
@@ -727,7 +799,7 @@ def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None):
     layouts = {bool(feeder.paired) for feeder in read_feeders}     # (every feeder of common says which it is)
     if len(layouts) != 1:
         raise ValueError('paired and single-ended samples in one set')
-    sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand)
+    sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand, per_sample_lengths=per_sample_lengths)
     if job_count == 1:
         for sample, read_feeder in enumerate(read_feeders):
             sample_set.add_sample(sample, read_feeder)
