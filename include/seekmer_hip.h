@@ -461,6 +461,50 @@ int skm_quant_em_blend(skm_quant *quant, int64_t n_cells, const int32_t *class_c
                        const double *weight, const double *cell_total, const double *x0,
                        const double *l, double rel_tol, double x_floor, int tpm, double *out,
                        int64_t *iters_out, double *counts_out);
+/* K DIFFERENT class tables over the same n_tx transcripts in shared EM launches (the companion of
+ * skm_quant_em_many, which runs K count vectors on one table).  The tables are given as one host CSR:
+ * table s owns classes [table_class_offsets[s], table_class_offsets[s + 1]) of class_offsets /
+ * class_counts, class c the targets [class_offsets[c], class_offsets[c + 1]) of class_targets, each
+ * target in [0, n_tx).  Table s starts from x0[s][n_tx] with the effective lengths l[s][n_tx].  The
+ * tables are stacked into one block-diagonal problem (transcript t of table s is transcript s n_tx + t)
+ * whose steps run in launches with one grid row per table; every table meets its own stopping rule
+ * and is frozen from then on.  out[s][n_tx] and iters[s] (optional) are bit for bit what
+ * skm_quant_create + skm_quant_em give for table s alone; tpm != 0: scaled as quantify() scales
+ * (seekmer/infer.py:127-129).  A table without classes gives zeros and 0 steps.  The tables run in
+ * groups of consecutive tables: stacked transcripts, classes and pairs of a group stay below 2^31, its
+ * buffers within about 2 GiB (skm_set_quant_groups), its tables at most SKM_SET_QUANT_GROUP when that
+ * is set (tests).  SKM_ERR_UNDEFINED when a table leaves no abundance above x_floor (the message names
+ * the lowest such table); SKM_ERR_ARG, before any device work, for negative sizes, NULL arrays,
+ * offsets that are not monotone and targets outside [0, n_tx); n_tables == 0 does nothing.  A class
+ * without a tuple entry counts in its table's total and in nothing else, as in skm_quant_create (it is
+ * left out of the stacked problem); a table whose classes are all such is SKM_ERR_ARG. */
+int skm_quant_em_tables(int device, int64_t n_tx, int64_t n_tables, const int64_t *table_class_offsets,
+                        const int64_t *class_offsets, const int32_t *class_targets,
+                        const double *class_counts, const double *x0, const double *l, double rel_tol,
+                        double x_floor, int64_t max_iters, int tpm, double *out, int64_t *iters);
+/* The group cut of skm_quant_em_tables and skm_sample_set_quantify on the host alone (no GPU is
+ * touched; tests): tables of table_classes[i] classes and table_ids[i] (class, target) pairs, at most
+ * max_slots a group -> group g = tables [group_first[g], group_first[g + 1]), g < *n_groups
+ * (group_first has room for n_tables + 1).  A table joins the group under way while the group keeps
+ * at most max_slots (and 32768) tables, (tables) n_tx, its classes and its pairs below 2^31, and
+ * tables * n_tx * 96 + classes * 64 + pairs * 24 bytes within 2^31; a group always holds one table. */
+int skm_set_quant_groups(int64_t n_tables, int64_t n_tx, const int64_t *table_classes,
+                         const int64_t *table_ids, int64_t max_slots, int64_t *n_groups,
+                         int64_t *group_first);
+/* quantify(summary) for every sample of a set, in shared EM launches as skm_quant_em_tables runs
+ * them; the class tuples are gathered on the device from the set's table into the stacked problem.
+ * lengths[n_tx] = the transcript lengths.  Sample i's effective lengths come from its own histogram
+ * when the set keeps them (skm_sample_set_keep_histograms), from the pooled one otherwise; its start
+ * vector is 1 / effective length over numpy's sum, its total its aligned units.  tpm[S][n_tx],
+ * effective_lengths[S][n_tx] (optional) and iters[S] (optional) for the S = *n_samples samples named
+ * so far are bit for bit what infer.quantify() gives on the sample's summary; a sample without
+ * classes gives zeros and 0 steps.  Waits for everything added to be mapped and keeps adders waiting,
+ * as _summary.  SKM_ERR_ARG when cap_samples (rows of room) is below S or a class names a transcript
+ * not below n_tx; SKM_ERR_UNDEFINED as skm_quant_em_tables. */
+int skm_sample_set_quantify(skm_sample_set *set, const double *lengths, int64_t n_tx, double rel_tol,
+                            double x_floor, int64_t max_iters, int64_t cap_samples,
+                            int64_t *n_samples, double *tpm, double *effective_lengths,
+                            int64_t *iters);
 /* The connected components of the (class, transcript) graph and the tiles the one-GPU EM steps them in
  * (diagnostics, tests).  info[0] = tiles were built, [1] = tiles, [2] = components above the tile capacity
  * (any: the EM steps the whole table as one problem), [3] = the EM of this handle runs on the tiles,

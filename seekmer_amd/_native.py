@@ -139,6 +139,11 @@ HIP_SYMBOLS = {
                                          ctypes.c_double, ctypes.c_int, c_f64p, c_i64p]),
     'skm_quant_em_blend': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, c_f64p, c_i64p, c_f64p]),
+    'skm_quant_em_tables': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p,
+                                           ctypes.c_double, ctypes.c_double, c_i64, ctypes.c_int, c_f64p, c_i64p]),
+    'skm_set_quant_groups': (ctypes.c_int, [c_i64, c_i64, c_i64p, c_i64p, c_i64, c_i64p, c_i64p]),
+    'skm_sample_set_quantify': (ctypes.c_int, [ctypes.c_void_p, c_f64p, c_i64, ctypes.c_double, ctypes.c_double, c_i64,
+                                               c_i64, c_i64p, c_f64p, c_f64p, c_i64p]),
     'skm_quant_timing': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_quant_components': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i32p, c_i32p]),
     'skm_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),

@@ -561,7 +561,7 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
     // first-use costs of the GPU side that would otherwise fall into the sample's own run.
     std::thread warm([device]() {
         if (hipSetDevice(device) != hipSuccess) return;
-        warm_code_map(); warm_code_classes(); warm_code_em(); warm_code_em_batch(); warm_code_quant_setup();
+        warm_code_map(); warm_code_classes(); warm_code_em(); warm_code_em_batch(); warm_code_em_set(); warm_code_quant_setup();
         static std::once_flag streams_once;
         std::call_once(streams_once, []() {
             hipStream_t a = nullptr, b = nullptr;
@@ -3836,6 +3836,387 @@ extern "C" int skm_quant_bootstrap_share_tpm(skm_quant *q, int64_t n_boot, int64
                                              int64_t max_iters, double *out, int64_t *iters_out)
 {
     return bootstrap_impl(q, n_boot, seed, x0, l, rel_tol, x_floor, max_iters, out, nullptr, iters_out, true, first, step);
+}
+
+// ---- many class tables over the same transcripts in shared EM launches (skm_em_set.hip) ------------
+// The tables of a GROUP are stacked into one block-diagonal problem on a handle of the call's own (class
+// views without component tiles: quant_alloc's several_ranks switch), set up once by quant_setup and
+// stepped by the segmented kernels until every slot has met its own stopping rule.  A group holds as
+// many consecutive tables as keep
+//   - slots * T below 2^31 (stacked transcript ids are int32) and the classes and pairs below 2^31,
+//   - slots at most SET_QUANT_MAX_SLOTS (gridDim.y) and at most SKM_SET_QUANT_GROUP (tests),
+//   - set_quant_bytes(), an estimate of the group's buffers and of the set-up's scratch, within
+//     SET_QUANT_GROUP_BYTES (2 GiB); a single table above that still runs, as a group of its own.
+// The next group reuses the buffers (they are sized for the largest group before the first runs).
+namespace {
+
+constexpr int64_t SET_QUANT_MAX_SLOTS = 32768;
+constexpr int64_t SET_QUANT_GROUP_BYTES = 1LL << 31;
+
+int64_t set_quant_bytes(int64_t slots, int64_t n_tx, int64_t n_classes, int64_t n_ids)
+{
+    return slots * n_tx * 96 + n_classes * 64 + n_ids * 24;
+}
+
+int64_t set_quant_slot_cap()
+{
+    const char *e = getenv("SKM_SET_QUANT_GROUP");                // (looked up at every call)
+    const int64_t asked = e ? atoll(e) : 0;
+    return asked > 0 ? std::min(asked, SET_QUANT_MAX_SLOTS) : SET_QUANT_MAX_SLOTS;
+}
+
+// group g = tables [first[g], first[g + 1]); `first` ends with n_tables
+void set_quant_cut(int64_t n_tables, int64_t n_tx, const int64_t *table_classes, const int64_t *table_ids, int64_t max_slots,
+                   std::vector<int64_t> *first)
+{
+    first->assign(1, 0);
+    int64_t slots = 0, classes = 0, ids = 0;
+    for (int64_t i = 0; i < n_tables; ++i) {
+        const bool fits = slots < max_slots && (slots + 1) * n_tx < (1LL << 31) && classes + table_classes[i] < (1LL << 31)
+                          && ids + table_ids[i] < (1LL << 31)
+                          && set_quant_bytes(slots + 1, n_tx, classes + table_classes[i], ids + table_ids[i]) <= SET_QUANT_GROUP_BYTES;
+        if (slots > 0 && !fits) {
+            first->push_back(i);
+            slots = classes = ids = 0;
+        }
+        ++slots; classes += table_classes[i]; ids += table_ids[i];
+    }
+    if (n_tables > 0) first->push_back(n_tables);
+}
+
+struct SetQuantRun {
+    // (the scratch before the handle: the handle's destructor, which runs first, drains the stream)
+    DBuf<EmSetSlot> slots;
+    DBuf<unsigned long long> running;
+    DBuf<double> out, sums;
+    std::unique_ptr<skm_quant> q;
+    int64_t n_tx = 0;
+};
+
+// room for the largest group of the cut
+int set_quant_open(SetQuantRun &run, int device, int64_t n_tx, const std::vector<int64_t> &first, const int64_t *table_classes,
+                   const int64_t *table_ids)
+{
+    int64_t slots = 1, classes = 0, ids = 0;
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        int64_t c = 0, m = 0;
+        for (int64_t i = first[g]; i < first[g + 1]; ++i) { c += table_classes[i]; m += table_ids[i]; }
+        slots = std::max(slots, first[g + 1] - first[g]);
+        classes = std::max(classes, c);
+        ids = std::max(ids, m);
+    }
+    if (slots * n_tx >= (1LL << 31)) return fail(SKM_ERR_ARG, "%lld transcripts: stacked ids do not fit 32 bits", (long long)n_tx);
+    run.n_tx = n_tx;
+    run.q.reset(new skm_quant());
+    SKM_TRY(quant_alloc(run.q.get(), device, slots * n_tx, classes, ids, true));
+    SKM_TRY(run.slots.ensure((size_t)slots));
+    SKM_TRY(run.running.ensure(2));
+    SKM_TRY(run.out.ensure((size_t)(slots * n_tx)));
+    SKM_TRY(run.sums.ensure((size_t)(slots * ((n_tx + 8191) / 8192 + 2))));
+    return SKM_OK;
+}
+
+// One group of n tables.  The caller has queued on the handle's stream whatever fills, for the stacked
+// problem: cls_offset [C + 1] (from 0), ids [M] (slot s's ids + s T), cls_count [C] -- classes table by
+// table in each table's own order --, eff_len and x0 [n][T].  slot_classes / slot_total: classes and sum
+// of the class counts of every table.  out [n][T] and iters [n] (host) get what skm_quant_create +
+// skm_quant_em give for each table alone; tpm: scaled as quantify() scales (infer.py:127-129).
+int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, const double *slot_total, int64_t C, int64_t M,
+                    double rel_tol, double x_floor, int64_t max_iters, bool tpm, double *out, int64_t *iters, int64_t first_table)
+{
+    skm_quant *q = run.q.get();
+    const int64_t T = run.n_tx;
+    // (on every way out, the failing ones too: copies from the callers' and this function's pageable staging
+    // vectors may still be queued, and those vectors go before the handle's destructor drains the stream)
+    struct Drain { hipStream_t stream; ~Drain() { (void)hipStreamSynchronize(stream); } } drain{q->stream};
+    if (C == 0) {                                                 // (quantify(): no class -> zeros, infer.py:106-107)
+        HIP_TRY(hipStreamSynchronize(q->stream));
+        if (out) std::fill(out, out + n * T, 0.0);
+        for (int64_t i = 0; i < n && iters; ++i) iters[i] = 0;
+        return SKM_OK;
+    }
+    q->n_tx = n * T; q->n_classes = C; q->n_ids = M;
+    SKM_TRY(quant_finish_setup(q, nullptr));
+    // every transcript has its rows, slot s those of transcripts [s T, (s + 1) T)
+    std::vector<int64_t> row_cut((size_t)n + 1);
+    HIP_TRY(hipMemcpy2DAsync(row_cut.data(), 8, q->tx_row.p, (size_t)T * 8, 8, (size_t)n + 1, hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    std::vector<EmSetSlot> slots((size_t)n);
+    int64_t cls = 0, largest_classes = 0, largest_rows = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        EmSetSlot &d = slots[(size_t)i];
+        d.cls_first = cls; d.cls_end = cls += slot_classes[i];
+        d.row_first = row_cut[(size_t)i]; d.row_end = row_cut[(size_t)i + 1];
+        if (d.row_end - d.row_first < T || d.row_end > q->n_rows)
+            return fail(SKM_ERR_STATE, "the stacked class views give table %lld rows [%lld, %lld)", (long long)(first_table + i),
+                        (long long)d.row_first, (long long)d.row_end);
+        d.n_total = slot_total[i];
+        d.done = slot_classes[i] == 0 ? 1 : 0;
+        d.iters = 0; d.undefined = 0;
+        if (slot_classes[i]) {
+            largest_classes = std::max(largest_classes, slot_classes[i]);
+            largest_rows = std::max(largest_rows, d.row_end - d.row_first);
+        }
+    }
+    if (cls != C) return fail(SKM_ERR_STATE, "the tables of the group hold %lld classes, not %lld", (long long)cls, (long long)C);
+    EmSetProblem p{};
+    p.cls_offset = q->cls_offset.p; p.ids = q->ids.p; p.cls_count = q->cls_count.p; p.inner = q->inner.p;
+    p.row_start = q->row_start.p; p.row_tx = q->row_tx.p; p.tx_cls = q->tx_cls.p; p.tx_row = q->tx_row.p;
+    p.row_sum = q->row_sum.p; p.eff_len = q->eff_len.p; p.x[0] = q->x0.p; p.x[1] = q->x1.p;
+    p.rel_tol = rel_tol; p.x_floor = x_floor; p.max_iters = max_iters;
+    p.slots = run.slots.p; p.n_slots = (int)n;
+    p.n_parts = em_set_parts(largest_rows);
+    SKM_TRY(q->part_max.ensure((size_t)(n * p.n_parts)));
+    SKM_TRY(q->part_flags.ensure((size_t)(n * p.n_parts)));
+    p.part_max = q->part_max.p; p.part_flags = q->part_flags.p;
+    p.arrivals = q->arrivals.p;
+    HIP_TRY(hipMemcpyAsync(run.slots.p, slots.data(), (size_t)n * sizeof(EmSetSlot), hipMemcpyHostToDevice, q->stream));
+    // Steps are queued in chunks with the host one chunk ahead, as em_run does; what the host reads at a
+    // chunk's end is the number of slots still running.
+    const int64_t chunk = 16;
+    int64_t k = 0;
+    auto enqueue_chunk = [&](int slot) -> int {
+        HIP_TRY(hipMemsetAsync(run.running.p + slot, 0, 8, q->stream));
+        for (int64_t i = 0; i < chunk; ++i, ++k) launch_em_set_step(p, largest_classes, k, i > 0, q->stream);
+        launch_em_set_decide(p, k, run.running.p + slot, q->stream);
+        q->launches += 2 * chunk + 1;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(q->pinned + 8 * slot, run.running.p + slot, 8, hipMemcpyDeviceToHost, q->stream));
+        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
+        return SKM_OK;
+    };
+    SKM_TRY(enqueue_chunk(0));
+    for (int slot = 0;; slot ^= 1) {
+        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
+        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
+        if (q->pinned[8 * slot] == 0) break;
+        if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the EM of the stacked tables does not stop");
+    }
+    HIP_TRY(hipMemcpyAsync(slots.data(), run.slots.p, (size_t)n * sizeof(EmSetSlot), hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));             // (with it the look-ahead chunk: no-ops)
+    for (int64_t i = 0; i < n; ++i) {
+        if (slots[(size_t)i].undefined)
+            return fail(SKM_ERR_UNDEFINED, "table %lld: no abundance above x_floor: numpy raises on max() of an empty selection",
+                        (long long)(first_table + i));
+        if (iters) iters[i] = (int64_t)slots[(size_t)i].iters;
+        q->iters_total += (double)slots[(size_t)i].iters;
+    }
+    launch_em_set_result(run.slots.p, (int)n, q->x0.p, q->x1.p, T, run.out.p, q->stream);
+    if (tpm) {
+        double *const totals = run.sums.p + n * ((T + 8191) / 8192);  // (sum, sum / 1e6) per table
+        launch_np_sum_many(run.out.p, T, n, T, 1000000.0, run.sums.p, totals, q->stream);
+        launch_divide_many(run.out.p, T, n, T, totals + 1, true, 0.001, q->stream);
+        launch_np_sum_many(run.out.p, T, n, T, 1000000.0, run.sums.p, totals, q->stream);
+        launch_divide_many(run.out.p, T, n, T, totals + 1, false, 0.0, q->stream);
+        for (int64_t i = 0; i < n; ++i)                   // (quantify() does not scale the zeros of a table without classes)
+            if (slot_classes[i] == 0) HIP_TRY(hipMemsetAsync(run.out.p + i * T, 0, (size_t)T * 8, q->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    if (out) HIP_TRY(hipMemcpyAsync(out, run.out.p, (size_t)(n * T) * 8, hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    return SKM_OK;
+}
+
+}  // namespace
+
+extern "C" int skm_set_quant_groups(int64_t n_tables, int64_t n_tx, const int64_t *table_classes, const int64_t *table_ids,
+                                    int64_t max_slots, int64_t *n_groups, int64_t *group_first)
+{
+    if (n_tables < 0 || n_tx <= 0 || max_slots < 1 || !n_groups || (n_tables && (!table_classes || !table_ids || !group_first)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    for (int64_t i = 0; i < n_tables; ++i)
+        if (table_classes[i] < 0 || table_ids[i] < 0) return fail(SKM_ERR_ARG, "negative size of table %lld", (long long)i);
+    std::vector<int64_t> first;
+    set_quant_cut(n_tables, n_tx, table_classes, table_ids, std::min(max_slots, SET_QUANT_MAX_SLOTS), &first);
+    *n_groups = (int64_t)first.size() - 1;
+    if (n_tables) std::copy(first.begin(), first.end(), group_first);
+    return SKM_OK;
+}
+
+extern "C" int skm_quant_em_tables(int device, int64_t n_tx, int64_t n_tables, const int64_t *table_class_offsets,
+                                   const int64_t *class_offsets, const int32_t *class_targets, const double *class_counts,
+                                   const double *x0, const double *l, double rel_tol, double x_floor, int64_t max_iters,
+                                   int tpm, double *out, int64_t *iters)
+{
+    if (n_tables < 0 || n_tx <= 0) return fail(SKM_ERR_ARG, "bad argument");
+    if (n_tables == 0) return SKM_OK;                             // (nothing to do, with or without a GPU)
+    if (!table_class_offsets || !x0 || !l || !out) return fail(SKM_ERR_ARG, "NULL argument");
+    if (table_class_offsets[0] < 0) return fail(SKM_ERR_ARG, "negative class offset");
+    for (int64_t s = 0; s < n_tables; ++s)
+        if (table_class_offsets[s + 1] < table_class_offsets[s]) return fail(SKM_ERR_ARG, "table offsets are not monotone");
+    const int64_t c_lo = table_class_offsets[0], c_hi = table_class_offsets[n_tables];
+    if (c_hi > c_lo && (!class_offsets || !class_targets || !class_counts)) return fail(SKM_ERR_ARG, "NULL class arrays");
+    for (int64_t c = c_lo; c < c_hi; ++c)
+        if (class_offsets[c + 1] < class_offsets[c] || class_offsets[c] < 0) return fail(SKM_ERR_ARG, "class offsets are not monotone");
+    if (c_hi > c_lo)
+        for (int64_t j = class_offsets[c_lo]; j < class_offsets[c_hi]; ++j)
+            if (class_targets[j] < 0 || class_targets[j] >= n_tx)
+                return fail(SKM_ERR_ARG, "class target %d outside [0, n_tx)", (int)class_targets[j]);
+    std::vector<int64_t> classes((size_t)n_tables), ids((size_t)n_tables), first;
+    std::vector<double> total((size_t)n_tables);
+    // A class without a tuple entry adds its count to the table's total and nothing else: no transcript's
+    // sum reads it (skm_quant_create keeps it, with the key of no transcript).  In the stacked order that key
+    // would put it behind the classes of EVERY table, outside its own table's range, so such classes are left
+    // out of the stacked problem; the total still counts them.  A table of nothing but such classes has no
+    // defined problem and no place here.
+    for (int64_t s = 0; s < n_tables; ++s) {
+        const int64_t a = table_class_offsets[s], b = table_class_offsets[s + 1];
+        int64_t named = 0;
+        for (int64_t c = a; c < b; ++c) named += class_offsets[c + 1] > class_offsets[c];
+        if (b > a && named == 0) return fail(SKM_ERR_ARG, "table %lld: none of its %lld classes names a transcript", (long long)s, (long long)(b - a));
+        classes[(size_t)s] = named;
+        ids[(size_t)s] = b > a ? class_offsets[b] - class_offsets[a] : 0;
+        total[(size_t)s] = b > a ? np_sum_host(class_counts + a, b - a) : 0.0;     // (as skm_quant_create)
+    }
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(set_device(device));
+    set_quant_cut(n_tables, n_tx, classes.data(), ids.data(), set_quant_slot_cap(), &first);
+    std::vector<int64_t> offsets;                                 // (staging, declared before the run: its handle's destructor,
+    std::vector<int32_t> stacked;                                 //  which drains the stream, then runs before they go)
+    std::vector<double> counts;
+    SetQuantRun run;
+    SKM_TRY(set_quant_open(run, device, n_tx, first, classes.data(), ids.data()));
+    skm_quant *q = run.q.get();
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        const int64_t t0 = first[g], n = first[g + 1] - t0;
+        int64_t C = 0, M = 0;
+        for (int64_t s = 0; s < n; ++s) { C += classes[(size_t)(t0 + s)]; M += ids[(size_t)(t0 + s)]; }
+        if (C) {
+            offsets.resize((size_t)C + 1);
+            counts.resize((size_t)C);
+            stacked.resize((size_t)M);
+            int64_t k = 0, j_out = 0;
+            for (int64_t s = 0; s < n; ++s) {
+                const int32_t base = (int32_t)(s * n_tx);
+                for (int64_t c = table_class_offsets[t0 + s]; c < table_class_offsets[t0 + s + 1]; ++c) {
+                    if (class_offsets[c + 1] == class_offsets[c]) continue;
+                    offsets[(size_t)k] = j_out;
+                    counts[(size_t)k++] = class_counts[c];
+                    for (int64_t j = class_offsets[c]; j < class_offsets[c + 1]; ++j) stacked[(size_t)j_out++] = class_targets[j] + base;
+                }
+            }
+            offsets[(size_t)C] = j_out;
+            if (k != C || j_out != M) return fail(SKM_ERR_STATE, "stacked %lld classes and %lld ids of %lld and %lld", (long long)k, (long long)j_out, (long long)C, (long long)M);
+            HIP_TRY(hipMemcpyAsync(q->cls_offset.p, offsets.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->cls_count.p, counts.data(), (size_t)C * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->ids.p, stacked.data(), (size_t)M * 4, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->x0.p, x0 + t0 * n_tx, (size_t)(n * n_tx) * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->eff_len.p, l + t0 * n_tx, (size_t)(n * n_tx) * 8, hipMemcpyHostToDevice, q->stream));
+        }
+        SKM_TRY(set_quant_group(run, n, classes.data() + t0, total.data() + t0, C, M, rel_tol, x_floor, max_iters, tpm != 0,
+                                out + t0 * n_tx, iters ? iters + t0 : nullptr, t0));
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_quantify(skm_sample_set *s, const double *lengths, int64_t n_tx, double rel_tol, double x_floor,
+                                       int64_t max_iters, int64_t cap_samples, int64_t *n_samples, double *tpm,
+                                       double *effective_lengths, int64_t *iters)
+{
+    if (!s || !lengths || !n_samples || n_tx <= 0 || cap_samples < 0 || (cap_samples && !tpm))
+        return fail(SKM_ERR_ARG, "bad argument");
+    {
+        std::lock_guard<std::mutex> counting(s->mu);              // (before any device work)
+        *n_samples = (int64_t)s->sample_units.size();
+    }
+    if (cap_samples < *n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)*n_samples);
+    if (*n_samples == 0) return SKM_OK;
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    const skm_sample_set::View &v = s->view;
+    const int64_t S = (int64_t)v.units.size();
+    *n_samples = S;
+    if (cap_samples < S) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)S);
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    // a tuple's ids index the stacked abundance vectors: none may lie outside the caller's transcripts
+    for (size_t k = 0; k < v.order.size(); ++k) {
+        const int64_t c = v.order[k];
+        if (v.len[c] <= 0) return fail(SKM_ERR_STATE, "class %lld of the set has no tuple", (long long)c);   // (it would leave its sample's range)
+        for (int64_t j = 0; j < v.len[c]; ++j)
+            if (v.arena[(size_t)(v.start[c] + j)] < 0 || v.arena[(size_t)(v.start[c] + j)] >= n_tx)
+                return fail(SKM_ERR_ARG, "the set's classes name transcript %d: not below n_tx = %lld", (int)v.arena[(size_t)(v.start[c] + j)],
+                            (long long)n_tx);
+    }
+    std::vector<int64_t> classes((size_t)S), ids((size_t)S), first;
+    std::vector<double> total((size_t)S);
+    for (int64_t i = 0; i < S; ++i) {
+        classes[(size_t)i] = v.sample_class_offsets[(size_t)i + 1] - v.sample_class_offsets[(size_t)i];
+        ids[(size_t)i] = v.sample_rows[(size_t)i];
+        total[(size_t)i] = (double)v.sample_aligned[(size_t)i];   // n = its aligned units
+    }
+    set_quant_cut(S, n_tx, classes.data(), ids.data(), set_quant_slot_cap(), &first);
+    // the class tuples stay where the mapper left them: a group's are gathered from the table's arena into
+    // the stacked problem on the device, by the classes' places there -- a few words per class from the host
+    DBuf<double> lengths_dev;
+    DBuf<unsigned long long> hist;
+    DBuf<int64_t> src, dst;
+    DBuf<int32_t> add;
+    std::vector<int64_t> h_src, h_dst;                            // (staging, before the run: see skm_quant_em_tables)
+    std::vector<int32_t> h_add;
+    std::vector<double> h_count;
+    SetQuantRun run;
+    SKM_TRY(set_quant_open(run, m->ix->device, n_tx, first, classes.data(), ids.data()));
+    skm_quant *q = run.q.get();
+    int64_t slots_max = 1, classes_max = 1;
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        slots_max = std::max(slots_max, first[g + 1] - first[g]);
+        classes_max = std::max(classes_max, v.sample_class_offsets[(size_t)first[g + 1]] - v.sample_class_offsets[(size_t)first[g]]);
+    }
+    SKM_TRY(lengths_dev.ensure((size_t)n_tx));
+    SKM_TRY(src.ensure((size_t)classes_max)); SKM_TRY(dst.ensure((size_t)classes_max + 1)); SKM_TRY(add.ensure((size_t)classes_max));
+    if (s->keep_hist) SKM_TRY(hist.ensure((size_t)slots_max * MAX_FRAGMENT_LENGTH));
+    HIP_TRY(hipStreamSynchronize(m->stream));                     // (the table, the arena and the histograms are final)
+    HIP_TRY(hipMemcpyAsync(lengths_dev.p, lengths, (size_t)n_tx * 8, hipMemcpyHostToDevice, q->stream));
+    const int64_t hist_rows = (int64_t)(s->hist.cap / MAX_FRAGMENT_LENGTH);     // (a sample past them has an empty histogram)
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        const int64_t t0 = first[g], n = first[g + 1] - t0;
+        const int64_t k0 = v.sample_class_offsets[(size_t)t0], C = v.sample_class_offsets[(size_t)(t0 + n)] - k0;
+        h_src.resize((size_t)C); h_dst.resize((size_t)C + 1); h_add.resize((size_t)C); h_count.resize((size_t)C);
+        int64_t M = 0;
+        for (int64_t i = 0; i < n; ++i)
+            for (int64_t k = v.sample_class_offsets[(size_t)(t0 + i)]; k < v.sample_class_offsets[(size_t)(t0 + i) + 1]; ++k) {
+                const int64_t c = v.order[(size_t)k];
+                h_src[(size_t)(k - k0)] = v.start[(size_t)c];
+                h_dst[(size_t)(k - k0)] = M;
+                h_add[(size_t)(k - k0)] = (int32_t)(i * n_tx);
+                h_count[(size_t)(k - k0)] = (double)v.count[(size_t)c];
+                M += v.len[(size_t)c];
+            }
+        h_dst[(size_t)C] = M;
+        if (s->keep_hist) {
+            const int64_t have = std::max<int64_t>(0, std::min(n, hist_rows - t0));
+            HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)n * MAX_FRAGMENT_LENGTH * 8, q->stream));
+            if (have) HIP_TRY(hipMemcpyAsync(hist.p, s->hist.p + t0 * MAX_FRAGMENT_LENGTH, (size_t)have * MAX_FRAGMENT_LENGTH * 8,
+                                             hipMemcpyDeviceToDevice, q->stream));
+            launch_effective_lengths_many(hist.p, n, lengths_dev.p, n_tx, q->eff_len.p, q->stream);
+        } else {
+            launch_effective_lengths(m->counters.p + CTR_FLD, lengths_dev.p, n_tx, q->eff_len.p, q->stream);
+            launch_repeat_row(q->eff_len.p, n_tx, n, q->stream);
+        }
+        if (effective_lengths)
+            HIP_TRY(hipMemcpyAsync(effective_lengths + t0 * n_tx, q->eff_len.p, (size_t)(n * n_tx) * 8, hipMemcpyDeviceToHost, q->stream));
+        if (C) {
+            // the start vector of skm_quant_infer, per sample: reciprocal, numpy's sum, divide
+            double *const totals = run.sums.p + n * ((n_tx + 8191) / 8192);
+            launch_reciprocal(q->eff_len.p, n * n_tx, q->x0.p, q->stream);
+            launch_np_sum_many(q->x0.p, n_tx, n, n_tx, 1.0, run.sums.p, totals, q->stream);
+            launch_divide_many(q->x0.p, n_tx, n, n_tx, totals, false, 0.0, q->stream);
+            HIP_TRY(hipMemcpyAsync(src.p, h_src.data(), (size_t)C * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(dst.p, h_dst.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(add.p, h_add.data(), (size_t)C * 4, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->cls_offset.p, h_dst.data(), (size_t)(C + 1) * 8, hipMemcpyHostToDevice, q->stream));
+            HIP_TRY(hipMemcpyAsync(q->cls_count.p, h_count.data(), (size_t)C * 8, hipMemcpyHostToDevice, q->stream));
+            launch_stack_tuples(src.p, dst.p, add.p, C, m->arena.p, q->ids.p, q->stream);
+            HIP_TRY(hipGetLastError());
+        }
+        SKM_TRY(set_quant_group(run, n, classes.data() + t0, total.data() + t0, C, M, rel_tol, x_floor, max_iters, true,
+                                tpm + t0 * n_tx, iters ? iters + t0 : nullptr, t0));
+    }
+    return SKM_OK;
 }
 
 extern "C" int skm_quant_timing(skm_quant *q, double timing[4])

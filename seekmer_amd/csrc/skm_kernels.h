@@ -337,6 +337,54 @@ void launch_blend_counts(const double *own, const int32_t *class_cell, const dou
                          int64_t n_cells, int64_t first, int64_t n_rows, int64_t n_classes, double *rows, hipStream_t stream);
 // y[i][k] = x[i][perm[k]] for n_rows vectors of n doubles
 void launch_permute_rows_f64(const double *x, const int32_t *perm, int64_t n, int64_t n_rows, double *y, hipStream_t stream);
+// ---- the EM for many class tables over the same transcripts, stacked into one block-diagonal problem
+// (skm_em_set.hip): table s of the group -- slot s -- owns stacked transcripts [s T, (s + 1) T), a class
+// range and a row range of the stacked views, its own total and its own stopping rule.
+struct EmSetSlot {                // 64 bytes, in HBM
+    int64_t cls_first, cls_end;   // internal classes of the slot
+    int64_t row_first, row_end;   // rows of the slot
+    double n_total;               // sum of its class counts
+    unsigned long long done;      // its control words: stopped (set from the start for a slot without classes),
+    unsigned long long iters;     // steps judged so far = its step count once stopped,
+    unsigned long long undefined; // no abundance above x_floor
+};
+struct EmSetProblem {
+    const int64_t *cls_offset;    // the stacked views: as EmProblem
+    const int32_t *ids;
+    const double *cls_count;
+    double *inner;
+    const int64_t *row_start;
+    const int32_t *row_tx;
+    const int32_t *tx_cls;
+    const int64_t *tx_row;
+    double *row_sum;
+    const double *eff_len;        // [slots][T]
+    double *x[2];                 // [slots][T] ping-pong
+    double rel_tol, x_floor;
+    int64_t max_iters;
+    EmSetSlot *slots;             // [n_slots]
+    int n_slots;
+    int n_parts;                  // blocks per slot of the rows launch = partials per slot (em_set_parts)
+    double *part_max;             // [n_slots][n_parts]
+    unsigned int *part_flags;     // [n_slots][n_parts] bit0 = any, bit1 = nan
+    unsigned int *arrivals;       // [slots T] as EmProblem
+};
+// partials per slot for a group whose largest slot has `largest_rows` rows
+int em_set_parts(int64_t largest_rows);
+// one step (inner, rows + finalize) of every running slot; judge_previous: block (0, s) of the inner
+// launch first applies slot s's stopping rule to finalize pass `step`
+void launch_em_set_step(const EmSetProblem &p, int64_t largest_classes, int64_t step, bool judge_previous, hipStream_t stream);
+// the stopping rule of every running slot for finalize pass steps_done; *running (zero before) += slots that go on
+void launch_em_set_decide(const EmSetProblem &p, int64_t steps_done, unsigned long long *running, hipStream_t stream);
+// out[s][t] = x[iters_s & 1][s T + t], zeros for a slot without classes
+void launch_em_set_result(const EmSetSlot *slots, int n_slots, const double *x0, const double *x1, int64_t n_tx, double *out,
+                          hipStream_t stream);
+// ids[dst[k] + j] = arena[src[k] + j] + add[k] for j < dst[k + 1] - dst[k]
+void launch_stack_tuples(const int64_t *src, const int64_t *dst, const int32_t *add, int64_t n_classes, const int32_t *arena,
+                         int32_t *ids, hipStream_t stream);
+// rows 1 .. n - 1 of x[n][n_tx] = row 0 (n <= 65536)
+void launch_repeat_row(double *x, int64_t n_tx, int64_t n, hipStream_t stream);
+
 // device-side construction of the two CSR views (skm_quant_setup.hip)
 struct QuantBuild {
     int64_t n_tx, n_classes, n_ids;
@@ -416,6 +464,7 @@ void warm_code_map();
 void warm_code_classes();
 void warm_code_em();
 void warm_code_em_batch();
+void warm_code_em_set();
 void warm_code_quant_setup();
 
 }  // namespace skm

@@ -14,8 +14,10 @@ the GPU once.  The second round is then many EM problems on one structure:
 the cells' blended counts are made on the device and eight cells at a time run
 side by side in the batched EM (`_QuantHandle.em_blend`), each with the steps
 and the bits of `set_counts` + the EM kernels for that cell alone -- the loop
-that SKM_IMPUTE_SERIAL=1 still selects.  The first round stays one cell at a
-time: the cells' own tables have different structures.
+that SKM_IMPUTE_SERIAL=1 still selects.  The first round -- the cells' own
+tables, whose structures differ -- can run as one block-diagonal problem in
+shared launches (`first_round`; SKM_SET_QUANT_SERIAL=1 keeps the loop, and so
+does SKM_IMPUTE_SERIAL=1: with it both rounds run one cell at a time).
 The arithmetic that decides results is the reference's, cited per function.
 """
 import logging
@@ -64,13 +66,15 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
         _LOG.info('Mapped all reads.')
         summaries = sample_set.summarize()
     else:
+        sample_set = None
         map_results = mapper.map_multiple_samples(index, feeders, job_count=job_count, debug=debug,
                                                   device=device, strand=strand)
         _LOG.info('Mapped all reads.')
         pool_fragment_lengths(map_results)
         summaries = [result.summarize() for result in map_results]
     _LOG.info('First round quantification...')
-    base = numpy.asarray([infer.quantify(summary) for summary in summaries])
+    base = first_round(summaries, sample_set, device=device)
+    del sample_set
     if power is not None:
         _LOG.info('Weighting cells.')
         weight = cell_weights(index, base, output_path, seed=seed)
@@ -102,6 +106,55 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
 SAMPLE_SET_MIN_CELLS = 2
 SAMPLE_SET_MAX_CELL_BYTES = 640 << 20     # the files of the largest cell: what 2 M pairs of 2 x 75 bases with short names come to
 SAMPLE_SET_COMPRESSED_RATIO = 4           # a compressed file counts this many times its size (an estimate of its text; not measured)
+
+
+# Where the first round -- every cell's own table -- runs in shared EM launches (mapper.SampleSet.quantify
+# for cells mapped through a set, infer.quantify_tables otherwise) instead of infer.quantify() cell by cell.
+# Measured ("Many class tables in shared EM launches"; profiles/set_quant_ab.log: the first round
+# from mapped tables, the forms alternating in one process, against the parent commit's loop on the same GPU
+# right after; ms for all cells, the later repetitions of three): 64 cells of 20 k pairs on 944 transcripts
+# 10.6-10.9 (set) and 6.7-6.8 (tables) against 112.6-119.8 (10 x, 17 x); 512 such cells 75.1-75.9 and
+# 56.8-59.5 against 914.4-937.6 (12 x, 16 x); 8 such cells 3.8-3.9 against 14.6-14.7 (3.8 x); 64 cells of
+# 50 k pairs on 190 402 transcripts (2.63 M classes in all) 180.8-182.6 and 176.8-179.4 against 227.4-238.1
+# (1.3 x: a gap of 50 ms against a spread of 11).  At 2 cells of 20 k pairs the forms are level (3.4-3.5
+# against 3.6 ms), 3 to 7 cells were not run: the loop stays below 8.  The rule is those points and what lies
+# between them, nothing rounded up: on tables of up to 944 transcripts from 8 cells and up to the 1 773 517
+# classes in all of the 512 cells; on larger tables, up to the 190 402 transcripts and 2 629 763 classes in all
+# that were measured, only from the 64 cells that were measured there -- fewer cells on such a table were not
+# run, and the gain shrinks both with fewer cells (10 x to 3.8 x on the small table) and with more
+# transcripts (10 x to 1.3 x at 64 cells): the shared launches step the whole table, the loop's EM runs in
+# component tiles where it can.
+SET_QUANT_MIN_SAMPLES = 8
+SET_QUANT_SMALL_TRANSCRIPTS = 944
+SET_QUANT_SMALL_CLASSES = 1_773_517
+SET_QUANT_LARGE_MIN_SAMPLES = 64
+SET_QUANT_MAX_TRANSCRIPTS = 190_402
+SET_QUANT_MAX_CLASSES = 2_629_763
+
+
+def use_set_quant(n_samples, n_tx, n_classes):
+    """The rule of first_round() and of infer.run_many: samples, transcripts, classes of all samples together.
+    SKM_SET_QUANT_SERIAL=1 (exactly that value, looked up at every call) selects the loop over the samples
+    whatever the shape."""
+    if os.environ.get('SKM_SET_QUANT_SERIAL') == '1':
+        return False
+    if n_samples >= SET_QUANT_MIN_SAMPLES and n_tx <= SET_QUANT_SMALL_TRANSCRIPTS and n_classes <= SET_QUANT_SMALL_CLASSES:
+        return True
+    return n_samples >= SET_QUANT_LARGE_MIN_SAMPLES and n_tx <= SET_QUANT_MAX_TRANSCRIPTS and n_classes <= SET_QUANT_MAX_CLASSES
+
+
+def first_round(summaries, sample_set=None, device=0):
+    """quantify() of every cell's own table (seekmer/impute.py:98): f8[cells, n_tx].  Inside the regime of
+    use_set_quant the cells run in shared EM launches -- from the set's resident table when they were mapped
+    through one, from the summaries otherwise -- bit for bit what the loop gives.  SKM_IMPUTE_SERIAL=1, the
+    switch that keeps the second round one cell at a time, keeps this round so as well."""
+    if summaries and os.environ.get('SKM_IMPUTE_SERIAL') != '1' \
+            and use_set_quant(len(summaries), summaries[0].effective_lengths.size,
+                                   sum(summary.class_count.size for summary in summaries)):
+        if sample_set is not None:
+            return numpy.asarray(sample_set.quantify())
+        return numpy.asarray(infer.quantify_tables(summaries, device=device))
+    return numpy.asarray([infer.quantify(summary) for summary in summaries])
 
 
 def cell_text_bytes(group):

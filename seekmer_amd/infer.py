@@ -18,7 +18,7 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'run_many', 'quantify', 'quantify_many', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+__all__ = ['run', 'run_many', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
            'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
@@ -158,10 +158,16 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     launches in one mapper.SampleSet that keeps a fragment-length histogram per sample; every other
     sample is mapped by itself on the same index handle.  SKM_INFER_MANY_PER_SAMPLE=1 maps every
     sample by itself.  `seed` is used for every sample, so a sample's `-b N` replicates are those of
-    `infer -b N --seed S` on it.  One process, one GPU; no readmap (a set has none)."""
+    `infer -b N --seed S` on it.  One process, one GPU; no readmap (a set has none).
+
+    Inside the regime of impute.use_set_quant the main estimates of the samples that went through the set
+    come from SampleSet.quantify() -- shared EM launches on the set's resident table, the bits of the loop;
+    SKM_SET_QUANT_SERIAL=1 keeps quantify() sample by sample.  `-b N` stays per sample.  SKM_TRACE_INFER
+    prints the host wall time per phase on stderr."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
+    trace = _phase_trace()
     mapper.strand_mode(strand)
     groups = sample_groups(fastq_paths, single_ended)
     if not groups:
@@ -185,6 +191,8 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     paired = not single_ended
     in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
     summaries, means = [None] * len(groups), [None] * len(groups)
+    set_estimates = {}
+    trace('index load')
     if in_set:
         _LOG.info('Mapping %d samples in shared launches', len(in_set))
         feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
@@ -193,6 +201,18 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
                                            strand=strand, per_sample_lengths=True)
         for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
             summaries[i], means[i] = summary, mean
+        trace('mapping (set)')
+        # (the main estimates of the set's samples in shared EM launches, from the table where it lies)
+        if all(summaries[i].total for i in in_set) and impute.use_set_quant(
+                len(in_set), index.transcripts.size, sum(summaries[i].class_count.size for i in in_set)):
+            try:
+                set_estimates = dict(zip(in_set, sample_set.quantify()))
+            except _native.NativeError as error:
+                # (a sample that leaves no abundance above the floor: the loop below writes the samples before
+                # it and raises at that one, as it always has)
+                if error.code != _native.SKM_ERR_UNDEFINED:
+                    raise
+            trace('quantification (set)')
         del sample_set
     for i, group in enumerate(groups):
         if summaries[i] is not None:
@@ -203,23 +223,52 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
         del map_result
     _LOG.info('Mapped all reads')
+    trace('mapping (one by one)')
     for name, summary in zip(names, summaries):
         if summary.total == 0:
             raise ValueError('sample %s has no reads' % name)
         if bootstrap > 0 and summary.aligned > RESAMPLE_LIMIT:
             raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
                              % (RESAMPLE_LIMIT, name, summary.aligned))
-    for name, summary in zip(names, summaries):
+    for i, (name, summary) in enumerate(zip(names, summaries)):
         _LOG.info('Quantifying sample %s', name)
-        main_result = quantify(summary, device=device)
+        main_result = set_estimates[i] if i in set_estimates else quantify(summary, device=device)
+        trace('quantification', pause=True)
         bootstrapped_results = bootstrap_quantify(summary, main_result, bootstrap, seed=seed, device=device)
+        trace('bootstraps', pause=True)
         sample_path = output_path / name
         sample_path.mkdir(exist_ok=True)
         output_results(sample_path, index, start_time, summary, main_result, bootstrapped_results)
+        trace('writing', pause=True)
     with (output_path / 'samples.tsv').open('w') as f:
         for name, summary, mean in zip(names, summaries, means):
             f.write('%s\t%d\t%d\t%.2f\n' % (name, summary.total, summary.aligned, mean))
+    trace('writing', pause=True)
+    trace(None)
     _LOG.info('Wrote results to %s', output_path)
+
+
+def _phase_trace():
+    """SKM_TRACE_INFER (set to anything): run_many's host wall time per phase on stderr.  trace(phase) closes the
+    lap since the last call and prints it; with pause=True the lap is added to the phase's sum instead, and
+    trace(None) prints the sums.  Without the switch the calls do nothing."""
+    import sys
+    import time
+    if os.environ.get('SKM_TRACE_INFER') is None:
+        return lambda phase, pause=False: None
+    state = {'last': time.perf_counter(), 'sums': {}}
+
+    def trace(phase, pause=False):
+        now = time.perf_counter()
+        lap, state['last'] = now - state['last'], now
+        if phase is None:
+            for name, total in state['sums'].items():
+                print('[run_many] %-24s %10.1f ms' % (name, total * 1e3), file=sys.stderr)
+        elif pause:
+            state['sums'][phase] = state['sums'].get(phase, 0.0) + lap
+        else:
+            print('[run_many] %-24s %10.1f ms' % (phase, lap * 1e3), file=sys.stderr)
+    return trace
 
 
 RESAMPLE_LIMIT = 2 ** 32 - 1        # units one multinomial draw can resample (skm_quant_bootstrap*)
@@ -525,6 +574,63 @@ def quantify_many(results, class_counts, device=0, return_iters=False):
         if owned:
             quant.close()
     return (out, iters) if return_iters else out
+
+
+def _table_csr(results):
+    """(class offsets, class targets, class counts) of a summary; a summary without class tuples has
+    no classes here (quantify() returns zeros for it before it looks at the counts)."""
+    if results.class_map.size == 0:
+        return numpy.zeros(1, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int32), numpy.zeros(0, dtype='f8')
+    offsets = getattr(results, 'class_offsets', None)
+    targets = getattr(results, 'class_targets', None)
+    if offsets is None or targets is None:
+        offsets, targets = _csr_from_class_map(results.class_map, results.class_count.size)
+    offsets = numpy.asarray(offsets, dtype=numpy.int64)
+    return offsets - offsets[0], numpy.asarray(targets, dtype=numpy.int32)[offsets[0]:offsets[-1]], \
+        numpy.asarray(results.class_count, dtype='f8')
+
+
+def quantify_tables(results_list, device=0, return_iters=False):
+    """quantify() for K DIFFERENT class tables over the same transcripts (the companion of quantify_many,
+    which runs K count vectors on one table): [K, n_tx] TPM, row k what quantify(results_list[k]) returns
+    bit for bit -- every table starts from 1 / its effective lengths as quantify() does
+    (seekmer/infer.py:116-119) --, with the EM steps of each when return_iters is set.  The tables are
+    stacked into one block-diagonal problem and stepped in shared launches, each to its own stopping
+    rule (skm_quant_em_tables).  Tables of different n_tx raise ValueError."""
+    results_list = list(results_list)
+    n = len(results_list)
+    sizes = {results.effective_lengths.size for results in results_list}
+    if len(sizes) > 1:
+        raise ValueError('the tables must share their transcripts: n_tx = %s' % sorted(sizes))
+    n_tx = sizes.pop() if sizes else 0
+    out = numpy.zeros((n, n_tx), dtype='f8')
+    iters = numpy.zeros(max(n, 1), dtype=numpy.int64)
+    if n and n_tx:
+        lengths = numpy.zeros((n, n_tx), dtype='f8')
+        start = numpy.zeros((n, n_tx), dtype='f8')
+        table_offsets = numpy.zeros(n + 1, dtype=numpy.int64)
+        offsets, targets, counts = [numpy.zeros(1, dtype=numpy.int64)], [], []
+        n_ids = 0
+        for k, results in enumerate(results_list):
+            lengths[k] = results.effective_lengths.astype('f8')
+            x = numpy.ones(n_tx, dtype='f8') / lengths[k]
+            x /= x.sum()
+            start[k] = x
+            table = _table_csr(results)
+            offsets.append(table[0][1:] + n_ids)
+            targets.append(table[1])
+            counts.append(table[2])
+            n_ids += int(table[0][-1])
+            table_offsets[k + 1] = table_offsets[k] + table[2].size
+        offsets = numpy.ascontiguousarray(numpy.concatenate(offsets), dtype=numpy.int64)
+        targets = numpy.ascontiguousarray(numpy.concatenate(targets + [numpy.zeros(1, dtype=numpy.int32)]), dtype=numpy.int32)
+        counts = numpy.ascontiguousarray(numpy.concatenate(counts + [numpy.zeros(1, dtype='f8')]), dtype='f8')
+        _native.check(_native.hip().skm_quant_em_tables(
+            device, n_tx, n, _native.ptr(table_offsets, _native.c_i64p), _native.ptr(offsets, _native.c_i64p),
+            _native.ptr(targets, _native.c_i32p), _native.ptr(counts, _native.c_f64p), _native.ptr(start, _native.c_f64p),
+            _native.ptr(lengths, _native.c_f64p), REL_TOL, X_FLOOR, 0, 1, _native.ptr(out, _native.c_f64p),
+            _native.ptr(iters, _native.c_i64p)))
+    return (out, iters[:n]) if return_iters else out
 
 
 def quantify_resident(map_result, comm=None, return_iters=False, return_effective_lengths=False):

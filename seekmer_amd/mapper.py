@@ -724,6 +724,37 @@ class SampleSet:
         """One number per sample: MapResult.harmonic_mean_fragment_length of the sample mapped alone."""
         return harmonic_mean_fragment_lengths(self.sample_fragment_length_counts)
 
+    def quantify(self, return_iters=False, return_effective_lengths=False):
+        """infer.quantify(summary) for every sample of the set in shared EM launches
+        (skm_sample_set_quantify): f8[n_samples, n_tx] TPM, row i bit for bit what quantify() gives on
+        summarize()[i] -- sample i's own effective lengths with per_sample_lengths, the pooled ones
+        otherwise; zeros for a sample without aligned units.  Optionally the EM steps per sample and
+        the effective lengths [n_samples, n_tx].  NativeError SKM_ERR_UNDEFINED when a sample leaves
+        no abundance above the floor, as quantify() on it."""
+        from .infer import REL_TOL, X_FLOOR
+        lengths = numpy.ascontiguousarray(self.index.transcripts['length'], dtype='f8')
+        while True:       # (samples may be added meanwhile: the call says when there are more than the rows it was given)
+            cap = len(self)
+            n = ctypes.c_int64(cap)
+            rows = max(cap, 1)
+            tpm = numpy.zeros((rows, lengths.size), dtype='f8')
+            effective = numpy.zeros((rows, lengths.size), dtype='f8') if return_effective_lengths else None
+            iters = numpy.zeros(rows, dtype=numpy.int64)
+            code = _native.hip().skm_sample_set_quantify(
+                self._handle, _native.ptr(lengths, _native.c_f64p), lengths.size, REL_TOL, X_FLOOR, 0, cap,
+                ctypes.byref(n), _native.ptr(tpm, _native.c_f64p),
+                _native.ptr(effective, _native.c_f64p) if effective is not None else None, _native.ptr(iters, _native.c_i64p))
+            if code == _native.SKM_ERR_ARG and n.value > cap:
+                continue
+            _native.check(code)
+            break
+        out = (tpm[:n.value],)
+        if return_iters:
+            out += (iters[:n.value],)
+        if return_effective_lengths:
+            out += (effective[:n.value],)
+        return out if len(out) > 1 else out[0]
+
     def export(self):
         """[(class_offsets, class_targets, class_counts, first_seen), ...] per sample, each as
         MapResult.export() gives them for the sample alone (first_seen counted inside the sample)."""
