@@ -243,7 +243,11 @@ int skm_mapper_export(skm_mapper *mapper, int64_t *class_offsets,
                       int32_t *class_targets, int64_t *class_counts,
                       int64_t *first_seen, int64_t *fld);
 /* MapResult.merge_fragment_lengths / Counter.update with foreign data: merge
- * an exported table (e.g. another GPU's) into this one. */
+ * an exported table (e.g. another GPU's) into this one.  The classes of one call are distinct
+ * tuples.  Two different tuples with one 64-bit key -- in the call, or one of them in the table --
+ * refuse the merge with SKM_ERR_COLLISION (skm_mapper_merge_device likewise): a refused merge leaves
+ * the unit totals (summary[2], summary[3]) and the histogram untouched; classes of the call may
+ * have been added, so the table is good for skm_mapper_reset only. */
 int skm_mapper_merge(skm_mapper *mapper, int64_t n_classes,
                      const int64_t *class_offsets, const int32_t *class_targets,
                      const int64_t *class_counts, const int64_t *first_seen,
@@ -275,7 +279,14 @@ int skm_mapper_clear(skm_mapper *mapper);           /* MapResult.clear, mapper.p
 int skm_mapper_reset(skm_mapper *mapper);
 /* stats[0]=pack kernel ns [1]=map kernel ns [2]=class kernels ns [3]=batches
  * [4]=units (HIP-event times accumulated over batches on the mapper stream)
- * [5]=EM ns [6]=EM steps of the skm_quant_infer calls made on this mapper */
+ * [5]=EM ns [6]=EM steps of the skm_quant_infer calls made on this mapper
+ * [7]=times the class table grew with units in flight, i.e. after a pass of a batch whose bounded
+ * probes deferred units (0 unless a batch outgrew what was reserved for it).
+ * Test hook SKM_TEST_CLASS_SLOTS=N (power of two, 2 <= N <= 2^30; SKM_ERR_ARG otherwise), read by
+ * skm_mapper_create: the table starts at N slots and the reservation ahead of a batch leaves the
+ * slot count alone, so batches take the defer / grow / retry path; the growth steps themselves and
+ * the sizing of the merges are those of production.  skm_mapper_clear and skm_mapper_reset keep
+ * the table as large as it has grown. */
 int skm_mapper_timing(skm_mapper *mapper, double stats[8]);
 /* Access counters of the instrumented build of the map kernel (they define the
  * algorithmic bytes): enable, map, then read.  out[0]=reads

@@ -215,6 +215,8 @@ struct skm_mapper {
     int want_stats = 0;               // 0 production, 1 counting build, 2 census build
     double t_pack_ns = 0, t_map_ns = 0, t_class_ns = 0, batches = 0;
     double t_em_ns = 0, em_iters = 0;          // skm_quant_infer calls on this mapper
+    bool test_class_slots = false;             // SKM_TEST_CLASS_SLOTS: table_reserve[_for_sample] leave the slot count alone
+    int64_t deferred_grows = 0;                // table_grow calls with units in flight (after a pass that deferred units)
     unsigned long long stats_total[48] = {0};
     // ---- host batches: staging lanes + one worker (skm_mapper_map_batch[_async])
     // A host batch is copied to HBM on a lane's own stream by the thread that submits it (the
@@ -884,6 +886,7 @@ int table_grow(skm_mapper *m, uint64_t want_slots, int64_t units_in_flight)
     uint64_t need = n_slots;
     while (need < want_slots) need <<= 1;
     if (need == n_slots) return SKM_OK;
+    if (units_in_flight > 0) m->deferred_grows += 1;
     DBuf<ClassSlot> new_slots;
     DBuf<int64_t> forward;
     auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
@@ -916,7 +919,7 @@ int table_reserve_for_sample(skm_mapper *m, int64_t sample_units)
     const double expect = (double)m->host_classes + (double)std::min<int64_t>(sample_units, 1LL << 29) / 8.0 + 1024.0;
     uint64_t want = 1 << 16;
     while ((double)want * 0.5 < expect && want < (1ULL << 26)) want <<= 1;
-    SKM_TRY(table_grow(m, want, 0));
+    if (!m->test_class_slots) SKM_TRY(table_grow(m, want, 0));
     SKM_TRY(m->class_list.ensure((size_t)(expect + 1024.0), true, m->stream));
     SKM_TRY(m->arena.ensure((size_t)(m->host_arena_used + (int64_t)(expect * 6.0) + 1024), true, m->stream));
     bind_table(m, m->t.slot_mask + 1);
@@ -931,7 +934,7 @@ int table_reserve(skm_mapper *m, int64_t n_units)
     const double expect = (double)m->host_classes + (double)n_units / 8.0 + 1024.0;
     uint64_t want = 1 << 16;
     while ((double)want * 0.5 < expect) want <<= 1;
-    SKM_TRY(table_grow(m, want, 0));
+    if (!m->test_class_slots) SKM_TRY(table_grow(m, want, 0));
     // registry and arena can never need more than one entry per unit / id of the batch
     SKM_TRY(m->class_list.ensure((size_t)(m->host_classes + n_units + 1024), true, m->stream));
     bind_table(m, m->t.slot_mask + 1);
@@ -1157,7 +1160,15 @@ extern "C" int skm_mapper_create(skm_index *ix, skm_mapper **out)
         sscanf(v, "%d,%d,%d,%d,%d,%d,%d", &m->vote[0], &m->vote[1], &m->vote[2], &m->vote[3], &m->vote[4],
                &m->vote[5], &m->vote[6]);
     HIP_TRY(hipStreamCreateWithFlags(m->packed_stream.out(), hipStreamNonBlocking));   // (10 ms: not at the first piece's push)
-    SKM_TRY(table_reset(m.get(), 1 << 16));
+    uint64_t first_slots = 1 << 16;
+    if (const char *v = getenv("SKM_TEST_CLASS_SLOTS")) {        // test hook: a table that has to grow under a batch
+        const long long n = atoll(v);
+        if (n < 2 || n > (1LL << 30) || (n & (n - 1)))
+            return fail(SKM_ERR_ARG, "SKM_TEST_CLASS_SLOTS must be a power of two from 2 to 2^30, not '%s'", v);
+        first_slots = (uint64_t)n;
+        m->test_class_slots = true;
+    }
+    SKM_TRY(table_reset(m.get(), first_slots));
     HIP_TRY(hipStreamSynchronize(m->stream));
     *out = m.release();                                     // (the caller's handle from here on)
     return SKM_OK;
@@ -2073,13 +2084,20 @@ extern "C" int skm_mapper_merge_device(skm_mapper *m, const skm_device_table *ta
     }
     SKM_TRY(m->arena.ensure((size_t)(m->host_arena_used + table->n_ids + 1024), true, m->stream));
     bind_table(m, m->t.slot_mask + 1);
-    launch_class_merge_device(m->t, n_classes, table->class_start, table->class_len, table->ids, table->class_count,
-                              (const unsigned long long *)table->first_seen, (unsigned long long)table->unaligned,
-                              (unsigned long long)table->units, (const unsigned long long *)table->fld, m->stream);
+    if (n_classes) {
+        launch_class_merge_device(m->t, n_classes, table->class_start, table->class_len, table->ids, table->class_count,
+                                  (const unsigned long long *)table->first_seen, m->stream);
+        HIP_TRY(hipGetLastError());
+        SKM_TRY(read_error(m));
+    }
+    // totals and histogram only once the classes are in: a failed merge leaves them untouched (the
+    // hand-over of a table happens once per sample: the launch boundary is on no hot path)
+    launch_class_add_totals(m->t, (unsigned long long)table->unaligned, (unsigned long long)table->units,
+                            (const unsigned long long *)table->fld, m->stream);
     HIP_TRY(hipGetLastError());
     unsigned long long ctr[8];
     HIP_TRY(hipMemcpyAsync(ctr, m->counters.p, sizeof(ctr), hipMemcpyDeviceToHost, m->stream));
-    SKM_TRY(read_error(m));
+    HIP_TRY(hipStreamSynchronize(m->stream));
     m->host_arena_used = (int64_t)ctr[CTR_ARENA];
     m->host_classes = (int64_t)ctr[CTR_CLASSES];
     m->host_units = ctr[CTR_UNITS];
@@ -2133,7 +2151,7 @@ extern "C" int skm_mapper_timing(skm_mapper *m, double stats[8])
     std::lock_guard<std::mutex> lock(m->mu);
     stats[0] = m->t_pack_ns; stats[1] = m->t_map_ns; stats[2] = m->t_class_ns;
     stats[3] = m->batches; stats[4] = (double)m->units_done;
-    stats[5] = m->t_em_ns; stats[6] = m->em_iters; stats[7] = 0;
+    stats[5] = m->t_em_ns; stats[6] = m->em_iters; stats[7] = (double)m->deferred_grows;
     return SKM_OK;
 }
 

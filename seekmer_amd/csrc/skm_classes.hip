@@ -527,14 +527,19 @@ class_add_totals_kernel(ClassTable t, unsigned long long unaligned, unsigned lon
 
 void launch_class_merge_device(const ClassTable &t, int64_t n_classes, const int64_t *class_start,
                                const int64_t *class_len, const int32_t *ids, const double *class_counts,
-                               const unsigned long long *first_seen, unsigned long long unaligned,
-                               unsigned long long units, const unsigned long long *fld, hipStream_t stream)
+                               const unsigned long long *first_seen, hipStream_t stream)
 {
-    if (n_classes) {
-        hipLaunchKernelGGL(class_merge_kernel<double>, dim3(grid_for(n_classes)), dim3(256), 0, stream, t,
-                           n_classes, class_start, class_len, ids, class_counts, (const int64_t *)first_seen);
-        hipLaunchKernelGGL(class_totals_kernel, dim3(1), dim3(64), 0, stream, t, (const unsigned long long *)nullptr);
-    }
+    if (n_classes == 0) return;
+    hipLaunchKernelGGL(class_merge_kernel<double>, dim3(grid_for(n_classes)), dim3(256), 0, stream, t,
+                       n_classes, class_start, class_len, ids, class_counts, (const int64_t *)first_seen);
+    hipLaunchKernelGGL(class_totals_kernel, dim3(1), dim3(64), 0, stream, t, (const unsigned long long *)nullptr);
+}
+
+// (a launch of its own: the caller reads the merge's error word first, so that a refused merge
+// leaves totals and histogram as they were)
+void launch_class_add_totals(const ClassTable &t, unsigned long long unaligned, unsigned long long units,
+                             const unsigned long long *fld, hipStream_t stream)
+{
     hipLaunchKernelGGL(class_add_totals_kernel, dim3(1), dim3(256), 0, stream, t, unaligned, units, fld);
 }
 

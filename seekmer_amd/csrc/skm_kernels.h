@@ -189,8 +189,9 @@ void launch_class_merge(const ClassTable &t, int64_t n_classes, const int64_t *c
 // doubles) + its unit totals and histogram: nothing crosses the host
 void launch_class_merge_device(const ClassTable &t, int64_t n_classes, const int64_t *class_start,
                                const int64_t *class_len, const int32_t *ids, const double *class_counts,
-                               const unsigned long long *first_seen, unsigned long long unaligned,
-                               unsigned long long units, const unsigned long long *fld, hipStream_t stream);
+                               const unsigned long long *first_seen, hipStream_t stream);
+void launch_class_add_totals(const ClassTable &t, unsigned long long unaligned, unsigned long long units,
+                             const unsigned long long *fld, hipStream_t stream);
 
 // ---- quantification (skm_em.hip, skm_quant_setup.hip)
 constexpr int EM_ROW_CAP = 512;   // longest run of one transcript's classes summed by one lane group

@@ -301,10 +301,13 @@ class MapResult:
         return stats
 
     def timing(self):
+        """skm_mapper_timing by name; 'deferred_grows' (stats[7]) counts the times the class table
+        grew under a batch whose bounded probes had deferred units."""
         out = (ctypes.c_double * 8)()
         _native.check(_native.hip().skm_mapper_timing(self._handle, out))
         return {'pack_ns': out[0], 'map_ns': out[1], 'class_ns': out[2],
-                'batches': int(out[3]), 'units': int(out[4]), 'em_ns': out[5], 'em_iterations': int(out[6])}
+                'batches': int(out[3]), 'units': int(out[4]), 'em_ns': out[5], 'em_iterations': int(out[6]),
+                'deferred_grows': int(out[7])}
 
 
 class ReadMapper:
