@@ -3035,13 +3035,35 @@ bool em_uses_tiles(const skm_quant *q)
            (q->tiles.n_oversize == 0 || q->tiles.residual.built);
 }
 
+// The host one chunk of steps ahead of the device.  enqueue(slot) queues a chunk and, behind it, the copy
+// of what the host reads about it to q->pinned + 8 * slot; chunk i + 1 is already queued when the host
+// waits for chunk i's words, so the GPU never idles at a check-point (a converged EM turns at most one
+// chunk of launches into no-ops).  Returns once stopped(words) says so, with the look-ahead chunk still
+// queued and `words` those of the chunk that stopped.
+template <class Enqueue, class Stopped>
+int em_run_chunks_ahead(skm_quant *q, unsigned long long (&words)[8], Enqueue enqueue, Stopped stopped)
+{
+    auto enqueue_chunk = [&](int slot) -> int {
+        SKM_TRY(enqueue(slot));
+        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
+        return SKM_OK;
+    };
+    SKM_TRY(enqueue_chunk(0));
+    for (int slot = 0;; slot ^= 1) {
+        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
+        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
+        memcpy(words, q->pinned + 8 * slot, sizeof(words));
+        if (stopped(words)) return SKM_OK;
+    }
+}
+bool em_ctl_done(const unsigned long long *ctl) { return ctl[CTL_DONE] != 0; }
+
 // The component form of em_run's loop (after its preamble: control block cleared, ev[0] recorded).  Every
 // chunk is ONE launch that steps all the tiles `chunk` times in LDS and leaves every step's abundances in
 // the snapshot buffer -- the next chunk starts from the last of them -- plus the one-block launch that
 // judges the chunk's steps in order.  The host stays one chunk ahead as before; the look-ahead chunk that
 // finds the EM stopped (at step K) copies the tiles' entries of step K from the snapshots to x[K & 1],
 // where the callers look for the result: no step runs twice and the stop costs no launch of its own.
-constexpr int CTL_WORD_TILE_FAULT = 4;        // control block word em_local_chunk_kernel raises (skm_em.hip: CTL_TILE_FAULT)
 int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters_out)
 {
     auto &t = q->tiles;
@@ -3087,25 +3109,18 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(q->pinned + 8 * slot, q->ctl.p, 8 * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, q->stream));
-        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
         return SKM_OK;
     };
     unsigned long long ctl[8] = {0};
-    SKM_TRY(enqueue_chunk(0));
-    for (int slot = 0;; slot ^= 1) {
-        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
-        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
-        memcpy(ctl, q->pinned + 8 * slot, sizeof(ctl));
-        if (ctl[0]) break;
-    }
+    SKM_TRY(em_run_chunks_ahead(q, ctl, enqueue_chunk, em_ctl_done));
     // (a tile above the capacity cannot come out of the set-up; the kernel that meets one leaves it alone,
     // says so here and stops the run rather than going on with abundances nobody stepped)
-    if (ctl[CTL_WORD_TILE_FAULT]) {
+    if (ctl[CTL_TILE_FAULT]) {
         HIP_TRY(hipStreamSynchronize(q->stream));
         return fail(SKM_ERR_STATE, "a component tile exceeds the tile capacity: the class views of this handle are damaged");
     }
     // (the look-ahead chunk, queued above, is the copy of step `steps` of the tiles to x[steps & 1])
-    const int64_t steps = (int64_t)ctl[1];
+    const int64_t steps = (int64_t)ctl[CTL_ITERS];
     HIP_TRY(hipEventRecord(q->ev[1], q->stream));
     HIP_TRY(hipEventSynchronize(q->ev[1]));
     float ms = 0;
@@ -3113,7 +3128,7 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
     q->t_em_ns += ms * 1e6;
     q->iters_total += (double)steps;
     if (iters_out) *iters_out = steps;
-    if (ctl[3]) return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
+    if (ctl[CTL_UNDEFINED]) return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
     return SKM_OK;
 }
 
@@ -3136,10 +3151,7 @@ int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int6
     const int64_t chunk = fixed_iters > 0 ? std::min<int64_t>(fixed_iters, chunk_steps) : chunk_steps;
     HIP_TRY(hipEventRecord(q->ev[0], q->stream));
     if (em_uses_tiles(q) && chunk <= EM_CHUNK_MAX) return em_run_tiles(q, p, chunk, iters_out);
-    // Steps are enqueued in chunks; after each chunk the control block is copied to pinned
-    // memory and an event recorded.  The host stays one chunk ahead: chunk i+1 is already
-    // queued when it waits for chunk i's verdict, so the GPU never idles at a check-point
-    // (a converged EM turns at most one chunk of launches into no-ops).
+    // Steps are enqueued in chunks, the control block copied to pinned memory behind each (em_run_chunks_ahead).
     static const bool unfused_rows = getenv("SKM_EM_UNFUSED") != nullptr;
     auto enqueue_chunk = [&](int slot) -> int {
         for (int64_t i = 0; i < chunk; ++i, ++k) {
@@ -3170,26 +3182,19 @@ int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int6
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(q->pinned + 8 * slot, q->ctl.p, 8 * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, q->stream));
-        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
         return SKM_OK;
     };
     unsigned long long ctl[8] = {0};
-    SKM_TRY(enqueue_chunk(0));
-    for (int slot = 0;; slot ^= 1) {
-        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
-        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
-        memcpy(ctl, q->pinned + 8 * slot, sizeof(ctl));
-        if (ctl[0]) break;
-    }
+    SKM_TRY(em_run_chunks_ahead(q, ctl, enqueue_chunk, em_ctl_done));
     HIP_TRY(hipStreamSynchronize(q->stream));             // drain the look-ahead chunk (no-ops)
     HIP_TRY(hipEventRecord(q->ev[1], q->stream));
     HIP_TRY(hipEventSynchronize(q->ev[1]));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
     q->t_em_ns += ms * 1e6;
-    q->iters_total += (double)ctl[1];
-    if (iters_out) *iters_out = (int64_t)ctl[1];
-    if (ctl[3]) return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
+    q->iters_total += (double)ctl[CTL_ITERS];
+    if (iters_out) *iters_out = (int64_t)ctl[CTL_ITERS];
+    if (ctl[CTL_UNDEFINED]) return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
     return SKM_OK;
 }
 
@@ -3607,19 +3612,20 @@ int em_group_run(skm_quant *q, int64_t n_problems, Fill &&fill, bool batched, in
             HIP_TRY(hipMemcpyAsync(look, w.mgr.p, 24 * 8, hipMemcpyDeviceToHost, q->stream));
             HIP_TRY(hipMemcpyAsync(look + 24, w.ctl.p, 8 * 8, hipMemcpyDeviceToHost, q->stream));
             HIP_TRY(hipStreamSynchronize(q->stream));
-            if (look[3])
+            const unsigned long long *const all_done = look + 24;   // (the head of the control block, behind mgr's words)
+            if (look[MGR_UNDEFINED])
                 return fail(SKM_ERR_UNDEFINED, "no abundance above x_floor: numpy raises on max() of an empty selection");
-            if (look[24]) break;                                 // every problem of the group has finished
+            if (all_done[BCTL_ALL_DONE]) break;                  // every problem of the group has finished
             if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the batched EM does not stop");
             // The tail: nothing left to put in, a few problems still running.  A step of the
             // working set costs the same however many places are live (~5 single-problem steps), so
             // the last three or fewer go on one by one in the single-problem EM, from where they are.
             int live = 0;
-            for (int r = 0; r < EM_BATCH; ++r) live += look[8 + r] != 0;
-            if (look[0] >= look[1] && live <= 3) {
+            for (int r = 0; r < EM_BATCH; ++r) live += look[MGR_REP + r] != 0;
+            if (look[MGR_NEXT] >= look[MGR_COUNT] && live <= 3) {
                 for (int r = 0; r < EM_BATCH; ++r) {
-                    if (look[8 + r] == 0) continue;
-                    const int64_t rep = (int64_t)look[8 + r] - 1, since = (int64_t)look[16 + r];
+                    if (look[MGR_REP + r] == 0) continue;
+                    const int64_t rep = (int64_t)look[MGR_REP + r] - 1, since = (int64_t)look[MGR_SINCE + r];
                     launch_em_batch_take(p.x[k & 1], T, r, q->x0.p, q->stream);
                     launch_em_batch_take(w.cls_count.p, C, r, q->cls_count.p, q->stream);
                     HIP_TRY(hipGetLastError());
@@ -3994,22 +4000,17 @@ int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, co
     const int64_t chunk = 16;
     int64_t k = 0;
     auto enqueue_chunk = [&](int slot) -> int {
+        if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the EM of the stacked tables does not stop");
         HIP_TRY(hipMemsetAsync(run.running.p + slot, 0, 8, q->stream));
         for (int64_t i = 0; i < chunk; ++i, ++k) launch_em_set_step(p, largest_classes, k, i > 0, q->stream);
         launch_em_set_decide(p, k, run.running.p + slot, q->stream);
         q->launches += 2 * chunk + 1;
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(q->pinned + 8 * slot, run.running.p + slot, 8, hipMemcpyDeviceToHost, q->stream));
-        HIP_TRY(hipEventRecord(q->chunk_ev[slot], q->stream));
         return SKM_OK;
     };
-    SKM_TRY(enqueue_chunk(0));
-    for (int slot = 0;; slot ^= 1) {
-        SKM_TRY(enqueue_chunk(slot ^ 1));                 // stay one chunk ahead
-        HIP_TRY(hipEventSynchronize(q->chunk_ev[slot]));
-        if (q->pinned[8 * slot] == 0) break;
-        if (k > (1LL << 24)) return fail(SKM_ERR_STATE, "the EM of the stacked tables does not stop");
-    }
+    unsigned long long look[8];                           // ([0]: slots still running)
+    SKM_TRY(em_run_chunks_ahead(q, look, enqueue_chunk, [](const unsigned long long *w) { return w[0] == 0; }));
     HIP_TRY(hipMemcpyAsync(slots.data(), run.slots.p, (size_t)n * sizeof(EmSetSlot), hipMemcpyDeviceToHost, q->stream));
     HIP_TRY(hipStreamSynchronize(q->stream));             // (with it the look-ahead chunk: no-ops)
     for (int64_t i = 0; i < n; ++i) {

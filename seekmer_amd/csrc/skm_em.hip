@@ -7,8 +7,7 @@
 // (class, transcript) pairs, four launches on one stream and no
 // floating-point atomics, so every step is bitwise reproducible:
 //   em_inner     -- one lane per class: S_c = sum of x over the tuple in tuple
-//                   order (as numpy.bincount accumulates it), inner_c = S_c /
-//                   count_c                                   (infer.py:155-156)
+//                   order, inner_c = S_c / count_c            (infer.py:155-156)
 //   em_rows      -- 8 lanes per row (a run of <= 512 classes of ONE transcript):
 //                   sum of x_t / inner_c over the run          (infer.py:157)
 //   em_finalize  -- one lane per transcript: x'_t = (sum of its rows) / l_t /
@@ -20,57 +19,32 @@
 //                   latches `done`, after which every later launch is a no-op
 //                   -- the host enqueues steps in chunks and still stops at
 //                   exactly the reference's iteration count.
+// The arithmetic of the step is skm_em_core.h's; the kernels here are its grids and layouts.
 // All three are gather/stream kernels bound by HBM/L2 bandwidth: no MFMA.
-#include "skm_kernels.h"
+#include "skm_em_core.h"
 
 namespace skm {
 
-enum { CTL_DONE = 0, CTL_ITERS = 1, CTL_UNDEFINED = 3, CTL_TILE_FAULT = 4 };
-
 __device__ bool em_evaluate(const EmProblem &p, int n_parts, int64_t steps_done, bool publish);
 
-// eval_parts > 0: the finalize pass before this launch (number `steps_done`) has not been
-// judged yet -- do it here, in every block, before starting the next step
+// the whole table of an EmProblem, as em_inner_body and em_rows_finalize_body see it (skm_em_core.h)
+struct EmWholeTable {
+    const EmProblem &p;
+    __device__ __forceinline__ int64_t cls_first() const { return 0; }
+    __device__ __forceinline__ int64_t cls_end() const { return p.n_classes; }
+    __device__ __forceinline__ int64_t row_first() const { return 0; }
+    __device__ __forceinline__ int64_t row_end() const { return p.n_rows; }
+    __device__ __forceinline__ double n_total() const { return p.n_total; }
+    __device__ __forceinline__ bool done() const { return p.ctl[CTL_DONE] != 0; }
+    __device__ __forceinline__ bool judge(int eval_parts, int64_t steps_done) const { return em_evaluate(p, eval_parts, steps_done, true); }
+    __device__ __forceinline__ int64_t part() const { return blockIdx.x; }          // judged by em_evaluate in the next launch
+};
+
 __global__ void __launch_bounds__(256)
 em_inner_kernel(EmProblem p, int parity, int eval_parts, int64_t steps_done)
 {
-    // the first class's row is fetched before the verdict on the previous step is known: its
-    // latency then runs under the judging instead of after it
-    const int64_t c_first = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    int64_t begin_first = 0, end_first = 0;
-    double count_first = 1.0;
-    if (c_first < p.n_classes) {
-        begin_first = p.cls_offset[c_first];
-        end_first = p.cls_offset[c_first + 1];
-        count_first = p.cls_count[c_first];
-    }
-    if (eval_parts > 0 && blockIdx.x == 0) {
-        // Block 0 judges the step before this one and latches the verdict; the other blocks do not
-        // wait for it.  If the EM has just stopped they compute one pass of `inner` that nobody
-        // reads (x is not touched by this kernel, and every later launch sees the latch and
-        // returns): 13 us once per EM, against every block re-reading all the partials every step
-        // (34.5 -> 32.8 us per step).
-        if (p.ctl[CTL_DONE]) return;            // (block-uniform)
-        if (em_evaluate(p, eval_parts, steps_done, true)) return;
-    } else if (p.ctl[CTL_DONE]) {
-        return;
-    }
-    const double *__restrict__ x = p.x[parity];
-    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < p.n_classes;
-         c += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t begin = c == c_first ? begin_first : p.cls_offset[c];
-        const int64_t end = c == c_first ? end_first : p.cls_offset[c + 1];
-        const double count = c == c_first ? count_first : p.cls_count[c];
-        double s = 0.0;
-        int64_t j = begin;
-        for (; j + 4 <= end; j += 4) {          // four independent gathers in flight, summed in order
-            const int32_t t0 = p.ids[j], t1 = p.ids[j + 1], t2 = p.ids[j + 2], t3 = p.ids[j + 3];
-            const double x0 = x[t0], x1 = x[t1], x2 = x[t2], x3 = x[t3];
-            s += x0; s += x1; s += x2; s += x3;
-        }
-        for (; j < end; ++j) s += x[p.ids[j]];
-        p.inner[c] = s / count;
-    }
+    em_inner_body(p, EmWholeTable{p}, parity, eval_parts > 0 && blockIdx.x == 0, eval_parts, steps_done, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                  (int64_t)gridDim.x * blockDim.x);
 }
 
 __global__ void __launch_bounds__(256)
@@ -81,133 +55,20 @@ em_rows_kernel(EmProblem p, int parity)
     const int sub = threadIdx.x & 7;
     for (int64_t r = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; r < p.n_rows;
          r += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-        const int64_t begin = p.row_start[r], end = p.row_start[r + 1];
-        const double xt = x[p.row_tx[r]];
-        double s = 0.0;
-        int64_t e = begin + sub;
-        for (; e + 8 < end; e += 16) {          // two independent gathers in flight per lane
-            const int32_t c0 = p.tx_cls[e], c1 = p.tx_cls[e + 8];
-            const double i0 = p.inner[c0], i1 = p.inner[c1];
-            s += xt / i0;
-            s += xt / i1;
-        }
-        for (; e < end; e += 8) s += xt / p.inner[p.tx_cls[e]];
-        s += __shfl_xor(s, 4, 8);
-        s += __shfl_xor(s, 2, 8);
-        s += __shfl_xor(s, 1, 8);
+        const double s = em_row_sum<true>(p.tx_cls, p.inner, p.row_start[r], p.row_start[r + 1], sub, x[p.row_tx[r]]);
         if (sub == 0) p.row_sum[r] = s;
     }
 }
 
-// em_rows and em_finalize in ONE launch (one rank: nothing to all-reduce between them).  Every
-// transcript has at least one row (skm_quant_setup.hip), nearly every transcript exactly one: the
-// 8-lane group that has summed such a row finalizes its transcript on the spot -- x'_t, NaN -> 0,
-// the relative change -- with the arithmetic of em_finalize_kernel (a = 0.0 + row sum), and the
-// block's partials of the stopping rule come out of this kernel.  The rows of a transcript that
-// sits in more than EM_ROW_CAP classes may be summed by different blocks; the group whose row
-// arrives LAST adds them up in row order and finalizes: row sums cross blocks as 8-byte
-// agent-scope atomic stores and loads (write-through / L2-bypassing: the XCDs' L2s are not
-// coherent), the store completed (s_waitcnt) before the arrival is counted.  One launch (5.1 us)
-// and one launch gap less per step; bit for bit em_rows + em_finalize.
-// TO_ACC (several ranks): the transcript's numerator goes to p.acc instead -- em_rows +
-// em_rows_to_acc in one launch -- for the all-reduce that sits in front of em_finalize there.
+// em_rows and em_finalize in ONE launch (one rank: nothing to all-reduce between them): one launch
+// (5.1 us) and one launch gap less per step; bit for bit em_rows + em_finalize.  TO_ACC (several
+// ranks): em_rows + em_rows_to_acc in one launch.
 template <bool TO_ACC>
 __global__ void __launch_bounds__(256, 8)       // (8 waves per SIMD: the 2048-block grid is resident at once)
 em_rows_finalize_kernel(EmProblem p, int parity)
 {
-    if (p.ctl[CTL_DONE]) return;
-    __shared__ double s_max[4];
-    __shared__ unsigned int s_flags[4];
-    const double *__restrict__ x = p.x[parity];
-    double *__restrict__ x_new = p.x[parity ^ 1];
-    const int sub = threadIdx.x & 7;
-    double local_max = 0.0;
-    unsigned int flags = 0;
-    for (int64_t r = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; r < p.n_rows;
-         r += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-        const int64_t begin = p.row_start[r], end = p.row_start[r + 1];
-        const int32_t t = p.row_tx[r];
-        const double xt = x[t];
-        // (what the finalize needs is asked for with x[t]: one round trip for all of it)
-        const int64_t first_row = p.tx_row[t], rows_of_t = p.tx_row[t + 1] - first_row;
-        const double eff = p.eff_len[t];
-        double s = 0.0;
-        int64_t e = begin + sub;
-        for (; e + 8 < end; e += 16) {          // two independent gathers in flight per lane
-            const int32_t c0 = p.tx_cls[e], c1 = p.tx_cls[e + 8];
-            const double i0 = p.inner[c0], i1 = p.inner[c1];
-            s += xt / i0;
-            s += xt / i1;
-        }
-        for (; e < end; e += 8) s += xt / p.inner[p.tx_cls[e]];
-        s += __shfl_xor(s, 4, 8);
-        s += __shfl_xor(s, 2, 8);
-        s += __shfl_xor(s, 1, 8);
-        // 1: the transcript's only row; 2: the last of its rows to arrive (this group adds them up); 0: neither
-        int mode = 0;
-        unsigned long long *const sums = reinterpret_cast<unsigned long long *>(p.row_sum);
-        if (sub == 0) {
-            if (rows_of_t == 1) {
-                mode = 1;
-            } else {
-                __hip_atomic_store(&sums[r], (unsigned long long)__double_as_longlong(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned int before = atomicAdd(&p.arrivals[t], 1u);
-                mode = (int64_t)before + 1 == rows_of_t ? 2 : 0;
-            }
-        }
-        mode = __shfl(mode, 0, 8);
-        if (mode == 0) continue;
-        double a = 0.0;
-        if (mode == 1) {
-            a += s;
-        } else {
-            // (the eight lanes fetch eight row sums at a time; they are added in row order, as
-            // em_finalize_kernel adds them: a transcript in 100 000 classes has 200 rows)
-            for (int64_t k0 = 0; k0 < rows_of_t; k0 += 8) {
-                const int64_t k = k0 + sub;
-                const double mine = k < rows_of_t
-                    ? __longlong_as_double((long long)__hip_atomic_load(&sums[first_row + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    : 0.0;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const double v = __shfl(mine, j, 8);
-                    if (k0 + j < rows_of_t) a += v;
-                }
-            }
-            if (sub == 0) atomicExch(&p.arrivals[t], 0u);             // (for the next step)
-        }
-        if (sub != 0) continue;
-        if (TO_ACC) {
-            p.acc[t] = a;
-            continue;
-        }
-        double v = a / eff / p.n_total;                               // infer.py:158
-        if (v != v) v = 0.0;                                          // infer.py:159
-        x_new[t] = v;
-        if (v > p.x_floor) {                                          // infer.py:160
-            const double change = fabs(v - xt) / v;
-            if (change != change) flags |= 2u;
-            else if (change > local_max) local_max = change;
-            flags |= 1u;
-        }
-    }
-    for (int d = 32; d > 0; d >>= 1) {
-        const double o = __shfl_xor(local_max, d, 64);
-        local_max = o > local_max ? o : local_max;
-        flags |= __shfl_xor(flags, d, 64);
-    }
-    if (TO_ACC) return;                         // (em_finalize judges the step there)
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_max[wave] = local_max; s_flags[wave] = flags; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = s_max[0];
-        unsigned int f = s_flags[0];
-        for (int w = 1; w < 4; ++w) { m = s_max[w] > m ? s_max[w] : m; f |= s_flags[w]; }
-        p.part_max[blockIdx.x] = m;             // judged by em_evaluate in the next launch
-        p.part_flags[blockIdx.x] = f;
-    }
+    em_rows_finalize_body<TO_ACC>(p, EmWholeTable{p}, parity, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                                  (int64_t)gridDim.x * blockDim.x);
 }
 
 // multi-GPU only (the unfused form, SKM_EM_UNFUSED): rows -> per-transcript numerators for the all-reduce
@@ -216,11 +77,8 @@ em_rows_to_acc_kernel(EmProblem p)
 {
     if (p.ctl[CTL_DONE]) return;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < p.n_tx;
-         t += (int64_t)gridDim.x * blockDim.x) {
-        double a = 0.0;
-        for (int64_t r = p.tx_row[t]; r < p.tx_row[t + 1]; ++r) a += p.row_sum[r];
-        p.acc[t] = a;
-    }
+         t += (int64_t)gridDim.x * blockDim.x)
+        p.acc[t] = em_rows_stored_sum<1>(p.row_sum, p.tx_row[t], p.tx_row[t + 1], 0);
 }
 
 template <bool FROM_ACC>
@@ -228,45 +86,20 @@ __global__ void __launch_bounds__(256)
 em_finalize_kernel(EmProblem p, int parity)
 {
     if (p.ctl[CTL_DONE]) return;
-    __shared__ double s_max[4];
-    __shared__ unsigned int s_flags[4];
     const double *__restrict__ x_old = p.x[parity];
     double *__restrict__ x_new = p.x[parity ^ 1];
     double local_max = 0.0;
     unsigned int flags = 0;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < p.n_tx;
          t += (int64_t)gridDim.x * blockDim.x) {
-        double a;
-        if (FROM_ACC) {
-            a = p.acc[t];
-        } else {
-            a = 0.0;
-            for (int64_t r = p.tx_row[t]; r < p.tx_row[t + 1]; ++r) a += p.row_sum[r];
-        }
-        double v = a / p.eff_len[t] / p.n_total;                 // infer.py:158
-        if (v != v) v = 0.0;                                     // infer.py:159
+        const double a = FROM_ACC ? p.acc[t] : em_rows_stored_sum<1>(p.row_sum, p.tx_row[t], p.tx_row[t + 1], 0);
+        const double v = em_new_abundance(a, p.eff_len[t], p.n_total);
         x_new[t] = v;
-        if (v > p.x_floor) {                                     // infer.py:160
-            const double r = fabs(v - x_old[t]) / v;
-            if (r != r) flags |= 2u;
-            else if (r > local_max) local_max = r;
-            flags |= 1u;
-        }
+        em_note_change(v, x_old[t], p.x_floor, local_max, flags);
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        const double o = __shfl_xor(local_max, d, 64);
-        local_max = o > local_max ? o : local_max;
-        flags |= __shfl_xor(flags, d, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_max[wave] = local_max; s_flags[wave] = flags; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = s_max[0];
-        unsigned int f = s_flags[0];
-        for (int w = 1; w < 4; ++w) { m = s_max[w] > m ? s_max[w] : m; f |= s_flags[w]; }
-        p.part_max[blockIdx.x] = m;             // judged by em_evaluate in the next launch
-        p.part_flags[blockIdx.x] = f;
+    if (em_block_reduce<1>(local_max, flags)) {
+        p.part_max[blockIdx.x] = local_max;     // judged by em_evaluate in the next launch
+        p.part_flags[blockIdx.x] = flags;
     }
 }
 
@@ -278,8 +111,6 @@ em_finalize_kernel(EmProblem p, int parity)
 // enqueued chunk so that the host can read the state.
 __device__ bool em_evaluate(const EmProblem &p, int n_parts, int64_t steps_done, bool publish)
 {
-    __shared__ double s_max[4];
-    __shared__ unsigned int s_flags[4];
     __shared__ int s_done;
     double m = 0.0;
     unsigned int f = 0;
@@ -296,32 +127,14 @@ __device__ bool em_evaluate(const EmProblem &p, int n_parts, int64_t steps_done,
             f |= p.extra_flags[first + b];
         }
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        const double o = __shfl_xor(m, d, 64);
-        m = o > m ? o : m;
-        f |= __shfl_xor(f, d, 64);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_max[wave] = m; s_flags[wave] = f; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 0; w < 4; ++w) { m = s_max[w] > m ? s_max[w] : m; f |= s_flags[w]; }
-        bool done, undefined = false;
-        if (p.fixed_iters > 0) {
-            done = steps_done >= p.fixed_iters;
-        } else if (!(f & 1u)) {
-            undefined = true;                 // numpy raises on max() of an empty selection
-            done = true;
-        } else {
-            done = (f & 2u) || !(m > p.rel_tol);                 // NaN propagates through max()
-            if (p.max_iters > 0 && steps_done >= p.max_iters) done = true;
-        }
+    if (em_block_reduce<1>(m, f)) {
+        const EmVerdict verdict = em_stop_rule(f, m, p.rel_tol, steps_done, p.max_iters, p.fixed_iters);
         if (publish) {
-            if (undefined) p.ctl[CTL_UNDEFINED] = 1;
+            if (verdict.undefined) p.ctl[CTL_UNDEFINED] = 1;
             p.ctl[CTL_ITERS] = (unsigned long long)steps_done;
-            p.ctl[CTL_DONE] = done ? 1ULL : 0ULL;
+            p.ctl[CTL_DONE] = verdict.done ? 1ULL : 0ULL;
         }
-        s_done = done ? 1 : 0;
+        s_done = verdict.done ? 1 : 0;
     }
     __syncthreads();
     return s_done != 0;
@@ -337,17 +150,14 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 // ---- the EM of independent components, a chunk of steps per launch (EmTiles, skm_kernels.h)
 // One workgroup per tile.  The tile's pairs in both views (16-bit tile-local indices), the class counts,
 // `inner`, the effective lengths and both abundance vectors live in LDS for the whole chunk; a step is
-//   class phase  one lane per class: S_c over the tuple in tuple order, inner_c = S_c / count_c
-//                (the arithmetic of em_inner_kernel).  A lane takes EM_CLASS_BATCH entries at a time: the
+//   class phase  one lane per class: S_c over the tuple in tuple order, inner_c = S_c / count_c.  A lane
+//                takes EM_CLASS_BATCH entries at a time: the
 //                indices, then the abundances -- all of them in flight at once -- and adds them one after
 //                the other in tuple order; an entry past the tuple's end is not added (a select: adding
 //                +0.0 would turn a sum of -0.0 into +0.0).  The set-up lists a tile's classes by the
 //                number of such batches, so the 64 classes of a wave take like numbers of turns.
-//   row phase    eight lanes per transcript, its rows of <= EM_ROW_CAP entries one after the other: lane
-//                `sub` adds x_t / inner_c for entries begin + sub + 8 k in ascending k, the xor 4, 2, 1
-//                butterfly, the row sums added in row order from 0.0, then x'_t = a / l_t / n, NaN -> 0
-//                and the relative change (the arithmetic of em_rows_finalize_kernel, association for
-//                association)
+//   row phase    eight lanes per transcript, its rows of <= EM_ROW_CAP entries one after the other, the
+//                row sums added in row order from 0.0, then the finalize (skm_em_core.h)
 // with two workgroup barriers and nothing that crosses workgroups.  Each step's partials of the stopping
 // rule go to step_max / step_flags [step][tile]; em_local_decide_kernel judges the steps in order.
 // Every step's abundances also go to tl.snap[step][transcript]: the next chunk starts from the last of
@@ -473,41 +283,26 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, int n_steps, 
                 double a = 0.0;
                 do {                                    // (a transcript in no class has one empty row)
                     const int row_end = min(begin + EM_ROW_CAP, end);
-                    double s = 0.0;
-                    for (int e = begin + sub; e < row_end; e += 8) s += xt / s_inner[s_tx_cls[e]];
-                    s += __shfl_xor(s, 4, 8);
-                    s += __shfl_xor(s, 2, 8);
-                    s += __shfl_xor(s, 1, 8);
-                    a += s;
+                    a += em_row_sum<false>(s_tx_cls, s_inner, begin, row_end, sub, xt);
                     begin = row_end;
                 } while (begin < end);
                 if (turn == sub) { my_a = a; my_xt = xt; my_i = i; }
             }
         }
         if (my_i >= 0) {
-            double v = my_a / s_eff[my_i] / p.n_total;                    // infer.py:158
-            if (v != v) v = 0.0;                                          // infer.py:159
+            const double v = em_new_abundance(my_a, s_eff[my_i], p.n_total);
             x_new[my_i] = v;
             tl.snap[step * p.n_tx + s_tx[my_i]] = v;
-            if (v > p.x_floor) {                                          // infer.py:160
-                const double change = fabs(v - my_xt) / v;
-                if (change != change) flags |= 2u;
-                else if (change > local_max) local_max = change;
-                flags |= 1u;
-            }
+            em_note_change(v, my_xt, p.x_floor, local_max, flags);
         }
-        for (int d = 32; d > 0; d >>= 1) {
-            const double o = __shfl_xor(local_max, d, 64);
-            local_max = o > local_max ? o : local_max;
-            flags |= __shfl_xor(flags, d, 64);
-        }
+        em_wave_reduce<1>(local_max, flags);
         if ((tid & 63) == 0) { s_max[step][wave] = local_max; s_flags[step][wave] = flags; }
         __syncthreads();
     }
     if (tid < n_steps) {
-        double m = s_max[tid][0];
-        unsigned int f = s_flags[tid][0];
-        for (int w = 1; w < 4; ++w) { m = s_max[tid][w] > m ? s_max[tid][w] : m; f |= s_flags[tid][w]; }
+        double m;
+        unsigned int f;
+        em_fold_waves(s_max[tid], s_flags[tid], 1, m, f);
         tl.step_max[tid * tl.n_tiles + tile] = m;
         tl.step_flags[tid * tl.n_tiles + tile] = f;
     }
@@ -542,33 +337,18 @@ em_local_decide_kernel(EmProblem p, EmTiles tl, int64_t first_step, int n_steps)
             m = o > m ? o : m;
             f |= step_flags[b];
         }
-        for (int d = 32; d > 0; d >>= 1) {
-            const double o = __shfl_xor(m, d, 64);
-            m = o > m ? o : m;
-            f |= __shfl_xor(f, d, 64);
-        }
+        em_wave_reduce<1>(m, f);
         if (lane == 0) { s_max[step] = m; s_flags[step] = f; }
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
     for (int s = 0; s < n_steps; ++s) {
         const int64_t steps_done = first_step + s + 1;
-        const double m = s_max[s];
-        const unsigned int f = s_flags[s];
-        bool done, undefined = false;
-        if (p.fixed_iters > 0) {
-            done = steps_done >= p.fixed_iters;
-        } else if (!(f & 1u)) {
-            undefined = true;                 // numpy raises on max() of an empty selection
-            done = true;
-        } else {
-            done = (f & 2u) || !(m > p.rel_tol);                 // NaN propagates through max()
-            if (p.max_iters > 0 && steps_done >= p.max_iters) done = true;
-        }
-        if (undefined) p.ctl[CTL_UNDEFINED] = 1;
+        const EmVerdict verdict = em_stop_rule(s_flags[s], s_max[s], p.rel_tol, steps_done, p.max_iters, p.fixed_iters);
+        if (verdict.undefined) p.ctl[CTL_UNDEFINED] = 1;
         p.ctl[CTL_ITERS] = (unsigned long long)steps_done;
-        p.ctl[CTL_DONE] = done ? 1ULL : 0ULL;
-        if (done) break;
+        p.ctl[CTL_DONE] = verdict.done ? 1ULL : 0ULL;
+        if (verdict.done) break;
     }
 }
 

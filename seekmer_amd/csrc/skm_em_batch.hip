@@ -16,13 +16,13 @@
 // -- so that one gathered sector carries all eight, the index arrays are read once for the
 // eight, and there is one launch where there were eight.
 //
-// Every replicate still runs ITS OWN iteration: the additions are the single-problem kernels'
-// additions in the same order (skm_em.hip), its total divides its own numerators (place_total),
+// Every replicate still runs ITS OWN iteration: the step's arithmetic is the single-problem kernels'
+// (skm_em_core.h, with the replicates as a stride), its total divides its own numerators (place_total),
 // the stopping rule (infer.py:160) is judged per replicate, and a replicate that has stopped is
 // frozen (its x is carried from buffer to buffer unchanged) while the others go on, so its result
 // and its step count are exactly what the one-by-one run gives -- bit for bit
 // (tests/test_gpu_parity.py::test_bootstrap_draw_and_em, tests/test_gpu_em_many.py).
-#include "skm_kernels.h"
+#include "skm_em_core.h"
 
 #include <algorithm>
 
@@ -32,7 +32,6 @@ namespace {
 
 constexpr int R = EM_BATCH;
 static_assert(R == 8, "the row sums pair lanes and replicates eight by eight");
-enum { BCTL_ALL_DONE = 0, BCTL_LAST_STEP = 1, BCTL_DONE = 8, BCTL_ITERS = 16, BCTL_UNDEFINED = 24 };
 
 // The stopping rule for each replicate over the partials of finalize pass `steps_done`; returns
 // the mask of replicates that have stopped (now or earlier).  Block 0 of the next em_inner launch
@@ -60,15 +59,10 @@ __device__ unsigned int evaluate_batch(const EmBatchProblem &p, int n_parts, int
             f |= s_flags[k][r];
         }
         const bool latched = p.ctl[BCTL_DONE + r] != 0;
-        bool done, undefined = false;
-        if (!(f & 1u)) {
-            undefined = true;                 // numpy raises on max() of an empty selection
-            done = true;
-        } else {
-            done = (f & 2u) || !(m > p.rel_tol);                 // NaN propagates through max()
-        }
+        const EmVerdict verdict = em_stop_rule(f, m, p.rel_tol, steps_done, 0, 0);
+        const bool done = verdict.done;
         if (publish && !latched && done) {
-            if (undefined) p.ctl[BCTL_UNDEFINED + r] = 1;
+            if (verdict.undefined) p.ctl[BCTL_UNDEFINED + r] = 1;
             p.ctl[BCTL_ITERS + r] = (unsigned long long)steps_done;
             p.ctl[BCTL_DONE + r] = 1;
         }
@@ -84,10 +78,6 @@ __device__ unsigned int evaluate_batch(const EmBatchProblem &p, int n_parts, int
     }
     return mask;
 }
-
-// mgr words: see "the working set kept full by the device" below
-enum { MGR_NEXT = 0, MGR_COUNT = 1, MGR_FINISHED = 2, MGR_UNDEFINED = 3, MGR_REP = 8, MGR_SINCE = 16, MGR_TAKE = 24,
-       MGR_PUT = 32 };
 
 // What a latched stop means, place by place (one lane): the replicate's step count is recorded, its
 // result is to be taken, the next replicate of the group (if any) is to be put in its place; the plan
@@ -154,17 +144,7 @@ em_inner_batch_kernel(EmBatchProblem p, int parity, int eval_parts, int64_t step
     const int r = threadIdx.x & (R - 1);
     for (int64_t c = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / R; c < p.n_classes;
          c += ((int64_t)gridDim.x * blockDim.x) / R) {
-        const int64_t begin = p.cls_offset[c], end = p.cls_offset[c + 1];
-        double s = 0.0;
-        int64_t j = begin;
-        for (; j + 4 <= end; j += 4) {
-            const int32_t t0 = p.ids[j], t1 = p.ids[j + 1], t2 = p.ids[j + 2], t3 = p.ids[j + 3];
-            const double x0 = x[(int64_t)t0 * R + r], x1 = x[(int64_t)t1 * R + r];
-            const double x2 = x[(int64_t)t2 * R + r], x3 = x[(int64_t)t3 * R + r];
-            s += x0; s += x1; s += x2; s += x3;
-        }
-        for (; j < end; ++j) s += x[(int64_t)p.ids[j] * R + r];
-        p.inner[c * R + r] = s / p.cls_count[c * R + r];
+        p.inner[c * R + r] = em_tuple_sum<R>(p.ids, p.cls_offset[c], p.cls_offset[c + 1], x, r) / p.cls_count[c * R + r];
     }
 }
 
@@ -176,28 +156,37 @@ em_rows_batch_kernel(EmBatchProblem p, int parity)
     const int sub = threadIdx.x & 7;
     for (int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; row < p.n_rows;
          row += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-        const int64_t begin = p.row_start[row], end = p.row_start[row + 1];
-        const double *__restrict__ xt = x + (int64_t)p.row_tx[row] * R;
         double xr[R], s[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { xr[r] = xt[r]; s[r] = 0.0; }
-        for (int64_t e = begin + sub; e < end; e += 8) {
-            const double *__restrict__ inner = p.inner + (int64_t)p.tx_cls[e] * R;
-#pragma unroll
-            for (int r = 0; r < R; ++r) s[r] += xr[r] / inner[r];
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            s[r] += __shfl_xor(s[r], 4, 8);
-            s[r] += __shfl_xor(s[r], 2, 8);
-            s[r] += __shfl_xor(s[r], 1, 8);
-        }
+        em_row_sums<R>(p.tx_cls, p.inner, p.row_start[row], p.row_start[row + 1], sub, x + (int64_t)p.row_tx[row] * R, xr, s);
         if (sub == 0) {
             double *__restrict__ out = p.row_sum + row * R;
 #pragma unroll
             for (int r = 0; r < R; ++r) out[r] = s[r];
         }
     }
+}
+
+// x'_t of one (transcript, place): a stopped replicate keeps its result and notes no change
+__device__ __forceinline__ void finalize_place(double a, double eff, double n_total, bool stopped, double before, double x_floor,
+                                               double &x_new, double &local_max, unsigned int &flags)
+{
+    const double v = em_new_abundance(a, eff, n_total);
+    if (stopped) {
+        x_new = before;
+    } else {
+        x_new = v;
+        em_note_change(v, before, x_floor, local_max, flags);
+    }
+}
+
+// the block's partials of place r (lane i holds those of place i % R)
+__device__ __forceinline__ void write_partials(const EmBatchProblem &p, int r, bool stopped, double m, unsigned int f)
+{
+    if (!em_block_reduce<R>(m, f)) return;
+    // a frozen replicate reports "selected, no change": it stays stopped whatever is judged
+    if (stopped) { m = 0.0; f = 1u; }
+    p.part_max[blockIdx.x * R + r] = m;
+    p.part_flags[blockIdx.x * R + r] = f;
 }
 
 __global__ void __launch_bounds__(256)
@@ -207,8 +196,6 @@ em_finalize_batch_kernel(EmBatchProblem p, int parity)
     // R lanes per transcript, lane r = replicate r (as in em_inner_batch): a lane follows ONE chain of
     // dependent loads instead of eight, and there are eight times the lanes to hide it.  The
     // arithmetic per (transcript, replicate) is unchanged; maxima and flags do not care about order.
-    __shared__ double s_max[4][R];
-    __shared__ unsigned int s_flags[4][R];
     const double *__restrict__ x_old = p.x[parity];
     double *__restrict__ x_new = p.x[parity ^ 1];
     const int r = threadIdx.x & (R - 1);
@@ -218,40 +205,10 @@ em_finalize_batch_kernel(EmBatchProblem p, int parity)
     unsigned int flags = 0;
     for (int64_t t = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / R; t < p.n_tx;
          t += ((int64_t)gridDim.x * blockDim.x) / R) {
-        double a = 0.0;
-        for (int64_t row = p.tx_row[t]; row < p.tx_row[t + 1]; ++row) a += p.row_sum[row * R + r];
-        const double before = x_old[t * R + r];
-        double v = a / p.eff_len[t] / n_total;                   // infer.py:158
-        if (v != v) v = 0.0;                                     // infer.py:159
-        if (stopped) {
-            x_new[t * R + r] = before;                           // a stopped replicate keeps its result
-        } else {
-            x_new[t * R + r] = v;
-            if (v > p.x_floor) {                                 // infer.py:160
-                const double change = fabs(v - before) / v;
-                if (change != change) flags |= 2u;
-                else if (change > local_max) local_max = change;
-                flags |= 1u;
-            }
-        }
+        const double a = em_rows_stored_sum<R>(p.row_sum, p.tx_row[t], p.tx_row[t + 1], r);
+        finalize_place(a, p.eff_len[t], n_total, stopped, x_old[t * R + r], p.x_floor, x_new[t * R + r], local_max, flags);
     }
-    const int wave = threadIdx.x >> 6;
-    for (int d = 32; d >= R; d >>= 1) {                          // over the lanes of the wave that hold replicate r
-        const double o = __shfl_xor(local_max, d, 64);
-        local_max = o > local_max ? o : local_max;
-        flags |= __shfl_xor(flags, d, 64);
-    }
-    if ((threadIdx.x & 63) < R) { s_max[wave][r] = local_max; s_flags[wave][r] = flags; }
-    __syncthreads();
-    if (threadIdx.x < R) {
-        double m = s_max[0][r];
-        unsigned int f = s_flags[0][r];
-        for (int w = 1; w < 4; ++w) { m = s_max[w][r] > m ? s_max[w][r] : m; f |= s_flags[w][r]; }
-        // a frozen replicate reports "selected, no change": it stays stopped whatever is judged
-        if (stopped) { m = 0.0; f = 1u; }
-        p.part_max[blockIdx.x * R + r] = m;
-        p.part_flags[blockIdx.x * R + r] = f;
-    }
+    write_partials(p, r, stopped, local_max, flags);
 }
 
 // em_rows_batch and em_finalize_batch in ONE launch (skm_em.hip: em_rows_finalize_kernel is the
@@ -259,14 +216,11 @@ em_finalize_batch_kernel(EmBatchProblem p, int parity)
 // 8-lane group holds all eight replicates' row sums; lane r finalizes replicate r of the row's
 // transcript -- all eight lanes busy, with em_finalize_batch_kernel's arithmetic (a = 0.0 + row sum)
 // -- when the transcript has this one row (every transcript of the benchmarked tables has), and for a
-// transcript of several rows the group whose row arrives last adds them up in row order (row sums
-// cross blocks as agent-scope atomic stores / loads, the store completed before the arrival counts).
+// transcript of several rows the group whose row arrives last adds them up in row order.
 __global__ void __launch_bounds__(256)
 em_rows_finalize_batch_kernel(EmBatchProblem p, int parity)
 {
     if (p.ctl[BCTL_ALL_DONE]) return;
-    __shared__ double s_max[4][R];
-    __shared__ unsigned int s_flags[4][R];
     const double *__restrict__ x = p.x[parity];
     double *__restrict__ x_new = p.x[parity ^ 1];
     const int sub = threadIdx.x & 7;
@@ -278,23 +232,10 @@ em_rows_finalize_batch_kernel(EmBatchProblem p, int parity)
          row += ((int64_t)gridDim.x * blockDim.x) >> 3) {
         const int64_t begin = p.row_start[row], end = p.row_start[row + 1];
         const int32_t t = p.row_tx[row];
-        const double *__restrict__ xt = x + (int64_t)t * R;
         const int64_t first_row = p.tx_row[t], rows_of_t = p.tx_row[t + 1] - first_row;
         const double eff = p.eff_len[t];
         double xr[R], s[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { xr[r] = xt[r]; s[r] = 0.0; }
-        for (int64_t e = begin + sub; e < end; e += 8) {
-            const double *__restrict__ inner = p.inner + (int64_t)p.tx_cls[e] * R;
-#pragma unroll
-            for (int r = 0; r < R; ++r) s[r] += xr[r] / inner[r];
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            s[r] += __shfl_xor(s[r], 4, 8);
-            s[r] += __shfl_xor(s[r], 2, 8);
-            s[r] += __shfl_xor(s[r], 1, 8);
-        }
+        em_row_sums<R>(p.tx_cls, p.inner, begin, end, sub, x + (int64_t)t * R, xr, s);
         double mine = s[0], before = xr[0];                    // replicate `sub` of this row
 #pragma unroll
         for (int r = 1; r < R; ++r) { mine = sub == r ? s[r] : mine; before = sub == r ? xr[r] : before; }
@@ -302,50 +243,15 @@ em_rows_finalize_batch_kernel(EmBatchProblem p, int parity)
         if (rows_of_t == 1) {
             a += mine;
         } else {
-            unsigned long long *const sums = reinterpret_cast<unsigned long long *>(p.row_sum);
-            __hip_atomic_store(&sums[row * R + sub], (unsigned long long)__double_as_longlong(mine), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // (the eight stores of the group are complete: the wait above is per wave, and the group is in one)
-            unsigned int arrived = 0;
-            if (sub == 0) arrived = atomicAdd(&p.arrivals[t], 1u) + 1u;
-            arrived = __shfl(arrived, 0, 8);
+            // every lane publishes its replicate's sum; lane 0 counts the row's arrival for the group
+            const unsigned int arrived = __shfl(em_row_publish(p.row_sum, row * R + sub, mine, &p.arrivals[t], sub == 0), 0, 8);
             if ((int64_t)arrived != rows_of_t) continue;          // another row of this transcript is still to come
-            for (int64_t k = 0; k < rows_of_t; ++k)
-                a += __longlong_as_double((long long)__hip_atomic_load(&sums[(first_row + k) * R + sub], __ATOMIC_RELAXED,
-                                                                       __HIP_MEMORY_SCOPE_AGENT));
-            if (sub == 0) atomicExch(&p.arrivals[t], 0u);         // (for the next step)
+            a = em_rows_published_sum<R>(p.row_sum, first_row, rows_of_t, sub);
+            if (sub == 0) em_row_arrivals_reset(&p.arrivals[t]);
         }
-        double v = a / eff / n_total;                             // infer.py:158
-        if (v != v) v = 0.0;                                      // infer.py:159
-        if (stopped) {
-            x_new[(int64_t)t * R + sub] = before;                 // a stopped replicate keeps its result
-        } else {
-            x_new[(int64_t)t * R + sub] = v;
-            if (v > p.x_floor) {                                  // infer.py:160
-                const double change = fabs(v - before) / v;
-                if (change != change) flags |= 2u;
-                else if (change > local_max) local_max = change;
-                flags |= 1u;
-            }
-        }
+        finalize_place(a, eff, n_total, stopped, before, p.x_floor, x_new[(int64_t)t * R + sub], local_max, flags);
     }
-    const int wave = threadIdx.x >> 6;
-    for (int d = 32; d >= R; d >>= 1) {                          // over the lanes of the wave that hold replicate `sub`
-        const double o = __shfl_xor(local_max, d, 64);
-        local_max = o > local_max ? o : local_max;
-        flags |= __shfl_xor(flags, d, 64);
-    }
-    if ((threadIdx.x & 63) < R) { s_max[wave][sub] = local_max; s_flags[wave][sub] = flags; }
-    __syncthreads();
-    if (threadIdx.x < R) {
-        double m = s_max[0][sub];
-        unsigned int f = s_flags[0][sub];
-        for (int w = 1; w < 4; ++w) { m = s_max[w][sub] > m ? s_max[w][sub] : m; f |= s_flags[w][sub]; }
-        if (stopped) { m = 0.0; f = 1u; }                        // (see em_finalize_batch_kernel)
-        p.part_max[blockIdx.x * R + sub] = m;
-        p.part_flags[blockIdx.x * R + sub] = f;
-    }
+    write_partials(p, sub, stopped, local_max, flags);
 }
 
 __global__ void __launch_bounds__(256)
@@ -371,10 +277,7 @@ em_batch_take_kernel(const double *__restrict__ x, int64_t n_tx, int r, double *
 // to be taken, the next replicate of the group (if any) is to be put in its place -- and a grid-wide
 // kernel carries the plan out: result out, pre-drawn class counts and the common start vector in,
 // the place's partials of "the step before" set to "still changing".  The host only queues steps
-// and looks now and then whether everything has finished.  mgr words: [0] next replicate to start,
-// [1] replicates in the group, [2] finished, [3] a replicate had no abundance above x_floor,
-// [8 + r] replicate in place r + 1 (0: idle), [16 + r] the step it started at, [24 + r] / [32 + r]
-// the plan of this step: replicate to take / to put, + 1.
+// and looks now and then whether everything has finished.  (mgr: the MGR_ words of skm_kernels.h)
 __global__ void em_batch_assign_kernel(EmBatchProblem p, unsigned long long *mgr, int64_t *iters_out, int64_t step)
 {
     if (threadIdx.x != 0 || p.ctl[BCTL_ALL_DONE]) return;

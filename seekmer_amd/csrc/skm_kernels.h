@@ -214,8 +214,7 @@ struct EmProblem {
     double *acc;                  // [T] numerators (multi-GPU all-reduce buffer)
     double n_total;               // sum of class counts over all ranks
     double rel_tol, x_floor;
-    // control block: [0]=done [1]=iters [2]=ticket [3]=undefined; partials follow
-    unsigned long long *ctl;
+    unsigned long long *ctl;      // control block: the CTL_ words below
     double *part_max;             // [EM_FINAL_BLOCKS]
     unsigned int *part_flags;     // [EM_FINAL_BLOCKS] bit0 = any, bit1 = nan
     int64_t max_iters, fixed_iters;
@@ -230,6 +229,8 @@ struct EmProblem {
     const unsigned int *extra_flags;
     int64_t n_extra, extra_first;
 };
+// words of EmProblem::ctl: stopped, steps judged so far, no abundance above x_floor, a tile above the capacity
+enum { CTL_DONE = 0, CTL_ITERS = 1, CTL_UNDEFINED = 3, CTL_TILE_FAULT = 4 };
 #ifndef SKM_EM_FINAL_BLOCKS
 #define SKM_EM_FINAL_BLOCKS 2048
 #endif
@@ -242,7 +243,7 @@ void launch_em_rows_finalize(const EmProblem &p, int parity, hipStream_t stream)
 void launch_em_rows_acc(const EmProblem &p, int parity, hipStream_t stream);   // several ranks: em_rows + em_rows_to_acc
 void launch_em_rows_to_acc(const EmProblem &p, hipStream_t stream);
 void launch_em_finalize(const EmProblem &p, int parity, bool from_acc, hipStream_t stream);
-// out = the result of an EM that latched after ctl[1] steps (x0 if even, x1 if odd)
+// out = the result of an EM that latched after ctl[CTL_ITERS] steps (x0 if even, x1 if odd)
 void launch_em_result(const unsigned long long *ctl, const double *x0, const double *x1, int64_t n, double *out,
                       hipStream_t stream);
 
@@ -303,9 +304,7 @@ struct EmBatchProblem {
     double *x[2];                 // [T][EM_BATCH] ping-pong
     double *place_total;          // [EM_BATCH] sum of the class counts of the problem in each place (the refill writes it)
     double rel_tol, x_floor;
-    // control block (32 words): [0] all stopped [1] step at which the last one stopped,
-    // [8 + r] replicate r stopped, [16 + r] its step count, [24 + r] undefined (no x above x_floor)
-    unsigned long long *ctl;
+    unsigned long long *ctl;      // control block (32 words): the BCTL_ words below
     double *part_max;             // [EM_FINAL_BLOCKS][EM_BATCH]
     unsigned int *part_flags;     // [EM_FINAL_BLOCKS][EM_BATCH]
     int managed;                  // the device refills the places (launch_em_batch_manage): see skm_em_batch.hip
@@ -314,11 +313,18 @@ struct EmBatchProblem {
     int fused;                    // rows and finalize are one launch (em_rows_finalize_batch_kernel)
     unsigned int *arrivals;       // [T] rows of a many-row transcript summed so far in this step (zero between steps)
 };
+// words of EmBatchProblem::ctl: all stopped, the step at which the last one stopped; + r: replicate r
+// stopped, its step count, undefined (no x above x_floor)
+enum { BCTL_ALL_DONE = 0, BCTL_LAST_STEP = 1, BCTL_DONE = 8, BCTL_ITERS = 16, BCTL_UNDEFINED = 24 };
+// words of `mgr` below: next replicate to start, replicates in the group, finished, a replicate had no
+// abundance above x_floor; + r: replicate in place r + 1 (0: idle), the step it started at, the plan
+// of this step: replicate to take / to put, + 1
+enum { MGR_NEXT = 0, MGR_COUNT = 1, MGR_FINISHED = 2, MGR_UNDEFINED = 3, MGR_REP = 8, MGR_SINCE = 16, MGR_TAKE = 24,
+       MGR_PUT = 32 };
 // The working set kept full by the device: `mgr` is 64 words of HBM; counts_all[i][C] the class counts
 // of replicate i of the group (internal class order), totals[2 i] their sum (pairs, as launch_np_sum_many
 // leaves them), out_all[i][T] its result, iters_out[i] its step count (device memory).  _init fills the first places; _manage after EVERY step takes what has stopped and
-// puts the next replicates in.  ctl[0] is set once every replicate of the group has finished; mgr[2]
-// counts the finished ones, mgr[3] != 0: a replicate had no abundance above x_floor.
+// puts the next replicates in.  ctl[BCTL_ALL_DONE] is set once every replicate of the group has finished.
 void launch_em_batch_manage_init(const EmBatchProblem &p, unsigned long long *mgr, unsigned long long *host_pinned64,
                                  int64_t n_reps, const double *counts_all, const double *totals, const double *x_start,
                                  double *out_all, hipStream_t stream);

@@ -284,6 +284,58 @@ def test_em_row_and_tuple_edges_against_extended_precision(oracle, native_libs, 
         quant.close()
 
 
+_UNFUSED_CHILD = '''
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from seekmer_amd import infer
+d = np.load(sys.argv[2])
+quant = infer._QuantHandle.from_csr(int(d['n_tx']), d['offsets'], d['targets'], d['counts'])
+try:
+    x, it = quant.em(d['x0'], d['l'])
+    x3, it3 = quant.em(d['x0'], d['l'], fixed_iters=3)
+    boot, _, boot_it = quant.bootstrap(9, int(d['seed']), d['x0'], d['l'])
+finally:
+    quant.close()
+np.savez(sys.argv[3], x=x, it=it, x3=x3, it3=it3, boot=boot, boot_it=boot_it)
+'''
+
+
+def test_unfused_em_equals_fused(native_libs, tmp_path):
+    """SKM_EM_UNFUSED=1 (read once per process: a fresh child) runs rows and finalize as two launches,
+    single-problem and batched, with the whole-table kernels only: bit for bit and step for step what
+    this process computes with the fused and tile kernels."""
+    import os
+    import subprocess
+    import sys
+    from seekmer_amd import infer
+    n_tx = 300
+    offsets, targets, counts, zeroed = _edge_table(n_tx, n_tx)
+    x0, l = _edge_start(n_tx, zeroed, n_tx)
+    given, got = str(tmp_path / 'given.npz'), str(tmp_path / 'unfused.npz')
+    np.savez(given, n_tx=n_tx, offsets=offsets, targets=targets, counts=counts.astype('f8'), x0=x0, l=l,
+             seed=np.uint64(SEEDS[2]))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    proc = subprocess.run(['timeout', '-k', '10', '120', sys.executable, '-c', _UNFUSED_CHILD, root, given, got],
+                          env=dict(os.environ, SKM_EM_UNFUSED='1'), capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    child = np.load(got)
+    quant = infer._QuantHandle.from_csr(n_tx, offsets, targets, counts.astype('f8'))
+    try:
+        x, it = quant.em(x0, l)
+        x3, it3 = quant.em(x0, l, fixed_iters=3)
+        boot, _, boot_it = quant.bootstrap(9, SEEDS[2], x0, l)
+    finally:
+        quant.close()
+    assert it3 == 3
+    np.testing.assert_array_equal(child['it'], it)
+    np.testing.assert_array_equal(child['it3'], it3)
+    np.testing.assert_array_equal(child['boot_it'], boot_it)
+    np.testing.assert_array_equal(child['x'], x)
+    np.testing.assert_array_equal(child['x3'], x3)
+    np.testing.assert_array_equal(child['boot'], boot)
+
+
 def test_em_single_transcript(oracle, native_libs):
     from seekmer_amd import infer
     offsets = np.array([0, 1, 3, 6], dtype=np.int64)
