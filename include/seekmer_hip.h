@@ -233,6 +233,14 @@ int skm_mapper_keep_spans(skm_mapper *mapper, int enable);
 #define SKM_STRAND_FR 1
 #define SKM_STRAND_RF 2
 int skm_mapper_set_strand(skm_mapper *mapper, int mode);
+/* A fragment-length model for the effective lengths: p[2000], finite weights >= 0 that sum to 1
+ * (mapper.fragment_length_weights makes them; SKM_ERR_ARG for a negative or non-finite one).  The
+ * mapper keeps them in HBM, and skm_quant_infer then takes eff_t = sum_i max(len_t - i, 1) * p[i]
+ * from them instead of from the histogram, on one rank and with a communicator (every rank must
+ * hold the same weights).  NULL: back to the histogram.  It may be set or cleared at any time and
+ * affects only later quantification calls; the histogram is counted and exported as ever, and
+ * skm_mapper_reset / skm_mapper_clear leave the model in place. */
+int skm_mapper_set_length_weights(skm_mapper *mapper, const double *p);
 /* Counter sizes (MapResult.summarize, seekmer/mapper.py:77-104):
  * summary[0]=C classes [1]=M (class,target) rows [2]=unaligned [3]=total units */
 int skm_mapper_summary(skm_mapper *mapper, int64_t summary[4]);
@@ -335,6 +343,10 @@ int skm_sample_set_create(skm_index *index, int paired, skm_sample_set **out);
 int skm_sample_set_destroy(skm_sample_set *set);
 /* only while the set holds no units (SKM_ERR_STATE otherwise) */
 int skm_sample_set_set_strand(skm_sample_set *set, int mode);
+/* skm_mapper_set_length_weights for the set: skm_sample_set_quantify then computes ONE row of
+ * effective lengths from p and gives it to every sample, whether or not the set keeps a histogram
+ * per sample, and its effective_lengths output carries those lengths.  NULL: back to the histograms. */
+int skm_sample_set_set_length_weights(skm_sample_set *set, const double *p);
 /* Units [first_unit, first_unit + n) of `sample` as packed reads (skm_packed_reads): unit
  * first_unit + r = read r of mate1 (+ read r of mate2 in a paired set; NULL in a single-ended one).
  * n = mate1->n_reads = mate2->n_reads; the pieces' `stream` and `first_read` are not looked at. */
@@ -404,6 +416,13 @@ int skm_effective_lengths(int device, const int64_t *fld, const double *lengths,
  * within 256 MB each (SKM_EFF_MANY_GROUP in the environment: rows per group at most, for tests). */
 int skm_effective_lengths_many(int device, int64_t n, const int64_t *fld, const double *lengths,
                                int64_t n_tx, double *out);
+/* The same rule with p given instead of counted: n rows of weights p[n][2000] -> out[n][n_tx],
+ * out[s][t] = sum_i max(lengths[t] - i, 1) * p[s][i] accumulated for i = 0..1999 in order, multiply
+ * and add separate -- bit for bit the numpy loop over the same p.  Grouped as the call above
+ * (SKM_EFF_MANY_GROUP).  SKM_ERR_ARG, before any device work, for a negative or non-finite weight,
+ * a NULL array or a negative size; n == 0 or n_tx == 0 does nothing. */
+int skm_effective_lengths_weights(int device, int64_t n, const double *p, const double *lengths,
+                                  int64_t n_tx, double *out);
 
 /* Device-resident class table for infer.em / infer.quantify
  * (seekmer/infer.py:88-168).  class_counts are f8 as in

@@ -9,7 +9,7 @@ from . import index_builder
 from . import infer
 
 
-def main(argv=None):
+def make_parser():
     parser = argparse.ArgumentParser(prog='seekmer_amd', description='A fast RNA-seq tool',
                                      formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('-v', '--version', action='version', version='Seekmer 2019.0.0 (MI355X)')
@@ -19,7 +19,21 @@ def main(argv=None):
     infer.add_subcommand_parser(subparsers)
     infer.add_many_subcommand_parser(subparsers)
     impute.add_subcommand_parser(subparsers)
+    return parser
+
+
+def parse_args(argv=None, parser=None):
+    """The command line as the options a subcommand's run() takes; exits on a command line that cannot be."""
+    parser = parser or make_parser()
     opts = vars(parser.parse_args(argv))
+    if opts['subcommand'] in ('infer', 'infer-many', 'impute'):
+        infer.length_model_option(parser, opts)
+    return opts
+
+
+def main(argv=None):
+    parser = make_parser()
+    opts = parse_args(argv, parser)
     logging.basicConfig(level=logging.DEBUG if opts['debug'] else logging.INFO,
                         format='%(levelname)-5s %(asctime)s %(name)s: %(message)s',
                         datefmt='%Y-%m-%d %H:%M:%S', stream=sys.stderr)

@@ -91,6 +91,7 @@ HIP_SYMBOLS = {
                                              c_i32p, c_i32p, c_i64, c_i64p]),
     'skm_mapper_keep_spans': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_mapper_set_length_weights': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_mapper_summary': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_mapper_export': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i64p, c_i64p, c_i64p]),
     'skm_mapper_merge': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
@@ -104,9 +105,11 @@ HIP_SYMBOLS = {
     'skm_mapper_access_stats': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_effective_lengths': (ctypes.c_int, [ctypes.c_int, c_i64p, c_f64p, c_i64, c_f64p]),
     'skm_effective_lengths_many': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_f64p, c_i64, c_f64p]),
+    'skm_effective_lengths_weights': (ctypes.c_int, [ctypes.c_int, c_i64, c_f64p, c_f64p, c_i64, c_f64p]),
     'skm_sample_set_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp]),
     'skm_sample_set_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_sample_set_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_set_length_weights': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_sample_set_add_packed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(PackedReads),
                                                  ctypes.POINTER(PackedReads)]),
     'skm_sample_set_add_batch': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_void_p, c_i64p, c_i64]),

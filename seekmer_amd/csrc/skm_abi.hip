@@ -7,6 +7,7 @@
 
 #include <dlfcn.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -197,6 +198,10 @@ struct skm_mapper {
     DBuf<uint64_t> rec_key;
     bool keep_spans = false, last_spans = false;   // spans wanted / written by the last batch
     int strand = SKM_STRAND_NONE;                  // skm_mapper_set_strand (under mu)
+    // skm_mapper_set_length_weights (under mu): p[2000] of a fragment-length model; while it is in use the
+    // quantification calls take the effective lengths from it and not from the histogram
+    DBuf<double> length_weights;
+    bool use_length_weights = false;
     DBuf<int32_t> unit_entries;
     DBuf<unsigned long long> batch_ctl;  // [0]=ids_cursor [8..2007]=fld [2048..2063]=stats
     int grid_blocks = 0;
@@ -1912,6 +1917,39 @@ extern "C" int skm_mapper_set_strand(skm_mapper *m, int mode)
     return SKM_OK;
 }
 
+namespace {
+
+// the weights of a fragment-length model: every one finite and >= 0 (checked on the host, before any device work)
+bool length_weights_valid(const double *p, int64_t count)
+{
+    for (int64_t i = 0; i < count; ++i)
+        if (!(p[i] >= 0.0) || std::isinf(p[i])) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int skm_mapper_set_length_weights(skm_mapper *m, const double *p)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!m) return fail(SKM_ERR_ARG, "NULL mapper");
+    if (p && !length_weights_valid(p, MAX_FRAGMENT_LENGTH))
+        return fail(SKM_ERR_ARG, "a fragment-length weight is negative or not finite");
+    SKM_TRY(wait_jobs(m, 0, false));
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!p) {
+        m->use_length_weights = false;
+        return SKM_OK;
+    }
+    SKM_TRY(set_device(m->ix->device));
+    SKM_TRY(m->length_weights.ensure(MAX_FRAGMENT_LENGTH));
+    // (no quantification call is under way: they hold mu until their stream has drained)
+    HIP_TRY(hipMemcpy(m->length_weights.p, p, MAX_FRAGMENT_LENGTH * 8, hipMemcpyHostToDevice));
+    m->use_length_weights = true;
+    return SKM_OK;
+}
+
 extern "C" int skm_mapper_summary(skm_mapper *m, int64_t summary[4])
 {
     if (!m || !summary) return fail(SKM_ERR_ARG, "NULL argument");
@@ -2554,6 +2592,14 @@ extern "C" int skm_sample_set_set_strand(skm_sample_set *s, int mode)
     return skm_mapper_set_strand(s->m, mode);
 }
 
+extern "C" int skm_sample_set_set_length_weights(skm_sample_set *s, const double *p)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    return skm_mapper_set_length_weights(s->m, p);
+}
+
 extern "C" int skm_sample_set_keep_histograms(skm_sample_set *s, int enable)
 {
     if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
@@ -2782,6 +2828,20 @@ extern "C" int skm_effective_lengths(int device, const int64_t *fld, const doubl
     return SKM_OK;
 }
 
+namespace {
+
+// rows per group of n > 0 rows of 2000 words in, n_tx > 0 words out: 256 MB of output rows and of input rows
+// at most (16 777 rows: one launch's gridDim.y holds them); SKM_EFF_MANY_GROUP (tests): fewer
+int64_t effective_lengths_group(int64_t n, int64_t n_tx)
+{
+    int64_t group = std::min<int64_t>((int64_t)(1LL << 25) / n_tx, (int64_t)(1LL << 25) / MAX_FRAGMENT_LENGTH);
+    if (const char *v = getenv("SKM_EFF_MANY_GROUP"))
+        if (atoll(v) > 0) group = std::min<int64_t>(group, atoll(v));
+    return std::max<int64_t>(1, std::min(group, n));
+}
+
+}  // namespace
+
 // Groups of histograms, so that the rows staged in HBM, in and out, stay within 256 MB each (as many_rows_in);
 // the lengths go up once.
 extern "C" int skm_effective_lengths_many(int device, int64_t n, const int64_t *fld, const double *lengths,
@@ -2793,12 +2853,7 @@ extern "C" int skm_effective_lengths_many(int device, int64_t n, const int64_t *
     if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
     SKM_TRY(set_device(device));
     if (n == 0 || n_tx == 0) return SKM_OK;
-    // rows per group: 256 MB of output rows and of histograms at most (16 777 rows: one launch's gridDim.y holds them);
-    // SKM_EFF_MANY_GROUP (tests): fewer
-    int64_t group = std::min<int64_t>((int64_t)(1LL << 25) / n_tx, (int64_t)(1LL << 25) / MAX_FRAGMENT_LENGTH);
-    if (const char *v = getenv("SKM_EFF_MANY_GROUP"))
-        if (atoll(v) > 0) group = std::min<int64_t>(group, atoll(v));
-    group = std::max<int64_t>(1, std::min(group, n));
+    const int64_t group = effective_lengths_group(n, n_tx);
     DBuf<unsigned long long> d_fld; DBuf<double> d_len, d_out;
     auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
     SKM_TRY(d_fld.ensure((size_t)group * MAX_FRAGMENT_LENGTH)); SKM_TRY(d_len.ensure(n_tx)); SKM_TRY(d_out.ensure((size_t)(group * n_tx)));
@@ -2807,6 +2862,34 @@ extern "C" int skm_effective_lengths_many(int device, int64_t n, const int64_t *
         const int64_t here = std::min(group, n - first);
         HIP_TRY(hipMemcpy(d_fld.p, fld + first * MAX_FRAGMENT_LENGTH, (size_t)here * MAX_FRAGMENT_LENGTH * 8, hipMemcpyHostToDevice));
         launch_effective_lengths_many(d_fld.p, here, d_len.p, n_tx, d_out.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out + first * n_tx, d_out.p, (size_t)(here * n_tx) * 8, hipMemcpyDeviceToHost));
+    }
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    return SKM_OK;
+}
+
+// The same rule for n rows of given weights, grouped as the histograms above.
+extern "C" int skm_effective_lengths_weights(int device, int64_t n, const double *p, const double *lengths,
+                                             int64_t n_tx, double *out)
+{
+    if (n < 0 || n_tx < 0 || !p || !lengths || !out) return fail(SKM_ERR_ARG, "bad argument");
+    if (!length_weights_valid(p, n * MAX_FRAGMENT_LENGTH))
+        return fail(SKM_ERR_ARG, "a fragment-length weight is negative or not finite");
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(set_device(device));
+    if (n == 0 || n_tx == 0) return SKM_OK;
+    const int64_t group = effective_lengths_group(n, n_tx);
+    DBuf<double> d_p, d_len, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_p.ensure((size_t)group * MAX_FRAGMENT_LENGTH)); SKM_TRY(d_len.ensure(n_tx)); SKM_TRY(d_out.ensure((size_t)(group * n_tx)));
+    HIP_TRY(hipMemcpy(d_len.p, lengths, n_tx * 8, hipMemcpyHostToDevice));
+    for (int64_t first = 0; first < n; first += group) {
+        const int64_t here = std::min(group, n - first);
+        HIP_TRY(hipMemcpy(d_p.p, p + first * MAX_FRAGMENT_LENGTH, (size_t)here * MAX_FRAGMENT_LENGTH * 8, hipMemcpyHostToDevice));
+        launch_effective_lengths_weights(d_p.p, here, d_len.p, n_tx, d_out.p, nullptr);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(out + first * n_tx, d_out.p, (size_t)(here * n_tx) * 8, hipMemcpyDeviceToHost));
     }
@@ -3350,7 +3433,10 @@ extern "C" int skm_quant_infer(skm_mapper *m, skm_comm *comm, const double *leng
     }
     q->n_total = (double)aligned;
     HIP_TRY(hipMemcpyAsync(q->x1.p, lengths, n_tx * 8, hipMemcpyHostToDevice, q->stream));
-    launch_effective_lengths(fld.p, q->x1.p, n_tx, q->eff_len.p, q->stream);
+    if (m->use_length_weights)                 // a fragment-length model: the same on every rank
+        launch_effective_lengths_weights(m->length_weights.p, 1, q->x1.p, n_tx, q->eff_len.p, q->stream);
+    else
+        launch_effective_lengths(fld.p, q->x1.p, n_tx, q->eff_len.p, q->stream);
     // (the effective lengths go home at the end, with the TPM: a copy to pageable memory holds the
     // host up, and the kernels that follow are not launched meanwhile)
     // quantify(): no class -> zeros (infer.py:106-107); over several ranks "no class anywhere"
@@ -4206,7 +4292,10 @@ extern "C" int skm_sample_set_quantify(skm_sample_set *s, const double *lengths,
                 M += v.len[(size_t)c];
             }
         h_dst[(size_t)C] = M;
-        if (s->keep_hist) {
+        if (m->use_length_weights) {              // a fragment-length model: one row for every sample
+            launch_effective_lengths_weights(m->length_weights.p, 1, lengths_dev.p, n_tx, q->eff_len.p, q->stream);
+            launch_repeat_row(q->eff_len.p, n_tx, n, q->stream);
+        } else if (s->keep_hist) {
             const int64_t have = std::max<int64_t>(0, std::min(n, hist_rows - t0));
             HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)n * MAX_FRAGMENT_LENGTH * 8, q->stream));
             if (have) HIP_TRY(hipMemcpyAsync(hist.p, s->hist.p + t0 * MAX_FRAGMENT_LENGTH, (size_t)have * MAX_FRAGMENT_LENGTH * 8,

@@ -355,13 +355,52 @@ em_local_decide_kernel(EmProblem p, EmTiles tl, int64_t first_step, int n_steps)
 // MapResult.effective_lengths, mapper.py:134-141: p = fld / fld.sum();
 // eff_t = sum_i max(len_t - i, 1) * p_i accumulated for i = 0..1999 in order
 // (compiled with -ffp-contract=off: separate multiply and add, as numpy).
-// blockIdx.y is the histogram: row y of fld[gridDim.y][2000] gives row y of out[gridDim.y][n_tx], each by
-// the arithmetic of a launch on that row alone (the lengths are shared).
-__global__ void __launch_bounds__(256)
-effective_lengths_kernel(const unsigned long long *__restrict__ fld,
-                         const double *__restrict__ lengths, int64_t n_tx, double *__restrict__ out)
+// Where p comes from is a Source: stage() by the whole block (row `row` of the source's table; it ends
+// on a barrier when it wrote LDS), then weight(i) = p_i for wave 0, which packs the bins.
+
+// p = fld / fld.sum() of the histogram fld[row][2000]
+struct HistogramWeights {
+    struct Staged {
+        unsigned long long counts[MAX_FRAGMENT_LENGTH];
+        unsigned long long part[4];
+    };
+    const unsigned long long *fld;
+    double total;
+    __device__ __forceinline__ void stage(int64_t row, Staged &lds)
+    {
+        fld += row * MAX_FRAGMENT_LENGTH;
+        // the histogram once into LDS (coalesced), its total by a block reduction (integers: any order)
+        unsigned long long mine = 0;
+        for (int i = threadIdx.x; i < MAX_FRAGMENT_LENGTH; i += blockDim.x) {
+            lds.counts[i] = fld[i];
+            mine += lds.counts[i];
+        }
+        for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
+        if ((threadIdx.x & 63) == 0) lds.part[threadIdx.x >> 6] = mine;
+        __syncthreads();
+        total = (double)(long long)(lds.part[0] + lds.part[1] + lds.part[2] + lds.part[3]);
+    }
+    __device__ __forceinline__ double weight(int i, const Staged &lds) const
+    {
+        return (double)(long long)lds.counts[i] / total;
+    }
+};
+
+// p as it was made on the host (mapper.fragment_length_weights): row `row` of p[n][2000], read where it
+// lies -- each weight is read once, by wave 0, 64 neighbours at a time
+struct GivenWeights {
+    struct Staged {};
+    const double *p;
+    __device__ __forceinline__ void stage(int64_t row, Staged &) { p += row * MAX_FRAGMENT_LENGTH; }
+    __device__ __forceinline__ double weight(int i, const Staged &) const { return p[i]; }
+};
+
+// blockIdx.y is the row: row y of the source gives row y of out[gridDim.y][n_tx], each by the arithmetic
+// of a launch on that row alone (the lengths are shared).
+template <class Source>
+__device__ __forceinline__ void effective_lengths_rows(Source source, const double *__restrict__ lengths, int64_t n_tx,
+                                                       double *__restrict__ out)
 {
-    fld += (int64_t)blockIdx.y * MAX_FRAGMENT_LENGTH;
     out += (int64_t)blockIdx.y * n_tx;
     // Only the bins with p_i != 0 are visited: a term max(len - i, 1) * 0.0 is +0.0 and adding
     // +0.0 leaves the running sum as it is, bit for bit (the sum starts at +0.0 and every term
@@ -369,25 +408,15 @@ effective_lengths_kernel(const unsigned long long *__restrict__ fld,
     // histogram has a few hundred occupied bins out of 2000.
     __shared__ double p[MAX_FRAGMENT_LENGTH];
     __shared__ int bin[MAX_FRAGMENT_LENGTH];
-    __shared__ unsigned long long counts[MAX_FRAGMENT_LENGTH];
-    __shared__ unsigned long long part[4];
+    __shared__ typename Source::Staged staged;
     __shared__ int n_bins;
-    // the histogram once into LDS (coalesced), its total by a block reduction (integers: any order)
-    unsigned long long mine = 0;
-    for (int i = threadIdx.x; i < MAX_FRAGMENT_LENGTH; i += blockDim.x) {
-        counts[i] = fld[i];
-        mine += counts[i];
-    }
-    for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    const double total = (double)(long long)(part[0] + part[1] + part[2] + part[3]);
+    source.stage((int64_t)blockIdx.y, staged);
     // wave 0 packs the non-zero bins in bin order (ballot + prefix count per 64 bins)
     if (threadIdx.x < 64) {
         int n = 0;
         for (int first = 0; first < MAX_FRAGMENT_LENGTH; first += 64) {
             const int i = first + (int)threadIdx.x;
-            const double v = i < MAX_FRAGMENT_LENGTH ? (double)(long long)counts[i] / total : 0.0;
+            const double v = i < MAX_FRAGMENT_LENGTH ? source.weight(i, staged) : 0.0;
             const bool keep = i < MAX_FRAGMENT_LENGTH && !(v == 0.0);
             const unsigned long long kept = __ballot(keep);
             if (keep) {
@@ -412,6 +441,22 @@ effective_lengths_kernel(const unsigned long long *__restrict__ fld,
         }
         out[t] = acc;
     }
+}
+
+__global__ void __launch_bounds__(256)
+effective_lengths_kernel(const unsigned long long *__restrict__ fld,
+                         const double *__restrict__ lengths, int64_t n_tx, double *__restrict__ out)
+{
+    effective_lengths_rows(HistogramWeights{fld, 0.0}, lengths, n_tx, out);
+}
+
+// The same rule with p given instead of counted: a fragment-length model (--fragment-length / --sd).
+// Weights are finite and >= 0 (the callers check), so a skipped bin is a zero bin as above.
+__global__ void __launch_bounds__(256)
+effective_lengths_weights_kernel(const double *__restrict__ p,
+                                 const double *__restrict__ lengths, int64_t n_tx, double *__restrict__ out)
+{
+    effective_lengths_rows(GivenWeights{p}, lengths, n_tx, out);
 }
 
 // Counter-based generator for the bootstrap draw (the reference draws from
@@ -932,13 +977,26 @@ void launch_effective_lengths(const unsigned long long *fld, const double *lengt
                        lengths, n_tx, out);
 }
 
+// rows of one launch (n <= 65535: gridDim.y; the callers' groups are smaller).  Every block packs its row
+// first: few blocks per row when there are many of them.
+static unsigned effective_lengths_blocks_per_row(int64_t n, int64_t n_tx)
+{
+    return std::min<unsigned>(grid_for(n_tx), n >= 64 ? 16u : 256u);
+}
+
 void launch_effective_lengths_many(const unsigned long long *fld, int64_t n, const double *lengths, int64_t n_tx,
                                    double *out, hipStream_t stream)
 {
-    // n <= 65535 (gridDim.y; the caller's groups are smaller).  Every block packs its histogram first: few
-    // blocks per histogram when there are many of them.
-    const unsigned per_row = std::min<unsigned>(grid_for(n_tx), n >= 64 ? 16u : 256u);
-    hipLaunchKernelGGL(effective_lengths_kernel, dim3(per_row, (unsigned)n), dim3(256), 0, stream, fld, lengths, n_tx, out);
+    hipLaunchKernelGGL(effective_lengths_kernel, dim3(effective_lengths_blocks_per_row(n, n_tx), (unsigned)n), dim3(256), 0,
+                       stream, fld, lengths, n_tx, out);
+}
+
+void launch_effective_lengths_weights(const double *p, int64_t n, const double *lengths, int64_t n_tx, double *out,
+                                      hipStream_t stream)
+{
+    // one row: the grid of launch_effective_lengths
+    const unsigned per_row = n == 1 ? (unsigned)grid_for(n_tx) : effective_lengths_blocks_per_row(n, n_tx);
+    hipLaunchKernelGGL(effective_lengths_weights_kernel, dim3(per_row, (unsigned)n), dim3(256), 0, stream, p, lengths, n_tx, out);
 }
 
 int multinomial_tile(int64_t n_classes)

@@ -457,6 +457,10 @@ void launch_effective_lengths(const unsigned long long *fld, const double *lengt
 // the same for n <= 65535 histograms fld[n][2000] -> out[n][n_tx], row by row what the launch above gives
 void launch_effective_lengths_many(const unsigned long long *fld, int64_t n, const double *lengths, int64_t n_tx,
                                    double *out, hipStream_t stream);
+// the same rule with p given instead of counted (a fragment-length model): p[n][2000] -> out[n][n_tx],
+// 1 <= n <= 65535, weights finite and >= 0
+void launch_effective_lengths_weights(const double *p, int64_t n, const double *lengths, int64_t n_tx, double *out,
+                                      hipStream_t stream);
 // multinomial(n_draws, counts / n_draws) over the classes whose inclusive cumulative counts are
 // `cum`: counts[c * stride] = draws of class c (f8).  tile_total: 4096 unsigned ints of scratch.
 // false = table too large for the tiled draw.

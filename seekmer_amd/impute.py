@@ -36,12 +36,15 @@ _LOG = logging.getLogger(__name__)
 
 
 def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, power,
-        device=0, seed=None, strand=None, **__):
+        device=0, seed=None, strand=None, length_model=None, **__):
     """The entrypoint of the imputation module (seekmer/impute.py:54-125).
     `seed` fixes the 2-means split of the weights (the reference leaves it to
-    numpy's global generator).  strand: None, 'fr' or 'rf' for every cell (mapper.MapResult)."""
+    numpy's global generator).  strand: None, 'fr' or 'rf' for every cell (mapper.MapResult).
+    length_model: None, or (mean, sd) of --fragment-length / --sd: every cell's effective lengths come
+    from that model instead of the pooled histogram (mapper.fragment_length_weights)."""
     import pandas
     mapper.strand_mode(strand)
+    length_model, _ = mapper.length_model_weights(length_model)
     for path in fastq_paths:
         if not pathlib.Path(path).exists():
             raise ValueError(f'invalid FastQ file: {path}')
@@ -50,6 +53,7 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
     except FileExistsError:
         _LOG.warning('The output folder exists. Overriding...')
     _LOG.info('Inferring transcript abundance')
+    infer._log_length_model(length_model, single_ended)
     index = common.KMerIndex.load(index_path)
     _LOG.info('Mapping all reads')
     width = 1 if single_ended else 2
@@ -62,13 +66,13 @@ def run(index_path, output_path, fastq_paths, job_count, single_ended, debug, po
     if use_sample_set(groups):
         # (the set's one histogram IS the pooled one: every summary carries it)
         sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count),
-                                           device=device, strand=strand)
+                                           device=device, strand=strand, length_model=length_model)
         _LOG.info('Mapped all reads.')
         summaries = sample_set.summarize()
     else:
         sample_set = None
         map_results = mapper.map_multiple_samples(index, feeders, job_count=job_count, debug=debug,
-                                                  device=device, strand=strand)
+                                                  device=device, strand=strand, length_model=length_model)
         _LOG.info('Mapped all reads.')
         pool_fragment_lengths(map_results)
         summaries = [result.summarize() for result in map_results]
@@ -353,3 +357,4 @@ def add_subcommand_parser(subparsers):
     parser.add_argument('--seed', type=int, default=None,
                         help='seed of the 2-means split of the cell weights (default: random)')
     infer.add_strand_arguments(parser)
+    infer.add_length_model_arguments(parser)

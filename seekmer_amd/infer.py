@@ -28,7 +28,7 @@ X_FLOOR = 1e-8          # seekmer/infer.py:160
 
 
 def run(index_path, output_path, fastq_paths, job_count, save_readmap,
-        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, **__):
+        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, length_model=None, **__):
     """The entrypoint of the inference module (seekmer/infer.py:27-85).
 
     Started as one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m
@@ -40,22 +40,27 @@ def run(index_path, output_path, fastq_paths, job_count, save_readmap,
     of the whole sample.  A rank that fails ends the job (parallel.Ranks.fail).
 
     strand: None, 'fr' (--fr-stranded) or 'rf' (--rf-stranded): every rank's mapper keeps only the
-    targets that lie in the library's orientation (mapper.MapResult)."""
+    targets that lie in the library's orientation (mapper.MapResult).
+
+    length_model: None, or (mean, sd) of --fragment-length / --sd: the effective lengths come from that
+    model (mapper.fragment_length_weights) instead of the observed histogram, on every rank's mapper, so
+    whichever rank quantifies holds it.  The histogram is still counted, logged and written."""
     from . import parallel
     start_time = datetime.datetime.utcnow()
     ranks = parallel.Ranks.from_env()
     try:
         _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-             bootstrap, debug, device, seed, parse_threads, strand=strand)
+             bootstrap, debug, device, seed, parse_threads, strand=strand, length_model=length_model)
     except BaseException as error:          # noqa: B902 -- one rank: re-raised as it is
         ranks.fail(error)
     ranks.close()
 
 
 def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-         bootstrap, debug, device, seed, parse_threads, strand=None):
+         bootstrap, debug, device, seed, parse_threads, strand=None, length_model=None):
     from . import parallel
     mapper.strand_mode(strand)              # (an unknown mode fails before any file is touched)
+    length_model, _ = mapper.length_model_weights(length_model)      # (and so does a model that cannot be)
     if ranks.world > 1:
         device = ranks.local_rank
         if save_readmap:
@@ -68,6 +73,7 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
     ranks.barrier()
     readmap = (output_path / 'readmap.txt').open('wt') if save_readmap else None
     _LOG.info('Inferring transcript abundance')
+    _log_length_model(length_model, single_ended)
     # (the readers' threads page-lock against THIS GPU; their arena is page-locked by a helper thread
     # from here on, under the index load and upload)
     _native.check(_native.hip().skm_pinned_set_device(device))
@@ -83,7 +89,8 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         index.device_handle(device)
         _LOG.info('Mapping all reads')
         map_result = mapper.map_reads(index, read_feeder, job_count=job_count,
-                                      readmap=readmap, debug=debug, device=device, strand=strand)
+                                      readmap=readmap, debug=debug, device=device, strand=strand,
+                                      length_model=length_model)
     finally:
         ahead.finish()
     _LOG.info('Mapped all reads')
@@ -105,6 +112,14 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         output_results(output_path, index, start_time, summarized_results,
                        main_result, bootstrapped_results)
         _LOG.info('Wrote results to %s', output_path)
+
+
+def _log_length_model(length_model, single_ended):
+    if length_model is None:
+        return
+    _LOG.info('Effective lengths from the fragment-length model: mean %g, sd %g', *length_model)
+    if not single_ended:
+        _LOG.info('The model overrides the observed fragment-length histogram of the paired reads')
 
 
 def sample_groups(fastq_paths, single_ended):
@@ -149,7 +164,7 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
-             strand=None, names=None, **__):
+             strand=None, names=None, length_model=None, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -163,12 +178,16 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     Inside the regime of impute.use_set_quant the main estimates of the samples that went through the set
     come from SampleSet.quantify() -- shared EM launches on the set's resident table, the bits of the loop;
     SKM_SET_QUANT_SERIAL=1 keeps quantify() sample by sample.  `-b N` stays per sample.  SKM_TRACE_INFER
-    prints the host wall time per phase on stderr."""
+    prints the host wall time per phase on stderr.
+
+    length_model: None or (mean, sd), as run(): every sample's effective lengths come from the model, in the
+    set and for the samples mapped by themselves; samples.tsv keeps the observed harmonic means."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
     trace = _phase_trace()
     mapper.strand_mode(strand)
+    length_model, _ = mapper.length_model_weights(length_model)
     groups = sample_groups(fastq_paths, single_ended)
     if not groups:
         raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
@@ -185,6 +204,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     except FileExistsError:
         _LOG.warning('The output folder exists. Overriding...')
     _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    _log_length_model(length_model, single_ended)
     _native.check(_native.hip().skm_pinned_set_device(device))
     index = common.KMerIndex.load(index_path)
     index.device_handle(device)
@@ -198,7 +218,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
                    else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
         sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
-                                           strand=strand, per_sample_lengths=True)
+                                           strand=strand, per_sample_lengths=True, length_model=length_model)
         for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
             summaries[i], means[i] = summary, mean
         trace('mapping (set)')
@@ -219,7 +239,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
             continue
         _LOG.info('Mapping sample %s', names[i])
         map_result = mapper.map_reads(index, _feeder(list(group), paired, None, None, False), job_count=job_count,
-                                      debug=debug, device=device, strand=strand)
+                                      debug=debug, device=device, strand=strand, length_model=length_model)
         summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
         del map_result
     _LOG.info('Mapped all reads')
@@ -763,7 +783,7 @@ def _generate_run_info(bootstrapped_abundance, index, results, start_time):
                                         minlength=results.class_count.size) \
         if results.class_map.size else numpy.zeros(results.class_count.size, dtype=numpy.int64)
     unique_count = results.class_count[class_target_count == 1].sum()
-    return {
+    run_info = {
         'n_targets': len(index.transcripts),
         'n_bootstraps': len(bootstrapped_abundance),
         'n_processed': results.total,
@@ -776,6 +796,10 @@ def _generate_run_info(bootstrapped_abundance, index, results, start_time):
         'start_time': start_time.isoformat(sep=' '),
         'call': ' '.join([shlex.quote(arg) for arg in sys.argv]),
     }
+    length_model = getattr(results, 'length_model', None)
+    if length_model is not None:          # (--fragment-length / --sd: the effective lengths are the model's)
+        run_info['fragment_length_model'] = {'mean': length_model[0], 'sd': length_model[1]}
+    return run_info
 
 
 def _output_abundance_table(output_path, index, results, est_counts, main_abundance):
@@ -848,6 +872,7 @@ def add_subcommand_parser(subparsers):
                         help='parse plain FASTQ files with N threads (default: up to 8; 0: one thread, '
                              'the batches of the reference)')
     add_strand_arguments(parser)
+    add_length_model_arguments(parser)
 
 
 def add_many_subcommand_parser(subparsers):
@@ -875,6 +900,33 @@ def add_many_subcommand_parser(subparsers):
     parser.add_argument('--names', type=str, default=None, metavar='A,B,C',
                         help='name the samples (default: each sample\'s first file name up to its first ".")')
     add_strand_arguments(parser)
+    add_length_model_arguments(parser)
+
+
+def add_length_model_arguments(parser):
+    """-l/--fragment-length MEAN and --sd SD (kallisto's -l and -s; -s is --single-ended here): both or
+    neither, which length_model_option checks once the arguments are parsed."""
+    parser.add_argument('-l', '--fragment-length', type=float, dest='fragment_length', default=None, metavar='MEAN',
+                        help='take the effective lengths from a normal fragment-length model with this mean '
+                             'instead of the observed histogram (with --sd; needed for single-ended reads)')
+    parser.add_argument('--sd', type=float, dest='sd', default=None, metavar='SD',
+                        help='standard deviation of the fragment-length model (with --fragment-length)')
+
+
+def length_model_option(parser, opts):
+    """The parsed options' 'fragment_length' and 'sd' -> 'length_model' (None | (mean, sd)); one without
+    the other, or a model that mapper.fragment_length_weights refuses, is an argparse error."""
+    mean, sd = opts.pop('fragment_length', None), opts.pop('sd', None)
+    if (mean is None) != (sd is None):
+        parser.error('-l/--fragment-length and --sd go together: give both or neither')
+    opts['length_model'] = None
+    if mean is not None:
+        try:
+            mapper.fragment_length_weights(mean, sd)
+        except ValueError as error:
+            parser.error(str(error))
+        opts['length_model'] = (mean, sd)
+    return opts
 
 
 def add_strand_arguments(parser):

@@ -25,7 +25,7 @@ from . import _native
 from .common import PackedReadFeeder, PackedReads, ReadBatch
 
 __all__ = ('MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet', 'SummarizedResult',
-           'map_reads', 'map_multiple_samples', 'map_sample_set')
+           'fragment_length_weights', 'map_reads', 'map_multiple_samples', 'map_sample_set')
 
 MAX_FRAGMENT_LENGTH = 2000          # seekmer/_mapper.pyx:18-20
 
@@ -41,15 +41,43 @@ def strand_mode(strand):
     return STRAND_MODES[strand]
 
 
+def fragment_length_weights(mean, sd):
+    """The fragment-length model of --fragment-length MEAN --sd SD: f8[2000], a normal density cut to
+    the bins 1..1999 and normalised.  These weights stand in for fld / fld.sum() in the effective-length
+    rule (seekmer/mapper.py:134-141).  They are made here, once, on the host: the device reads them as
+    they are (skm_effective_lengths_weights), so it and a numpy model of the rule share the same p."""
+    mean, sd = float(mean), float(sd)
+    if not (numpy.isfinite(mean) and numpy.isfinite(sd) and 0 < mean < MAX_FRAGMENT_LENGTH and sd > 0):
+        raise ValueError('a fragment-length model needs 0 < mean < %d and sd > 0, both finite, not (%r, %r)'
+                         % (MAX_FRAGMENT_LENGTH, mean, sd))
+    i = numpy.arange(float(MAX_FRAGMENT_LENGTH))
+    w = numpy.exp(-0.5 * ((i - mean) / sd) ** 2)
+    w[0] = 0
+    total = w.sum()
+    if not total > 0:
+        raise ValueError('the fragment-length model (%r, %r) has no weight on any length 1..%d'
+                         % (mean, sd, MAX_FRAGMENT_LENGTH - 1))
+    return w / total
+
+
+def length_model_weights(length_model):
+    """None | (mean, sd) -> (None | (float mean, float sd), None | the model's weights)"""
+    if length_model is None:
+        return None, None
+    mean, sd = length_model
+    weights = numpy.ascontiguousarray(fragment_length_weights(mean, sd), dtype='f8')
+    return (float(mean), float(sd)), weights
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
                  'fragment_length_frequencies', 'effective_lengths',
-                 'class_offsets', 'class_targets', '_map_result']
+                 'class_offsets', 'class_targets', '_map_result', 'length_model']
 
     def __init__(self, aligned, unaligned, total, class_map, class_count,
                  fragment_length_frequencies, effective_lengths,
-                 class_offsets=None, class_targets=None, map_result=None):
+                 class_offsets=None, class_targets=None, map_result=None, length_model=None):
         self.aligned = aligned
         self.unaligned = unaligned
         self.total = total
@@ -60,6 +88,7 @@ class SummarizedResult:
         self.class_offsets = class_offsets
         self.class_targets = class_targets
         self._map_result = map_result
+        self.length_model = length_model      # (mean, sd) when the effective lengths come from a model
 
     def detach(self):
         """Let go of the MapResult the summary came from (its table is in the summary): the mapper's
@@ -71,13 +100,17 @@ class SummarizedResult:
 class MapResult:
     """A mapping result collection with a lock (seekmer/mapper.py:40-145)."""
 
-    def __init__(self, index, readmap=None, device=0, keep_spans=False, strand=None):
+    def __init__(self, index, readmap=None, device=0, keep_spans=False, strand=None, length_model=None):
         """keep_spans: also store every unit's MappedSpan (begin, end, anchor) for
         ReadMapper.last_batch -- parity tests and diagnostics; inference does not read them.
         strand: None (unstranded), 'fr' (--fr-stranded: mate 1 in the transcript's orientation) or
         'rf' (--rf-stranded: mate 1 antisense); every mapped unit keeps only the targets of that
-        orientation (skm_mapper_set_strand)."""
+        orientation (skm_mapper_set_strand).
+        length_model: None, or (mean, sd) of a fragment-length model (fragment_length_weights): the
+        effective lengths then come from it, here and in infer.quantify_resident
+        (skm_mapper_set_length_weights); the histogram is counted and reported as ever."""
         mode = strand_mode(strand)
+        model, weights = length_model_weights(length_model)
         self.lock = threading.Lock()
         self.index = index
         self.readmap = readmap
@@ -92,6 +125,16 @@ class MapResult:
         self.strand = strand
         if mode != _native.SKM_STRAND_NONE:
             _native.check(_native.hip().skm_mapper_set_strand(self._handle, mode))
+        self.length_model, self._length_weights = None, None
+        if model is not None:
+            self.set_length_model(model)
+
+    def set_length_model(self, length_model):
+        """(mean, sd), or None for the observed histogram again; it affects later calls only."""
+        model, weights = length_model_weights(length_model)
+        _native.check(_native.hip().skm_mapper_set_length_weights(
+            self._handle, _native.ptr(weights, _native.c_f64p) if weights is not None else None))
+        self.length_model, self._length_weights = model, weights
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
@@ -222,6 +265,7 @@ class MapResult:
             class_offsets=offsets,
             class_targets=targets,
             map_result=self,
+            length_model=self.length_model,
         )
 
     def merge_fragment_lengths(self, fragment_length_counts):
@@ -254,6 +298,8 @@ class MapResult:
 
     def _effective_lengths(self, fld):
         length = self.transcript_lengths
+        if self._length_weights is not None:
+            return _effective_lengths_weights(length, self._length_weights, self.device)[0]
         out = numpy.zeros(length.shape, dtype='f8')
         _native.check(_native.hip().skm_effective_lengths(
             self.device, _native.ptr(numpy.ascontiguousarray(fld, dtype=numpy.int64), _native.c_i64p),
@@ -262,7 +308,9 @@ class MapResult:
 
     @property
     def effective_lengths(self):
-        """seekmer/mapper.py:134-141 (computed on the GPU)"""
+        """seekmer/mapper.py:134-141 (computed on the GPU); with a length model, from its weights"""
+        if self._length_weights is not None:
+            return self._effective_lengths(None)
         return self._effective_lengths(self.fragment_length_counts)
 
     def clear(self):
@@ -434,11 +482,12 @@ def _drain_worker(mapper, reads_queue, errors):
             pass
 
 
-def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0, strand=None):
+def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0, strand=None, length_model=None):
     """Map reads (seekmer/mapper.py:148-193).  Unlike the reference's CPU workers the device
     calls can fail; a worker's exception is re-raised here once every thread has stopped,
-    instead of being lost with its thread.  strand: None, 'fr' or 'rf' (MapResult)."""
-    map_result = _new_result(index, strand, readmap=readmap, device=device)
+    instead of being lost with its thread.  strand: None, 'fr' or 'rf'; length_model: None or
+    (mean, sd) (MapResult)."""
+    map_result = _new_result(index, strand, length_model, readmap=readmap, device=device)
     try:
         if debug or job_count <= 1 or isinstance(read_feeder, PackedReadFeeder):
             # (a packed feeder parses with its own threads and is drained natively: the GIL is not held)
@@ -470,21 +519,22 @@ def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device
     return map_result
 
 
-def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0, strand=None):
+def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0, strand=None, length_model=None):
     """Map reads for multiple samples (seekmer/mapper.py:196-234); a failed sample raises.
-    strand: None, 'fr' or 'rf' for every sample (MapResult)."""
+    strand: None, 'fr' or 'rf', length_model: None or (mean, sd), for every sample (MapResult)."""
     strand_mode(strand)
+    length_model_weights(length_model)
     map_results = []
     if debug:
         for read_feeder in read_feeders:
-            result = _new_result(index, strand, device=device)
+            result = _new_result(index, strand, length_model, device=device)
             map_results.append(result)
             ReadMapper(index, result)(read_feeder)
     else:
         pool = multiprocessing.pool.ThreadPool(job_count)
         pending = []
         for read_feeder in read_feeders:
-            result = _new_result(index, strand, device=device)
+            result = _new_result(index, strand, length_model, device=device)
             map_results.append(result)
             pending.append(pool.apply_async(_map, args=(index, result, read_feeder)))
         pool.close()
@@ -494,10 +544,13 @@ def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0
     return map_results
 
 
-def _new_result(index, strand, **kwargs):
-    """MapResult(index, **kwargs, strand=strand); unstranded, the call is the one of before."""
+def _new_result(index, strand, length_model=None, **kwargs):
+    """MapResult(index, **kwargs, strand=strand, length_model=length_model); unstranded and without
+    a model, the call is the one of before."""
     if strand is not None:
         kwargs['strand'] = strand
+    if length_model is not None:
+        kwargs['length_model'] = length_model
     return MapResult(index, **kwargs)
 
 
@@ -580,6 +633,17 @@ def _effective_lengths_many(lengths, fld, device):
     return out
 
 
+def _effective_lengths_weights(lengths, weights, device):
+    """The same rule with p given (fragment_length_weights) instead of counted: weights f8[2000] or
+    f8[n, 2000] -> f8[n, n_tx] in one native call."""
+    weights = numpy.ascontiguousarray(weights, dtype='f8').reshape(-1, MAX_FRAGMENT_LENGTH)
+    out = numpy.zeros((weights.shape[0], lengths.size), dtype='f8')
+    _native.check(_native.hip().skm_effective_lengths_weights(
+        device, weights.shape[0], _native.ptr(weights, _native.c_f64p), _native.ptr(lengths, _native.c_f64p),
+        lengths.size, _native.ptr(out, _native.c_f64p)))
+    return out
+
+
 def harmonic_mean_fragment_lengths(counts):
     """MapResult.harmonic_mean_fragment_length (seekmer/mapper.py:117-132) for every row of
     counts[n, 2000]: a list of n numbers, 0 for an empty histogram."""
@@ -608,13 +672,16 @@ class SampleSet:
     every launch from the units' spans: sample_fragment_length_counts, and every summary then carries
     its own sample's histogram and effective lengths, those of a MapResult fed the sample alone -- what
     an ordinary `infer` of the sample needs.  There is no readmap.  ``strand`` (None, 'fr', 'rf')
-    applies to every sample.
+    applies to every sample.  So does ``length_model`` (None, or (mean, sd): fragment_length_weights):
+    with one, every sample's effective lengths are the model's -- one row, made once, in summarize()
+    and in quantify() -- whatever the histograms hold; those are counted and reported as ever.
 
     Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
     where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
 
-    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False):
+    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None):
         mode = strand_mode(strand)
+        self.length_model, self._length_weights = length_model_weights(length_model)
         self.index = index
         self.paired = bool(paired)
         self.device = device
@@ -627,6 +694,9 @@ class SampleSet:
             _native.check(_native.hip().skm_sample_set_set_strand(self._handle, mode))
         if self.per_sample_lengths:
             _native.check(_native.hip().skm_sample_set_keep_histograms(self._handle, 1))
+        if self._length_weights is not None:
+            _native.check(_native.hip().skm_sample_set_set_length_weights(
+                self._handle, _native.ptr(self._length_weights, _native.c_f64p)))
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
@@ -783,7 +853,8 @@ class SampleSet:
         (one shared, read-only pair of arrays), i.e. what the samples' MapResults hold after
         impute.pool_fragment_lengths.  With per_sample_lengths item i carries sample i's own histogram
         and effective lengths: read-only rows of two arrays, the lengths of all samples made in one
-        device call."""
+        device call.  With a length model the histograms are those, and every item carries the model's
+        effective lengths: one shared row from one launch."""
         sizes = self.sizes()
         tables = self.export()
         lengths = numpy.ascontiguousarray(self.index.transcripts['length'], dtype='f8')
@@ -791,18 +862,24 @@ class SampleSet:
             flds = self.sample_fragment_length_counts[:len(sizes)]
             if len(flds) != len(sizes):
                 raise RuntimeError('samples were added while the set was summarized')
-            effectives = _effective_lengths_many(lengths, flds, self.device)
             flds.setflags(write=False)
-            effectives.setflags(write=False)
         else:
             fld = self.fragment_length_counts
-            effective = _effective_lengths(lengths, fld, self.device)
             fld.setflags(write=False)
+            flds = [fld] * len(sizes)
+        if self._length_weights is not None:
+            effective = _effective_lengths_weights(lengths, self._length_weights, self.device)[0]
             effective.setflags(write=False)
+            effectives = [effective] * len(sizes)
+        elif self.per_sample_lengths:
+            effectives = _effective_lengths_many(lengths, flds, self.device)
+            effectives.setflags(write=False)
+        else:
+            effective = _effective_lengths(lengths, fld, self.device)
+            effective.setflags(write=False)
+            effectives = [effective] * len(sizes)
         summaries = []
         for i, ((offsets, targets, counts, _), (_, _, unaligned, _)) in enumerate(zip(tables, sizes)):
-            if self.per_sample_lengths:
-                fld, effective = flds[i], effectives[i]
             if targets.size:
                 class_ids = numpy.repeat(numpy.arange(counts.size, dtype=numpy.int64), numpy.diff(offsets))
                 class_map = numpy.vstack([class_ids, targets.astype(numpy.int64)])
@@ -812,17 +889,19 @@ class SampleSet:
             aligned = class_count.sum()
             summaries.append(SummarizedResult(
                 aligned=int(aligned), unaligned=int(unaligned), total=int(aligned + unaligned), class_map=class_map,
-                class_count=class_count, fragment_length_frequencies=fld, effective_lengths=effective,
-                class_offsets=offsets, class_targets=targets))
+                class_count=class_count, fragment_length_frequencies=flds[i], effective_lengths=effectives[i],
+                class_offsets=offsets, class_targets=targets, length_model=self.length_model))
         return summaries
 
 
-def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_sample_lengths=False):
+def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_sample_lengths=False,
+                   length_model=None):
     """map_multiple_samples for many small samples (single cells): sample i = read_feeders[i], all of
     them mapped through ONE SampleSet in shared launches.  Each of `job_count` threads takes a sample
     at a time, parses its files completely and adds it; results do not depend on the thread count.
     The feeders must agree on paired / single-ended.  strand: None, 'fr' or 'rf' for every sample.
     per_sample_lengths: every sample keeps its own fragment-length histogram (SampleSet).
+    length_model: None or (mean, sd), for every sample (SampleSet).
     A failed sample raises."""
     strand_mode(strand)
     read_feeders = list(read_feeders)
@@ -833,7 +912,8 @@ def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_
     layouts = {bool(feeder.paired) for feeder in read_feeders}     # (every feeder of common says which it is)
     if len(layouts) != 1:
         raise ValueError('paired and single-ended samples in one set')
-    sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand, per_sample_lengths=per_sample_lengths)
+    sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand, per_sample_lengths=per_sample_lengths,
+                           length_model=length_model)
     if job_count == 1:
         for sample, read_feeder in enumerate(read_feeders):
             sample_set.add_sample(sample, read_feeder)
