@@ -11,8 +11,8 @@
  *
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
- *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_comm_*,
- *                          skm_device_*)
+ *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_bias_*,
+ *                          skm_comm_*, skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
  *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_synth_*)
  */
@@ -115,6 +115,19 @@ int skm_index_info(const skm_index *index, int64_t info[8]);
  * the table, and a run of the read's k-mers shares a minimizer.  Results identical by
  * construction (no false negatives); SKM_NO_SIGNATURES=1 leaves it out. */
 int skm_index_layout(const skm_index *index, int64_t layout[8]);
+/* The transcripts' own sequences, for the sequence-bias correction (skm_bias_correct): rebuilt in HBM from
+ * the index alone -- a target row (e, o) of a contig of length L with pooled bases S says T_e[o .. o + L) = S
+ * for e >= 0 and T_~e[o + 25 - L .. o + 25) = revcomp(S) for e < 0 -- as 2-bit codes plus one "known" bit per
+ * base; a base no row covers (a transcript shorter than 25, a k-mer the builder dropped) is unknown.
+ * lengths[n_tx]: the transcript lengths (whole numbers below 2^31).  Built once per handle: a second call
+ * with the same n_tx does nothing (another n_tx: SKM_ERR_STATE).  SKM_ERR_ARG when a row names a transcript
+ * at or above n_tx or leaves its length.  skm_index_create keeps the host rows the pool is made from until
+ * then; a handle that is never asked holds nothing of it on the device. */
+int skm_index_build_transcripts(skm_index *index, const double *lengths, int64_t n_tx);
+/* A download of the pool, for tests: bases_out[sum of lengths] = the transcripts back to back as 'ACGT'
+ * ('N' where unknown), known_out[sum of lengths] = 1 / 0; either may be NULL.  SKM_ERR_STATE before
+ * skm_index_build_transcripts. */
+int skm_index_transcript_bases(skm_index *index, char *bases_out, uint8_t *known_out);
 
 /* ------------------------------------------------------------------ mapper
  * One handle = ReadMapper + the MapResult it feeds
@@ -241,6 +254,19 @@ int skm_mapper_set_strand(skm_mapper *mapper, int mode);
  * affects only later quantification calls; the histogram is counted and exported as ever, and
  * skm_mapper_reset / skm_mapper_clear leave the model in place. */
 int skm_mapper_set_length_weights(skm_mapper *mapper, const double *p);
+/* Sequence bias (--bias): a mapper asked to (enable != 0) counts, after every batch it maps, the hexamer
+ * each aligned unit starts with -- the first six bases of mate 1 or of the single read, first base in the
+ * top two bits of the 12-bit code; aligned = the unit's tuple is not empty after the strand filter; a unit
+ * with a base among the six that is not an upper-case A, C, G or T is not counted.  The counts are exact
+ * integers and do not depend on how the reads were cut into batches or pieces.  They are zeroed and kept
+ * exactly where the fragment-length histogram is (skm_mapper_reset zeroes, skm_mapper_clear keeps), and
+ * skm_mapper_merge* and skm_mapper_exchange_tables add no observations.  The setting survives
+ * skm_mapper_reset and skm_mapper_clear and can only change while the handle holds no units and has
+ * nothing queued, as skm_mapper_set_strand (SKM_ERR_STATE otherwise).  The map kernel is the same either way:
+ * the counting is a kernel of its own over the batch's records.
+ * skm_mapper_bias_observed: out[4096]; SKM_ERR_STATE on a mapper that does not count. */
+int skm_mapper_set_bias(skm_mapper *mapper, int enable);
+int skm_mapper_bias_observed(skm_mapper *mapper, int64_t out[4096]);
 /* Counter sizes (MapResult.summarize, seekmer/mapper.py:77-104):
  * summary[0]=C classes [1]=M (class,target) rows [2]=unaligned [3]=total units */
 int skm_mapper_summary(skm_mapper *mapper, int64_t summary[4]);
@@ -423,6 +449,27 @@ int skm_effective_lengths_many(int device, int64_t n, const int64_t *fld, const 
  * a NULL array or a negative size; n == 0 or n_tx == 0 does nothing. */
 int skm_effective_lengths_weights(int device, int64_t n, const double *p, const double *lengths,
                                   int64_t n_tx, double *out);
+
+/* The sequence-bias correction of the effective lengths ("Sequence bias"), on the
+ * pool of skm_index_build_transcripts.  strand: SKM_STRAND_*, observed[4096] (skm_mapper_bias_observed),
+ * tpm[n_tx] the first pass's abundances, eff[n_tx] its effective lengths.  The windows of transcript t are
+ * the positions p <= len_t - 6 with six known bases, h+ their hexamer and h- its reverse complement, the
+ * shares (s+, s-) = (1/2, 1/2), (1, 0) for FR, (0, 1) for RF:
+ *   E[h] = sum_t tpm_t sum_p (s+ [h+ = h] + s- [h- = h])
+ *   b[h] = ((O[h] + 1) / (sum O + 4096)) / (E[h] / sum E) where E[h] > 0, 1 elsewhere; all 1 when sum O = 0
+ *          or sum E = 0
+ *   eff_out[t] = eff[t] * (1 / n_t) sum_p (s+ b[h+] + s- b[h-]), eff[t] for a transcript without windows
+ * expected_out[4096] and b_out[4096] are optional.  E is accumulated in 96-bit fixed point (tpm_t scaled
+ * by 2^94 / sum_t tpm_t n_t and rounded, three 32-bit limbs summed apart) with integer atomics and every
+ * transcript's sum over its windows runs in a fixed order, so all three outputs are the same bits on every run and for every grid size
+ * (SKM_BIAS_BLOCKS in the environment caps the grids: tests).  SKM_ERR_ARG, before any device work, for NULL
+ * arrays, a negative size, a non-finite or negative tpm, a negative count or an unknown strand mode;
+ * SKM_ERR_STATE when the pool has not been built; SKM_ERR_ARG when n_tx is not the pool's.
+ * This call and skm_index_build_transcripts run once per sample and once per index: they allocate their
+ * scratch with hipMalloc and work on the default stream with blocking copies, which also wait for work
+ * queued on this process's other blocking streams; they are not meant for a loop. */
+int skm_bias_correct(skm_index *index, int strand, const int64_t *observed, const double *tpm, const double *eff,
+                     int64_t n_tx, double *expected_out, double *b_out, double *eff_out);
 
 /* Device-resident class table for infer.em / infer.quantify
  * (seekmer/infer.py:88-168).  class_counts are f8 as in

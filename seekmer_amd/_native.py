@@ -71,6 +71,8 @@ HIP_SYMBOLS = {
     'skm_index_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_index_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_index_layout': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_index_build_transcripts': (ctypes.c_int, [ctypes.c_void_p, c_f64p, c_i64]),
+    'skm_index_transcript_bases': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'skm_mapper_create': (ctypes.c_int, [ctypes.c_void_p, c_void_pp]),
     'skm_mapper_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_mapper_map_batch': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64p, c_i64,
@@ -92,6 +94,8 @@ HIP_SYMBOLS = {
     'skm_mapper_keep_spans': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_set_length_weights': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
+    'skm_mapper_set_bias': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_mapper_bias_observed': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_mapper_summary': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_mapper_export': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i64p, c_i64p, c_i64p]),
     'skm_mapper_merge': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
@@ -106,6 +110,7 @@ HIP_SYMBOLS = {
     'skm_effective_lengths': (ctypes.c_int, [ctypes.c_int, c_i64p, c_f64p, c_i64, c_f64p]),
     'skm_effective_lengths_many': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_f64p, c_i64, c_f64p]),
     'skm_effective_lengths_weights': (ctypes.c_int, [ctypes.c_int, c_i64, c_f64p, c_f64p, c_i64, c_f64p]),
+    'skm_bias_correct': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64p, c_f64p, c_f64p, c_i64, c_f64p, c_f64p, c_f64p]),
     'skm_sample_set_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp]),
     'skm_sample_set_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_sample_set_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -4,6 +4,7 @@
 #include "../../include/seekmer_hip.h"
 #include "skm_kernels.h"
 #include "skm_pool.h"
+#include "skm_bias.h"
 
 #include <dlfcn.h>
 #include <algorithm>
@@ -117,6 +118,7 @@ public:
     H operator->() const { return h_; }
     H *out() { reset(); return &h_; }          // for the call that acquires a new one
     void reset(H h = nullptr) { if (h_) (void)Free(h_); h_ = h; }
+    H release() { return std::exchange(h_, nullptr); }     // hand the resource to another owner
 
 private:
     H h_ = nullptr;
@@ -169,6 +171,16 @@ struct skm_index {
     // caller's, the device copy goes with the last one (garbage collectors finalise a mapper and
     // its index in any order; a mapper destroyed after its index used to read freed memory here)
     std::atomic<int> holders{1};
+    // ---- the transcript pool of the sequence-bias correction (skm_bias.h), built by
+    // skm_index_build_transcripts from the host rows below, which are dropped once it stands (all under pool_mu)
+    std::mutex pool_mu;
+    std::vector<PoolContig> pool_contigs;
+    std::vector<Coord> pool_targets;
+    bool pool_built = false;
+    TxPool pool{};
+    DevMem pool_codes, pool_known, pool_tx_word, pool_tx_len, pool_tx_windows;
+    std::vector<int64_t> pool_tx_base;        // [n_tx + 1] first base of every transcript in a download
+    std::vector<int32_t> pool_windows;        // [n_tx] n_t, host copy
 };
 
 struct skm_mapper {
@@ -198,6 +210,8 @@ struct skm_mapper {
     DBuf<uint64_t> rec_key;
     bool keep_spans = false, last_spans = false;   // spans wanted / written by the last batch
     int strand = SKM_STRAND_NONE;                  // skm_mapper_set_strand (under mu)
+    bool bias = false;                             // skm_mapper_set_bias (under mu): count the aligned units' first hexamers
+    DBuf<unsigned long long> bias_observed;        // [4096], zeroed where the histogram is
     // skm_mapper_set_length_weights (under mu): p[2000] of a fragment-length model; while it is in use the
     // quantification calls take the effective lengths from it and not from the histogram
     DBuf<double> length_weights;
@@ -802,6 +816,14 @@ extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *
             }
         }
     }
+    {   // what the transcript pool is rebuilt from, should a caller ask for it (skm_index_build_transcripts)
+        const Coord *ht = (const Coord *)targets;
+        ix->pool_targets.assign(ht, ht + n_targets);
+        ix->pool_contigs.resize((size_t)n_contigs);
+        for (int64_t c = 0; c < n_contigs; ++c)
+            ix->pool_contigs[(size_t)c] = PoolContig{hc[c].target_offset, (int32_t)hc[c].offset, (int32_t)hc[c].length,
+                                                     (int32_t)hc[c].target_length, 0};
+    }
     *out = ix.release();                                  // (the caller's handle from here on)
     return SKM_OK;
 }
@@ -832,6 +854,163 @@ extern "C" int skm_index_layout(const skm_index *ix, int64_t layout[8])
     if (!ix || !layout) return fail(SKM_ERR_ARG, "NULL argument");
     for (int i = 0; i < 8; ++i) layout[i] = ix->layout[i];
     return SKM_OK;
+}
+
+// ---- the transcript pool and the sequence-bias correction (skm_bias.hip) ----------------------------
+extern "C" int skm_index_build_transcripts(skm_index *ix, const double *lengths, int64_t n_tx)
+{
+    if (!ix || n_tx < 0 || (n_tx && !lengths)) return fail(SKM_ERR_ARG, "bad argument");
+    for (int64_t t = 0; t < n_tx; ++t)
+        if (!(lengths[t] >= 0.0 && lengths[t] < 2147483648.0) || lengths[t] != std::floor(lengths[t]))
+            return fail(SKM_ERR_ARG, "transcript %lld: its length is not a whole number below 2^31", (long long)t);
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    if (ix->pool_built) {
+        if (ix->pool.n_tx == n_tx) return SKM_OK;
+        return fail(SKM_ERR_STATE, "the transcript pool of this index holds %lld transcripts, not %lld",
+                    (long long)ix->pool.n_tx, (long long)n_tx);
+    }
+    SKM_TRY(set_device(ix->device));
+    std::vector<int64_t> tx_word((size_t)n_tx + 1, 0), tx_base((size_t)n_tx + 1, 0);
+    std::vector<int32_t> tx_len((size_t)n_tx, 0);
+    for (int64_t t = 0; t < n_tx; ++t) {
+        tx_len[(size_t)t] = (int32_t)lengths[t];
+        tx_word[(size_t)t + 1] = tx_word[(size_t)t] + (tx_len[(size_t)t] + 31) / 32;      // every transcript starts a word
+        tx_base[(size_t)t + 1] = tx_base[(size_t)t] + tx_len[(size_t)t];
+    }
+    const int64_t n_words = tx_word[(size_t)n_tx];
+    const int64_t n_contigs = (int64_t)ix->pool_contigs.size(), n_targets = (int64_t)ix->pool_targets.size();
+    DevMem codes, known, d_word, d_len, d_windows, d_contigs, d_targets, d_bad;
+    HIP_TRY(hipMalloc(codes.out(), (size_t)(n_words + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(known.out(), (size_t)(n_words + 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(d_word.out(), (size_t)(n_tx + 1) * sizeof(int64_t)));
+    HIP_TRY(hipMalloc(d_len.out(), (size_t)(n_tx + 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(d_windows.out(), (size_t)(n_tx + 1) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(d_contigs.out(), (size_t)(n_contigs + 1) * sizeof(PoolContig)));
+    HIP_TRY(hipMalloc(d_targets.out(), (size_t)(n_targets + 1) * sizeof(Coord)));
+    HIP_TRY(hipMalloc(d_bad.out(), sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(codes, 0, (size_t)(n_words + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipMemset(known, 0, (size_t)(n_words + 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(d_bad, 0, sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpy(d_word, tx_word.data(), (size_t)(n_tx + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (n_tx) HIP_TRY(hipMemcpy(d_len, tx_len.data(), (size_t)n_tx * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n_contigs)
+        HIP_TRY(hipMemcpy(d_contigs, ix->pool_contigs.data(), (size_t)n_contigs * sizeof(PoolContig), hipMemcpyHostToDevice));
+    if (n_targets)
+        HIP_TRY(hipMemcpy(d_targets, ix->pool_targets.data(), (size_t)n_targets * sizeof(Coord), hipMemcpyHostToDevice));
+    TxPool pool{(uint64_t *)codes.get(), (uint32_t *)known.get(), (const int64_t *)d_word.get(),
+                (const int32_t *)d_len.get(), n_tx, n_words};
+    launch_bias_pool_scatter(ix->d.seq2, (const PoolContig *)d_contigs.get(), n_contigs, (const Coord *)d_targets.get(), pool,
+                             (unsigned long long *)d_bad.get(), nullptr);
+    launch_bias_windows(pool, (int32_t *)d_windows.get(), nullptr);
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    std::vector<int32_t> windows((size_t)n_tx, 0);
+    HIP_TRY(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
+    if (n_tx) HIP_TRY(hipMemcpy(windows.data(), d_windows, (size_t)n_tx * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (bad)
+        return fail(SKM_ERR_ARG, "%llu target rows name a transcript at or above %lld or leave its length: these are not the "
+                                 "lengths of this index", bad, (long long)n_tx);
+    ix->pool = pool;
+    ix->pool_codes.reset(codes.release()); ix->pool_known.reset(known.release()); ix->pool_tx_word.reset(d_word.release());
+    ix->pool_tx_len.reset(d_len.release()); ix->pool_tx_windows.reset(d_windows.release());
+    ix->pool_tx_base = std::move(tx_base);
+    ix->pool_windows = std::move(windows);
+    ix->pool_built = true;
+    std::vector<PoolContig>().swap(ix->pool_contigs);
+    std::vector<Coord>().swap(ix->pool_targets);
+    return SKM_OK;
+}
+
+extern "C" int skm_index_transcript_bases(skm_index *ix, char *bases_out, uint8_t *known_out)
+{
+    if (!ix) return fail(SKM_ERR_ARG, "NULL index");
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    if (!ix->pool_built) return fail(SKM_ERR_STATE, "the transcript pool has not been built: call skm_index_build_transcripts");
+    SKM_TRY(set_device(ix->device));
+    const int64_t n_tx = ix->pool.n_tx, n_words = ix->pool.n_words;
+    std::vector<uint64_t> codes((size_t)n_words + 1);
+    std::vector<uint32_t> known((size_t)n_words + 1);
+    std::vector<int64_t> tx_word((size_t)n_tx + 1);
+    HIP_TRY(hipMemcpy(codes.data(), ix->pool_codes, (size_t)(n_words + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(known.data(), ix->pool_known, (size_t)(n_words + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tx_word.data(), ix->pool_tx_word, (size_t)(n_tx + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int64_t t = 0; t < n_tx; ++t) {
+        const int64_t first = ix->pool_tx_base[(size_t)t], len = ix->pool_tx_base[(size_t)t + 1] - first;
+        for (int64_t p = 0; p < len; ++p) {
+            const size_t w = (size_t)(tx_word[(size_t)t] + (p >> 5));
+            const bool is_known = (known[w] >> (31 - (p & 31))) & 1u;
+            if (bases_out) bases_out[first + p] = is_known ? "ACGT"[(codes[w] >> (62 - 2 * (p & 31))) & 3u] : 'N';
+            if (known_out) known_out[first + p] = is_known ? 1 : 0;
+        }
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_bias_correct(skm_index *ix, int strand, const int64_t *observed, const double *tpm, const double *eff,
+                                int64_t n_tx, double *expected_out, double *b_out, double *eff_out)
+{
+    if (!ix || !observed || n_tx < 0 || (n_tx && (!tpm || !eff || !eff_out))) return fail(SKM_ERR_ARG, "NULL array or negative size");
+    if (strand != SKM_STRAND_NONE && strand != SKM_STRAND_FR && strand != SKM_STRAND_RF)
+        return fail(SKM_ERR_ARG, "unknown strand mode %d", strand);
+    for (int i = 0; i < BIAS_BINS; ++i)
+        if (observed[i] < 0) return fail(SKM_ERR_ARG, "observed count %d is negative", i);
+    for (int64_t t = 0; t < n_tx; ++t)
+        if (!(tpm[t] >= 0.0) || std::isinf(tpm[t]))
+            return fail(SKM_ERR_ARG, "the abundance of transcript %lld is negative or not finite", (long long)t);
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    if (!ix->pool_built) return fail(SKM_ERR_STATE, "the transcript pool has not been built: call skm_index_build_transcripts");
+    if (n_tx != ix->pool.n_tx)
+        return fail(SKM_ERR_ARG, "%lld transcripts, but the pool holds %lld", (long long)n_tx, (long long)ix->pool.n_tx);
+    SKM_TRY(set_device(ix->device));
+    // E in 96-bit fixed point: W_t = round(tpm_t * 2^94 / sum_t tpm_t n_t) < 2^95, handed to the device as three
+    // 32-bit limbs that are summed apart (a limb's sum stays below 2^63 for 2^31 additions: no carries)
+    double total = 0.0;
+    for (int64_t t = 0; t < n_tx; ++t) total += tpm[t] * (double)ix->pool_windows[(size_t)t];
+    const double fixed_one = 0x1p94;
+    if (total != 0.0 && (std::isinf(total) || std::isinf(fixed_one / total)))
+        return fail(SKM_ERR_ARG, "the abundances are too large or too small to scale");
+    std::vector<unsigned long long> weight((size_t)n_tx * BIAS_LIMBS + 1, 0);      // [limb][n_tx]
+    if (total > 0.0)
+        for (int64_t t = 0; t < n_tx; ++t) {
+            if (ix->pool_windows[(size_t)t] == 0) continue;            // (no window: its weight is never added, whatever it is)
+            const double w = tpm[t] * (fixed_one / total);             // (a double at or above 2^52 is a whole number)
+            // clamped as a double, before the conversion: one transcript may hold everything with the scale rounded up
+            unsigned __int128 fixed = w >= 0x1p95 ? ((unsigned __int128)1 << 95) - 1
+                                                  : (unsigned __int128)(w < 0x1p52 ? w + 0.5 : w);
+            for (int k = 0; k < BIAS_LIMBS; ++k) weight[(size_t)(k * n_tx + t)] = (unsigned long long)(fixed >> (32 * k)) & 0xffffffffULL;
+        }
+    const double share = strand == SKM_STRAND_NONE ? 0.5 : 1.0;
+    int blocks = ix->cu_count * 4;
+    if (const char *v = getenv("SKM_BIAS_BLOCKS")) {                 // test hook: the grid of the two kernels over the pool
+        const long long n = atoll(v);
+        if (n < 1) return fail(SKM_ERR_ARG, "SKM_BIAS_BLOCKS must be at least 1, not '%s'", v);
+        blocks = (int)std::min<long long>(n, blocks);
+    }
+    DevMem d_weight, d_observed, d_expected, d_expected_out, d_b, d_eff, d_eff_out;
+    HIP_TRY(hipMalloc(d_weight.out(), (size_t)(n_tx * BIAS_LIMBS + 1) * 8));
+    HIP_TRY(hipMalloc(d_eff.out(), (size_t)(n_tx + 1) * 8));
+    HIP_TRY(hipMalloc(d_eff_out.out(), (size_t)(n_tx + 1) * 8));
+    HIP_TRY(hipMalloc(d_observed.out(), BIAS_BINS * 8));
+    HIP_TRY(hipMalloc(d_expected.out(), BIAS_LIMBS * BIAS_BINS * 8));
+    HIP_TRY(hipMalloc(d_expected_out.out(), BIAS_BINS * 8));
+    HIP_TRY(hipMalloc(d_b.out(), BIAS_BINS * 8));
+    HIP_TRY(hipMemset(d_expected, 0, BIAS_LIMBS * BIAS_BINS * 8));
+    HIP_TRY(hipMemcpy(d_observed, observed, BIAS_BINS * 8, hipMemcpyHostToDevice));
+    if (n_tx) {
+        HIP_TRY(hipMemcpy(d_weight, weight.data(), (size_t)n_tx * BIAS_LIMBS * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_eff, eff, (size_t)n_tx * 8, hipMemcpyHostToDevice));
+    }
+    launch_bias_expected(ix->pool, (const unsigned long long *)d_weight.get(), strand, (unsigned long long *)d_expected.get(),
+                         blocks, nullptr);
+    launch_bias_weights((const unsigned long long *)d_observed.get(), (const unsigned long long *)d_expected.get(),
+                        share * (total / fixed_one), (double *)d_expected_out.get(), (double *)d_b.get(), nullptr);
+    launch_bias_lengths(ix->pool, (const int32_t *)ix->pool_tx_windows.get(), (const double *)d_b.get(), strand,
+                        (const double *)d_eff.get(), (double *)d_eff_out.get(), blocks, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (expected_out) HIP_TRY(hipMemcpy(expected_out, d_expected_out, BIAS_BINS * 8, hipMemcpyDeviceToHost));
+    if (b_out) HIP_TRY(hipMemcpy(b_out, d_b, BIAS_BINS * 8, hipMemcpyDeviceToHost));
+    if (n_tx) HIP_TRY(hipMemcpy(eff_out, d_eff_out, (size_t)n_tx * 8, hipMemcpyDeviceToHost));
+    return SKM_OK;                                                   // (the copies home have waited for the kernels)
 }
 
 // ------------------------------------------------------------------- mapper
@@ -1061,6 +1240,11 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     // launched unstranded)
     if (m->strand != SKM_STRAND_NONE) {
         launch_strand_filter(b, m->strand, m->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (m->bias) {             // --bias: the first hexamers of the units that are still aligned
+        launch_bias_observed(m->records.p, record_words, words, paired, m->rec_tuple.p, m->rec_unit.p, n_units,
+                             m->bias_observed.p, m->stream);
         HIP_TRY(hipGetLastError());
     }
     if (salt) {
@@ -1917,6 +2101,40 @@ extern "C" int skm_mapper_set_strand(skm_mapper *m, int mode)
     return SKM_OK;
 }
 
+extern "C" int skm_mapper_set_bias(skm_mapper *m, int enable)
+{
+    if (!m) return fail(SKM_ERR_ARG, "NULL mapper");
+    (void)wait_jobs(m, 0, false);
+    bool queued;
+    {
+        std::lock_guard<std::mutex> hold(m->q_mu);
+        queued = !m->jobs.empty() || m->packed_busy || !m->pending[0].empty() || !m->pending[1].empty();
+    }
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (queued || m->units_done != 0)
+        return fail(SKM_ERR_STATE, "hexamer counting can only change on an empty mapper (new, or after "
+                                   "skm_mapper_reset / skm_mapper_clear)");
+    if (enable) {
+        SKM_TRY(set_device(m->ix->device));
+        SKM_TRY(m->bias_observed.ensure(BIAS_BINS));
+        HIP_TRY(hipMemsetAsync(m->bias_observed.p, 0, BIAS_BINS * sizeof(unsigned long long), m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    m->bias = enable != 0;
+    return SKM_OK;
+}
+
+extern "C" int skm_mapper_bias_observed(skm_mapper *m, int64_t out[4096])
+{
+    if (!m || !out) return fail(SKM_ERR_ARG, "NULL argument");
+    SKM_TRY(wait_jobs(m, 0, false));           // queued host batches first
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->bias) return fail(SKM_ERR_STATE, "this mapper does not count hexamers: call skm_mapper_set_bias(mapper, 1) before mapping");
+    SKM_TRY(set_device(m->ix->device));
+    HIP_TRY(hipMemcpy(out, m->bias_observed.p, BIAS_BINS * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return SKM_OK;
+}
+
 namespace {
 
 // the weights of a fragment-length model: every one finite and >= 0 (checked on the host, before any device work)
@@ -2176,6 +2394,7 @@ extern "C" int skm_mapper_reset(skm_mapper *m)
     std::lock_guard<std::mutex> lock(m->mu);
     SKM_TRY(set_device(m->ix->device));
     SKM_TRY(table_reset(m, m->t.slot_mask + 1));
+    if (m->bias) HIP_TRY(hipMemsetAsync(m->bias_observed.p, 0, BIAS_BINS * sizeof(unsigned long long), m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));         // (readers of the table use streams of their own)
     m->last_units = 0;
     m->last_ids = 0;

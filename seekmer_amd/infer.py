@@ -18,7 +18,7 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'run_many', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+__all__ = ['run', 'run_many', 'bias_correct', 'bias_pass', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
            'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
@@ -28,7 +28,8 @@ X_FLOOR = 1e-8          # seekmer/infer.py:160
 
 
 def run(index_path, output_path, fastq_paths, job_count, save_readmap,
-        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, length_model=None, **__):
+        single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, length_model=None,
+        bias=False, **__):
     """The entrypoint of the inference module (seekmer/infer.py:27-85).
 
     Started as one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m
@@ -44,23 +45,29 @@ def run(index_path, output_path, fastq_paths, job_count, save_readmap,
 
     length_model: None, or (mean, sd) of --fragment-length / --sd: the effective lengths come from that
     model (mapper.fragment_length_weights) instead of the observed histogram, on every rank's mapper, so
-    whichever rank quantifies holds it.  The histogram is still counted, logged and written."""
+    whichever rank quantifies holds it.  The histogram is still counted, logged and written.
+
+    bias: --bias, the sequence-bias correction (bias_correct): the mapper also counts the hexamer every aligned
+    unit starts with; after the first quantification the effective lengths are rescaled by the hexamer
+    weights that follow from the counts and that estimate, and the EM runs once more from it.  One rank only."""
     from . import parallel
     start_time = datetime.datetime.utcnow()
     ranks = parallel.Ranks.from_env()
     try:
         _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-             bootstrap, debug, device, seed, parse_threads, strand=strand, length_model=length_model)
+             bootstrap, debug, device, seed, parse_threads, strand=strand, length_model=length_model, bias=bias)
     except BaseException as error:          # noqa: B902 -- one rank: re-raised as it is
         ranks.fail(error)
     ranks.close()
 
 
 def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-         bootstrap, debug, device, seed, parse_threads, strand=None, length_model=None):
+         bootstrap, debug, device, seed, parse_threads, strand=None, length_model=None, bias=False):
     from . import parallel
     mapper.strand_mode(strand)              # (an unknown mode fails before any file is touched)
     length_model, _ = mapper.length_model_weights(length_model)      # (and so does a model that cannot be)
+    if bias and ranks.world > 1:
+        raise ValueError(BIAS_ONE_RANK)
     if ranks.world > 1:
         device = ranks.local_rank
         if save_readmap:
@@ -90,7 +97,7 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         _LOG.info('Mapping all reads')
         map_result = mapper.map_reads(index, read_feeder, job_count=job_count,
                                       readmap=readmap, debug=debug, device=device, strand=strand,
-                                      length_model=length_model)
+                                      length_model=length_model, bias=bias)
     finally:
         ahead.finish()
     _LOG.info('Mapped all reads')
@@ -107,11 +114,57 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
         _LOG.info('Aligned %d reads (%.2f%%)', summarized_results.aligned,
                   100.0 * summarized_results.aligned / summarized_results.total)
         _LOG.info('Quantified transcripts')
+    if bias:
+        summarized_results, main_result = bias_pass(index, summarized_results, main_result, map_result.bias_observed(),
+                                                    strand, device=device)
     bootstrapped_results = bootstrap_ranks(summarized_results, main_result, bootstrap, ranks, seed=seed, device=device)
     if ranks.rank == 0:
         output_results(output_path, index, start_time, summarized_results,
                        main_result, bootstrapped_results)
         _LOG.info('Wrote results to %s', output_path)
+
+
+BIAS_ONE_RANK = ('--bias runs in one process on one GPU: the hexamer counts of several ranks are not merged '
+                 '(start it without a launcher)')
+
+
+def bias_correct(index, summarized, tpm, observed, strand, device=0):
+    """The sequence-bias correction of the effective lengths (DESIGN.md section 4, "Sequence bias";
+    skm_bias_correct): (eff', b, E) from the summary's effective lengths, the first pass's TPM, the observed
+    hexamer counts int64[4096] (MapResult.bias_observed) and the strand mode (None, 'fr', 'rf').  b f8[4096] are
+    the hexamer weights, E f8[4096] the expected counts.  The transcripts' sequences are rebuilt on the device
+    from the index, once per index handle (skm_index_build_transcripts)."""
+    mode = mapper.strand_mode(strand)
+    handle = index.device_handle(device)
+    lengths = numpy.ascontiguousarray(index.transcripts['length'], dtype='f8')
+    tpm = numpy.ascontiguousarray(tpm, dtype='f8')
+    eff = numpy.ascontiguousarray(summarized.effective_lengths, dtype='f8')
+    observed = numpy.ascontiguousarray(observed, dtype=numpy.int64)
+    if observed.shape != (4096,) or tpm.shape != lengths.shape or eff.shape != lengths.shape:
+        raise ValueError('bias_correct takes observed[4096] and one abundance and one effective length per transcript')
+    _native.check(_native.hip().skm_index_build_transcripts(handle, _native.ptr(lengths, _native.c_f64p), lengths.size))
+    corrected = numpy.zeros(lengths.size, dtype='f8')
+    weights = numpy.zeros(4096, dtype='f8')
+    expected = numpy.zeros(4096, dtype='f8')
+    _native.check(_native.hip().skm_bias_correct(
+        handle, mode, _native.ptr(observed, _native.c_i64p), _native.ptr(tpm, _native.c_f64p), _native.ptr(eff, _native.c_f64p),
+        lengths.size, _native.ptr(expected, _native.c_f64p), _native.ptr(weights, _native.c_f64p),
+        _native.ptr(corrected, _native.c_f64p)))
+    return corrected, weights, expected
+
+
+def bias_pass(index, summarized, tpm, observed, strand, device=0):
+    """The second pass of --bias: (summary with eff', the observed counts and the weights; corrected TPM).  The EM
+    is the one of the first pass (quantify), with l = eff' and started from the first result; the bootstraps
+    of the caller then start from the corrected result and use eff', as they read both from what is returned."""
+    corrected, weights, _ = bias_correct(index, summarized, tpm, observed, strand, device=device)
+    _LOG.info('Sequence bias: %d observed hexamers, weights from %g to %g', int(observed.sum()), weights.min(), weights.max())
+    summary = mapper.SummarizedResult(
+        summarized.aligned, summarized.unaligned, summarized.total, summarized.class_map, summarized.class_count,
+        summarized.fragment_length_frequencies, corrected, class_offsets=summarized.class_offsets,
+        class_targets=summarized.class_targets, length_model=summarized.length_model, bias_observed=observed,
+        bias_weights=weights)
+    return summary, quantify(summary, x0=numpy.asarray(tpm, dtype='f8'), device=device)
 
 
 def _log_length_model(length_model, single_ended):
@@ -164,7 +217,7 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
-             strand=None, names=None, length_model=None, **__):
+             strand=None, names=None, length_model=None, bias=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -181,7 +234,10 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     prints the host wall time per phase on stderr.
 
     length_model: None or (mean, sd), as run(): every sample's effective lengths come from the model, in the
-    set and for the samples mapped by themselves; samples.tsv keeps the observed harmonic means."""
+    set and for the samples mapped by themselves; samples.tsv keeps the observed harmonic means.
+
+    bias: --bias, as run(): every sample is then mapped by a mapper of its own (a sample set does not count
+    hexamers), the path of SKM_INFER_MANY_PER_SAMPLE=1, and gets the second pass of bias_pass."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -209,7 +265,9 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     index = common.KMerIndex.load(index_path)
     index.device_handle(device)
     paired = not single_ended
-    in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
+    in_set = [] if bias else sample_set_members([impute.cell_text_bytes(group) for group in groups],
+                                                impute.SAMPLE_SET_MAX_CELL_BYTES)
+    observed = [None] * len(groups)
     summaries, means = [None] * len(groups), [None] * len(groups)
     set_estimates = {}
     trace('index load')
@@ -239,8 +297,11 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
             continue
         _LOG.info('Mapping sample %s', names[i])
         map_result = mapper.map_reads(index, _feeder(list(group), paired, None, None, False), job_count=job_count,
-                                      debug=debug, device=device, strand=strand, length_model=length_model)
+                                      debug=debug, device=device, strand=strand, length_model=length_model,
+                                      bias=bias)
         summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
+        if bias:
+            observed[i] = map_result.bias_observed()
         del map_result
     _LOG.info('Mapped all reads')
     trace('mapping (one by one)')
@@ -253,6 +314,8 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     for i, (name, summary) in enumerate(zip(names, summaries)):
         _LOG.info('Quantifying sample %s', name)
         main_result = set_estimates[i] if i in set_estimates else quantify(summary, device=device)
+        if bias:
+            summary, main_result = bias_pass(index, summary, main_result, observed[i], strand, device=device)
         trace('quantification', pause=True)
         bootstrapped_results = bootstrap_quantify(summary, main_result, bootstrap, seed=seed, device=device)
         trace('bootstraps', pause=True)
@@ -799,6 +862,8 @@ def _generate_run_info(bootstrapped_abundance, index, results, start_time):
     length_model = getattr(results, 'length_model', None)
     if length_model is not None:          # (--fragment-length / --sd: the effective lengths are the model's)
         run_info['fragment_length_model'] = {'mean': length_model[0], 'sd': length_model[1]}
+    if getattr(results, 'bias_weights', None) is not None:      # (--bias: the effective lengths carry the hexamer weights)
+        run_info['bias'] = True
     return run_info
 
 
@@ -827,6 +892,7 @@ def _output_arrays(output_path, index, results, run_info, est_counts, bootstrapp
     PyTables/h5py are not installed here, so the kallisto-compatible HDF5
     container itself is out of reach; dataset names
     are kept ('aux/ids', 'est_counts', 'bootstrap/bs0', ...)."""
+    bias_weights = getattr(results, 'bias_weights', None)        # (None without --bias: the reference's placeholders)
     arrays = {
         'aux/call': numpy.frombuffer(run_info['call'].encode() or b' ', dtype='S1'),
         'aux/index_version': numpy.asarray([run_info['index_version']]),
@@ -838,8 +904,8 @@ def _output_arrays(output_path, index, results, run_info, est_counts, bootstrapp
         'aux/lengths': numpy.asarray(index.transcripts['length']),
         'aux/fld': results.fragment_length_frequencies.astype('i4'),
         'aux/eff_lengths': results.effective_lengths.astype('f8'),
-        'aux/bias_observed': numpy.ones(4096, dtype='i4'),
-        'aux/bias_normalized': numpy.ones(4096, dtype='f8'),
+        'aux/bias_observed': numpy.ones(4096, dtype='i4') if bias_weights is None else results.bias_observed.astype('i4'),
+        'aux/bias_normalized': numpy.ones(4096, dtype='f8') if bias_weights is None else bias_weights.astype('f8'),
         'est_counts': est_counts.astype('f8'),
     }
     for i, bootstrap in enumerate(bootstrapped_abundance):
@@ -873,6 +939,7 @@ def add_subcommand_parser(subparsers):
                              'the batches of the reference)')
     add_strand_arguments(parser)
     add_length_model_arguments(parser)
+    add_bias_argument(parser)
 
 
 def add_many_subcommand_parser(subparsers):
@@ -901,6 +968,14 @@ def add_many_subcommand_parser(subparsers):
                         help='name the samples (default: each sample\'s first file name up to its first ".")')
     add_strand_arguments(parser)
     add_length_model_arguments(parser)
+    add_bias_argument(parser)
+
+
+def add_bias_argument(parser):
+    """--bias (kallisto's flag): dest 'bias'."""
+    parser.add_argument('--bias', action='store_true', dest='bias',
+                        help='correct the effective lengths for sequence bias: the hexamers the aligned reads start '
+                             'with against those the expressed transcripts offer, then a second EM (one GPU)')
 
 
 def add_length_model_arguments(parser):

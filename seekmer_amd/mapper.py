@@ -73,11 +73,12 @@ class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
                  'fragment_length_frequencies', 'effective_lengths',
-                 'class_offsets', 'class_targets', '_map_result', 'length_model']
+                 'class_offsets', 'class_targets', '_map_result', 'length_model', 'bias_observed', 'bias_weights']
 
     def __init__(self, aligned, unaligned, total, class_map, class_count,
                  fragment_length_frequencies, effective_lengths,
-                 class_offsets=None, class_targets=None, map_result=None, length_model=None):
+                 class_offsets=None, class_targets=None, map_result=None, length_model=None,
+                 bias_observed=None, bias_weights=None):
         self.aligned = aligned
         self.unaligned = unaligned
         self.total = total
@@ -89,6 +90,9 @@ class SummarizedResult:
         self.class_targets = class_targets
         self._map_result = map_result
         self.length_model = length_model      # (mean, sd) when the effective lengths come from a model
+        # --bias (infer.bias_pass): the observed hexamer counts and the weights the effective lengths carry
+        self.bias_observed = bias_observed
+        self.bias_weights = bias_weights
 
     def detach(self):
         """Let go of the MapResult the summary came from (its table is in the summary): the mapper's
@@ -100,7 +104,7 @@ class SummarizedResult:
 class MapResult:
     """A mapping result collection with a lock (seekmer/mapper.py:40-145)."""
 
-    def __init__(self, index, readmap=None, device=0, keep_spans=False, strand=None, length_model=None):
+    def __init__(self, index, readmap=None, device=0, keep_spans=False, strand=None, length_model=None, bias=False):
         """keep_spans: also store every unit's MappedSpan (begin, end, anchor) for
         ReadMapper.last_batch -- parity tests and diagnostics; inference does not read them.
         strand: None (unstranded), 'fr' (--fr-stranded: mate 1 in the transcript's orientation) or
@@ -108,7 +112,9 @@ class MapResult:
         orientation (skm_mapper_set_strand).
         length_model: None, or (mean, sd) of a fragment-length model (fragment_length_weights): the
         effective lengths then come from it, here and in infer.quantify_resident
-        (skm_mapper_set_length_weights); the histogram is counted and reported as ever."""
+        (skm_mapper_set_length_weights); the histogram is counted and reported as ever.
+        bias: also count the hexamer every aligned unit starts with (skm_mapper_set_bias), for the
+        sequence-bias correction of infer.bias_correct: bias_observed()."""
         mode = strand_mode(strand)
         model, weights = length_model_weights(length_model)
         self.lock = threading.Lock()
@@ -128,6 +134,17 @@ class MapResult:
         self.length_model, self._length_weights = None, None
         if model is not None:
             self.set_length_model(model)
+        self.bias = bool(bias)
+        if self.bias:
+            _native.check(_native.hip().skm_mapper_set_bias(self._handle, 1))
+
+    def bias_observed(self):
+        """int64[4096]: how many aligned units start with each hexamer (first base in the top two bits of
+        the code; a unit with anything but an upper-case A, C, G or T among the six is not counted).  A
+        MapResult made with bias=True; NativeError SKM_ERR_STATE otherwise."""
+        out = numpy.zeros(4096, dtype=numpy.int64)
+        _native.check(_native.hip().skm_mapper_bias_observed(self._handle, _native.ptr(out, _native.c_i64p)))
+        return out
 
     def set_length_model(self, length_model):
         """(mean, sd), or None for the observed histogram again; it affects later calls only."""
@@ -482,12 +499,13 @@ def _drain_worker(mapper, reads_queue, errors):
             pass
 
 
-def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0, strand=None, length_model=None):
+def map_reads(index, read_feeder, job_count=1, readmap=None, debug=False, device=0, strand=None, length_model=None,
+              bias=False):
     """Map reads (seekmer/mapper.py:148-193).  Unlike the reference's CPU workers the device
     calls can fail; a worker's exception is re-raised here once every thread has stopped,
     instead of being lost with its thread.  strand: None, 'fr' or 'rf'; length_model: None or
-    (mean, sd) (MapResult)."""
-    map_result = _new_result(index, strand, length_model, readmap=readmap, device=device)
+    (mean, sd); bias: count the aligned units' first hexamers (MapResult)."""
+    map_result = _new_result(index, strand, length_model, bias, readmap=readmap, device=device)
     try:
         if debug or job_count <= 1 or isinstance(read_feeder, PackedReadFeeder):
             # (a packed feeder parses with its own threads and is drained natively: the GIL is not held)
@@ -544,13 +562,16 @@ def map_multiple_samples(index, read_feeders, job_count=1, debug=False, device=0
     return map_results
 
 
-def _new_result(index, strand, length_model=None, **kwargs):
-    """MapResult(index, **kwargs, strand=strand, length_model=length_model); unstranded and without
-    a model, the call is the one of before."""
+def _new_result(index, strand, length_model=None, bias=False, **kwargs):
+    """MapResult(index, **kwargs, strand=strand, length_model=length_model, bias=bias); unstranded,
+    without a model and without counting, the call is the one of before (a stand-in for MapResult
+    need not know the later keywords)."""
     if strand is not None:
         kwargs['strand'] = strand
     if length_model is not None:
         kwargs['length_model'] = length_model
+    if bias:
+        kwargs['bias'] = True
     return MapResult(index, **kwargs)
 
 
