@@ -413,6 +413,21 @@ int skm_sample_set_keep_histograms(skm_sample_set *set, int enable);
  * SKM_ERR_STATE if the set does not keep them, SKM_ERR_ARG if cap_samples (rows of room in fld) is
  * below the samples named so far. */
 int skm_sample_set_histograms(skm_sample_set *set, int64_t cap_samples, int64_t *fld);
+/* Sequence bias (--bias) in a set.  enable != 0: the set also counts, per sample, the hexamer each aligned
+ * unit starts with -- the rule of skm_mapper_set_bias, word for word -- in a kernel of its own
+ * (sample_bias_kernel, skm_samples.hip) between the strand filter and class counting of every launch; a set
+ * that was not asked launches what it always has.  Only while the set holds no units (SKM_ERR_STATE
+ * otherwise).  The counts are rows of 4096 64-bit words in HBM (32 KB) indexed by the sample NUMBER, so such
+ * a set numbers its samples below 2^15 (1 GiB of rows): an add call that names a larger one fails with
+ * SKM_ERR_ARG.  Inside the kernel a block counts in 32-bit LDS bins that hold at most the 4096 records it
+ * owns.
+ * skm_sample_set_bias_observed: out[n_samples][4096], in sample order: row i is skm_mapper_bias_observed of a
+ * mapper fed sample i alone (all zero for a sample without units), whatever the interleaving, the cut into
+ * launches or the adding threads.  Waits for everything added to be mapped and keeps adders waiting while it
+ * reads, as skm_sample_set_histograms.  SKM_ERR_STATE if the set does not count, SKM_ERR_ARG if cap_samples
+ * (rows of room in out) is below the samples named so far. */
+int skm_sample_set_keep_bias(skm_sample_set *set, int enable);
+int skm_sample_set_bias_observed(skm_sample_set *set, int64_t cap_samples, int64_t *out);
 /* DIAGNOSTICS, with no promise of stability: the set's bookkeeping on the host alone (no GPU is
  * touched), for tests.  They run the cutting, the log and the ordering by (sample, local first
  * seen) that the set itself runs; _split bisects the log on the host where the set does it in a
@@ -470,6 +485,26 @@ int skm_effective_lengths_weights(int device, int64_t n, const double *p, const 
  * queued on this process's other blocking streams; they are not meant for a loop. */
 int skm_bias_correct(skm_index *index, int strand, const int64_t *observed, const double *tpm, const double *eff,
                      int64_t n_tx, double *expected_out, double *b_out, double *eff_out);
+/* skm_bias_correct for n samples in one call (the samples of a sample set): observed[n][4096], tpm[n][n_tx],
+ * eff[n][n_tx] -> expected_out[n][4096], b_out[n][4096] (both optional), eff_out[n][n_tx].  Row s is bit for bit
+ * what skm_bias_correct returns for sample s alone: E is summed in the same fixed point with integer atomics, b
+ * comes from integers, and a transcript's sum over its windows keeps the order that depends on the transcript
+ * alone.  The sample is a grid dimension of the kernels; the lengths kernel holds the b tables of several
+ * samples in LDS and decodes every transcript once for all of them (skm_bias.hip).  Scratch is allocated once,
+ * for a group of consecutive rows whose buffers -- 5 words per transcript and 6 per hexamer a row -- stay
+ * within 256 MB (and 32768 rows); SKM_BIAS_MANY_GROUP in the environment caps the rows per group (tests), and
+ * SKM_BIAS_BLOCKS keeps its meaning.  The argument checks of skm_bias_correct apply to every row before any
+ * device work (SKM_ERR_ARG); SKM_ERR_STATE when the pool has not been built; n == 0 does nothing. */
+int skm_bias_correct_many(skm_index *index, int strand, int64_t n, const int64_t *observed, const double *tpm,
+                          const double *eff, int64_t n_tx, double *expected_out, double *b_out, double *eff_out);
+/* The host's half of E (libseekmer_host.so; no GPU): total_out = sum_t tpm[t] * windows[t] added in transcript
+ * order, and W_t = round(tpm[t] * 2^94 / total), clamped below 2^95, as three 32-bit limbs lowest first:
+ * limbs_out[k * n_tx + t].  A transcript without windows gets limbs 0; so does every transcript when the total
+ * is 0.  SKM_ERR_ARG for a NULL array, a negative size or window count, a negative or non-finite abundance, and
+ * for a total that cannot be scaled (it, or 2^94 over it, is not finite).  skm_bias_correct and
+ * skm_bias_correct_many call the same function (skm_bias_weights.h). */
+int skm_bias_fixed_weights(const double *tpm, const int32_t *windows, int64_t n_tx, uint64_t *limbs_out,
+                           double *total_out);
 
 /* Device-resident class table for infer.em / infer.quantify
  * (seekmer/infer.py:88-168).  class_counts are f8 as in

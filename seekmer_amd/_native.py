@@ -111,6 +111,8 @@ HIP_SYMBOLS = {
     'skm_effective_lengths_many': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_f64p, c_i64, c_f64p]),
     'skm_effective_lengths_weights': (ctypes.c_int, [ctypes.c_int, c_i64, c_f64p, c_f64p, c_i64, c_f64p]),
     'skm_bias_correct': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64p, c_f64p, c_f64p, c_i64, c_f64p, c_f64p, c_f64p]),
+    'skm_bias_correct_many': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_i64, c_i64p, c_f64p, c_f64p, c_i64, c_f64p,
+                                             c_f64p, c_f64p]),
     'skm_sample_set_create': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_void_pp]),
     'skm_sample_set_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_sample_set_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -124,6 +126,8 @@ HIP_SYMBOLS = {
     'skm_sample_set_histogram': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_sample_set_keep_histograms': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_sample_set_histograms': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
+    'skm_sample_set_keep_bias': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_bias_observed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
     'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),
     'skm_sample_set_split': (ctypes.c_int, [c_i64, c_i64p, c_i64p, c_i32p, c_i64, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
                                             c_i64p]),
@@ -209,6 +213,7 @@ HOST_SYMBOLS = {
     'skm_synth_free': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_synth_fastq_write': (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_int, ctypes.c_int, c_i64,
                                              ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]),
+    'skm_bias_fixed_weights': (ctypes.c_int, [c_f64p, c_i32p, c_i64, c_u64p, c_f64p]),
     'skm_synth_reads': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, c_i64p, c_i64, c_i64,
                                        c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_void_p]),

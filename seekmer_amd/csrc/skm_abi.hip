@@ -5,6 +5,7 @@
 #include "skm_kernels.h"
 #include "skm_pool.h"
 #include "skm_bias.h"
+#include "skm_bias_weights.h"
 
 #include <dlfcn.h>
 #include <algorithm>
@@ -946,6 +947,34 @@ extern "C" int skm_index_transcript_bases(skm_index *ix, char *bases_out, uint8_
     return SKM_OK;
 }
 
+namespace {
+
+// the grid of the two kernels over the pool; SKM_BIAS_BLOCKS (test hook) caps it
+int bias_blocks(const skm_index *ix, int *blocks)
+{
+    *blocks = ix->cu_count * 4;
+    if (const char *v = getenv("SKM_BIAS_BLOCKS")) {
+        const long long n = atoll(v);
+        if (n < 1) return fail(SKM_ERR_ARG, "SKM_BIAS_BLOCKS must be at least 1, not '%s'", v);
+        *blocks = (int)std::min<long long>(n, *blocks);
+    }
+    return SKM_OK;
+}
+
+// rows per group of skm_bias_correct_many: a row's buffers in HBM are BIAS_LIMBS + 2 words per transcript (weights,
+// eff, eff') and BIAS_LIMBS + 3 per hexamer (O, E's limbs, E, b); a group's stay within 256 MB, and a group holds
+// at most BIAS_MANY_MAX_GROUP rows (a grid dimension).  SKM_BIAS_MANY_GROUP (tests): fewer.
+int64_t bias_many_group(int64_t n, int64_t n_tx)
+{
+    const int64_t row_bytes = ((BIAS_LIMBS + 2) * n_tx + (BIAS_LIMBS + 3) * (int64_t)BIAS_BINS) * 8;
+    int64_t group = std::min<int64_t>((int64_t)(1LL << 28) / row_bytes, BIAS_MANY_MAX_GROUP);
+    if (const char *v = getenv("SKM_BIAS_MANY_GROUP"))
+        if (atoll(v) > 0) group = std::min<int64_t>(group, atoll(v));
+    return std::max<int64_t>(1, std::min(group, n));
+}
+
+}  // namespace
+
 extern "C" int skm_bias_correct(skm_index *ix, int strand, const int64_t *observed, const double *tpm, const double *eff,
                                 int64_t n_tx, double *expected_out, double *b_out, double *eff_out)
 {
@@ -962,30 +991,15 @@ extern "C" int skm_bias_correct(skm_index *ix, int strand, const int64_t *observ
     if (n_tx != ix->pool.n_tx)
         return fail(SKM_ERR_ARG, "%lld transcripts, but the pool holds %lld", (long long)n_tx, (long long)ix->pool.n_tx);
     SKM_TRY(set_device(ix->device));
-    // E in 96-bit fixed point: W_t = round(tpm_t * 2^94 / sum_t tpm_t n_t) < 2^95, handed to the device as three
-    // 32-bit limbs that are summed apart (a limb's sum stays below 2^63 for 2^31 additions: no carries)
+    // E in 96-bit fixed point (skm_bias_weights.h): W_t as three 32-bit limbs that the device sums apart
     double total = 0.0;
-    for (int64_t t = 0; t < n_tx; ++t) total += tpm[t] * (double)ix->pool_windows[(size_t)t];
-    const double fixed_one = 0x1p94;
-    if (total != 0.0 && (std::isinf(total) || std::isinf(fixed_one / total)))
-        return fail(SKM_ERR_ARG, "the abundances are too large or too small to scale");
+    const double fixed_one = BIAS_FIXED_ONE;
     std::vector<unsigned long long> weight((size_t)n_tx * BIAS_LIMBS + 1, 0);      // [limb][n_tx]
-    if (total > 0.0)
-        for (int64_t t = 0; t < n_tx; ++t) {
-            if (ix->pool_windows[(size_t)t] == 0) continue;            // (no window: its weight is never added, whatever it is)
-            const double w = tpm[t] * (fixed_one / total);             // (a double at or above 2^52 is a whole number)
-            // clamped as a double, before the conversion: one transcript may hold everything with the scale rounded up
-            unsigned __int128 fixed = w >= 0x1p95 ? ((unsigned __int128)1 << 95) - 1
-                                                  : (unsigned __int128)(w < 0x1p52 ? w + 0.5 : w);
-            for (int k = 0; k < BIAS_LIMBS; ++k) weight[(size_t)(k * n_tx + t)] = (unsigned long long)(fixed >> (32 * k)) & 0xffffffffULL;
-        }
+    if (!bias_fixed_weights(tpm, ix->pool_windows.data(), n_tx, weight.data(), &total))
+        return fail(SKM_ERR_ARG, "the abundances are too large or too small to scale");
     const double share = strand == SKM_STRAND_NONE ? 0.5 : 1.0;
-    int blocks = ix->cu_count * 4;
-    if (const char *v = getenv("SKM_BIAS_BLOCKS")) {                 // test hook: the grid of the two kernels over the pool
-        const long long n = atoll(v);
-        if (n < 1) return fail(SKM_ERR_ARG, "SKM_BIAS_BLOCKS must be at least 1, not '%s'", v);
-        blocks = (int)std::min<long long>(n, blocks);
-    }
+    int blocks = 0;
+    SKM_TRY(bias_blocks(ix, &blocks));
     DevMem d_weight, d_observed, d_expected, d_expected_out, d_b, d_eff, d_eff_out;
     HIP_TRY(hipMalloc(d_weight.out(), (size_t)(n_tx * BIAS_LIMBS + 1) * 8));
     HIP_TRY(hipMalloc(d_eff.out(), (size_t)(n_tx + 1) * 8));
@@ -1011,6 +1025,74 @@ extern "C" int skm_bias_correct(skm_index *ix, int strand, const int64_t *observ
     if (b_out) HIP_TRY(hipMemcpy(b_out, d_b, BIAS_BINS * 8, hipMemcpyDeviceToHost));
     if (n_tx) HIP_TRY(hipMemcpy(eff_out, d_eff_out, (size_t)n_tx * 8, hipMemcpyDeviceToHost));
     return SKM_OK;                                                   // (the copies home have waited for the kernels)
+}
+
+extern "C" int skm_bias_correct_many(skm_index *ix, int strand, int64_t n, const int64_t *observed, const double *tpm,
+                                     const double *eff, int64_t n_tx, double *expected_out, double *b_out, double *eff_out)
+{
+    if (!ix || n < 0 || n_tx < 0 || (n && (!observed || (n_tx && (!tpm || !eff || !eff_out)))))
+        return fail(SKM_ERR_ARG, "NULL array or negative size");
+    if (strand != SKM_STRAND_NONE && strand != SKM_STRAND_FR && strand != SKM_STRAND_RF)
+        return fail(SKM_ERR_ARG, "unknown strand mode %d", strand);
+    for (int64_t i = 0; i < n * BIAS_BINS; ++i)
+        if (observed[i] < 0) return fail(SKM_ERR_ARG, "row %lld: observed count %lld is negative", (long long)(i / BIAS_BINS), (long long)(i % BIAS_BINS));
+    for (int64_t i = 0; i < n * n_tx; ++i)
+        if (!(tpm[i] >= 0.0) || std::isinf(tpm[i]))
+            return fail(SKM_ERR_ARG, "row %lld: the abundance of transcript %lld is negative or not finite", (long long)(i / n_tx), (long long)(i % n_tx));
+    std::lock_guard<std::mutex> lock(ix->pool_mu);
+    if (!ix->pool_built) return fail(SKM_ERR_STATE, "the transcript pool has not been built: call skm_index_build_transcripts");
+    if (n_tx != ix->pool.n_tx)
+        return fail(SKM_ERR_ARG, "%lld transcripts, but the pool holds %lld", (long long)n_tx, (long long)ix->pool.n_tx);
+    if (n == 0) return SKM_OK;
+    // every row's total (skm_bias_weights.h) and the scale that takes its E back, before any device work
+    const int64_t group = bias_many_group(n, n_tx);
+    std::vector<unsigned long long> weight((size_t)(group * n_tx * BIAS_LIMBS) + 1, 0);     // [row][limb][n_tx], a group's
+    std::vector<double> totals((size_t)n, 0.0), scale((size_t)n, 0.0);
+    const double share = strand == SKM_STRAND_NONE ? 0.5 : 1.0;
+    for (int64_t s = 0; s < n; ++s) {
+        if (!bias_fixed_total(tpm + s * n_tx, ix->pool_windows.data(), n_tx, &totals[(size_t)s]))
+            return fail(SKM_ERR_ARG, "row %lld: the abundances are too large or too small to scale", (long long)s);
+        scale[(size_t)s] = share * (totals[(size_t)s] / BIAS_FIXED_ONE);
+    }
+    SKM_TRY(set_device(ix->device));
+    int blocks = 0;
+    SKM_TRY(bias_blocks(ix, &blocks));
+    DBuf<unsigned long long> d_weight, d_observed, d_expected;
+    DBuf<double> d_scale, d_expected_out, d_b, d_eff, d_eff_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_weight.ensure((size_t)(group * n_tx * BIAS_LIMBS) + 1));
+    SKM_TRY(d_eff.ensure((size_t)(group * n_tx) + 1)); SKM_TRY(d_eff_out.ensure((size_t)(group * n_tx) + 1));
+    SKM_TRY(d_observed.ensure((size_t)group * BIAS_BINS)); SKM_TRY(d_expected.ensure((size_t)group * BIAS_LIMBS * BIAS_BINS));
+    SKM_TRY(d_expected_out.ensure((size_t)group * BIAS_BINS)); SKM_TRY(d_b.ensure((size_t)group * BIAS_BINS));
+    SKM_TRY(d_scale.ensure((size_t)group));
+    for (int64_t first = 0; first < n; first += group) {
+        const int64_t here = std::min(group, n - first);
+        for (int64_t s = 0; s < here; ++s)
+            bias_fixed_limbs(tpm + (first + s) * n_tx, ix->pool_windows.data(), n_tx, totals[(size_t)(first + s)],
+                             weight.data() + s * n_tx * BIAS_LIMBS);
+        HIP_TRY(hipMemsetAsync(d_expected.p, 0, (size_t)here * BIAS_LIMBS * BIAS_BINS * 8, nullptr));
+        HIP_TRY(hipMemcpy(d_observed.p, observed + first * BIAS_BINS, (size_t)here * BIAS_BINS * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_scale.p, scale.data() + first, (size_t)here * 8, hipMemcpyHostToDevice));
+        if (n_tx) {
+            HIP_TRY(hipMemcpy(d_weight.p, weight.data(), (size_t)(here * n_tx * BIAS_LIMBS) * 8, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_eff.p, eff + first * n_tx, (size_t)(here * n_tx) * 8, hipMemcpyHostToDevice));
+        }
+        // (results do not depend on a grid: with many rows a row's share of the device is smaller)
+        const int rows_lengths = (int)((here + BIAS_LENGTHS_G - 1) / BIAS_LENGTHS_G);
+        const int blocks_expected = (int)std::max<int64_t>(std::min<int64_t>(blocks, 4), std::min<int64_t>(blocks, (int64_t)ix->cu_count * 8 / (here * BIAS_LIMBS)));
+        const int blocks_lengths = (int)std::max<int64_t>(std::min<int64_t>(blocks, 4), std::min<int64_t>(blocks, (int64_t)ix->cu_count * 8 / rows_lengths));
+        launch_bias_expected_many(ix->pool, d_weight.p, here, strand, d_expected.p, blocks_expected, nullptr);
+        launch_bias_weights_many(d_observed.p, d_expected.p, d_scale.p, here, d_expected_out.p, d_b.p, nullptr);
+        launch_bias_lengths_many(ix->pool, (const int32_t *)ix->pool_tx_windows.get(), d_b.p, here, strand, d_eff.p, d_eff_out.p,
+                                 blocks_lengths, nullptr);
+        HIP_TRY(hipGetLastError());
+        if (expected_out) HIP_TRY(hipMemcpy(expected_out + first * BIAS_BINS, d_expected_out.p, (size_t)here * BIAS_BINS * 8, hipMemcpyDeviceToHost));
+        if (b_out) HIP_TRY(hipMemcpy(b_out + first * BIAS_BINS, d_b.p, (size_t)here * BIAS_BINS * 8, hipMemcpyDeviceToHost));
+        if (n_tx) HIP_TRY(hipMemcpy(eff_out + first * n_tx, d_eff_out.p, (size_t)(here * n_tx) * 8, hipMemcpyDeviceToHost));
+        else HIP_TRY(hipStreamSynchronize(nullptr));
+    }
+    drain.dismiss();                                                 // (the copies home have waited for the kernels)
+    return SKM_OK;
 }
 
 // ------------------------------------------------------------------- mapper
@@ -1145,7 +1227,8 @@ int read_error(skm_mapper *m)
 typedef std::function<int(uint32_t *, int, int)> RecordStage;
 int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_offsets,
                        int64_t n_units, int paired, int max_len, int64_t first_unit = -1,
-                       const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr)
+                       const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr,
+                       unsigned long long *sample_bias_rows = nullptr)
 {
     const int64_t unit_base = first_unit >= 0 ? first_unit : m->units_done;
     skm_index *ix = m->ix;
@@ -1245,6 +1328,10 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     if (m->bias) {             // --bias: the first hexamers of the units that are still aligned
         launch_bias_observed(m->records.p, record_words, words, paired, m->rec_tuple.p, m->rec_unit.p, n_units,
                              m->bias_observed.p, m->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (salt && sample_bias_rows) {   // a sample set that counts: the same rule, by the unit's sample
+        launch_sample_bias(b, *salt, sample_bias_rows, m->stream);
         HIP_TRY(hipGetLastError());
     }
     if (salt) {
@@ -2502,6 +2589,7 @@ void set_split_order(int64_t n_samples, int64_t n_classes, const int32_t *class_
 
 constexpr int64_t SET_MAX_SAMPLES = 1 << 24;
 constexpr int64_t SET_MAX_HIST_SAMPLES = 1 << 16;   // with a histogram per sample: rows of 16 KB by sample NUMBER, 1 GiB at most
+constexpr int64_t SET_MAX_BIAS_SAMPLES = 1 << 15;   // counting hexamers: rows of 32 KB (4096 x u64) by sample NUMBER, 1 GiB at most
 constexpr int64_t SET_MAX_QUEUED = 4 * PACKED_MAX_UNITS;     // units that may wait in HBM before an adder waits
 
 }  // namespace
@@ -2520,6 +2608,9 @@ struct skm_sample_set {
     // largest sample a launch has held + 1, every word up to hist.cap counted or zero; touched under m->mu
     bool keep_hist = false;
     DBuf<unsigned long long> hist;
+    // one row of observed hexamers per sample (skm_sample_set_keep_bias): [rows][4096], kept as `hist` is
+    bool keep_bias = false;
+    DBuf<unsigned long long> bias_rows;
     // ---- under mu
     std::mutex mu;
     std::condition_variable work_cv, done_cv;
@@ -2595,7 +2686,16 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
         if (s->hist.cap > held)
             HIP_TRY(hipMemsetAsync(s->hist.p + held, 0, (s->hist.cap - held) * sizeof(unsigned long long), m->stream));
     }
-    SKM_TRY(map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt));
+    if (s->keep_bias) {
+        int32_t largest = 0;
+        for (const SetPart &part : parts) largest = std::max(largest, part.sample);
+        const size_t held = s->bias_rows.cap;
+        SKM_TRY(s->bias_rows.ensure(((size_t)largest + 1) * BIAS_BINS, true, m->stream));
+        if (s->bias_rows.cap > held)
+            HIP_TRY(hipMemsetAsync(s->bias_rows.p + held, 0, (s->bias_rows.cap - held) * sizeof(unsigned long long), m->stream));
+    }
+    SKM_TRY(map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt,
+                               s->keep_bias ? s->bias_rows.p : nullptr));
     if (s->keep_hist) {
         // the spans of the attempt that stood (an overflowing entry arena runs the map kernel again), after
         // the pair rule; they stay until this mapper's next launch, which the set's worker starts after this one
@@ -2666,6 +2766,9 @@ int set_admit(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n_u
     if (s->keep_hist && sample >= SET_MAX_HIST_SAMPLES)
         return fail(SKM_ERR_ARG, "sample %lld: a set that keeps a histogram per sample numbers its samples below %lld",
                     (long long)sample, (long long)SET_MAX_HIST_SAMPLES);
+    if (s->keep_bias && sample >= SET_MAX_BIAS_SAMPLES)
+        return fail(SKM_ERR_ARG, "sample %lld: a set that counts hexamers per sample numbers its samples below %lld",
+                    (long long)sample, (long long)SET_MAX_BIAS_SAMPLES);
     s->done_cv.wait(hold, [&] { return s->error != SKM_OK || s->queued_units <= SET_MAX_QUEUED; });
     if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
     return SKM_OK;
@@ -2830,6 +2933,16 @@ extern "C" int skm_sample_set_keep_histograms(skm_sample_set *s, int enable)
     return SKM_OK;
 }
 
+extern "C" int skm_sample_set_keep_bias(skm_sample_set *s, int enable)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    std::lock_guard<std::mutex> hold(s->mu);
+    for (const int64_t units : s->sample_units)
+        if (units) return fail(SKM_ERR_STATE, "hexamer counts per sample can only be switched on an empty sample set");
+    s->keep_bias = enable != 0;
+    return SKM_OK;
+}
+
 extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit,
                                          const skm_packed_reads *mate1, const skm_packed_reads *mate2)
 {
@@ -2969,6 +3082,29 @@ extern "C" int skm_sample_set_histograms(skm_sample_set *s, int64_t cap_samples,
     std::fill(fld + rows * MAX_FRAGMENT_LENGTH, fld + n_samples * MAX_FRAGMENT_LENGTH, (int64_t)0);
     if (rows) {
         HIP_TRY(hipMemcpyAsync(fld, s->hist.p, (size_t)rows * MAX_FRAGMENT_LENGTH * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_bias_observed(skm_sample_set *s, int64_t cap_samples, int64_t *out)
+{
+    if (!s || cap_samples < 0 || (cap_samples && !out)) return fail(SKM_ERR_ARG, "bad argument");
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_hold(s, hold));
+    if (!s->keep_bias)
+        return fail(SKM_ERR_STATE, "the set does not count hexamers: call skm_sample_set_keep_bias(set, 1) before adding");
+    const int64_t n_samples = (int64_t)s->sample_units.size();
+    if (cap_samples < n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)n_samples);
+    if (n_samples == 0) return SKM_OK;
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    // (a sample that no launch has held -- no units -- may lie past the buffer: its row is zero)
+    const int64_t rows = std::min<int64_t>(n_samples, (int64_t)(s->bias_rows.cap / BIAS_BINS));
+    std::fill(out + rows * BIAS_BINS, out + n_samples * BIAS_BINS, (int64_t)0);
+    if (rows) {
+        HIP_TRY(hipMemcpyAsync(out, s->bias_rows.p, (size_t)rows * BIAS_BINS * 8, hipMemcpyDeviceToHost, m->stream));
         HIP_TRY(hipStreamSynchronize(m->stream));
     }
     return SKM_OK;

@@ -9,6 +9,16 @@ constexpr int BIAS_HEXAMER = 6;
 constexpr int BIAS_BINS = 4096;                   // 4^6 hexamers, first base in the top two bits
 constexpr int BIAS_LIMBS = 3;                     // E in 96-bit fixed point: three 32-bit limbs a weight, summed apart
 
+// samples whose b tables a block of the many-sample lengths kernel holds in LDS (32 KB each): 1, 2 or 4.  A
+// tuning build sets it (scripts/build_variant.sh NAME "-DSKM_BIAS_LENGTHS_G=4" skm_bias.hip); DESIGN.md section 4,
+// "Sequence bias", has the measurement behind the default.
+#ifndef SKM_BIAS_LENGTHS_G
+#define SKM_BIAS_LENGTHS_G 1
+#endif
+constexpr int BIAS_LENGTHS_G = SKM_BIAS_LENGTHS_G;
+static_assert(BIAS_LENGTHS_G == 1 || BIAS_LENGTHS_G == 2 || BIAS_LENGTHS_G == 4, "G x 32 KB of LDS: 1, 2 or 4");
+constexpr int64_t BIAS_MANY_MAX_GROUP = 32768;    // samples of one launch at most (a grid dimension holds 65535)
+
 // What the pool is rebuilt from, kept on the host by skm_index_create until the pool has been built: of
 // every contig its place in the pooled bases and its slice of the target rows (entry, offset).
 struct PoolContig {
@@ -56,5 +66,14 @@ void launch_bias_weights(const unsigned long long *observed, const unsigned long
 // one wave per transcript, its sum in a fixed order
 void launch_bias_lengths(const TxPool &pool, const int32_t *tx_windows, const double *b, int strand, const double *eff,
                          double *eff_out, int blocks, hipStream_t stream);
+// The same three for n samples in one launch each (skm_bias_correct_many); every row has the bits of the call above
+// on that row alone.  tx_weight[n][BIAS_LIMBS][n_tx], expected[n][BIAS_LIMBS][4096] (zeroed), observed[n][4096],
+// scale[n], expected_out[n][4096], b[n][4096], eff[n][n_tx], eff_out[n][n_tx]; n <= BIAS_MANY_MAX_GROUP.
+void launch_bias_expected_many(const TxPool &pool, const unsigned long long *tx_weight, int64_t n, int strand,
+                               unsigned long long *expected, int blocks, hipStream_t stream);
+void launch_bias_weights_many(const unsigned long long *observed, const unsigned long long *expected, const double *scale,
+                              int64_t n, double *expected_out, double *b, hipStream_t stream);
+void launch_bias_lengths_many(const TxPool &pool, const int32_t *tx_windows, const double *b, int64_t n, int strand,
+                              const double *eff, double *eff_out, int blocks, hipStream_t stream);
 
 }  // namespace skm

@@ -13,6 +13,10 @@
 //                  integer atomics, bit-reproducible for any grid
 //   weights        one block
 //   lengths        over the pool, b in LDS; a transcript's sum is one wave's, in a fixed order
+// skm_bias_correct_many runs the last three for many samples at once (the samples of a sample set): the sample
+// is a grid dimension of `expected` and of `weights`, and a block of `lengths` holds the b tables of
+// BIAS_LENGTHS_G samples in LDS and decodes a transcript's windows once for all of them.  Each kernel shares its
+// arithmetic with the single-sample one, so a row has the bits of the single call.
 // The kernels over the pool give one wave a transcript at a time: a lane takes the windows that start in
 // every 64th word, so a wave reads a transcript's words as one stretch.
 #include "../../include/seekmer_hip.h"
@@ -147,16 +151,16 @@ bias_observed_kernel(const uint32_t *__restrict__ records, int record_words, int
         if (bins[i]) atomicAdd(&observed[i], (unsigned long long)bins[i]);
 }
 
-__global__ void __launch_bounds__(BIAS_THREADS)
-bias_expected_kernel(TxPool pool, const unsigned long long *__restrict__ tx_weight, int plus, int minus,
-                     unsigned long long *expected)
+// one limb of one sample's weights over the pool, by a grid of `n_blocks` blocks of which this is `block`
+__device__ __forceinline__ void expected_limb(const TxPool &pool, const unsigned long long *__restrict__ tx_weight, int plus,
+                                              int minus, unsigned long long *expected, unsigned long long *bins,
+                                              int64_t block, int64_t n_blocks)
 {
-    __shared__ unsigned long long bins[BIAS_BINS];
     for (int i = threadIdx.x; i < BIAS_BINS; i += BIAS_THREADS) bins[i] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t wave = (blockIdx.x * (int64_t)BIAS_THREADS + threadIdx.x) >> 6;
-    const int64_t n_waves = (int64_t)gridDim.x * BIAS_WAVES;
+    const int64_t wave = (block * (int64_t)BIAS_THREADS + threadIdx.x) >> 6;
+    const int64_t n_waves = n_blocks * BIAS_WAVES;
     for (int64_t t = wave; t < pool.n_tx; t += n_waves) {
         const unsigned long long weight = tx_weight[t];
         if (weight == 0) continue;                                     // (most transcripts of a sample)
@@ -174,10 +178,28 @@ bias_expected_kernel(TxPool pool, const unsigned long long *__restrict__ tx_weig
 }
 
 __global__ void __launch_bounds__(BIAS_THREADS)
-bias_weights_kernel(const unsigned long long *__restrict__ observed, const unsigned long long *__restrict__ expected,
-                    double scale, double *__restrict__ expected_out, double *__restrict__ b)
+bias_expected_kernel(TxPool pool, const unsigned long long *__restrict__ tx_weight, int plus, int minus,
+                     unsigned long long *expected)
 {
-    __shared__ unsigned long long sums[1 + BIAS_LIMBS];
+    __shared__ unsigned long long bins[BIAS_BINS];
+    expected_limb(pool, tx_weight, plus, minus, expected, bins, blockIdx.x, gridDim.x);
+}
+
+// blockIdx.y = the limb, blockIdx.z = the sample: tx_weight[n][BIAS_LIMBS][n_tx], expected[n][BIAS_LIMBS][4096]
+__global__ void __launch_bounds__(BIAS_THREADS)
+bias_expected_many_kernel(TxPool pool, const unsigned long long *__restrict__ tx_weight, int plus, int minus,
+                          unsigned long long *expected)
+{
+    __shared__ unsigned long long bins[BIAS_BINS];
+    const int64_t row = (int64_t)blockIdx.z * BIAS_LIMBS + blockIdx.y;
+    expected_limb(pool, tx_weight + row * pool.n_tx, plus, minus, expected + row * BIAS_BINS, bins, blockIdx.x, gridDim.x);
+}
+
+// one block, one sample
+__device__ __forceinline__ void weights_of(const unsigned long long *__restrict__ observed,
+                                           const unsigned long long *__restrict__ expected, double scale,
+                                           double *__restrict__ expected_out, double *__restrict__ b, unsigned long long *sums)
+{
     if (threadIdx.x < 1 + BIAS_LIMBS) sums[threadIdx.x] = 0;
     __syncthreads();
     unsigned long long o = 0, e[BIAS_LIMBS] = {0, 0, 0};               // (integer sums: any order)
@@ -196,6 +218,25 @@ bias_weights_kernel(const unsigned long long *__restrict__ observed, const unsig
         expected_out[i] = e_i * scale;
         b[i] = any && e_i != 0.0 ? (((double)observed[i] + 1.0) / observed_total) / (e_i / expected_total) : 1.0;
     }
+}
+
+__global__ void __launch_bounds__(BIAS_THREADS)
+bias_weights_kernel(const unsigned long long *__restrict__ observed, const unsigned long long *__restrict__ expected,
+                    double scale, double *__restrict__ expected_out, double *__restrict__ b)
+{
+    __shared__ unsigned long long sums[1 + BIAS_LIMBS];
+    weights_of(observed, expected, scale, expected_out, b, sums);
+}
+
+// blockIdx.x = the sample: observed[n][4096], expected[n][BIAS_LIMBS][4096], scale[n], expected_out[n][4096], b[n][4096]
+__global__ void __launch_bounds__(BIAS_THREADS)
+bias_weights_many_kernel(const unsigned long long *__restrict__ observed, const unsigned long long *__restrict__ expected,
+                         const double *__restrict__ scale, double *__restrict__ expected_out, double *__restrict__ b)
+{
+    __shared__ unsigned long long sums[1 + BIAS_LIMBS];
+    const int64_t s = blockIdx.x;
+    weights_of(observed + s * BIAS_BINS, expected + s * BIAS_LIMBS * BIAS_BINS, scale[s], expected_out + s * BIAS_BINS,
+               b + s * BIAS_BINS, sums);
 }
 
 __global__ void __launch_bounds__(BIAS_THREADS)
@@ -226,6 +267,53 @@ bias_lengths_kernel(TxPool pool, const int32_t *__restrict__ tx_windows, const d
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
         if (lane == 0) eff_out[t] = eff[t] * (sum / (double)n_windows);
+    }
+}
+
+// The lengths of G samples at a time: blockIdx.y = the group of samples [G y, G y + G), whose b tables the block
+// holds in LDS (G x 32 KB).  A transcript's windows are read and decoded once; every sample keeps a sum of its
+// own that lane l feeds with the windows of the words l, l + 64, ... in position order and the 64 lanes close
+// in the butterfly of bias_lengths_kernel: the terms, their order and the expression are that kernel's, so row s
+// has the bits of the single call whatever G is.  A group past the last sample (n not a multiple of G) holds
+// tables of zeros for the missing samples and writes nothing for them.
+template <int G>
+__global__ void __launch_bounds__(BIAS_THREADS)
+bias_lengths_many_kernel(TxPool pool, const int32_t *__restrict__ tx_windows, const double *__restrict__ b, int64_t n,
+                         double share_plus, double share_minus, const double *__restrict__ eff, double *__restrict__ eff_out)
+{
+    __shared__ double weights[G][BIAS_BINS];
+    const int64_t first = (int64_t)blockIdx.y * G;
+    const int here = n - first < G ? (int)(n - first) : G;
+    for (int g = 0; g < G; ++g)
+        for (int i = threadIdx.x; i < BIAS_BINS; i += BIAS_THREADS) weights[g][i] = g < here ? b[(first + g) * BIAS_BINS + i] : 0.0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (blockIdx.x * (int64_t)BIAS_THREADS + threadIdx.x) >> 6;
+    const int64_t n_waves = (int64_t)gridDim.x * BIAS_WAVES;
+    for (int64_t t = wave; t < pool.n_tx; t += n_waves) {
+        const int32_t n_windows = tx_windows[t];
+        if (n_windows == 0) {
+            if (lane < here) eff_out[(first + lane) * pool.n_tx + t] = eff[(first + lane) * pool.n_tx + t];
+            continue;
+        }
+        const int32_t len = pool.tx_len[t], n_words = window_words(len);
+        const int64_t base = pool.tx_word[t];
+        double sum[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) sum[g] = 0.0;
+        for (int32_t w = lane; w < n_words; w += 64)
+            for_windows(pool, base, len, w, [&](uint32_t h) {
+                const uint32_t h_minus = revcomp6(h);
+#pragma unroll
+                for (int g = 0; g < G; ++g) sum[g] += share_plus * weights[g][h] + share_minus * weights[g][h_minus];
+            });
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            double total = sum[g];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+            if (lane == 0 && g < here) eff_out[(first + g) * pool.n_tx + t] = eff[(first + g) * pool.n_tx + t] * (total / (double)n_windows);
+        }
     }
 }
 
@@ -288,6 +376,33 @@ void launch_bias_lengths(const TxPool &pool, const int32_t *tx_windows, const do
     const double plus = strand == SKM_STRAND_NONE ? 0.5 : strand == SKM_STRAND_FR ? 1.0 : 0.0;
     hipLaunchKernelGGL(bias_lengths_kernel, dim3((unsigned)wave_grid(pool.n_tx, blocks)), dim3(BIAS_THREADS), 0, stream, pool,
                        tx_windows, b, plus, 1.0 - plus, eff, eff_out);
+}
+
+void launch_bias_expected_many(const TxPool &pool, const unsigned long long *tx_weight, int64_t n, int strand,
+                               unsigned long long *expected, int blocks, hipStream_t stream)
+{
+    if (pool.n_tx == 0 || n <= 0) return;
+    hipLaunchKernelGGL(bias_expected_many_kernel, dim3((unsigned)wave_grid(pool.n_tx, blocks), BIAS_LIMBS, (unsigned)n),
+                       dim3(BIAS_THREADS), 0, stream, pool, tx_weight, strand != SKM_STRAND_RF ? 1 : 0,
+                       strand != SKM_STRAND_FR ? 1 : 0, expected);
+}
+
+void launch_bias_weights_many(const unsigned long long *observed, const unsigned long long *expected, const double *scale,
+                              int64_t n, double *expected_out, double *b, hipStream_t stream)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(bias_weights_many_kernel, dim3((unsigned)n), dim3(BIAS_THREADS), 0, stream, observed, expected, scale,
+                       expected_out, b);
+}
+
+void launch_bias_lengths_many(const TxPool &pool, const int32_t *tx_windows, const double *b, int64_t n, int strand,
+                              const double *eff, double *eff_out, int blocks, hipStream_t stream)
+{
+    if (pool.n_tx == 0 || n <= 0) return;
+    const double plus = strand == SKM_STRAND_NONE ? 0.5 : strand == SKM_STRAND_FR ? 1.0 : 0.0;
+    constexpr int G = BIAS_LENGTHS_G;
+    hipLaunchKernelGGL(bias_lengths_many_kernel<G>, dim3((unsigned)wave_grid(pool.n_tx, blocks), (unsigned)((n + G - 1) / G)),
+                       dim3(BIAS_THREADS), 0, stream, pool, tx_windows, b, n, plus, 1.0 - plus, eff, eff_out);
 }
 
 }  // namespace skm

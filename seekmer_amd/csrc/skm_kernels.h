@@ -117,6 +117,10 @@ void launch_sample_salt(const MapBatch &b, const SampleSalt &salt, int *error, h
 // unit_begin / unit_end); hist holds MAX_FRAGMENT_LENGTH words for every sample the segments name
 void launch_sample_fld(const int32_t *unit_begin, const int32_t *unit_end, int64_t n_units, const SampleSalt &salt,
                        unsigned long long *hist, hipStream_t stream);
+// after the strand filter of a launch: rows[sample of the record's unit][hexamer] += 1 for every record whose
+// tuple is not empty, by the rule of launch_bias_observed (skm_bias.h); rows holds 4096 words for every sample the
+// segments name
+void launch_sample_bias(const MapBatch &b, const SampleSalt &salt, unsigned long long *rows, hipStream_t stream);
 // the set's segment log against the classes' global first-seen units: cls_sample[k], cls_local[k] =
 // the sample of class k and its first-seen unit counted inside that sample
 void launch_sample_assign(const int64_t *log_global, const int64_t *log_local, const int32_t *log_sample,

@@ -14,6 +14,9 @@
 // sample_fld_kernel after every launch: the units' final spans, through the map kernel's fragment length
 // rule, counted into the row of the unit's sample.
 //
+// A set that counts hexamers (--bias, skm_sample_set_keep_bias) runs sample_bias_kernel where a mapper runs
+// bias_observed_kernel (skm_bias.hip): the same rule, the count going into the row of the unit's sample.
+//
 // At export, sample_assign_kernel gives every class its sample and its first-seen unit counted inside
 // that sample from the set's segment log (global first unit, sample, local first unit of every
 // segment, in launch order).
@@ -100,6 +103,66 @@ sample_fld_kernel(const int32_t *__restrict__ unit_begin, const int32_t *__restr
     if (held >= 0) flush();
 }
 
+// First hexamers by sample: the rule of bias_observed_kernel (skm_bias.hip), counted into rows[sample][4096].
+// Records are not in unit order, but a block of the map kernel owns a range of units and writes their records
+// into the same range, so neighbouring records are mostly one sample's.  A block takes SAMPLE_BIAS_RUN
+// consecutive records, 256 at a time.  A tile whose records all belong to one sample (a block-wide vote) counts
+// in a 4096-bin LDS histogram that the block flushes, one 64-bit atomic per occupied bin, when that sample
+// changes and at the end; a mixed tile adds straight to HBM.  An LDS bin holds at most SAMPLE_BIAS_RUN < 2^32
+// counts between flushes; a row word is 64 bits wide.  Integer adds only: the rows do not depend on the grid, on
+// the cut into launches or on the order of arrival.
+constexpr int SAMPLE_BIAS_RUN = 4096;
+constexpr int SAMPLE_BIAS_BINS = 4096;            // (BIAS_BINS of skm_bias.h)
+constexpr int SAMPLE_BIAS_HEXAMER = 6;
+
+__global__ void __launch_bounds__(256)
+sample_bias_kernel(const uint32_t *__restrict__ records, int record_words, int words_per_read, int paired,
+                   const unsigned long long *__restrict__ rec_tuple, const int32_t *__restrict__ rec_unit,
+                   int64_t n_records, const int32_t *__restrict__ seg_first, const int32_t *__restrict__ seg_sample,
+                   int n_segments, unsigned long long *__restrict__ rows)
+{
+    __shared__ int32_t s_first[SAMPLE_LAUNCH_SEGMENTS], s_sample[SAMPLE_LAUNCH_SEGMENTS];
+    __shared__ uint32_t s_bins[SAMPLE_BIAS_BINS];
+    __shared__ int32_t s_ref;
+    for (int i = threadIdx.x; i < n_segments; i += blockDim.x) { s_first[i] = seg_first[i]; s_sample[i] = seg_sample[i]; }
+    for (int i = threadIdx.x; i < SAMPLE_BIAS_BINS; i += blockDim.x) s_bins[i] = 0;
+    __syncthreads();
+    const int64_t run_first = (int64_t)blockIdx.x * SAMPLE_BIAS_RUN;
+    const int64_t run_end = run_first + SAMPLE_BIAS_RUN < n_records ? run_first + SAMPLE_BIAS_RUN : n_records;
+    int64_t held = -1;                            // the sample whose counts s_bins holds (block-uniform)
+    auto flush = [&]() {                          // (called by the whole block)
+        __syncthreads();
+        for (int i = threadIdx.x; i < SAMPLE_BIAS_BINS; i += blockDim.x)
+            if (s_bins[i]) {
+                atomicAdd(&rows[held * SAMPLE_BIAS_BINS + i], (unsigned long long)s_bins[i]);
+                s_bins[i] = 0;
+            }
+        __syncthreads();
+    };
+    for (int64_t tile = run_first; tile < run_end; tile += blockDim.x) {
+        const int64_t r = tile + threadIdx.x;
+        const bool mine = r < run_end;
+        const int64_t unit = mine ? (int64_t)rec_unit[r] : 0;
+        const int32_t sample = mine ? s_sample[segment_find(s_first, n_segments, unit)] : -1;
+        if (threadIdx.x == 0) s_ref = sample;     // (the tile's first record exists)
+        __syncthreads();
+        const int32_t ref = s_ref;
+        const bool one_sample = __syncthreads_and(!mine || sample == ref) != 0;      // block-uniform
+        if (one_sample && held != ref) {
+            if (held >= 0) flush();
+            held = ref;
+        }
+        if (!mine || (rec_tuple[r] >> 40) == 0) continue;                  // unaligned (after the strand filter)
+        const uint32_t *record = records + unit * (paired ? 2 : 1) * record_words;   // mate 1, or the single read
+        if (record[3 * words_per_read] < (uint32_t)SAMPLE_BIAS_HEXAMER) continue;
+        if ((record[2 * words_per_read] >> (32 - SAMPLE_BIAS_HEXAMER)) != (1u << SAMPLE_BIAS_HEXAMER) - 1u) continue;
+        const uint32_t h = (uint32_t)(*reinterpret_cast<const uint64_t *>(record) >> (64 - 2 * SAMPLE_BIAS_HEXAMER));
+        if (one_sample) atomicAdd(&s_bins[h], 1u);
+        else atomicAdd(&rows[(int64_t)sample * SAMPLE_BIAS_BINS + h], 1ULL);
+    }
+    if (held >= 0) flush();
+}
+
 __global__ void __launch_bounds__(256)
 sample_assign_kernel(const int64_t *__restrict__ log_global, const int64_t *__restrict__ log_local,
                      const int32_t *__restrict__ log_sample, int64_t n_segments,
@@ -131,6 +194,15 @@ void launch_sample_fld(const int32_t *unit_begin, const int32_t *unit_end, int64
     const int64_t blocks = (n_units + SAMPLE_FLD_RUN - 1) / SAMPLE_FLD_RUN;        // (at most 2^21 units a launch)
     hipLaunchKernelGGL(sample_fld_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, unit_begin, unit_end,
                        n_units, salt.seg_first, salt.seg_sample, (int)salt.n_segments, hist);
+}
+
+void launch_sample_bias(const MapBatch &b, const SampleSalt &salt, unsigned long long *rows, hipStream_t stream)
+{
+    if (b.n_units <= 0 || salt.n_segments <= 0) return;
+    const int64_t blocks = (b.n_units + SAMPLE_BIAS_RUN - 1) / SAMPLE_BIAS_RUN;      // (at most 2^21 units a launch)
+    hipLaunchKernelGGL(sample_bias_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, b.records, b.record_words,
+                       b.words_per_read, b.paired, b.rec_tuple, b.rec_unit, b.n_units, salt.seg_first, salt.seg_sample,
+                       (int)salt.n_segments, rows);
 }
 
 void launch_sample_assign(const int64_t *log_global, const int64_t *log_local, const int32_t *log_sample,

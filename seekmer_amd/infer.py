@@ -18,7 +18,7 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'run_many', 'bias_correct', 'bias_pass', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+__all__ = ['run', 'run_many', 'bias_correct', 'bias_pass', 'bias_correct_many', 'bias_pass_many', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
            'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
@@ -167,6 +167,68 @@ def bias_pass(index, summarized, tpm, observed, strand, device=0):
     return summary, quantify(summary, x0=numpy.asarray(tpm, dtype='f8'), device=device)
 
 
+def bias_correct_many(index, summaries, tpms, observed, strand, device=0):
+    """bias_correct for S samples in one device call (skm_bias_correct_many): (eff'[S, n_tx], b[S, 4096], E[S, 4096])
+    from the summaries' effective lengths, the first pass's TPM rows [S, n_tx] and the observed counts int64[S, 4096]
+    (SampleSet.bias_observed).  Row s is bit for bit bias_correct on sample s.  Shapes that do not fit raise
+    ValueError before the device is touched."""
+    mode = mapper.strand_mode(strand)
+    summaries = list(summaries)
+    n = len(summaries)
+    lengths = numpy.ascontiguousarray(index.transcripts['length'], dtype='f8')
+    if any(numpy.shape(summary.effective_lengths) != lengths.shape for summary in summaries):
+        raise ValueError('bias_correct_many takes one effective length per transcript from every summary')
+    tpms = numpy.ascontiguousarray(tpms, dtype='f8').reshape(-1, lengths.size) if n == 0 else numpy.ascontiguousarray(tpms, dtype='f8')
+    observed = numpy.ascontiguousarray(observed, dtype=numpy.int64).reshape(-1, 4096) if n == 0 \
+        else numpy.ascontiguousarray(observed, dtype=numpy.int64)
+    if observed.shape != (n, 4096) or tpms.shape != (n, lengths.size):
+        raise ValueError('bias_correct_many takes observed[S, 4096] and tpms[S, n_tx] for its S = %d summaries, not %s and %s'
+                         % (n, observed.shape, tpms.shape))
+    eff = numpy.zeros((n, lengths.size), dtype='f8')
+    for k, summary in enumerate(summaries):
+        eff[k] = summary.effective_lengths
+    handle = index.device_handle(device)
+    _native.check(_native.hip().skm_index_build_transcripts(handle, _native.ptr(lengths, _native.c_f64p), lengths.size))
+    corrected = numpy.zeros((n, lengths.size), dtype='f8')
+    weights = numpy.zeros((n, 4096), dtype='f8')
+    expected = numpy.zeros((n, 4096), dtype='f8')
+    if n:
+        _native.check(_native.hip().skm_bias_correct_many(
+            handle, mode, n, _native.ptr(observed, _native.c_i64p), _native.ptr(tpms, _native.c_f64p),
+            _native.ptr(eff, _native.c_f64p), lengths.size, _native.ptr(expected, _native.c_f64p),
+            _native.ptr(weights, _native.c_f64p), _native.ptr(corrected, _native.c_f64p)))
+    return corrected, weights, expected
+
+
+def bias_pass_many(index, summaries, tpms, observed, strand, device=0):
+    """bias_pass for S samples: ([summary with eff', O and b, ...], corrected TPM [S, n_tx]), row k bit for bit
+    bias_pass on sample k.  The correction is one device call (bias_correct_many).  Inside the regime of
+    impute.use_set_quant the second EM of all samples runs in shared launches (quantify_tables started from the
+    first results); outside it, or under SKM_SET_QUANT_SERIAL=1, sample by sample."""
+    from . import impute
+    summaries = list(summaries)
+    tpms = numpy.ascontiguousarray(tpms, dtype='f8')
+    observed = numpy.ascontiguousarray(observed, dtype=numpy.int64)
+    corrected, weights, _ = bias_correct_many(index, summaries, tpms, observed, strand, device=device)
+    passed = []
+    for k, summarized in enumerate(summaries):
+        _LOG.info('Sequence bias: %d observed hexamers, weights from %g to %g', int(observed[k].sum()), weights[k].min(),
+                  weights[k].max())
+        passed.append(mapper.SummarizedResult(
+            summarized.aligned, summarized.unaligned, summarized.total, summarized.class_map, summarized.class_count,
+            summarized.fragment_length_frequencies, corrected[k], class_offsets=summarized.class_offsets,
+            class_targets=summarized.class_targets, length_model=summarized.length_model, bias_observed=observed[k],
+            bias_weights=weights[k]))
+    n_tx = index.transcripts.size
+    if passed and impute.use_set_quant(len(passed), n_tx, sum(summary.class_count.size for summary in passed)):
+        second = quantify_tables(passed, device=device, x0s=tpms)
+    else:
+        second = numpy.zeros((len(passed), n_tx), dtype='f8')
+        for k, summary in enumerate(passed):
+            second[k] = quantify(summary, x0=tpms[k], device=device)
+    return passed, second
+
+
 def _log_length_model(length_model, single_ended):
     if length_model is None:
         return
@@ -236,8 +298,11 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     length_model: None or (mean, sd), as run(): every sample's effective lengths come from the model, in the
     set and for the samples mapped by themselves; samples.tsv keeps the observed harmonic means.
 
-    bias: --bias, as run(): every sample is then mapped by a mapper of its own (a sample set does not count
-    hexamers), the path of SKM_INFER_MANY_PER_SAMPLE=1, and gets the second pass of bias_pass."""
+    bias: --bias, as run().  The samples that go through the set are mapped in a set that also counts every
+    sample's first hexamers (SampleSet(bias=True)) and get the second pass together, before the bootstraps and the
+    writing (bias_pass_many: one correction call, and inside the regime of impute.use_set_quant one shared second
+    EM); every other sample, and every sample under SKM_INFER_MANY_PER_SAMPLE=1, counts in a mapper of its own and
+    gets bias_pass.  The files are the same either way."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -265,8 +330,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     index = common.KMerIndex.load(index_path)
     index.device_handle(device)
     paired = not single_ended
-    in_set = [] if bias else sample_set_members([impute.cell_text_bytes(group) for group in groups],
-                                                impute.SAMPLE_SET_MAX_CELL_BYTES)
+    in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
     observed = [None] * len(groups)
     summaries, means = [None] * len(groups), [None] * len(groups)
     set_estimates = {}
@@ -276,9 +340,12 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
                    else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
         sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
-                                           strand=strand, per_sample_lengths=True, length_model=length_model)
+                                           strand=strand, per_sample_lengths=True, length_model=length_model, bias=bias)
         for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
             summaries[i], means[i] = summary, mean
+        if bias:
+            for i, row in zip(in_set, sample_set.bias_observed()):
+                observed[i] = row
         trace('mapping (set)')
         # (the main estimates of the set's samples in shared EM launches, from the table where it lies)
         if all(summaries[i].total for i in in_set) and impute.use_set_quant(
@@ -311,11 +378,29 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         if bootstrap > 0 and summary.aligned > RESAMPLE_LIMIT:
             raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
                              % (RESAMPLE_LIMIT, name, summary.aligned))
+    corrected = {}
+    if bias and in_set:
+        # the second pass of the set's samples together; a sample that leaves no abundance above the floor, in
+        # either pass, sends them all through the loop below, which writes the samples before it and raises there
+        try:
+            for i in in_set:
+                if i not in set_estimates:
+                    set_estimates[i] = quantify(summaries[i], device=device)
+            passed, second = bias_pass_many(index, [summaries[i] for i in in_set], [set_estimates[i] for i in in_set],
+                                            [observed[i] for i in in_set], strand, device=device)
+            corrected = {i: (passed[k], second[k]) for k, i in enumerate(in_set)}
+        except _native.NativeError as error:
+            if error.code != _native.SKM_ERR_UNDEFINED:
+                raise
+        trace('sequence bias (set)')
     for i, (name, summary) in enumerate(zip(names, summaries)):
         _LOG.info('Quantifying sample %s', name)
-        main_result = set_estimates[i] if i in set_estimates else quantify(summary, device=device)
-        if bias:
-            summary, main_result = bias_pass(index, summary, main_result, observed[i], strand, device=device)
+        if i in corrected:
+            summary, main_result = corrected[i]
+        else:
+            main_result = set_estimates[i] if i in set_estimates else quantify(summary, device=device)
+            if bias:
+                summary, main_result = bias_pass(index, summary, main_result, observed[i], strand, device=device)
         trace('quantification', pause=True)
         bootstrapped_results = bootstrap_quantify(summary, main_result, bootstrap, seed=seed, device=device)
         trace('bootstraps', pause=True)
@@ -673,19 +758,28 @@ def _table_csr(results):
         numpy.asarray(results.class_count, dtype='f8')
 
 
-def quantify_tables(results_list, device=0, return_iters=False):
+def quantify_tables(results_list, device=0, return_iters=False, x0s=None):
     """quantify() for K DIFFERENT class tables over the same transcripts (the companion of quantify_many,
     which runs K count vectors on one table): [K, n_tx] TPM, row k what quantify(results_list[k]) returns
     bit for bit -- every table starts from 1 / its effective lengths as quantify() does
     (seekmer/infer.py:116-119) --, with the EM steps of each when return_iters is set.  The tables are
     stacked into one block-diagonal problem and stepped in shared launches, each to its own stopping
-    rule (skm_quant_em_tables).  Tables of different n_tx raise ValueError."""
+    rule (skm_quant_em_tables).  Tables of different n_tx raise ValueError.
+
+    x0s: None, or [K, n_tx] start vectors: table k then starts from row k normalised as quantify() normalises its
+    x0 (a copy, x /= x.sum()), and row k of the result is quantify(results_list[k], x0=x0s[k]) bit for bit (a table
+    without class tuples gives zeros whatever its row holds, as quantify()).  A wrong number of rows or a wrong
+    width raises ValueError."""
     results_list = list(results_list)
     n = len(results_list)
     sizes = {results.effective_lengths.size for results in results_list}
     if len(sizes) > 1:
         raise ValueError('the tables must share their transcripts: n_tx = %s' % sorted(sizes))
     n_tx = sizes.pop() if sizes else 0
+    if x0s is not None:
+        x0s = numpy.asarray(x0s, dtype='f8')
+        if x0s.ndim != 2 or x0s.shape[0] != n or (n and x0s.shape[1] != n_tx):
+            raise ValueError('x0s must be [%d, %d]: one start vector per table, not %s' % (n, n_tx, x0s.shape))
     out = numpy.zeros((n, n_tx), dtype='f8')
     iters = numpy.zeros(max(n, 1), dtype=numpy.int64)
     if n and n_tx:
@@ -696,7 +790,10 @@ def quantify_tables(results_list, device=0, return_iters=False):
         n_ids = 0
         for k, results in enumerate(results_list):
             lengths[k] = results.effective_lengths.astype('f8')
-            x = numpy.ones(n_tx, dtype='f8') / lengths[k]
+            if x0s is None or results.class_map.size == 0:
+                x = numpy.ones(n_tx, dtype='f8') / lengths[k]
+            else:
+                x = x0s[k].copy()
             x /= x.sum()
             start[k] = x
             table = _table_csr(results)

@@ -696,11 +696,14 @@ class SampleSet:
     applies to every sample.  So does ``length_model`` (None, or (mean, sd): fragment_length_weights):
     with one, every sample's effective lengths are the model's -- one row, made once, in summarize()
     and in quantify() -- whatever the histograms hold; those are counted and reported as ever.
+    With ``bias`` the set also counts, per sample, the hexamer every aligned unit starts with
+    (skm_sample_set_keep_bias), for the sequence-bias correction of infer.bias_correct_many:
+    bias_observed().  Such a set numbers its samples below 2^15.
 
     Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
     where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
 
-    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None):
+    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None, bias=False):
         mode = strand_mode(strand)
         self.length_model, self._length_weights = length_model_weights(length_model)
         self.index = index
@@ -708,6 +711,7 @@ class SampleSet:
         self.device = device
         self.strand = strand
         self.per_sample_lengths = bool(per_sample_lengths)
+        self.bias = bool(bias)
         self._handle = ctypes.c_void_p()
         _native.check(_native.hip().skm_sample_set_create(index.device_handle(device), int(self.paired),
                                                           ctypes.byref(self._handle)))
@@ -718,6 +722,21 @@ class SampleSet:
         if self._length_weights is not None:
             _native.check(_native.hip().skm_sample_set_set_length_weights(
                 self._handle, _native.ptr(self._length_weights, _native.c_f64p)))
+        if self.bias:
+            _native.check(_native.hip().skm_sample_set_keep_bias(self._handle, 1))
+
+    def bias_observed(self):
+        """int64[n_samples, 4096]: row i is MapResult.bias_observed() of sample i mapped alone (zeros for a sample
+        without units).  Only a set made with bias=True; NativeError SKM_ERR_STATE otherwise."""
+        # (samples may be added meanwhile: the call says when there are more than the rows it was given)
+        while True:
+            out = numpy.zeros((len(self), 4096), dtype=numpy.int64)
+            code = _native.hip().skm_sample_set_bias_observed(self._handle, out.shape[0],
+                                                              _native.ptr(out, _native.c_i64p) if out.size else None)
+            if code == _native.SKM_ERR_ARG and len(self) > out.shape[0]:
+                continue
+            _native.check(code)
+            return out
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
@@ -916,13 +935,14 @@ class SampleSet:
 
 
 def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_sample_lengths=False,
-                   length_model=None):
+                   length_model=None, bias=False):
     """map_multiple_samples for many small samples (single cells): sample i = read_feeders[i], all of
     them mapped through ONE SampleSet in shared launches.  Each of `job_count` threads takes a sample
     at a time, parses its files completely and adds it; results do not depend on the thread count.
     The feeders must agree on paired / single-ended.  strand: None, 'fr' or 'rf' for every sample.
     per_sample_lengths: every sample keeps its own fragment-length histogram (SampleSet).
     length_model: None or (mean, sd), for every sample (SampleSet).
+    bias: the set counts every sample's first hexamers (SampleSet.bias_observed).
     A failed sample raises."""
     strand_mode(strand)
     read_feeders = list(read_feeders)
@@ -934,7 +954,7 @@ def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_
     if len(layouts) != 1:
         raise ValueError('paired and single-ended samples in one set')
     sample_set = SampleSet(index, layouts.pop(), device=device, strand=strand, per_sample_lengths=per_sample_lengths,
-                           length_model=length_model)
+                           length_model=length_model, bias=bias)
     if job_count == 1:
         for sample, read_feeder in enumerate(read_feeders):
             sample_set.add_sample(sample, read_feeder)
