@@ -12,7 +12,7 @@
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
  *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_bias_*,
- *                          skm_comm_*, skm_device_*)
+ *                          skm_gene_*, skm_comm_*, skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
  *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_synth_*)
  */
@@ -446,6 +446,39 @@ int skm_sample_set_split(int64_t n_entries, const int64_t *entry_global, const i
                          const int32_t *entry_sample, int64_t n_samples, int64_t n_classes,
                          const int64_t *first_seen, int32_t *class_sample, int64_t *class_local,
                          int64_t *order, int64_t *sample_class_offsets);
+
+/* ------------------------------------------------------------ gene-level tables
+ * ("Gene-level tables".)  tx_gene[n_tx] gives every transcript's gene number,
+ * 0 .. n_genes - 1, or -1 for a transcript without a gene; every call checks it on the host first
+ * (SKM_ERR_ARG for a value outside that range) and no kernel indexes by an unchecked value.
+ * skm_gene_sums: out[r][g] = the sum of values[r][t] over the transcripts t of gene g, added in
+ * ascending t, one after the other, from +0.0 -- numpy.add.at(out[r], tx_gene[named], values[r][named])
+ * bit for bit, whatever the grid.  Rows are staged in groups of at most 256 MB (SKM_GENE_GROUP, for
+ * tests: fewer rows per group). */
+int skm_gene_sums(int device, int64_t n_rows, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                  const double *values /*[n_rows][n_tx]*/, double *out /*[n_rows][n_genes]*/);
+/* Units that belong to exactly one gene (the rule of the reference's _calculate_uniquely_mapped_counts,
+ * seekmer/impute.py:149-183): a class whose transcripts all have tx_gene == g >= 0 adds its count to
+ * unique[sample][g]; one whose transcripts all have tx_gene == -1 adds to other[sample][1] (unnamed);
+ * every other class adds to other[sample][0] (ambiguous between genes).  Exact 64-bit integer sums.
+ * Any class table given as the CSR of skm_mapper_export; class_sample NULL = one sample.  A sample
+ * without classes gets zeros; so does every sample of an empty table.  SKM_ERR_ARG for a target not
+ * below n_tx, a sample not below n_samples, a negative count, offsets that do not ascend. */
+int skm_gene_unique_counts(int device, int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets,
+                           const int64_t *class_counts, const int32_t *class_sample, int64_t n_samples,
+                           int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                           int64_t *unique /*[n_samples][n_genes]*/, int64_t *other /*[n_samples][2]*/);
+/* The same on the table where it lies in HBM: nothing but tx_gene goes up, nothing but the result
+ * comes down.  SKM_ERR_ARG when a class names a transcript not below n_tx. */
+int skm_mapper_gene_counts(skm_mapper *mapper, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                           int64_t *unique /*[n_genes]*/, int64_t other[2]);
+/* Row i is skm_mapper_gene_counts of a mapper fed sample i alone (zeros for a sample without units).
+ * Waits for everything added to be mapped and keeps adders waiting while it reads, as _export; the
+ * classes' samples are the device arrays the set's view already holds.  SKM_ERR_ARG if cap_samples
+ * (rows of room in unique and other) is below the samples named so far.  Device rows are made for
+ * ranges of samples, 1 GiB of them at most (SKM_GENE_GROUP, for tests: fewer samples per range). */
+int skm_sample_set_gene_counts(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                               int64_t cap_samples, int64_t *unique /*[n_samples][n_genes]*/, int64_t *other);
 
 /* ------------------------------------------------------------ quantification
  * MapResult.effective_lengths (seekmer/mapper.py:134-141). */

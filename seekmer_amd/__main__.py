@@ -28,6 +28,8 @@ def parse_args(argv=None, parser=None):
     opts = vars(parser.parse_args(argv))
     if opts['subcommand'] in ('infer', 'infer-many', 'impute'):
         infer.length_model_option(parser, opts)
+    if opts['subcommand'] in ('infer', 'infer-many'):
+        infer.gene_option(opts)
     return opts
 
 

@@ -131,6 +131,11 @@ HIP_SYMBOLS = {
     'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),
     'skm_sample_set_split': (ctypes.c_int, [c_i64, c_i64p, c_i64p, c_i32p, c_i64, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
                                             c_i64p]),
+    'skm_gene_sums': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_i32p, c_f64p, c_f64p]),
+    'skm_gene_unique_counts': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_i32p, c_i64p, c_i32p, c_i64, c_i64, c_i64,
+                                              c_i32p, c_i64p, c_i64p]),
+    'skm_mapper_gene_counts': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32p, c_i64p, c_i64p]),
+    'skm_sample_set_gene_counts': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32p, c_i64, c_i64p, c_i64p]),
     'skm_quant_create': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64p, c_i32p, c_f64p,
                                         c_void_pp]),
     'skm_quant_create_from_mapper': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_void_pp]),

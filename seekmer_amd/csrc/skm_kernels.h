@@ -474,6 +474,28 @@ bool launch_multinomial(const unsigned long long *cum, int64_t n_classes, int64_
 void launch_u64_to_double(const unsigned long long *in, int64_t n, double *out, hipStream_t stream);
 void launch_double_to_u64(const double *in, int64_t n, unsigned long long *out, hipStream_t stream);
 
+// ---- gene-level tables (skm_genes.hip)
+// out[r][g] (r < n_rows <= 65535) = the sum of values[r][gene_tx[j]] for j = gene_off[g] .. gene_off[g + 1] - 1 in
+// that order, from +0.0: with gene_tx the transcripts by gene, ascending inside a gene, numpy.add.at bit for bit
+void launch_gene_sums(const double *values, int64_t n_rows, int64_t n_tx, const int64_t *gene_off,
+                      const int32_t *gene_tx, int64_t n_genes, double *out, hipStream_t stream);
+struct GeneClasses {              // a class table in HBM: a CSR (len = nullptr) or what class_compact leaves
+    int64_t n_classes;
+    const int64_t *start;         // [C]; [C + 1] offsets when len is nullptr
+    const int64_t *len;           // [C] or nullptr
+    const double *count_f64;      // [C] integers held as doubles, or nullptr: then count_i64
+    const int64_t *count_i64;
+    const int32_t *sample;        // [C] or nullptr: every class belongs to sample 0
+    const int32_t *ids;           // unsigned transcript ids, tuple order
+};
+// for the classes of the samples sample_first <= s < sample_end: unique[s - sample_first][g] += count where every id
+// of the class has tx_gene == g >= 0, other[s - sample_first][1] += count where every id has tx_gene == -1,
+// other[s - sample_first][0] += count otherwise (both zeroed by the caller).  tx_gene[n_tx] holds -1 .. n_genes - 1
+// (the caller has checked); an id not below n_tx sets *error = SKM_ERR_ARG and indexes nothing.
+void launch_gene_unique(const GeneClasses &t, const int32_t *tx_gene, int64_t n_tx, int64_t n_genes, int64_t sample_first,
+                        int64_t sample_end, unsigned long long *unique, unsigned long long *other, int *error,
+                        hipStream_t stream);
+
 // one hipFuncGetAttributes per translation unit: its code object is loaded now, not by a sample's first launch
 void warm_code_map();
 void warm_code_classes();

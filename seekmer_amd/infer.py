@@ -18,7 +18,7 @@ from . import _native
 from . import common
 from . import mapper
 
-__all__ = ['run', 'run_many', 'bias_correct', 'bias_pass', 'bias_correct_many', 'bias_pass_many', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
+__all__ = ['run', 'run_many', 'gene_map', 'gene_sums', 'gene_unique_counts', 'gene_table', 'bias_correct', 'bias_pass', 'bias_correct_many', 'bias_pass_many', 'quantify', 'quantify_many', 'quantify_tables', 'quantify_resident', 'em', 'output_results', 'bootstrap_quantify',
            'bootstrap_ranks']
 
 _LOG = logging.getLogger(__name__)
@@ -29,7 +29,7 @@ X_FLOOR = 1e-8          # seekmer/infer.py:160
 
 def run(index_path, output_path, fastq_paths, job_count, save_readmap,
         single_ended, bootstrap, debug, device=0, seed=None, parse_threads=None, strand=None, length_model=None,
-        bias=False, **__):
+        bias=False, genes=False, gene_map=None, **__):
     """The entrypoint of the inference module (seekmer/infer.py:27-85).
 
     Started as one process per GPU (`python -m torch.distributed.run --nproc-per-node N -m
@@ -49,25 +49,38 @@ def run(index_path, output_path, fastq_paths, job_count, save_readmap,
 
     bias: --bias, the sequence-bias correction (bias_correct): the mapper also counts the hexamer every aligned
     unit starts with; after the first quantification the effective lengths are rescaled by the hexamer
-    weights that follow from the counts and that estimate, and the EM runs once more from it.  One rank only."""
+    weights that follow from the counts and that estimate, and the EM runs once more from it.  One rank only.
+
+    genes / gene_map: --genes / --gene-map FILE (which implies --genes), the gene-level tables (gene_table):
+    abundance.genes.tsv, the genes/ datasets of abundance.npz and the gene counts of run_info.json, from the result
+    that is written (the corrected one with bias).  The genes are the index's, or those of the two-column file.
+    One rank only."""
     from . import parallel
     start_time = datetime.datetime.utcnow()
     ranks = parallel.Ranks.from_env()
     try:
         _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-             bootstrap, debug, device, seed, parse_threads, strand=strand, length_model=length_model, bias=bias)
+             bootstrap, debug, device, seed, parse_threads, strand=strand, length_model=length_model, bias=bias,
+             genes=genes or gene_map is not None, gene_map_path=gene_map)
     except BaseException as error:          # noqa: B902 -- one rank: re-raised as it is
         ranks.fail(error)
     ranks.close()
 
 
 def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, save_readmap, single_ended,
-         bootstrap, debug, device, seed, parse_threads, strand=None, length_model=None, bias=False):
+         bootstrap, debug, device, seed, parse_threads, strand=None, length_model=None, bias=False, genes=False,
+         gene_map_path=None):
     from . import parallel
     mapper.strand_mode(strand)              # (an unknown mode fails before any file is touched)
     length_model, _ = mapper.length_model_weights(length_model)      # (and so does a model that cannot be)
     if bias and ranks.world > 1:
         raise ValueError(BIAS_ONE_RANK)
+    if genes and ranks.world > 1:
+        raise ValueError(GENES_ONE_RANK)
+    index, gene_names = None, None
+    if genes:                               # (an index without genes fails before any read file is opened)
+        index = common.KMerIndex.load(index_path)
+        gene_names = gene_map(index, gene_map_path)
     if ranks.world > 1:
         device = ranks.local_rank
         if save_readmap:
@@ -92,7 +105,8 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
     # (the one-pass reader maps the text: its page tables are set up by helper threads while the index loads)
     ahead = common.Prefault(fastq_paths if one_pass and ranks.world == 1 else [], threads=4)
     try:
-        index = common.KMerIndex.load(index_path)
+        if index is None:
+            index = common.KMerIndex.load(index_path)
         index.device_handle(device)
         _LOG.info('Mapping all reads')
         map_result = mapper.map_reads(index, read_feeder, job_count=job_count,
@@ -119,13 +133,146 @@ def _run(ranks, start_time, index_path, output_path, fastq_paths, job_count, sav
                                                     strand, device=device)
     bootstrapped_results = bootstrap_ranks(summarized_results, main_result, bootstrap, ranks, seed=seed, device=device)
     if ranks.rank == 0:
+        gene_results = None
+        if genes:                           # (one rank: the mapper's table is the sample's, and still in HBM)
+            gene_results = gene_names + map_result.gene_unique_counts(gene_names[1], gene_names[0].size)
         output_results(output_path, index, start_time, summarized_results,
-                       main_result, bootstrapped_results)
+                       main_result, bootstrapped_results, genes=gene_results, device=device)
         _LOG.info('Wrote results to %s', output_path)
 
 
 BIAS_ONE_RANK = ('--bias runs in one process on one GPU: the hexamer counts of several ranks are not merged '
                  '(start it without a launcher)')
+
+
+GENES_ONE_RANK = ('--genes runs in one process on one GPU: the gene-level pass reads one resident class table '
+                  '(start it without a launcher)')
+NO_GENES = ('no transcript has a gene: build the index with a GTF annotation, or name the genes with '
+            '--gene-map FILE (transcript id, tab, gene id)')
+
+
+def gene_map(index, path=None):
+    """(gene_ids, tx_gene) for the gene-level tables: gene_ids the sorted distinct non-empty gene ids (an S array,
+    numpy.unique's order), tx_gene int32[T] the gene number of every transcript of the index, -1 for a transcript
+    without a gene.  The genes are index.transcripts['gene_id'] (from the GTF the index was built with) or, with
+    `path`, those of a two-column tab-separated file, transcript id then gene id: lines that begin with '#' are
+    comments, transcript ids are cut at the first '.' as index_builder.read_transcripts cuts them, a transcript
+    the file does not name has no gene, ids the index does not hold are counted and reported in one log line,
+    and one transcript given two different genes raises ValueError, as does a map that leaves no transcript with
+    a gene (NO_GENES).  The file may be compressed (common.decompress_and_open)."""
+    transcript_ids = numpy.asarray(index.transcripts['transcript_id'])
+    if path is None:
+        genes = numpy.asarray(index.transcripts['gene_id'])
+    else:
+        rows = {}
+        for row, id_ in enumerate(transcript_ids.tolist()):
+            rows.setdefault(id_, []).append(row)
+        named = [b''] * transcript_ids.size
+        unknown = 0
+        with common.decompress_and_open(path) as f:
+            for number, line in enumerate(f, 1):
+                line = line.rstrip(b'\r\n')
+                if not line.strip() or line.startswith(b'#'):
+                    continue
+                fields = line.split(b'\t')
+                if len(fields) < 2 or not fields[0].strip() or not fields[1].strip():
+                    raise ValueError('%s, line %d: expected a transcript id, a tab and a gene id' % (path, number))
+                id_, gene = fields[0].strip().split(b'.')[0], fields[1].strip()
+                if id_ not in rows:
+                    unknown += 1
+                    continue
+                for row in rows[id_]:
+                    if named[row] not in (b'', gene):
+                        raise ValueError('%s, line %d: transcript %s has the genes %s and %s'
+                                         % (path, number, id_.decode(), named[row].decode(), gene.decode()))
+                    named[row] = gene
+        if unknown:
+            _LOG.warning('%s names %d transcripts that the index does not hold', path, unknown)
+        genes = numpy.asarray(named, dtype='S') if named else numpy.zeros(0, dtype='S1')
+    has_gene = genes != b''
+    if not has_gene.any():
+        raise ValueError(NO_GENES)
+    gene_ids = numpy.unique(genes[has_gene])
+    tx_gene = numpy.full(genes.size, -1, dtype=numpy.int32)
+    tx_gene[has_gene] = numpy.searchsorted(gene_ids, genes[has_gene])
+    return gene_ids, tx_gene
+
+
+_gene_map = gene_map           # (run and run_many take the file's path as `gene_map`, the option's name)
+
+
+def gene_sums(tx_gene, n_genes, rows, device=0):
+    """f8[R, n_genes]: out[r][g] = the sum of rows[r][t] over the transcripts t with tx_gene[t] == g, added in
+    ascending t, one after the other, from +0.0 -- numpy.add.at(out[r], tx_gene[named], rows[r][named]) bit for
+    bit, on the device (skm_gene_sums).  rows f8[R, T] (one row: f8[T] gives f8[n_genes])."""
+    rows = numpy.ascontiguousarray(rows, dtype='f8')
+    one = rows.ndim == 1
+    if one:
+        rows = rows[None, :]
+    if rows.ndim != 2:
+        raise ValueError('gene_sums takes rows[R, T]')
+    tx_gene = mapper.gene_numbers(tx_gene, rows.shape[1])
+    n_genes = int(n_genes)
+    out = numpy.zeros((rows.shape[0], max(n_genes, 1)), dtype='f8')
+    _native.check(_native.hip().skm_gene_sums(
+        device, rows.shape[0], rows.shape[1], n_genes, _native.ptr(tx_gene, _native.c_i32p),
+        _native.ptr(rows, _native.c_f64p) if rows.size else None, _native.ptr(out, _native.c_f64p)))
+    out = out[:, :n_genes]
+    return out[0] if one else out
+
+
+def gene_unique_counts(results, tx_gene, n_genes, device=0):
+    """(unique int64[n_genes], other int64[2]) of any SummarizedResult's class table (skm_gene_unique_counts): a
+    class whose transcripts all lie in one named gene adds its count to unique[gene]; one whose transcripts are all
+    unnamed adds to other[1]; every other class adds to other[0] (ambiguous between genes).  The three add up to
+    results.aligned.  MapResult.gene_unique_counts gives the same from the table where it lies in HBM."""
+    class_count = numpy.ascontiguousarray(results.class_count, dtype=numpy.int64)
+    if getattr(results, 'class_offsets', None) is not None:
+        offsets, targets = results.class_offsets, results.class_targets
+    else:
+        offsets, targets = _csr_from_class_map(results.class_map, class_count.size)
+    offsets = numpy.ascontiguousarray(offsets, dtype=numpy.int64)
+    targets = numpy.ascontiguousarray(targets, dtype=numpy.int32)
+    tx_gene = mapper.gene_numbers(tx_gene, numpy.size(results.effective_lengths))
+    n_genes = int(n_genes)
+    unique = numpy.zeros(max(n_genes, 1), dtype=numpy.int64)
+    other = numpy.zeros(2, dtype=numpy.int64)
+    _native.check(_native.hip().skm_gene_unique_counts(
+        device, class_count.size, _native.ptr(offsets, _native.c_i64p),
+        _native.ptr(targets, _native.c_i32p) if targets.size else None,
+        _native.ptr(class_count, _native.c_i64p) if class_count.size else None, None, 1, tx_gene.size, n_genes,
+        _native.ptr(tx_gene, _native.c_i32p), _native.ptr(unique, _native.c_i64p), _native.ptr(other, _native.c_i64p)))
+    return unique[:n_genes], other
+
+
+GENE_COLUMNS = ('gene_id', 'n_transcripts', 'length', 'eff_length', 'est_count', 'tpm', 'unique_count')
+
+
+def gene_table(index, gene_ids, tx_gene, results, tpm, est_counts, unique, device=0):
+    """The columns of abundance.genes.tsv (GENE_COLUMNS) as a dict of arrays, one entry per gene of gene_ids, over
+    the gene's transcripts: tpm = sum of tpm; est_count = sum of est_count; length = sum of tpm x length / sum of
+    tpm where the gene has any tpm, otherwise the plain mean of its transcripts' lengths; eff_length the same from
+    the effective lengths; n_transcripts; unique_count = `unique` (gene_unique_counts).  The products are formed in
+    numpy; the sums are ONE gene_sums call with four rows (the plain means of the genes without tpm are numpy's,
+    in the same order).  Transcripts without a gene appear nowhere."""
+    tx_gene = numpy.asarray(tx_gene, dtype=numpy.int32)
+    n_genes = len(gene_ids)
+    tpm = numpy.asarray(tpm, dtype='f8')
+    length = numpy.asarray(index.transcripts['length'], dtype='f8')
+    effective = numpy.asarray(results.effective_lengths, dtype='f8')
+    sums = gene_sums(tx_gene, n_genes, numpy.stack([tpm, numpy.asarray(est_counts, dtype='f8'), tpm * length,
+                                                    tpm * effective]), device=device)
+    named = tx_gene >= 0
+    n_transcripts = numpy.bincount(tx_gene[named], minlength=n_genes).astype(numpy.int64)
+    columns = {'gene_id': numpy.asarray(gene_ids), 'n_transcripts': n_transcripts, 'est_count': sums[1], 'tpm': sums[0],
+               'unique_count': numpy.asarray(unique, dtype=numpy.int64)}
+    expressed = sums[0] > 0
+    for name, values, weighted in (('length', length, sums[2]), ('eff_length', effective, sums[3])):
+        plain = numpy.zeros(n_genes, dtype='f8')
+        numpy.add.at(plain, tx_gene[named], values[named])
+        columns[name] = numpy.where(expressed, weighted / numpy.where(expressed, sums[0], 1.0),
+                                    plain / numpy.maximum(n_transcripts, 1))
+    return columns
 
 
 def bias_correct(index, summarized, tpm, observed, strand, device=0):
@@ -279,7 +426,7 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
-             strand=None, names=None, length_model=None, bias=False, **__):
+             strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -302,7 +449,13 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     sample's first hexamers (SampleSet(bias=True)) and get the second pass together, before the bootstraps and the
     writing (bias_pass_many: one correction call, and inside the regime of impute.use_set_quant one shared second
     EM); every other sample, and every sample under SKM_INFER_MANY_PER_SAMPLE=1, counts in a mapper of its own and
-    gets bias_pass.  The files are the same either way."""
+    gets bias_pass.  The files are the same either way.
+
+    genes / gene_map: --genes / --gene-map, as run(): every folder gets what `infer --genes` writes for the sample,
+    and output/genes.tpm.tsv and output/genes.unique_counts.tsv hold genes as rows and samples as columns.  The
+    samples of the set get their gene-unique counts from ONE pass over the set's resident table
+    (SampleSet.gene_unique_counts), every other sample from its mapper's (MapResult.gene_unique_counts); the TPM
+    rows of all samples are summed per gene in one gene_sums call.  The files are the same either way."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -328,6 +481,9 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     _log_length_model(length_model, single_ended)
     _native.check(_native.hip().skm_pinned_set_device(device))
     index = common.KMerIndex.load(index_path)
+    genes = genes or gene_map is not None
+    gene_names = _gene_map(index, gene_map) if genes else None     # (fails before any read file is opened)
+    gene_counts = [None] * len(groups)
     index.device_handle(device)
     paired = not single_ended
     in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
@@ -346,6 +502,9 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         if bias:
             for i, row in zip(in_set, sample_set.bias_observed()):
                 observed[i] = row
+        if genes:                           # (one pass over the set's table where it lies)
+            for i, unique, other in zip(in_set, *sample_set.gene_unique_counts(gene_names[1], gene_names[0].size)):
+                gene_counts[i] = (unique, other)
         trace('mapping (set)')
         # (the main estimates of the set's samples in shared EM launches, from the table where it lies)
         if all(summaries[i].total for i in in_set) and impute.use_set_quant(
@@ -369,6 +528,8 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
         if bias:
             observed[i] = map_result.bias_observed()
+        if genes:
+            gene_counts[i] = map_result.gene_unique_counts(gene_names[1], gene_names[0].size)
         del map_result
     _LOG.info('Mapped all reads')
     trace('mapping (one by one)')
@@ -378,6 +539,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         if bootstrap > 0 and summary.aligned > RESAMPLE_LIMIT:
             raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
                              % (RESAMPLE_LIMIT, name, summary.aligned))
+    estimates = [None] * len(groups)        # (the TPM each sample is written with)
     corrected = {}
     if bias and in_set:
         # the second pass of the set's samples together; a sample that leaves no abundance above the floor, in
@@ -406,8 +568,16 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         trace('bootstraps', pause=True)
         sample_path = output_path / name
         sample_path.mkdir(exist_ok=True)
-        output_results(sample_path, index, start_time, summary, main_result, bootstrapped_results)
+        output_results(sample_path, index, start_time, summary, main_result, bootstrapped_results,
+                       genes=gene_names + gene_counts[i] if genes else None, device=device)
+        estimates[i] = main_result
         trace('writing', pause=True)
+    if genes:
+        gene_ids, tx_gene = gene_names
+        _output_gene_matrix(output_path / 'genes.tpm.tsv', gene_ids, names,
+                            gene_sums(tx_gene, gene_ids.size, numpy.stack(estimates), device=device), '%g')
+        _output_gene_matrix(output_path / 'genes.unique_counts.tsv', gene_ids, names,
+                            numpy.stack([unique for unique, _ in gene_counts]), '%d')
     with (output_path / 'samples.tsv').open('w') as f:
         for name, summary, mean in zip(names, summaries, means):
             f.write('%s\t%d\t%d\t%.2f\n' % (name, summary.total, summary.aligned, mean))
@@ -927,14 +1097,54 @@ def em(x, l, class_map, class_count, fixed_iters=0, return_iters=False, device=0
 
 # ------------------------------------------------------------------- outputs
 def output_results(output_path, index, start_time, results, main_abundance,
-                   bootstrapped_abundance):
-    """Output the quantification results (seekmer/infer.py:171-197)."""
+                   bootstrapped_abundance, genes=None, device=0):
+    """Output the quantification results (seekmer/infer.py:171-197).
+
+    genes: None, or (gene_ids, tx_gene, unique, other) of --genes (gene_map, gene_unique_counts): the run then
+    also writes abundance.genes.tsv, the genes/ datasets of abundance.npz and the gene counts of run_info.json;
+    every other byte is what it is without."""
     run_info = _generate_run_info(bootstrapped_abundance, index, results, start_time)
+    if genes is not None:
+        gene_ids, _, unique, other = genes
+        run_info.update(n_genes=int(len(gene_ids)), n_gene_unique=int(numpy.sum(unique)), n_gene_ambiguous=int(other[0]),
+                        n_gene_unnamed=int(other[1]))
+        _LOG.info('Genes: %d; units inside one gene %d, ambiguous between genes %d, of unnamed transcripts %d',
+                  run_info['n_genes'], run_info['n_gene_unique'], run_info['n_gene_ambiguous'], run_info['n_gene_unnamed'])
     with (output_path / 'run_info.json').open('w') as f:
         json.dump(run_info, f)
     est_counts = _infer_est_counts(index, results, main_abundance)
     _output_abundance_table(output_path, index, results, est_counts, main_abundance)
-    _output_arrays(output_path, index, results, run_info, est_counts, bootstrapped_abundance)
+    gene_arrays = {}
+    if genes is not None:
+        gene_ids, tx_gene, unique, _ = genes
+        table = gene_table(index, gene_ids, tx_gene, results, main_abundance, est_counts, unique, device=device)
+        _output_gene_table(output_path, table)
+        gene_arrays = {'genes/ids': table['gene_id'], 'genes/tpm': table['tpm'], 'genes/est_counts': table['est_count'],
+                       'genes/lengths': table['length'], 'genes/eff_lengths': table['eff_length'],
+                       'genes/unique_counts': table['unique_count']}
+        if len(bootstrapped_abundance):     # (all replicates in one call)
+            rows = gene_sums(tx_gene, len(gene_ids), numpy.stack(list(bootstrapped_abundance)), device=device)
+            for i, row in enumerate(rows):
+                gene_arrays['genes/bootstrap/bs{}'.format(i)] = row
+    _output_arrays(output_path, index, results, run_info, est_counts, bootstrapped_abundance, extra=gene_arrays)
+
+
+def _output_gene_table(output_path, table):
+    """abundance.genes.tsv: GENE_COLUMNS, one line per named gene in gene_ids order; tab separated, floats as %g"""
+    with (output_path / 'abundance.genes.tsv').open('w') as f:
+        f.write('\t'.join(GENE_COLUMNS) + '\n')
+        # (columns as Python lists: indexing numpy arrays element by element is most of such a loop's time)
+        columns = [numpy.asarray(table[name]).tolist() for name in GENE_COLUMNS]
+        f.writelines('%s\t%d\t%g\t%g\t%g\t%g\t%d\n' % (gene.decode(), n, length, eff, est, tpm, unique)
+                     for gene, n, length, eff, est, tpm, unique in zip(*columns))
+
+
+def _output_gene_matrix(path, gene_ids, names, matrix, fmt):
+    """genes as rows, samples as columns in sample order; a header line of the sample names"""
+    with path.open('w') as f:
+        f.write('\t'.join(['gene_id'] + list(names)) + '\n')
+        for gene, values in zip(numpy.asarray(gene_ids).tolist(), numpy.asarray(matrix).T.tolist()):
+            f.write('\t'.join([gene.decode()] + [fmt % value for value in values]) + '\n')
 
 
 def _generate_run_info(bootstrapped_abundance, index, results, start_time):
@@ -984,7 +1194,7 @@ def _infer_est_counts(index, results, main_abundance):
     return est_counts
 
 
-def _output_arrays(output_path, index, results, run_info, est_counts, bootstrapped_abundance):
+def _output_arrays(output_path, index, results, run_info, est_counts, bootstrapped_abundance, extra=None):
     """The datasets of abundance.h5 (seekmer/infer.py:255-325) as abundance.npz:
     PyTables/h5py are not installed here, so the kallisto-compatible HDF5
     container itself is out of reach; dataset names
@@ -1007,6 +1217,7 @@ def _output_arrays(output_path, index, results, run_info, est_counts, bootstrapp
     }
     for i, bootstrap in enumerate(bootstrapped_abundance):
         arrays['bootstrap/bs{}'.format(i)] = bootstrap
+    arrays.update(extra or {})              # (--genes: the genes/ datasets)
     with (output_path / 'abundance.npz').open('wb') as f:
         numpy.savez(f, **arrays)
 
@@ -1037,6 +1248,7 @@ def add_subcommand_parser(subparsers):
     add_strand_arguments(parser)
     add_length_model_arguments(parser)
     add_bias_argument(parser)
+    add_gene_arguments(parser)
 
 
 def add_many_subcommand_parser(subparsers):
@@ -1066,6 +1278,22 @@ def add_many_subcommand_parser(subparsers):
     add_strand_arguments(parser)
     add_length_model_arguments(parser)
     add_bias_argument(parser)
+    add_gene_arguments(parser)
+
+
+def add_gene_arguments(parser):
+    """--genes and --gene-map FILE: dest 'genes', 'gene_map' (gene_option makes the second imply the first)."""
+    parser.add_argument('--genes', action='store_true', dest='genes',
+                        help='also write gene-level tables: abundance.genes.tsv (sums per gene, and the reads that '
+                             'belong to exactly one gene) from the genes the index was built with (one GPU)')
+    parser.add_argument('--gene-map', type=pathlib.Path, dest='gene_map', default=None, metavar='FILE',
+                        help='take the genes from FILE (transcript id, tab, gene id) instead; implies --genes')
+
+
+def gene_option(opts):
+    """The parsed options: --gene-map implies --genes."""
+    opts['genes'] = bool(opts.get('genes')) or opts.get('gene_map') is not None
+    return opts
 
 
 def add_bias_argument(parser):

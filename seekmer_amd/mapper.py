@@ -69,6 +69,14 @@ def length_model_weights(length_model):
     return (float(mean), float(sd)), weights
 
 
+def gene_numbers(tx_gene, n_tx):
+    """tx_gene as the contiguous int32[n_tx] the native gene calls take (ValueError for another length)"""
+    tx_gene = numpy.ascontiguousarray(tx_gene, dtype=numpy.int32)
+    if tx_gene.shape != (n_tx,):
+        raise ValueError('a gene number for each of the %d transcripts, not %s' % (n_tx, tx_gene.shape))
+    return tx_gene if tx_gene.size else numpy.zeros(1, dtype=numpy.int32)[:0]
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
@@ -145,6 +153,18 @@ class MapResult:
         out = numpy.zeros(4096, dtype=numpy.int64)
         _native.check(_native.hip().skm_mapper_bias_observed(self._handle, _native.ptr(out, _native.c_i64p)))
         return out
+
+    def gene_unique_counts(self, tx_gene, n_genes):
+        """(unique int64[n_genes], other int64[2]) of the table where it lies in HBM (skm_mapper_gene_counts): the
+        units whose class lies inside one gene, by gene; other = (units ambiguous between genes, units of unnamed
+        transcripts only).  tx_gene int32[n_tx]: gene number of every transcript, -1 without one (infer.gene_map)."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        unique = numpy.zeros(max(int(n_genes), 1), dtype=numpy.int64)
+        other = numpy.zeros(2, dtype=numpy.int64)
+        _native.check(_native.hip().skm_mapper_gene_counts(
+            self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p),
+            _native.ptr(unique, _native.c_i64p), _native.ptr(other, _native.c_i64p)))
+        return unique[:int(n_genes)], other
 
     def set_length_model(self, length_model):
         """(mean, sd), or None for the observed histogram again; it affects later calls only."""
@@ -737,6 +757,28 @@ class SampleSet:
                 continue
             _native.check(code)
             return out
+
+    def gene_unique_counts(self, tx_gene, n_genes):
+        """(unique int64[n_samples, n_genes], other int64[n_samples, 2]): row i is MapResult.gene_unique_counts of
+        sample i mapped alone (zeros for a sample without units), from the set's table where it lies in HBM
+        (skm_sample_set_gene_counts)."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        n_genes = int(n_genes)
+        # (samples may be added meanwhile: the call says when there are more than the rows it was given)
+        while True:
+            rows = len(self)
+            unique = numpy.zeros((rows, max(n_genes, 1)), dtype=numpy.int64)
+            other = numpy.zeros((rows, 2), dtype=numpy.int64)
+            if n_genes == 0:
+                unique = unique[:, :0]
+            code = _native.hip().skm_sample_set_gene_counts(
+                self._handle, tx_gene.size, n_genes, _native.ptr(tx_gene, _native.c_i32p), rows,
+                _native.ptr(unique, _native.c_i64p) if unique.size else None,
+                _native.ptr(other, _native.c_i64p) if other.size else None)
+            if code == _native.SKM_ERR_ARG and len(self) > rows:
+                continue
+            _native.check(code)
+            return unique, other
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
