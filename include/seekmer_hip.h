@@ -653,7 +653,8 @@ int skm_sample_set_quantify(skm_sample_set *set, const double *lengths, int64_t 
 /* The connected components of the (class, transcript) graph and the tiles the one-GPU EM steps them in
  * (diagnostics, tests).  info[0] = tiles were built, [1] = tiles, [2] = components above the tile capacity
  * (any: the EM steps the whole table as one problem), [3] = the EM of this handle runs on the tiles,
- * [4..6] = tile capacity in pairs, classes, transcripts.  Optional arrays: tx_label[n_tx] = smallest
+ * [4..6] = tile capacity in pairs, classes, transcripts, [7] = transcript ids per packing run (a tile lies
+ * within one run).  Optional arrays: tx_label[n_tx] = smallest
  * transcript id of the transcript's component, tx_tile[n_tx] = its tile (n_tx: none), class_tile
  * [n_classes] = tile of every class in the caller's class order. */
 int skm_quant_components(skm_quant *quant, int64_t info[8], int32_t *tx_label, int32_t *tx_tile,

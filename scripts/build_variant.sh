@@ -10,9 +10,12 @@ cd "$(dirname "$0")/../seekmer_amd/csrc"
 make -s ../libseekmer_hip.so
 mkdir -p build_$name
 objs=""
-for src in skm_abi.hip skm_map.hip skm_classes.hip skm_em.hip skm_em_batch.hip skm_em_set.hip skm_quant_setup.hip skm_pool.hip skm_strand.hip skm_samples.hip skm_bias.hip; do
+for src in skm_abi.hip skm_map.hip skm_classes.hip skm_em.hip skm_em_batch.hip skm_em_set.hip skm_quant_setup.hip skm_pool.hip skm_strand.hip skm_samples.hip skm_bias.hip skm_genes.hip; do
   if [[ " $files " == *" $src "* ]]; then
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function $flags -c $src -o build_$name/${src%.hip}.o
+    # (the compiler's resource remarks beside the object, as the product build keeps them)
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function $flags \
+      -Rpass-analysis=kernel-resource-usage -c $src -o build_$name/${src%.hip}.o 2> build_$name/${src%.hip}.remarks \
+      || { cat build_$name/${src%.hip}.remarks; exit 1; }
     objs="$objs build_$name/${src%.hip}.o"
   else
     objs="$objs build/${src%.hip}.o"

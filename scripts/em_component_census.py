@@ -21,7 +21,7 @@ def tile_capacity():
     """(pairs, classes, transcripts): EM_TILE_* as seekmer_amd/csrc/skm_kernels.h defines them."""
     import re
     text = open(os.path.join(ROOT, 'seekmer_amd', 'csrc', 'skm_kernels.h')).read()
-    return tuple(int(re.search(r'\b%s = (\d+)' % name, text).group(1))
+    return tuple(int(re.search(r'#define SKM_%s (\d+)' % name, text).group(1))
                  for name in ('EM_TILE_PAIRS', 'EM_TILE_CLASSES', 'EM_TILE_TX'))
 
 

@@ -28,8 +28,8 @@ from em_component_census import labels    # noqa: E402
 
 def constants():
     text = open(os.path.join(ROOT, 'seekmer_amd', 'csrc', 'skm_kernels.h')).read()
-    return {name: int(re.search(r'\b%s(?: =|\b) (\d+)' % name, text).group(1))
-            for name in ('EM_TILE_PAIRS', 'EM_TILE_CLASSES', 'EM_TILE_TX', 'SKM_EM_TILE_SEGMENT', 'EM_TILE_CLASS_BATCH', 'EM_ROW_CAP')}
+    return {name: int(re.search(r'(?:#define SKM_%s|\b%s =) (\d+)' % (name, name), text).group(1))
+            for name in ('EM_TILE_PAIRS', 'EM_TILE_CLASSES', 'EM_TILE_TX', 'EM_TILE_SEGMENT', 'EM_TILE_CLASS_BATCH', 'EM_ROW_CAP')}
 
 
 def internal_order(class_map, n_tx):
@@ -56,10 +56,10 @@ def pack_tiles(n_tx, offsets, targets, k):
     c_classes = np.bincount(label[targets[offsets[:-1][lens > 0]]], minlength=n_tx)
     root_tile = np.full(n_tx, -1, dtype=np.int64)
     n_tiles = 0
-    for first in range(0, n_tx, k['SKM_EM_TILE_SEGMENT']):
+    for first in range(0, n_tx, k['EM_TILE_SEGMENT']):
         tx = pairs = classes = 0
         opened = False
-        for t in range(first, min(n_tx, first + k['SKM_EM_TILE_SEGMENT'])):
+        for t in range(first, min(n_tx, first + k['EM_TILE_SEGMENT'])):
             if c_tx[t] == 0:
                 continue
             if c_tx[t] > k['EM_TILE_TX'] or c_pairs[t] > k['EM_TILE_PAIRS'] or c_classes[t] > k['EM_TILE_CLASSES']:

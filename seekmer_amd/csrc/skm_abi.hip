@@ -4068,7 +4068,7 @@ extern "C" int skm_quant_components(skm_quant *q, int64_t info[8], int32_t *tx_l
     info[1] = t.n_tiles;
     info[2] = t.n_oversize;
     info[3] = em_uses_tiles(q) ? 1 : 0;
-    info[4] = EM_TILE_PAIRS; info[5] = EM_TILE_CLASSES; info[6] = EM_TILE_TX; info[7] = 0;
+    info[4] = EM_TILE_PAIRS; info[5] = EM_TILE_CLASSES; info[6] = EM_TILE_TX; info[7] = EM_TILE_SEGMENT;
     if (!t.built) {
         if (tx_label || tx_tile || class_tile) return fail(SKM_ERR_ARG, "no component tiles were built for this handle");
         return SKM_OK;

@@ -257,11 +257,24 @@ void launch_em_result(const unsigned long long *ctl, const double *x0, const dou
 // transcript id) are packed into TILES of at most EM_TILE_PAIRS pairs, EM_TILE_CLASSES classes and
 // EM_TILE_TX transcripts; one workgroup keeps a tile's two views, `inner` and both abundance vectors in
 // LDS and runs a whole chunk of steps with workgroup barriers only.
-constexpr int EM_TILE_PAIRS = 2048, EM_TILE_CLASSES = 512, EM_TILE_TX = 128;
-#ifndef SKM_EM_TILE_SEGMENT              // (a sweep aid, scripts/build_variant.sh: results do not depend on it)
-#define SKM_EM_TILE_SEGMENT 128
+// (the four values are sweep aids, scripts/build_variant.sh with skm_abi.hip, skm_em.hip and
+// skm_quant_setup.hip: results do not depend on them)
+#ifndef SKM_EM_TILE_PAIRS
+#define SKM_EM_TILE_PAIRS 2048
 #endif
+#ifndef SKM_EM_TILE_CLASSES
+#define SKM_EM_TILE_CLASSES 512
+#endif
+#ifndef SKM_EM_TILE_TX
+#define SKM_EM_TILE_TX 128
+#endif
+#ifndef SKM_EM_TILE_SEGMENT
+#define SKM_EM_TILE_SEGMENT 256
+#endif
+constexpr int EM_TILE_PAIRS = SKM_EM_TILE_PAIRS, EM_TILE_CLASSES = SKM_EM_TILE_CLASSES, EM_TILE_TX = SKM_EM_TILE_TX;
+static_assert(EM_TILE_PAIRS <= 65535 && EM_TILE_CLASSES <= 65535 && EM_TILE_TX <= 65535, "tile-local indices and offsets are 16 bits wide");
 constexpr int EM_TILE_SEGMENT = SKM_EM_TILE_SEGMENT;     // tiles are packed within runs of this many transcript ids (set-up)
+static_assert(EM_TILE_SEGMENT > 0, "a packing run holds at least one transcript id");
 constexpr int EM_CHUNK_MAX = 16;         // steps of one launch at most
 constexpr int EM_TILE_CLASS_BATCH = 4;   // tuple entries a lane of the class phase fetches together; the set-up
                                          // lists a tile's classes by their number of such batches

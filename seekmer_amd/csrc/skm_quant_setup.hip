@@ -836,43 +836,61 @@ cc_classes_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_class
     }
 }
 
-// One lane per run of EM_TILE_SEGMENT transcript ids: the components rooted there, in label order, go
+// One wave per run of EM_TILE_SEGMENT transcript ids: the components rooted there, in label order, go
 // into the run's tiles one after the other, a new tile whenever the next component would exceed a
 // capacity.  root_tile[r] = tile within the run, -1: not a root, -2: above the capacity by itself.
+// Components are disjoint, so a tile's three fills are sums of its components' sizes: the wave takes 64
+// ids at a time, forms the inclusive prefix sums of the sizes over its lanes (a component that goes into
+// no tile counts as 0) and finds the open tile's end with a ballot -- the first lane whose prefix sum,
+// less the sum at the tile's start, is above a capacity opens the next tile.  One turn of that loop per
+// tile; the fill of the tile left open is carried to the next 64 ids.
 __global__ void __launch_bounds__(256)
 tile_pack_kernel(const int32_t *__restrict__ comp, int64_t n_tx, int64_t n_segments, int32_t *__restrict__ root_tile,
                  int64_t *__restrict__ seg_tiles, unsigned long long *__restrict__ oversize)
 {
-    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < n_segments;
-         g += (int64_t)gridDim.x * blockDim.x) {
-        int tx = 0, pairs = 0, classes = 0, n = 0;
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t g = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; g < n_segments; g += n_waves) {
+        int tx = 0, pairs = 0, classes = 0, n = 0;          // (wave-uniform: the open tile's fill, the run's tiles)
         const int64_t last = min(n_tx, (g + 1) * EM_TILE_SEGMENT);
-        // (the walk is serial; the sizes of eight transcripts at a time are fetched ahead of it)
-        for (int64_t t0 = g * EM_TILE_SEGMENT; t0 < last; t0 += 8) {
-            int size[24];
-#pragma unroll
-            for (int k = 0; k < 24; ++k) size[k] = 3 * t0 + k < 3 * n_tx ? comp[3 * t0 + k] : 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int64_t t = t0 + k;
-                if (t >= last) break;
-                const int c_tx = size[3 * k], c_pairs = size[3 * k + 1], c_classes = size[3 * k + 2];
-                if (c_tx == 0) { root_tile[t] = -1; continue; }
-                if (c_tx > EM_TILE_TX || c_pairs > EM_TILE_PAIRS || c_classes > EM_TILE_CLASSES) {
-                    root_tile[t] = -2;
-                    atomicAdd(oversize, 1ULL);
-                    continue;
-                }
-                if (n == 0 || tx + c_tx > EM_TILE_TX || pairs + c_pairs > EM_TILE_PAIRS ||
-                    classes + c_classes > EM_TILE_CLASSES) {
-                    ++n;
-                    tx = pairs = classes = 0;
-                }
-                tx += c_tx; pairs += c_pairs; classes += c_classes;
-                root_tile[t] = n - 1;
+        for (int64_t t0 = g * EM_TILE_SEGMENT; t0 < last; t0 += 64) {
+            const int64_t t = t0 + lane;
+            int c_tx = 0, c_pairs = 0, c_classes = 0;
+            if (t < last) { c_tx = comp[3 * t]; c_pairs = comp[3 * t + 1]; c_classes = comp[3 * t + 2]; }
+            const bool root = c_tx > 0;
+            const bool big = c_tx > EM_TILE_TX || c_pairs > EM_TILE_PAIRS || c_classes > EM_TILE_CLASSES;
+            const bool packed = root && !big;
+            if (!packed) c_tx = c_pairs = c_classes = 0;
+            int s_tx = c_tx, s_pairs = c_pairs, s_classes = c_classes;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int a = __shfl_up(s_tx, d, 64), b = __shfl_up(s_pairs, d, 64), c = __shfl_up(s_classes, d, 64);
+                if (lane >= d) { s_tx += a; s_pairs += b; s_classes += c; }
             }
+            // (the prefix sums at the open tile's start: what the tile held before these 64 ids lies before lane 0)
+            int base_tx = -tx, base_pairs = -pairs, base_classes = -classes, opened = 0;   // opened: tiles begun up to this lane
+            const int before = n;
+            unsigned long long behind = ~0ULL;                  // the lanes behind the last tile start
+            for (;;) {
+                const bool over = packed && (n == 0 || s_tx - base_tx > EM_TILE_TX || s_pairs - base_pairs > EM_TILE_PAIRS ||
+                                             s_classes - base_classes > EM_TILE_CLASSES);
+                const unsigned long long starts = __ballot(over) & behind;
+                if (!starts) break;
+                const int at = __ffsll((long long)starts) - 1;
+                base_tx = __shfl(s_tx - c_tx, at, 64);
+                base_pairs = __shfl(s_pairs - c_pairs, at, 64);
+                base_classes = __shfl(s_classes - c_classes, at, 64);
+                ++n;
+                if (lane >= at) ++opened;
+                behind = at == 63 ? 0ULL : ~0ULL << (at + 1);   // (the component at the start fits by itself)
+            }
+            if (t < last) root_tile[t] = !root ? -1 : big ? -2 : before + opened - 1;
+            const unsigned long long bigs = __ballot(root && big);
+            if (bigs && lane == 0) atomicAdd(oversize, (unsigned long long)__popcll(bigs));
+            tx = __shfl(s_tx, 63, 64) - base_tx;
+            pairs = __shfl(s_pairs, 63, 64) - base_pairs;
+            classes = __shfl(s_classes, 63, 64) - base_classes;
         }
-        seg_tiles[g] = n;
+        if (lane == 0) seg_tiles[g] = n;
     }
 }
 
@@ -1014,7 +1032,7 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
                        q.tx_label, comp);
     hipLaunchKernelGGL(cc_classes_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C,
                        q.tx_label, comp);
-    hipLaunchKernelGGL(tile_pack_kernel, dim3(blocks_for(n_segments)), dim3(256), 0, stream, comp, T, n_segments,
+    hipLaunchKernelGGL(tile_pack_kernel, dim3(blocks_for(64 * n_segments)), dim3(256), 0, stream, comp, T, n_segments,
                        root_tile, seg_tiles, oversize);
     if (exclusive_scan_with_total(scratch, seg_tiles, seg_base, n_segments)) return -1;
     int end_bit = 1;

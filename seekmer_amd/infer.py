@@ -732,7 +732,7 @@ class _QuantHandle:
         _native.check(_native.hip().skm_quant_components(self.handle, _native.ptr(raw, _native.c_i64p),
                                                          None, None, None))
         info = {'built': bool(raw[0]), 'tiles': int(raw[1]), 'oversize': int(raw[2]), 'em_uses_tiles': bool(raw[3]),
-                'capacity': (int(raw[4]), int(raw[5]), int(raw[6]))}
+                'capacity': (int(raw[4]), int(raw[5]), int(raw[6])), 'segment': int(raw[7])}
         if not arrays or not info['built']:
             return info, None, None, None
         label = numpy.zeros(self.n_tx, dtype=numpy.int32)
