@@ -322,6 +322,14 @@ int skm_mapper_reset(skm_mapper *mapper);
  * the sizing of the merges are those of production.  skm_mapper_clear and skm_mapper_reset keep
  * the table as large as it has grown. */
 int skm_mapper_timing(skm_mapper *mapper, double stats[8]);
+/* *count = map kernel launches this mapper has repeated because a batch's target ids outgrew the entry
+ * arena (sized for about 8 ids a unit; the repeat runs in an arena of the first launch's cursor and
+ * takes exactly what every tuple needs, so one repeat always suffices).  0 for ordinary reads.
+ * Test hook SKM_TEST_MAP_BLOCKS=N (1 <= N <= 2^30; SKM_ERR_ARG otherwise), read by skm_mapper_create:
+ * the map kernel's grid is min(N, what the batch and the device give), so a small batch refills the
+ * unit contexts of a block many times and the block drains its tail as a large batch does; the
+ * workspace and the arena are sized from the blocks launched, as ever. */
+int skm_mapper_map_relaunches(skm_mapper *mapper, int64_t *count);
 /* Access counters of the instrumented build of the map kernel (they define the
  * algorithmic bytes): enable, map, then read.  out[0]=reads
  * [1]=read bases [2]=lookups [3]=slots probed [4]=ContigEntry reads [5]=target
@@ -384,6 +392,8 @@ int skm_sample_set_add_batch(skm_sample_set *set, int64_t sample, int64_t first_
                              const char *bases, const int64_t *offsets, int64_t n_units);
 /* waits for everything added to be mapped; the set's failure, if there is one */
 int skm_sample_set_sync(skm_sample_set *set);
+/* skm_mapper_map_relaunches of the set's launches (waits for everything added to be mapped) */
+int skm_sample_set_map_relaunches(skm_sample_set *set, int64_t *count);
 /* *n_samples = samples of the set; summary[4 i .. 4 i + 3] for the samples i < min(cap_samples,
  * *n_samples) = skm_mapper_summary of sample i: C classes, M (class, target) rows, unaligned (the
  * sample's units minus the sum of its class counts), total units.  With cap_samples = 0 (summary

@@ -105,6 +105,8 @@ HIP_SYMBOLS = {
     'skm_mapper_clear': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_mapper_reset': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_mapper_timing': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
+    'skm_mapper_map_relaunches': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_sample_set_map_relaunches': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_mapper_set_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_access_stats': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_effective_lengths': (ctypes.c_int, [ctypes.c_int, c_i64p, c_f64p, c_i64, c_f64p]),

@@ -237,6 +237,8 @@ struct skm_mapper {
     double t_em_ns = 0, em_iters = 0;          // skm_quant_infer calls on this mapper
     bool test_class_slots = false;             // SKM_TEST_CLASS_SLOTS: table_reserve[_for_sample] leave the slot count alone
     int64_t deferred_grows = 0;                // table_grow calls with units in flight (after a pass that deferred units)
+    int test_map_blocks = 0;                   // SKM_TEST_MAP_BLOCKS: a cap on the map kernel's grid (0: none)
+    int64_t map_relaunches = 0;                // map kernel launches repeated because the entry arena overflowed
     unsigned long long stats_total[48] = {0};
     // ---- host batches: staging lanes + one worker (skm_mapper_map_batch[_async])
     // A host batch is copied to HBM on a lane's own stream by the thread that submits it (the
@@ -1259,6 +1261,7 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     // (2 lists of max_target_count entries) would not fit the budget
     constexpr int64_t CONTEXTS = MAP_CONTEXTS;
     int64_t blocks = std::min<int64_t>((n_units + CONTEXTS - 1) / CONTEXTS, (int64_t)ix->cu_count * MAP_BLOCKS_PER_CU);
+    if (m->test_map_blocks) blocks = std::min<int64_t>(blocks, m->test_map_blocks);
     // per context: mask extension words (live + staging, two mates) for slices > 64 targets
     const int64_t ext_words = std::max<int64_t>(0, (ix->d.max_target_count + 63) / 64 - 1);
     SKM_TRY(m->workspace.ensure((size_t)(blocks * CONTEXTS * 4 * ext_words * 2 + 16)));
@@ -1270,7 +1273,7 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
                         (long long)n_units, max_len);
     }
     // entry arena: ~8 ids per unit plus one 2048-id slice of slack per wave
-    SKM_TRY(m->unit_entries.ensure((size_t)n_units * 8 + (size_t)blocks * (MAP_THREADS / 64) * 2048 + 4096));
+    SKM_TRY(m->unit_entries.ensure((size_t)n_units * 8 + (size_t)blocks * (MAP_THREADS / 64) * MAP_ARENA_CHUNK + 4096));
 
     MapBatch b{};
     b.records = m->records.p;
@@ -1297,9 +1300,19 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(m->ev[1], m->stream));
     unsigned long long ids = 0;
-    for (int attempt = 0; attempt < 3; ++attempt) {
+    // A launch whose ids outgrow the arena stores none of the tuples that do not fit and is run again
+    // in a larger one.  A wave takes max(its emission, MAP_ARENA_CHUNK) ids per grab and gives up what is
+    // left of a chunk that the next emission does not fit, so the cursor of such a launch depends on
+    // how the finished units happened to meet in emission waves, which differs from launch to launch:
+    // it bounds no later launch of the same kind.  The relaunch therefore takes exactly what each
+    // emission writes (ids_chunk = 0).  Its cursor is the sum of the batch's tuple lengths whatever the
+    // grouping, and that sum is at most the first launch's cursor, because every emission of the first
+    // launch lay wholly inside a chunk of its own wave and the chunks are disjoint.  An arena of the
+    // first cursor's size cannot overflow a second time.
+    for (int attempt = 0; attempt < 2; ++attempt) {
         b.unit_entries = m->unit_entries.p;
         b.ids_capacity = (int64_t)m->unit_entries.cap;
+        b.ids_chunk = attempt == 0 ? MAP_ARENA_CHUNK : 0;
         HIP_TRY(hipMemsetAsync(m->batch_ctl.p, 0, BC_WORDS * sizeof(unsigned long long), m->stream));
         launch_map_units(ix->d, b, m->grid_blocks, m->want_stats, m->stream);
         HIP_TRY(hipGetLastError());
@@ -1310,8 +1323,9 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
         ids = cursor_and_flag[0];
         if (cursor_and_flag[1]) return fail(SKM_ERR_STATE, "map kernel: the in-kernel scheduler stalled");
         if ((int64_t)ids <= b.ids_capacity) break;
-        if (attempt == 2) return fail(SKM_ERR_STATE, "entry arena overflow");
-        SKM_TRY(m->unit_entries.ensure((size_t)ids + 1024));
+        if (attempt == 1) return fail(SKM_ERR_STATE, "entry arena overflow");
+        SKM_TRY(m->unit_entries.ensure((size_t)ids));
+        m->map_relaunches += 1;
     }
     m->last_ids = (int64_t)ids;
     if (m->want_stats) {
@@ -1443,6 +1457,12 @@ extern "C" int skm_mapper_create(skm_index *ix, skm_mapper **out)
             return fail(SKM_ERR_ARG, "SKM_TEST_CLASS_SLOTS must be a power of two from 2 to 2^30, not '%s'", v);
         first_slots = (uint64_t)n;
         m->test_class_slots = true;
+    }
+    if (const char *v = getenv("SKM_TEST_MAP_BLOCKS")) {         // test hook: few blocks, so that contexts are refilled
+        const long long n = atoll(v);
+        if (n < 1 || n > (1LL << 30))
+            return fail(SKM_ERR_ARG, "SKM_TEST_MAP_BLOCKS must be a number from 1 to 2^30, not '%s'", v);
+        m->test_map_blocks = (int)n;
     }
     SKM_TRY(table_reset(m.get(), first_slots));
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -2499,6 +2519,15 @@ extern "C" int skm_mapper_timing(skm_mapper *m, double stats[8])
     return SKM_OK;
 }
 
+extern "C" int skm_mapper_map_relaunches(skm_mapper *m, int64_t *count)
+{
+    if (!m || !count) return fail(SKM_ERR_ARG, "NULL argument");
+    (void)wait_jobs(m, 0, false);
+    std::lock_guard<std::mutex> lock(m->mu);
+    *count = m->map_relaunches;
+    return SKM_OK;
+}
+
 // access counters of the STATS build of the map kernel (SKM_MAP_STATS=1):
 // [0]=reads [1]=read bases [2]=lookups [3]=slots [4]=contig reads [5]=targets
 // copied [6]=targets merged [7]=8-base fetches [8]=merges [9]=tuple ids
@@ -3019,6 +3048,13 @@ extern "C" int skm_sample_set_sync(skm_sample_set *s)
 {
     if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
     return set_wait(s);
+}
+
+extern "C" int skm_sample_set_map_relaunches(skm_sample_set *s, int64_t *count)
+{
+    if (!s || !count) return fail(SKM_ERR_ARG, "NULL argument");
+    SKM_TRY(set_wait(s));
+    return skm_mapper_map_relaunches(s->m, count);
 }
 
 extern "C" int skm_sample_set_summary(skm_sample_set *s, int64_t cap_samples, int64_t *n_samples, int64_t *summary)

@@ -28,6 +28,10 @@ struct MapBatch {
     Coord *unit_anchor;
     int32_t *unit_entries;        // signed target entries, units in arena order
     int64_t ids_capacity;
+    // ids a wave takes from the entry arena per atomic at the least (MAP_ARENA_CHUNK); 0: exactly what
+    // an emission writes, so that the final cursor is the sum of the tuple lengths (the relaunch
+    // after an overflow, map_batch_resident)
+    int32_t ids_chunk;
     unsigned long long *ids_cursor;
     unsigned long long *fld;      // [2000] batch-local histogram
     unsigned long long *stats;    // [16] access counters (STATS build only)
@@ -48,6 +52,7 @@ constexpr int MAP_BLOCKS_PER_CU = 4;
 #define SKM_MAP_CONTEXTS 480
 #endif
 constexpr int MAP_CONTEXTS = SKM_MAP_CONTEXTS;   // unit contexts per block: 16 words + 7 ring entries each, 4 blocks in 160 KB of LDS
+constexpr int MAP_ARENA_CHUNK = 2048;            // ids a wave takes from the entry arena per atomic
 
 void launch_pack_reads(const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                        int words_per_read, int record_words, uint32_t *records, hipStream_t stream);

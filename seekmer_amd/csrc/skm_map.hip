@@ -830,7 +830,6 @@ constexpr int SIGNED_CANDIDATES = SKM_SIGNED_CANDIDATES;            // ... with 
 
 
 constexpr int NCTX = MAP_CONTEXTS;    // unit contexts per block (LDS)
-constexpr int ARENA_CHUNK = 2048;     // ids a wave takes from the entry arena per atomic
 
 constexpr int FLD_WINDOW = 512;       // fragment lengths below this are counted in LDS
 
@@ -1486,7 +1485,7 @@ map_units_kernel(DevIndex ix, MapBatch b)
                 }
                 const int wave_total = __shfl(scan, 63, 64);
                 if (chunk_pos + wave_total > chunk_end) {
-                    const int64_t want = wave_total > ARENA_CHUNK ? wave_total : ARENA_CHUNK;
+                    const int64_t want = wave_total > b.ids_chunk ? wave_total : b.ids_chunk;
                     unsigned long long got = 0;
                     if (lane == 0) got = atomicAdd(b.ids_cursor, (unsigned long long)want);
                     chunk_pos = (int64_t)__shfl(got, 0, 64);

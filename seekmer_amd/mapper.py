@@ -387,12 +387,15 @@ class MapResult:
 
     def timing(self):
         """skm_mapper_timing by name; 'deferred_grows' (stats[7]) counts the times the class table
-        grew under a batch whose bounded probes had deferred units."""
+        grew under a batch whose bounded probes had deferred units, 'map_relaunches'
+        (skm_mapper_map_relaunches) the map kernel launches repeated in a larger entry arena."""
         out = (ctypes.c_double * 8)()
         _native.check(_native.hip().skm_mapper_timing(self._handle, out))
+        relaunches = ctypes.c_int64()
+        _native.check(_native.hip().skm_mapper_map_relaunches(self._handle, ctypes.byref(relaunches)))
         return {'pack_ns': out[0], 'map_ns': out[1], 'class_ns': out[2],
                 'batches': int(out[3]), 'units': int(out[4]), 'em_ns': out[5], 'em_iterations': int(out[6]),
-                'deferred_grows': int(out[7])}
+                'deferred_grows': int(out[7]), 'map_relaunches': relaunches.value}
 
 
 class ReadMapper:
@@ -834,6 +837,12 @@ class SampleSet:
     def sync(self):
         """Wait for everything added to be mapped; raises the set's failure."""
         _native.check(_native.hip().skm_sample_set_sync(self._handle))
+
+    def map_relaunches(self):
+        """MapResult.timing()['map_relaunches'] of the set's launches (waits for what was added)."""
+        n = ctypes.c_int64()
+        _native.check(_native.hip().skm_sample_set_map_relaunches(self._handle, ctypes.byref(n)))
+        return n.value
 
     def __bool__(self):
         return True                   # (a handle, not a container: its truth waits for nothing)
