@@ -12,9 +12,10 @@
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
  *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_bias_*,
- *                          skm_gene_*, skm_comm_*, skm_device_*)
+ *                          skm_gene_*, skm_barcodes_*, skm_units_group, skm_comm_*, skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
- *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_synth_*)
+ *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_packed_gather,
+ *                          skm_synth_*)
  */
 #ifndef SEEKMER_HIP_H
 #define SEEKMER_HIP_H
@@ -490,6 +491,42 @@ int skm_mapper_gene_counts(skm_mapper *mapper, int64_t n_tx, int64_t n_genes, co
 int skm_sample_set_gene_counts(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
                                int64_t cap_samples, int64_t *unique /*[n_samples][n_genes]*/, int64_t *other);
 
+/* ---------------------------------------------------------------- cell barcodes
+ * ("Cell barcodes".)  A pooled run -- one barcode read per unit beside the cDNA reads --
+ * is split into its cells on the GPU: skm_barcodes_assign says which whitelist entry every unit's barcode is,
+ * skm_units_group orders a run of units by cell, and skm_packed_gather (libseekmer_host.so, below) moves the reads
+ * into that order; the cells then enter a sample set as ordinary in-order segments.
+ *
+ * The whitelist: n barcodes of `length` characters back to back (n x length, no separators), 1 <= length <= 32,
+ * upper-case ACGT only, no barcode twice: SKM_ERR_ARG otherwise (the message names the entry).  The handle owns an
+ * open-addressing table in HBM (key = the 2 x length code bits, A0 C1 G2 T3, first base in the top bits; a power
+ * of two slots, at most half full), built on the host and uploaded once; cell i = barcode i.  A whitelist of up to
+ * 1024 entries is probed from a copy in LDS. */
+typedef struct skm_barcodes skm_barcodes;
+int skm_barcodes_create(int device, const char *barcodes /* n x length characters */, int64_t n, int length,
+                        skm_barcodes **out);
+int skm_barcodes_destroy(skm_barcodes *barcodes);
+/* The cell of every read of a piece of barcode reads (a host piece, as for skm_sample_set_add_packed; `stream` and
+ * `first_read` are not looked at).  The barcode of read r is its bases [start, start + length); in this order:
+ * the read is shorter than start + length: short; two or more of the window's positions are not upper-case ACGT:
+ * unreadable; all clean and equal to an entry: exact (even with another entry at distance 1); max_mismatches == 0:
+ * no match; otherwise the candidates are the entries that differ from the window in exactly one position, a
+ * non-clean position always counting as differing (so with one such position only the four bases there are tried):
+ * one candidate: corrected; none: no match; several: ambiguous.  cell[r] = the entry of an exact or corrected read,
+ * -1 for every other; cell_units[n] += the reads given to each entry; stats[5] += exact, corrected, ambiguous,
+ * no match, short + unreadable (they add up to n_reads).  max_mismatches is 0 or 1; calls on one handle run one
+ * after the other.  The window may lie anywhere in the read and straddle a code word. */
+int skm_barcodes_assign(skm_barcodes *barcodes, const skm_packed_reads *reads, int start, int max_mismatches,
+                        int32_t *cell /* [n_reads] */, int64_t *cell_units /* [n], added to */,
+                        int64_t stats[5] /* added to */);
+/* A run of n < 2^31 units by sample: sample[u] in [0, n_samples) or negative (dropped), n_samples <= 2^24 ->
+ * order[] = the kept units grouped by ascending sample and in their original order inside a sample (room for n;
+ * offsets[n_samples] are written), offsets[n_samples + 1]: sample s owns order[offsets[s] .. offsets[s + 1]).
+ * numpy.argsort(kind='stable') of the samples with the dropped units cut off: the stable radix sort of the class
+ * views (skm_quant_setup.hip), dropped units under key n_samples.  SKM_ERR_ARG for a sample >= n_samples. */
+int skm_units_group(int device, const int32_t *sample, int64_t n, int64_t n_samples, int32_t *order,
+                    int64_t *offsets /* [n_samples + 1] */);
+
 /* ------------------------------------------------------------ quantification
  * MapResult.effective_lengths (seekmer/mapper.py:134-141). */
 int skm_effective_lengths(int device, const int64_t *fld, const double *lengths,
@@ -833,6 +870,19 @@ int skm_pack_reads(const char *bases, const int64_t *offsets, int64_t n_reads, i
                    int variant);
 /* force the parser variant of readers opened from now on (-1: best available); tests */
 int skm_pack_set_variant(int variant);
+
+/* Selected reads of packed pieces as ONE new piece (the demultiplexer's gather: no GPU).  The n_sources pieces
+ * are numbered through -- read i of the concatenation is read i - (reads of the pieces before) of its piece --
+ * and output read k = read order[k] of that numbering, k < count: codes[count][code_words] (code_words >= every
+ * source's; the words beyond a source's are zero), lengths[count], and the exceptions of the chosen reads
+ * re-indexed to k and ascending: exception_reads[*n_exceptions], exception_masks[*n_exceptions][code_words].
+ * With codes == NULL the call only counts: *n_exceptions = the entries the same call will write (the sizing
+ * call).  SKM_ERR_STATE when there are more than cap_exceptions (*n_exceptions says how many); SKM_ERR_ARG for
+ * an order entry outside the pieces, a source wider than code_words, NULL arrays.  `stream`, `first_read` and
+ * the names of the sources are not looked at. */
+int skm_packed_gather(const skm_packed_reads *sources, int64_t n_sources, const int32_t *order, int64_t count,
+                      int32_t code_words, uint64_t *codes, uint32_t *lengths, uint32_t *exception_reads,
+                      uint32_t *exception_masks, int64_t cap_exceptions, int64_t *n_exceptions);
 
 /* Seeded synthetic data; integer arithmetic only. */
 int skm_synth_transcriptome(uint64_t seed, int64_t n_genes, int64_t *n_tx,

@@ -30,6 +30,8 @@ def parse_args(argv=None, parser=None):
         infer.length_model_option(parser, opts)
     if opts['subcommand'] in ('infer', 'infer-many'):
         infer.gene_option(opts)
+    if opts['subcommand'] == 'infer-many':
+        infer.barcode_option(parser, opts)
     return opts
 
 

@@ -138,6 +138,11 @@ HIP_SYMBOLS = {
                                               c_i32p, c_i64p, c_i64p]),
     'skm_mapper_gene_counts': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32p, c_i64p, c_i64p]),
     'skm_sample_set_gene_counts': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32p, c_i64, c_i64p, c_i64p]),
+    'skm_barcodes_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, c_i64, ctypes.c_int, c_void_pp]),
+    'skm_barcodes_destroy': (ctypes.c_int, [ctypes.c_void_p]),
+    'skm_barcodes_assign': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PackedReads), ctypes.c_int, ctypes.c_int,
+                                           c_i32p, c_i64p, c_i64p]),
+    'skm_units_group': (ctypes.c_int, [ctypes.c_int, c_i32p, c_i64, c_i64, c_i32p, c_i64p]),
     'skm_quant_create': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64p, c_i32p, c_f64p,
                                         c_void_pp]),
     'skm_quant_create_from_mapper': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_void_pp]),
@@ -215,6 +220,9 @@ HOST_SYMBOLS = {
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64p,
                                       ctypes.c_int]),
     'skm_pack_set_variant': (ctypes.c_int, [ctypes.c_int]),
+    'skm_packed_gather': (ctypes.c_int, [ctypes.POINTER(PackedReads), c_i64, c_i32p, c_i64, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                         c_i64p]),
     'skm_synth_transcriptome': (ctypes.c_int, [ctypes.c_uint64, c_i64, c_i64p, c_void_pp,
                                                c_void_pp]),
     'skm_synth_free': (ctypes.c_int, [ctypes.c_void_p]),

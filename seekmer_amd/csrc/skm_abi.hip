@@ -3396,6 +3396,161 @@ extern "C" int skm_sample_set_split(int64_t n_entries, const int64_t *entry_glob
     return SKM_OK;
 }
 
+// ------------------------------------------------------------ cell barcodes (skm_barcodes.hip)
+// The whitelist's table is built here, on the host, once per handle, and uploaded; the scratch of the assign calls
+// lives in the handle and grows with the largest piece.  All work is on the default stream with blocking copies.
+struct skm_barcodes {
+    ~skm_barcodes() { (void)hipSetDevice(device); }  // (then the members free the device memory)
+    int device = 0;
+    int length = 0;
+    int64_t n = 0;
+    uint32_t slot_bits = 1;
+    std::mutex mu;                                   // one assign call at a time: they share the scratch
+    DBuf<uint64_t> keys, codes;
+    DBuf<int32_t> cells, cell;
+    DBuf<uint32_t> lengths, clean, exception_reads, exception_masks;
+    DBuf<unsigned long long> units;                  // [n] + the five counters
+};
+
+extern "C" int skm_barcodes_create(int device, const char *barcodes, int64_t n, int length, skm_barcodes **out)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    if (!out || !barcodes) return fail(SKM_ERR_ARG, "bad argument");
+    if (length < 1 || length > 32) return fail(SKM_ERR_ARG, "barcodes of %d bases: 1 to 32 are possible", length);
+    if (n < 1 || n > (1LL << 28)) return fail(SKM_ERR_ARG, "a whitelist of %lld barcodes", (long long)n);
+    uint32_t slot_bits = 1;
+    while ((1LL << slot_bits) < 2 * n) ++slot_bits;
+    const uint32_t mask = (uint32_t)((1ULL << slot_bits) - 1);
+    std::vector<uint64_t> keys((size_t)mask + 1, 0);
+    std::vector<int32_t> cells((size_t)mask + 1, -1);
+    for (int64_t i = 0; i < n; ++i) {
+        uint64_t key = 0;
+        for (int j = 0; j < length; ++j) {
+            const char c = barcodes[i * length + j];
+            const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+            if (code < 0) return fail(SKM_ERR_ARG, "barcode %lld holds a character other than A, C, G, T", (long long)i);
+            key = key << 2 | (uint64_t)code;
+        }
+        uint32_t s = barcode_slot(key, slot_bits);
+        while (cells[s] >= 0) {
+            if (keys[s] == key) return fail(SKM_ERR_ARG, "barcodes %d and %lld are the same", cells[s], (long long)i);
+            s = (s + 1) & mask;
+        }
+        keys[s] = key;
+        cells[s] = (int32_t)i;
+    }
+    SKM_TRY(set_device(device));
+    auto b = std::make_unique<skm_barcodes>();
+    b->device = device; b->length = length; b->n = n; b->slot_bits = slot_bits;
+    SKM_TRY(b->keys.ensure(keys.size())); SKM_TRY(b->cells.ensure(cells.size()));
+    HIP_TRY(hipMemcpy(b->keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice));
+    *out = b.release();
+    return SKM_OK;
+}
+
+extern "C" int skm_barcodes_destroy(skm_barcodes *barcodes)
+{
+    delete barcodes;
+    return SKM_OK;
+}
+
+extern "C" int skm_barcodes_assign(skm_barcodes *b, const skm_packed_reads *reads, int start, int max_mismatches,
+                                   int32_t *cell, int64_t *cell_units, int64_t stats[5])
+{
+    if (!b || !reads || !cell_units || !stats) return fail(SKM_ERR_ARG, "bad argument");
+    if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a barcode that starts at base %d", start);
+    if (max_mismatches != 0 && max_mismatches != 1) return fail(SKM_ERR_ARG, "%d mismatches: 0 or 1", max_mismatches);
+    const int64_t n = reads->n_reads, n_exc = reads->n_exceptions;
+    if (n < 0 || n >= (1LL << 31) || n_exc < 0 || n_exc > n) return fail(SKM_ERR_ARG, "a piece of %lld reads", (long long)n);
+    if (n == 0) return SKM_OK;
+    const int64_t code_words = reads->code_words;
+    if (!cell || code_words < 0 || reads->read_stride < code_words || (code_words && !reads->codes) ||
+        (!reads->lengths && reads->uniform_len < 0) || (n_exc && (!reads->exception_reads || !reads->exception_masks)))
+        return fail(SKM_ERR_ARG, "not a piece of packed reads");
+    for (int64_t e = 0; e < n_exc; ++e)
+        if (reads->exception_reads[e] >= (uint64_t)n) return fail(SKM_ERR_ARG, "exception %lld names read %u of %lld", (long long)e, reads->exception_reads[e], (long long)n);
+    // the one or two words of every read that hold the window, as far as the piece has them
+    const int64_t first_word = start / 32;
+    const int offset = start % 32;
+    const int words = (int)std::max<int64_t>(0, std::min<int64_t>(code_words - first_word, offset + b->length > 32 ? 2 : 1));
+    std::lock_guard<std::mutex> hold(b->mu);
+    SKM_TRY(set_device(b->device));
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: the scratch is in use)
+    SKM_TRY(b->codes.ensure((size_t)std::max<int64_t>(n * words, 1))); SKM_TRY(b->clean.ensure(n)); SKM_TRY(b->cell.ensure(n));
+    SKM_TRY(b->units.ensure(b->n + BARCODE_STATS));
+    if (words && reads->read_stride == words) {
+        HIP_TRY(hipMemcpy(b->codes.p, reads->codes, (size_t)(n * words) * 8, hipMemcpyHostToDevice));
+    } else if (words) {
+        std::vector<uint64_t> window((size_t)(n * words));
+        for (int64_t r = 0; r < n; ++r)
+            for (int k = 0; k < words; ++k) window[r * words + k] = reads->codes[r * reads->read_stride + first_word + k];
+        HIP_TRY(hipMemcpy(b->codes.p, window.data(), window.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (reads->lengths) {
+        SKM_TRY(b->lengths.ensure(n));
+        HIP_TRY(hipMemcpy(b->lengths.p, reads->lengths, n * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(b->clean.p, 0xff, n * 4, nullptr));
+    HIP_TRY(hipMemsetAsync(b->units.p, 0, (b->n + BARCODE_STATS) * 8, nullptr));
+    if (n_exc && words) {
+        SKM_TRY(b->exception_reads.ensure(n_exc)); SKM_TRY(b->exception_masks.ensure(n_exc * words));
+        HIP_TRY(hipMemcpy(b->exception_reads.p, reads->exception_reads, n_exc * 4, hipMemcpyHostToDevice));
+        std::vector<uint32_t> planes((size_t)(n_exc * words));
+        for (int64_t e = 0; e < n_exc; ++e)
+            for (int k = 0; k < words; ++k) planes[e * words + k] = reads->exception_masks[e * code_words + first_word + k];
+        HIP_TRY(hipMemcpy(b->exception_masks.p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice));
+        launch_barcode_clean(b->exception_reads.p, b->exception_masks.p, n_exc, words, offset, b->clean.p, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    BarcodeTable table{b->keys.p, b->cells.p, b->slot_bits, b->length, b->n};
+    BarcodeWindows w{n, b->codes.p, words, offset, reads->lengths ? b->lengths.p : nullptr, reads->uniform_len, start, b->clean.p};
+    launch_barcode_assign(table, w, max_mismatches, b->cell.p, b->units.p, b->units.p + b->n, nullptr);
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> counted((size_t)b->n + BARCODE_STATS);
+    HIP_TRY(hipMemcpy(cell, b->cell.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counted.data(), b->units.p, counted.size() * 8, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    for (int64_t c = 0; c < b->n; ++c) cell_units[c] += (int64_t)counted[c];
+    for (int k = 0; k < BARCODE_STATS; ++k) stats[k] += (int64_t)counted[b->n + k];
+    return SKM_OK;
+}
+
+extern "C" int skm_units_group(int device, const int32_t *sample, int64_t n, int64_t n_samples, int32_t *order,
+                               int64_t *offsets)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    if (n < 0 || n >= (1LL << 31) || n_samples < 1 || n_samples > (1LL << 24) || !offsets || (n && (!sample || !order)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    SKM_TRY(set_device(device));
+    DBuf<int32_t> d_sample, d_iota, d_order; DBuf<uint32_t> d_keys, d_sorted; DBuf<int64_t> d_offsets; DBuf<int> d_error;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    SKM_TRY(d_sample.ensure(room)); SKM_TRY(d_iota.ensure(room)); SKM_TRY(d_order.ensure(room)); SKM_TRY(d_keys.ensure(room));
+    SKM_TRY(d_sorted.ensure(room)); SKM_TRY(d_offsets.ensure(n_samples + 1)); SKM_TRY(d_error.ensure(1));
+    HIP_TRY(hipMemsetAsync(d_error.p, 0, sizeof(int), nullptr));
+    if (n) HIP_TRY(hipMemcpy(d_sample.p, sample, n * 4, hipMemcpyHostToDevice));
+    launch_group_keys(d_sample.p, n, n_samples, d_keys.p, d_iota.p, d_error.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    int end_bit = 1;
+    while ((1LL << end_bit) <= n_samples) ++end_bit;      // (the keys go up to n_samples itself: the dropped units)
+    if (sort_pairs_u32(d_keys.p, d_sorted.p, d_iota.p, d_order.p, n, end_bit, nullptr) != 0)
+        return fail(SKM_ERR_HIP, "grouping %lld units: %s", (long long)n, quant_setup_failure());
+    launch_group_offsets(d_sorted.p, n, n_samples, d_offsets.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    int error = 0;
+    HIP_TRY(hipMemcpy(&error, d_error.p, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(offsets, d_offsets.p, (n_samples + 1) * 8, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    if (error) return fail(SKM_ERR_ARG, "a unit names a sample not below n_samples = %lld", (long long)n_samples);
+    if (offsets[n_samples]) HIP_TRY(hipMemcpy(order, d_order.p, offsets[n_samples] * 4, hipMemcpyDeviceToHost));
+    return SKM_OK;
+}
+
 // ------------------------------------------------------------ quantification
 extern "C" int skm_effective_lengths(int device, const int64_t *fld, const double *lengths,
                                      int64_t n_tx, double *out)

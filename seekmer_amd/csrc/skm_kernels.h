@@ -514,6 +514,47 @@ void launch_gene_unique(const GeneClasses &t, const int32_t *tx_gene, int64_t n_
                         int64_t sample_end, unsigned long long *unique, unsigned long long *other, int *error,
                         hipStream_t stream);
 
+// ---- cell barcodes (skm_barcodes.hip; DESIGN.md section 4, "Cell barcodes")
+// The stable radix sort of skm_quant_setup.hip for (uint32 key, int32 value) pairs on key bits [0, end_bit):
+// 0 = done (the stream has drained), < 0 = no memory or n >= 2^32 (quant_setup_failure() says which).
+int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *vals_in, int32_t *vals_out, int64_t n,
+                   int end_bit, hipStream_t stream);
+constexpr int BARCODE_LDS_MAX_ENTRIES = 1024;     // whitelists up to this size are probed from a copy in LDS
+constexpr int BARCODE_STATS = 5;                  // exact, corrected, ambiguous, no match, short or unreadable
+struct BarcodeTable {             // the whitelist in HBM: open addressing, linear probing, at most half full
+    const uint64_t *keys;         // [slots] the 2 L code bits of an entry (first base in the top bits of the 2 L)
+    const int32_t *cells;         // [slots] its cell index, -1 = empty slot
+    uint32_t slot_bits;           // slots = 1 << slot_bits
+    int32_t length;               // L, 1 .. 32
+    int64_t n_entries;
+};
+inline __host__ __device__ uint32_t barcode_slot(uint64_t key, uint32_t slot_bits)
+{
+    return (uint32_t)((key * 0x9E3779B97F4A7C15ULL) >> 32) >> (32 - slot_bits);       // slot_bits >= 1
+}
+struct BarcodeWindows {           // the window words of a piece's reads, compacted: what the assign kernel reads
+    int64_t n_reads;
+    const uint64_t *codes;        // [n_reads][words] the code words that hold the window (words = 0: no read reaches it)
+    int32_t words;                // 0, 1 or 2
+    int32_t offset;               // the window starts at base `offset` (0 .. 31) of the first word
+    const uint32_t *lengths;      // [n_reads], or nullptr: every read is uniform_len long
+    int64_t uniform_len;
+    int32_t start;                // the window is bases [start, start + L) of a read
+    const uint32_t *clean;        // [n_reads]: bit 31 - i set = window position i is an upper-case ACGT
+};
+// clean[r] for the n_exceptions reads that have a bit plane (clean[] preset to all ones): masks[e][words] are the
+// plane's 32-bit words that hold the window, offset = start % 32; exception_reads[e] < n_reads (the caller has checked)
+void launch_barcode_clean(const uint32_t *exception_reads, const uint32_t *masks, int64_t n_exceptions, int words,
+                          int offset, uint32_t *clean, hipStream_t stream);
+// cell[r] = the cell of read r or -1; cell_units[cell] and stats[BARCODE_STATS] are added to
+void launch_barcode_assign(const BarcodeTable &table, const BarcodeWindows &w, int max_mismatches, int32_t *cell,
+                           unsigned long long *cell_units, unsigned long long *stats, hipStream_t stream);
+// keys[u] = sample[u], or n_samples for a dropped unit (sample[u] < 0); vals[u] = u; a sample >= n_samples sets *error
+void launch_group_keys(const int32_t *sample, int64_t n, int64_t n_samples, uint32_t *keys, int32_t *vals, int *error,
+                       hipStream_t stream);
+// offsets[s] (s <= n_samples) = the first place of the ascending keys[0 .. n) whose key is >= s
+void launch_group_offsets(const uint32_t *sorted_keys, int64_t n, int64_t n_samples, int64_t *offsets, hipStream_t stream);
+
 // one hipFuncGetAttributes per translation unit: its code object is loaded now, not by a sample's first launch
 void warm_code_map();
 void warm_code_classes();

@@ -578,6 +578,14 @@ int sort_pairs(Scratch &scratch, const K *keys_in, K *keys_out, const int32_t *v
 
 }  // namespace
 
+// the sort above for callers outside this file (skm_barcodes.hip); the stream has drained on return
+int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *vals_in, int32_t *vals_out, int64_t n,
+                   int end_bit, hipStream_t stream)
+{
+    Scratch scratch(stream);
+    return sort_pairs<uint32_t>(scratch, keys_in, keys_out, vals_in, vals_out, n, end_bit);
+}
+
 int64_t quant_rows_upper_bound(int64_t n_tx, int64_t n_ids)
 {
     return n_tx + n_ids / EM_ROW_CAP + 1;

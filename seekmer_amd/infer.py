@@ -426,7 +426,8 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
-             strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, **__):
+             strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
+             barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -455,29 +456,51 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     and output/genes.tpm.tsv and output/genes.unique_counts.tsv hold genes as rows and samples as columns.  The
     samples of the set get their gene-unique counts from ONE pass over the set's resident table
     (SampleSet.gene_unique_counts), every other sample from its mapper's (MapResult.gene_unique_counts); the TPM
-    rows of all samples are summed per gene in one gene_sums call.  The files are the same either way."""
+    rows of all samples are summed per gene in one gene_sums call.  The files are the same either way.
+
+    barcodes: --barcodes WHITELIST.  The FASTQ files are then ONE pooled sample (one file with single_ended, two
+    otherwise) and `barcode_file` holds one barcode read per unit; the samples are the whitelist's cells with at
+    least `min_units` assigned units, named by the whitelist (mapper.map_barcoded: the barcodes are matched and the
+    units grouped on the GPU, bases [barcode_start, barcode_start + L) of a barcode read with at most
+    `barcode_mismatches` (0 or 1) substitutions).  All cells go through one sample set; every folder holds what
+    it would for a FASTQ pair of the cell's reads alone.  output/barcodes.tsv lists every whitelist entry
+    (barcode, name, assigned units, kept 0/1) and output/barcodes.json the demultiplexing summary.  Plain FASTQ
+    files only; `names` is refused."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
     trace = _phase_trace()
     mapper.strand_mode(strand)
     length_model, _ = mapper.length_model_weights(length_model)
-    groups = sample_groups(fastq_paths, single_ended)
-    if not groups:
-        raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
-    names = sample_names(groups, names)
+    whitelist = None
+    if barcodes is None:
+        if barcode_file is not None:
+            raise ValueError('--barcode-file goes with --barcodes')
+        groups = sample_groups(fastq_paths, single_ended)
+        if not groups:
+            raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
+        names = sample_names(groups, names)
+    else:
+        whitelist = barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start,
+                                    barcode_mismatches, min_units)
+        groups = [tuple(fastq_paths)]
     ranks = parallel.Ranks.from_env()
     if ranks.world > 1:
         ranks.close()
         raise ValueError('infer-many runs in one process on one GPU: start it without a launcher')
-    for path in fastq_paths:
+    for path in list(fastq_paths) + ([barcode_file] if whitelist is not None else []):
         if not pathlib.Path(path).exists():
             raise ValueError(f'invalid FastQ file: {path}')
+        if whitelist is not None and not common.PackedReadFeeder.eligible([path]):
+            raise ValueError(f'--barcodes reads plain FASTQ files: decompress {path} first')
     try:
         output_path.mkdir(parents=True)
     except FileExistsError:
         _LOG.warning('The output folder exists. Overriding...')
-    _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    if whitelist is None:
+        _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    else:
+        _LOG.info('Inferring transcript abundance of the cells of one pooled run (%d barcodes)', len(whitelist[0]))
     _log_length_model(length_model, single_ended)
     _native.check(_native.hip().skm_pinned_set_device(device))
     index = common.KMerIndex.load(index_path)
@@ -491,12 +514,35 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     summaries, means = [None] * len(groups), [None] * len(groups)
     set_estimates = {}
     trace('index load')
-    if in_set:
+    sample_set = None
+    if whitelist is not None:
+        # the cells of the pooled run are the samples, all of them in one set
+        table = mapper.BarcodeTable(*whitelist, device=device)
+        parse_threads = 0 if debug or job_count <= 1 else min(int(job_count), 8)     # (one large file: -j parses it)
+        sample_set, kept, demux = mapper.map_barcoded(
+            index, table, common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads),
+            common.PackedReadFeeder(list(fastq_paths), paired=paired, threads=parse_threads), paired, start=barcode_start,
+            mismatches=barcode_mismatches, min_units=min_units, device=device, strand=strand, per_sample_lengths=True,
+            length_model=length_model, bias=bias)
+        _LOG.info('Barcodes of %d units: %d exact, %d corrected, %d ambiguous, %d without a match, %d short or unreadable',
+                  demux['units'], *[demux[name] for name in mapper.BARCODE_STATS])
+        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units)
+        if not kept.size:
+            raise ValueError('no cell has %d units or more (see %s)' % (min_units, output_path / 'barcodes.tsv'))
+        names = [table.names[c] for c in kept]
+        _LOG.info('%d cells have %d units or more', len(names), min_units)
+        groups = [()] * len(names)
+        in_set = list(range(len(names)))
+        gene_counts, observed = [None] * len(names), [None] * len(names)
+        summaries, means = [None] * len(names), [None] * len(names)
+        trace('demultiplexing')
+    elif in_set:
         _LOG.info('Mapping %d samples in shared launches', len(in_set))
         feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
                    else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
         sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
                                            strand=strand, per_sample_lengths=True, length_model=length_model, bias=bias)
+    if in_set:
         for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
             summaries[i], means[i] = summary, mean
         if bias:
@@ -584,6 +630,43 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     trace('writing', pause=True)
     trace(None)
     _LOG.info('Wrote results to %s', output_path)
+
+
+def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start, barcode_mismatches,
+                    min_units):
+    """The checks of `infer-many --barcodes` that need no read file -> the whitelist (barcodes, names) of
+    mapper.read_whitelist.  ValueError for a combination that cannot be and for a malformed whitelist."""
+    if barcode_file is None:
+        raise ValueError('--barcodes needs the barcode reads: --barcode-file FASTQ')
+    if names is not None:
+        raise ValueError('--names does not go with --barcodes: the cells are named by the whitelist')
+    if len(fastq_paths) != (1 if single_ended else 2):
+        raise ValueError('--barcodes takes ONE pooled sample: %s, not %d'
+                         % ('one FASTQ file with -s' if single_ended else 'two FASTQ files (one with -s)', len(fastq_paths)))
+    if int(barcode_start) < 0:
+        raise ValueError('--barcode-start must be 0 or more, not %r' % (barcode_start,))
+    if barcode_mismatches not in (0, 1):
+        raise ValueError('--barcode-mismatches must be 0 or 1, not %r' % (barcode_mismatches,))
+    if int(min_units) < 1:
+        raise ValueError('--min-units must be 1 or more, not %r' % (min_units,))
+    return mapper.read_whitelist(barcodes)
+
+
+def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units):
+    """output/barcodes.tsv: barcode, name, assigned units, kept 0/1 per whitelist entry; output/barcodes.json: the
+    demultiplexing summary."""
+    is_kept = numpy.zeros(len(table), dtype=bool)
+    is_kept[kept] = True
+    with (output_path / 'barcodes.tsv').open('w') as f:
+        for barcode, name, units, flag in zip(table.barcodes, table.names, demux['cell_units'], is_kept):
+            f.write('%s\t%s\t%d\t%d\n' % (barcode, name, units, flag))
+    summary = {name: demux[name] for name in mapper.BARCODE_STATS}
+    summary.update(units=demux['units'], records=demux['records'], whitelist=len(table), barcode_length=table.length,
+                   barcode_start=int(start), barcode_mismatches=int(mismatches), min_units=int(min_units),
+                   cells=int(len(kept)), assigned=int(demux['exact'] + demux['corrected']))
+    with (output_path / 'barcodes.json').open('w') as f:
+        json.dump(summary, f, indent=4)
+        f.write('\n')
 
 
 def _phase_trace():
@@ -1279,6 +1362,48 @@ def add_many_subcommand_parser(subparsers):
     add_length_model_arguments(parser)
     add_bias_argument(parser)
     add_gene_arguments(parser)
+    add_barcode_arguments(parser)
+
+
+def add_barcode_arguments(parser):
+    """--barcodes and its companions: dest 'barcodes', 'barcode_file', 'barcode_start', 'barcode_mismatches',
+    'min_units' (barcode_option checks the combinations once the arguments are parsed)."""
+    parser.add_argument('--barcodes', type=pathlib.Path, dest='barcodes', default=None, metavar='WHITELIST',
+                        help='the FASTQ files are ONE pooled sample: split it into the cells of this whitelist (a '
+                             'barcode per line, optionally a tab and the cell\'s name) on the GPU; needs --barcode-file')
+    parser.add_argument('--barcode-file', type=pathlib.Path, dest='barcode_file', default=None, metavar='FASTQ',
+                        help='the barcode reads of the pooled sample, one per unit (with --barcodes)')
+    parser.add_argument('--barcode-start', type=int, dest='barcode_start', default=None, metavar='N',
+                        help='the barcode begins at base N of a barcode read (default 0)')
+    parser.add_argument('--barcode-mismatches', type=int, dest='barcode_mismatches', default=None, choices=(0, 1),
+                        help='substitutions a barcode may differ from its whitelist entry by (default 1)')
+    parser.add_argument('--min-units', type=int, dest='min_units', default=None, metavar='N',
+                        help='keep the cells with at least N assigned units (default 1)')
+
+
+def barcode_option(parser, opts):
+    """The parsed barcode options: a combination that cannot be is an argparse error; the defaults are filled in."""
+    given = [flag for flag, key in (('--barcode-file', 'barcode_file'), ('--barcode-start', 'barcode_start'),
+                                    ('--barcode-mismatches', 'barcode_mismatches'), ('--min-units', 'min_units'))
+             if opts.get(key) is not None]
+    if opts.get('barcodes') is None:
+        if given:
+            parser.error('%s goes with --barcodes' % given[0])
+    else:
+        if opts.get('barcode_file') is None:
+            parser.error('--barcodes needs the barcode reads: --barcode-file FASTQ')
+        if opts.get('names') is not None:
+            parser.error('--names does not go with --barcodes: the cells are named by the whitelist')
+        if len(opts['fastq_paths']) != (1 if opts['single_ended'] else 2):
+            parser.error('--barcodes takes ONE pooled sample: two FASTQ files, or one with -s')
+    if opts.get('barcode_start') is not None and opts['barcode_start'] < 0:
+        parser.error('--barcode-start must be 0 or more')
+    if opts.get('min_units') is not None and opts['min_units'] < 1:
+        parser.error('--min-units must be 1 or more')
+    for key, default in (('barcode_start', 0), ('barcode_mismatches', 1), ('min_units', 1)):
+        if opts.get(key) is None:
+            opts[key] = default
+    return opts
 
 
 def add_gene_arguments(parser):

@@ -15,17 +15,22 @@ sample's own table, bit for bit what a ``MapResult`` per sample gives.
 """
 import collections
 import ctypes
+import logging
 import multiprocessing.pool
+import os
 import queue
 import threading
 
 import numpy
 
 from . import _native
-from .common import PackedReadFeeder, PackedReads, ReadBatch
+from .common import PackedReadFeeder, PackedReads, ReadBatch, decompress_and_open
 
-__all__ = ('MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet', 'SummarizedResult',
-           'fragment_length_weights', 'map_reads', 'map_multiple_samples', 'map_sample_set')
+__all__ = ('BarcodeTable', 'DEMUX_CHUNK_UNITS', 'MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet',
+           'SummarizedResult', 'fragment_length_weights', 'group_units', 'map_barcoded', 'map_reads',
+           'map_multiple_samples', 'map_sample_set', 'read_whitelist')
+
+_LOG = logging.getLogger(__name__)
 
 MAX_FRAGMENT_LENGTH = 2000          # seekmer/_mapper.pyx:18-20
 
@@ -1019,3 +1024,304 @@ def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_
             job.get()                     # re-raises what the worker raised
     sample_set.sync()
     return sample_set
+
+
+# ---- cell barcodes: a pooled run split into its cells (include/seekmer_hip.h, skm_barcodes_*) ---------------
+
+DEMUX_CHUNK_UNITS = 1 << 22         # units grouped and gathered at a time (SKM_DEMUX_CHUNK_UNITS: fewer, for tests)
+BARCODE_STATS = ('exact', 'corrected', 'ambiguous', 'no_match', 'unreadable')    # skm_barcodes_assign's stats[5]
+MAX_BARCODE_LENGTH = 32
+
+
+def check_whitelist(barcodes, names=None):
+    """The whitelist rules ("Cell barcodes") -> (barcodes, names) as lists of str: one
+    length of 1..32, upper-case ACGT only, no barcode twice; names (default: the barcodes) unique and usable as
+    folder names.  ValueError otherwise; nothing native is touched."""
+    barcodes = [b.decode() if isinstance(b, bytes) else str(b) for b in barcodes]
+    names = list(barcodes) if names is None else [n.decode() if isinstance(n, bytes) else str(n) for n in names]
+    if not barcodes:
+        raise ValueError('the whitelist holds no barcode')
+    if len(names) != len(barcodes):
+        raise ValueError('%d names for %d barcodes' % (len(names), len(barcodes)))
+    length = len(barcodes[0])
+    if not 1 <= length <= MAX_BARCODE_LENGTH:
+        raise ValueError('barcodes of %d bases: 1 to %d are possible' % (length, MAX_BARCODE_LENGTH))
+    seen = set()
+    for barcode in barcodes:
+        if len(barcode) != length:
+            raise ValueError('barcode %r is not %d bases long like the first' % (barcode, length))
+        if barcode.strip('ACGT'):
+            raise ValueError('barcode %r holds a character other than upper-case A, C, G, T' % (barcode,))
+        if barcode in seen:
+            raise ValueError('barcode %r is listed twice' % (barcode,))
+        seen.add(barcode)
+    seen = set()
+    for name in names:
+        if name in ('', '.', '..') or '/' in name:
+            raise ValueError('%r cannot name a cell\'s output folder' % (name,))
+        if name in seen:
+            raise ValueError('cell name %r is used twice' % (name,))
+        seen.add(name)
+    return barcodes, names
+
+
+def read_whitelist(path):
+    """A whitelist file (possibly compressed) -> (barcodes, names): one barcode per line, an optional second
+    tab-separated column names the cell (default: the barcode); lines that start with '#' and empty lines are
+    skipped.  ValueError for anything check_whitelist refuses."""
+    barcodes, names = [], []
+    with decompress_and_open(path) as lines:
+        for line in lines:
+            line = line.decode() if isinstance(line, bytes) else line
+            line = line.rstrip('\r\n')
+            if not line or line.startswith('#'):
+                continue
+            fields = line.split('\t')
+            if len(fields) > 2:
+                raise ValueError('whitelist line %r: a barcode and at most one more column, the cell\'s name' % (line,))
+            barcodes.append(fields[0])
+            names.append(fields[1] if len(fields) == 2 else fields[0])
+    return check_whitelist(barcodes, names)
+
+
+class BarcodeTable:
+    """A whitelist of cell barcodes on the device (skm_barcodes): cell i = barcodes[i].  ``assign`` gives every
+    read of a piece of barcode reads its cell by the rule of DESIGN.md section 4, "Cell barcodes" (exact, or the
+    one entry at Hamming distance 1); ``cell_units`` int64[n] and ``stats`` int64[5] (BARCODE_STATS: exact,
+    corrected, ambiguous, no match, short or unreadable) run over all pieces assigned so far."""
+
+    def __init__(self, barcodes, names=None, device=0):
+        self.barcodes, self.names = check_whitelist(barcodes, names)
+        self.length = len(self.barcodes[0])
+        self.device = device
+        self.cell_units = numpy.zeros(len(self.barcodes), dtype=numpy.int64)
+        self.stats = numpy.zeros(len(BARCODE_STATS), dtype=numpy.int64)
+        self._handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_barcodes_create(device, ''.join(self.barcodes).encode(), len(self.barcodes),
+                                                        self.length, ctypes.byref(self._handle)))
+
+    @classmethod
+    def from_file(cls, path, device=0):
+        return cls(*read_whitelist(path), device=device)
+
+    def __len__(self):
+        return len(self.barcodes)
+
+    def __del__(self):
+        handle = getattr(self, '_handle', None)
+        if handle:
+            try:
+                _native.hip().skm_barcodes_destroy(handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    def assign(self, piece, start=0, mismatches=1):
+        """int32[piece.n_reads]: the cell of every read whose bases [start, start + L) are a whitelist entry or one
+        substitution away from exactly one, -1 for every other read."""
+        cell = numpy.full(max(piece.n_reads, 1), -1, dtype=numpy.int32)
+        _native.check(_native.hip().skm_barcodes_assign(
+            self._handle, ctypes.byref(piece.raw), int(start), int(mismatches), _native.ptr(cell, _native.c_i32p),
+            _native.ptr(self.cell_units, _native.c_i64p), _native.ptr(self.stats, _native.c_i64p)))
+        return cell[:piece.n_reads]
+
+
+def group_units(sample, n_samples, device=0):
+    """A run of units by sample on the GPU (skm_units_group): sample int32[n], negative = dropped ->
+    (order int32[kept], offsets int64[n_samples + 1]): order = the kept units by ascending sample, in their
+    original order inside a sample -- numpy.argsort(sample, kind='stable') without the dropped units."""
+    sample = numpy.ascontiguousarray(sample, dtype=numpy.int32)
+    order = numpy.zeros(max(sample.size, 1), dtype=numpy.int32)
+    offsets = numpy.zeros(int(n_samples) + 1, dtype=numpy.int64)
+    _native.check(_native.hip().skm_units_group(
+        device, _native.ptr(sample, _native.c_i32p) if sample.size else None, sample.size, int(n_samples),
+        _native.ptr(order, _native.c_i32p), _native.ptr(offsets, _native.c_i64p)))
+    return order[:offsets[-1]], offsets
+
+
+class _Gathered:
+    """One mate's reads of a chunk in grouped order (skm_packed_gather): arrays of its own, cut into the cells'
+    segments without another copy."""
+
+    def __init__(self, held, first_unit, order):
+        """held: consecutive pieces of one stream, the first of which holds unit `first_unit`'s predecessor or
+        it; order: chunk-relative unit numbers, relative to first_unit."""
+        sources = (_native.PackedReads * len(held))()
+        for k, piece in enumerate(held):
+            ctypes.memmove(ctypes.byref(sources[k]), ctypes.byref(piece.raw), ctypes.sizeof(_native.PackedReads))
+        at = numpy.ascontiguousarray(order + numpy.int32(first_unit - held[0].first_read), dtype=numpy.int32)
+        self.code_words = max(piece.code_words for piece in held)
+        cap = sum(piece.raw.n_exceptions for piece in held)
+        self.codes = numpy.empty((at.size, self.code_words), dtype=numpy.uint64)
+        self.lengths = numpy.empty(at.size, dtype=numpy.uint32)
+        self.exception_reads = numpy.empty(max(cap, 1), dtype=numpy.uint32)
+        self.exception_masks = numpy.empty((max(cap, 1), max(self.code_words, 1)), dtype=numpy.uint32)
+        n = ctypes.c_int64()
+        _native.check_host(_native.host().skm_packed_gather(
+            sources, len(held), _native.ptr(at, _native.c_i32p), at.size, self.code_words, self.codes.ctypes.data,
+            self.lengths.ctypes.data, self.exception_reads.ctypes.data, self.exception_masks.ctypes.data, cap,
+            ctypes.byref(n)), 'skm_packed_gather')
+        self.exception_reads = self.exception_reads[:n.value]
+        self.exception_masks = self.exception_masks[:n.value]
+        self.stream = held[0].stream
+        self.paired = held[0].paired
+
+    def segment(self, lo, hi):
+        a, b = numpy.searchsorted(self.exception_reads, (lo, hi))
+        return PackedReads.from_arrays(self.stream, 0, self.codes[lo:hi], self.lengths[lo:hi],
+                                       self.exception_reads[a:b] - numpy.uint32(lo), self.exception_masks[a:b],
+                                       paired=self.paired)
+
+
+def demux_chunks(pieces, paired, sample, n_samples, chunk_units, group, add):
+    """Phase 2 of map_barcoded: the cDNA pieces of a pooled run, as a packed reader hands them out (one stream
+    single-ended, two paired, each numbered by unit), against sample[u] for the run's units (int32, negative =
+    dropped).  The streams are paired by unit as sample_segments pairs them; every `chunk_units` units that all
+    streams cover are grouped -- group(sample[a:b], n_samples) -> (order, offsets), mapper.group_units -- each
+    mate is gathered once into that order (skm_packed_gather), and every sample present gets one
+    add(sample, first_unit, mate1, mate2 or None) with first_unit = its units so far.  The chunks are
+    [0, c), [c, 2c), ... whatever the pieces' sizes; reads beyond sample.size units are dropped.  Returns
+    (int64[n_samples] units added per sample, units walked)."""
+    n_units = int(sample.size)
+    chunk_units = max(1, int(chunk_units))
+    streams = ([], []) if paired else ([],)
+    ends = [0] * len(streams)
+    added = numpy.zeros(max(int(n_samples), 1), dtype=numpy.int64)
+    done = 0
+
+    def flush(upto):
+        nonlocal done
+        while done < upto:
+            end = min(done + chunk_units, upto)
+            order, offsets = group(sample[done:end], n_samples)
+            if len(order):
+                mates = [_Gathered(held, done, order) for held in streams]
+                for s in numpy.flatnonzero(numpy.diff(offsets)):
+                    lo, hi = int(offsets[s]), int(offsets[s + 1])
+                    segments = [mate.segment(lo, hi) for mate in mates]
+                    add(int(s), int(added[s]), segments[0], segments[1] if paired else None)
+                    added[s] += hi - lo
+            done = end
+            for held in streams:          # (a piece that ends at or below `done` is not needed again)
+                while held and held[0].first_read + held[0].n_reads <= done:
+                    held.pop(0)
+
+    for piece in pieces:
+        if piece.stream not in range(len(streams)):
+            raise ValueError('stream %d of a %s run' % (piece.stream, 'paired' if paired else 'single-ended'))
+        if not piece.is_cut and piece.n_reads == 0:
+            continue
+        k, first = piece.stream, piece.first_read
+        if first >= n_units:
+            continue                      # (the surplus of a longer file)
+        if first < ends[k]:               # a piece, or a cut, that replaces the reads from `first` on
+            if first < done:
+                raise ValueError('stream %d takes back unit %d, which is already in the set' % (k, first))
+            held = streams[k]
+            while held and held[-1].first_read >= first:
+                held.pop()
+            if held and held[-1].first_read + held[-1].n_reads > first:
+                held[-1] = _slice_piece(held[-1], 0, first - held[-1].first_read)
+            ends[k] = first
+        if piece.is_cut:
+            continue
+        if first != ends[k]:
+            raise ValueError('the reads of stream %d do not follow each other (unit %d after %d)' % (k, first, ends[k]))
+        streams[k].append(piece.held())
+        ends[k] = first + piece.n_reads
+        ready = min(min(ends), n_units)
+        flush(done + (ready - done) // chunk_units * chunk_units)
+    flush(min(min(ends), n_units))
+    return added[:int(n_samples)], done
+
+
+def fastq_records(path, threads=4):
+    """The records of a plain FASTQ file by the reference's rule (lines 4u .. 4u + 3 are record u whatever they
+    hold; a trailing name line alone is none), from its newlines alone (skm_fastq_count_newlines)."""
+    chunk = PackedReadFeeder.COUNT_CHUNK
+    size = os.stat(path).st_size
+    if size == 0:
+        return 0
+    n_chunks = (size + chunk - 1) // chunk
+    counts = numpy.zeros(n_chunks, dtype=numpy.int64)
+    open_line = ctypes.c_int(0)
+    _native.check_host(_native.host().skm_fastq_count_newlines(
+        str(path).encode(), chunk, 0, 1, max(1, int(threads)), _native.ptr(counts, _native.c_i64p), n_chunks,
+        ctypes.byref(open_line)), 'skm_fastq_count_newlines')
+    return (int(counts.sum()) + open_line.value + 2) // 4
+
+
+def _demux_chunk_units():
+    value = os.environ.get('SKM_DEMUX_CHUNK_UNITS')
+    if value is None:
+        return DEMUX_CHUNK_UNITS
+    if not value.isdigit() or not 1 <= int(value) <= DEMUX_CHUNK_UNITS:
+        raise ValueError('SKM_DEMUX_CHUNK_UNITS must be a whole number from 1 to %d, not %r' % (DEMUX_CHUNK_UNITS, value))
+    return int(value)
+
+
+def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mismatches=1, min_units=1, device=0,
+                 strand=None, per_sample_lengths=False, length_model=None, bias=False):
+    """One pooled run -> a SampleSet with one sample per kept cell.  table: a BarcodeTable; barcode_feeder: a
+    single-ended PackedReadFeeder over the barcode file; read_feeder: a PackedReadFeeder over the pooled cDNA
+    file (or pair of files).  The run holds min(records) units over these files (zip of the reference's feeders);
+    a surplus in any file is dropped with one log line.
+
+    Phase 1 drains the barcode file and assigns every piece on the GPU; cell[] of the whole run stays on the
+    host (4 bytes a unit).  The kept cells are those with at least `min_units` assigned units, numbered densely
+    in whitelist order: sample k of the set is cell kept[k].  Phase 2 walks the cDNA pieces in unit order
+    (demux_chunks: at most DEMUX_CHUNK_UNITS units a chunk, SKM_DEMUX_CHUNK_UNITS in the environment for fewer)
+    and adds every cell's reads of a chunk as one in-order segment.  Every kept cell goes through the set whatever
+    its size.  Returns (SampleSet, kept int64[n_kept], stats): stats maps BARCODE_STATS to counts over the run's
+    units, 'units' to their number and 'records' to the files' record counts (barcode file, cDNA files)."""
+    strand_mode(strand)
+    if int(min_units) < 1:
+        raise ValueError('min_units must be at least 1, not %r' % (min_units,))
+    if barcode_feeder.paired or len(barcode_feeder.paths) != 1:
+        raise ValueError('one barcode file, read single-ended')
+    if bool(read_feeder.paired) != bool(paired) or len(read_feeder.paths) != (2 if paired else 1):
+        raise ValueError('one pooled sample: %s' % ('two cDNA files' if paired else 'one cDNA file'))
+    chunk_units = _demux_chunk_units()
+    records = [fastq_records(path) for path in list(barcode_feeder.paths) + list(read_feeder.paths)]
+    n_units = min(records)
+    if len(set(records)) != 1:
+        _LOG.warning('The barcode file holds %d records, the cDNA files %s: the run is the first %d units of each',
+                     records[0], ' and '.join(str(n) for n in records[1:]), n_units)
+    if n_units >= 1 << 40:
+        raise ValueError('a run of %d units' % n_units)
+    # phase 1: the cell of every unit
+    cell = numpy.full(n_units, -1, dtype=numpy.int32)
+    units = 0
+    units_before, stats_before = table.cell_units.copy(), table.stats.copy()       # (the table's counters run on)
+    for piece in barcode_feeder:
+        if piece.is_cut or piece.n_reads == 0 or units >= n_units:
+            continue
+        if piece.first_read != units:
+            raise ValueError('the barcode reads do not follow each other (read %d after %d)' % (piece.first_read, units))
+        if units + piece.n_reads > n_units:
+            piece = _slice_piece(piece, 0, n_units - units)
+        cell[units:units + piece.n_reads] = table.assign(piece, start=start, mismatches=mismatches)
+        units += piece.n_reads
+    if units != n_units:
+        raise ValueError('the barcode file gave %d reads, its lines said %d' % (units, n_units))
+    cell_units = table.cell_units - units_before
+    kept = numpy.flatnonzero(cell_units >= int(min_units))
+    limit = 1 << 15 if bias else 1 << 16 if per_sample_lengths else 1 << 24
+    if kept.size > limit:
+        raise ValueError('%d cells have at least %d units, a set holds %d at most%s: raise --min-units'
+                         % (kept.size, min_units, limit, ' with --bias' if bias else ''))
+    number = numpy.full(len(table) + 1, -1, dtype=numpy.int32)       # (cell -1 reads the last entry: dropped)
+    number[kept] = numpy.arange(kept.size, dtype=numpy.int32)
+    sample = number[cell]
+    # phase 2: the reads, cell by cell, into the set
+    sample_set = SampleSet(index, paired, device=device, strand=strand, per_sample_lengths=per_sample_lengths,
+                           length_model=length_model, bias=bias)
+    if kept.size:
+        added, walked = demux_chunks(read_feeder, paired, sample, kept.size, chunk_units,
+                                     lambda part, n: group_units(part, n, device=device), sample_set.add_packed)
+        if walked != n_units or not numpy.array_equal(added, cell_units[kept]):
+            raise ValueError('the cDNA files gave %d units, their lines said %d' % (walked, n_units))
+        sample_set.sync()
+    stats = {name: int(value) for name, value in zip(BARCODE_STATS, table.stats - stats_before)}
+    stats.update(units=n_units, records=records, cells=int(kept.size), cell_units=cell_units)
+    return sample_set, kept, stats
