@@ -12,7 +12,7 @@
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
  *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_bias_*,
- *                          skm_gene_*, skm_barcodes_*, skm_units_group, skm_comm_*, skm_device_*)
+ *                          skm_gene_*, skm_barcodes_*, skm_umi_windows, skm_units_group, skm_comm_*, skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
  *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_packed_gather,
  *                          skm_synth_*)
@@ -439,6 +439,30 @@ int skm_sample_set_histograms(skm_sample_set *set, int64_t cap_samples, int64_t 
  * (rows of room in out) is below the samples named so far. */
 int skm_sample_set_keep_bias(skm_sample_set *set, int enable);
 int skm_sample_set_bias_observed(skm_sample_set *set, int64_t cap_samples, int64_t *out);
+/* UMI collapse ("UMI collapse").  umi_bases = 1 .. 16: every unit of the set comes with a UMI of
+ * that many bases (2 bits a base, below 4^umi_bases), and inside a sample a unit is a DUPLICATE when an earlier unit
+ * of the sample (a lower unit number) has the same UMI and the same class -- the same target tuple after the strand
+ * filter.  The first unit of every (sample, UMI, class) stays; every later one is removed as if it had never been
+ * added: it counts in no total, no class, no histogram per sample, no hexamer row, no first-seen unit.  A unit
+ * without a class (unaligned) is never removed.  The molecules live in an exact set in HBM (32-byte slots, at most
+ * half full: 64 bytes a molecule; sized ahead of every launch and grown by rehashing; an allocation that fails says
+ * so) that two kernels of every launch consult between the strand filter and everything that counts
+ * (skm_umi.hip); two molecules that share a 64-bit tag fail the call with SKM_ERR_COLLISION.  A set that was not
+ * asked launches what it always has.  Only before the set's first segment, and only in a set that keeps a
+ * histogram per sample (skm_sample_set_keep_histograms first; the POOLED histogram of skm_sample_set_histogram is
+ * counted inside the map kernel and still holds the removed units): SKM_ERR_STATE otherwise.  0 switches it off.
+ * SKM_TEST_UMI_SLOTS (a power of two >= 2, read by skm_sample_set_create) starts the molecule set at that many
+ * slots and grows it only when a launch finds it full, for tests.
+ * skm_sample_set_add_packed_umis: skm_sample_set_add_packed with umis[n], the UMI of every unit (SKM_ERR_ARG for
+ * one that does not fit umi_bases); they are copied with the reads.  In a set that keeps UMIs it is the only way to
+ * add (_add_packed and _add_batch return SKM_ERR_ARG), in any other set it returns SKM_ERR_ARG.
+ * skm_sample_set_umi_removed: removed[n_samples], the units removed so far per sample (zeros in a set that keeps no
+ * UMIs); every unit total the set reports (_summary, _export, the samples' unaligned counts) is the units added less
+ * these.  Waits and holds adders as _summary; SKM_ERR_ARG if cap_samples is below the samples named so far. */
+int skm_sample_set_keep_umis(skm_sample_set *set, int umi_bases);
+int skm_sample_set_add_packed_umis(skm_sample_set *set, int64_t sample, int64_t first_unit, const skm_packed_reads *mate1,
+                                   const skm_packed_reads *mate2, const uint32_t *umis);
+int skm_sample_set_umi_removed(skm_sample_set *set, int64_t cap_samples, int64_t *removed);
 /* DIAGNOSTICS, with no promise of stability: the set's bookkeeping on the host alone (no GPU is
  * touched), for tests.  They run the cutting, the log and the ordering by (sample, local first
  * seen) that the set itself runs; _split bisects the log on the host where the set does it in a
@@ -519,6 +543,14 @@ int skm_barcodes_destroy(skm_barcodes *barcodes);
 int skm_barcodes_assign(skm_barcodes *barcodes, const skm_packed_reads *reads, int start, int max_mismatches,
                         int32_t *cell /* [n_reads] */, int64_t *cell_units /* [n], added to */,
                         int64_t stats[5] /* added to */);
+/* The UMI of every read of a piece of barcode reads (a host piece, as for skm_barcodes_assign): bases
+ * [start, start + length), 1 <= length <= 16, as 2 bits a base (A0 C1 G2 T3), the first base in the top bits of the
+ * 2 x length used bits of umi[r].  A read that is shorter than start + length, or that holds a position in the
+ * window that is not an upper-case ACGT, has no UMI: umi[r] = 0, cell[r] = -1 (cell -- in/out, the cells of
+ * skm_barcodes_assign -- may be NULL) and *n_unreadable += 1.  The window may lie anywhere in the read, before or
+ * after the barcode, and straddle a code word; only the window's words are uploaded. */
+int skm_umi_windows(int device, const skm_packed_reads *reads, int start, int length, int32_t *cell /* in/out, may be NULL */,
+                    uint32_t *umi /* [n_reads] */, int64_t *n_unreadable /* added to */);
 /* A run of n < 2^31 units by sample: sample[u] in [0, n_samples) or negative (dropped), n_samples <= 2^24 ->
  * order[] = the kept units grouped by ascending sample and in their original order inside a sample (room for n;
  * offsets[n_samples] are written), offsets[n_samples + 1]: sample s owns order[offsets[s] .. offsets[s + 1]).

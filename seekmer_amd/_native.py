@@ -130,6 +130,12 @@ HIP_SYMBOLS = {
     'skm_sample_set_histograms': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
     'skm_sample_set_keep_bias': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_sample_set_bias_observed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
+    'skm_sample_set_keep_umis': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_add_packed_umis': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(PackedReads),
+                                                      ctypes.POINTER(PackedReads), c_u32p]),
+    'skm_sample_set_umi_removed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
+    'skm_umi_windows': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(PackedReads), ctypes.c_int, ctypes.c_int, c_i32p, c_u32p,
+                                       c_i64p]),
     'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),
     'skm_sample_set_split': (ctypes.c_int, [c_i64, c_i64p, c_i64p, c_i32p, c_i64, c_i64, c_i64p, c_i32p, c_i64p, c_i64p,
                                             c_i64p]),

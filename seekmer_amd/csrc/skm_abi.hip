@@ -1226,11 +1226,14 @@ int read_error(skm_mapper *m)
 // record); nullptr = pack_reads_kernel over ASCII bases + offsets
 // salt: the batch is a launch of a sample set -- the segments whose samples go into the records' keys
 // before class counting (skm_samples.hip); nullptr = one sample, keys as the map kernel made them
+// collapse: a sample set that keeps UMIs -- what removes the duplicate units' records (skm_umi.hip) once the map
+// attempt that stood and the strand filter have run, before anything counts; nullptr = nothing is launched
 typedef std::function<int(uint32_t *, int, int)> RecordStage;
+typedef std::function<int(const MapBatch &)> BatchStage;
 int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_offsets,
                        int64_t n_units, int paired, int max_len, int64_t first_unit = -1,
                        const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr,
-                       unsigned long long *sample_bias_rows = nullptr)
+                       unsigned long long *sample_bias_rows = nullptr, const BatchStage *collapse = nullptr)
 {
     const int64_t unit_base = first_unit >= 0 ? first_unit : m->units_done;
     skm_index *ix = m->ix;
@@ -1339,6 +1342,7 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
         launch_strand_filter(b, m->strand, m->stream);
         HIP_TRY(hipGetLastError());
     }
+    if (collapse) SKM_TRY((*collapse)(b));
     if (m->bias) {             // --bias: the first hexamers of the units that are still aligned
         launch_bias_observed(m->records.p, record_words, words, paired, m->rec_tuple.p, m->rec_unit.p, n_units,
                              m->bias_observed.p, m->stream);
@@ -1404,7 +1408,8 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
         HIP_TRY(hipStreamSynchronize(m->stream));
         const int err = *reinterpret_cast<int *>(m->pinned + 16);
         if (err == SKM_ERR_COLLISION)
-            return fail(SKM_ERR_COLLISION, "two different class tuples share a 64-bit key");
+            return fail(SKM_ERR_COLLISION, collapse ? "two different class tuples, or two different molecules, share a 64-bit key"
+                                                    : "two different class tuples share a 64-bit key");
         if (err == SKM_ERR_ARG) return fail(SKM_ERR_ARG, "a packed read is longer than its code words hold");
         if (err) return fail(err, "class table kernel reported error %d", err);
         m->host_arena_used = (int64_t)m->pinned[CTR_ARENA];
@@ -2564,6 +2569,8 @@ struct SetChunk {                        // the reads of one added segment where
     const int64_t *offsets = nullptr;    // [reads + 1], as the caller gave them
     int64_t origin = 0;                  // the sample's unit of the segment's first read
     int max_len = 0;
+    std::shared_ptr<uint32_t> umis;      // a set that keeps UMIs: umis[u - umi_origin] of the segment's unit u, in HBM
+    int64_t umi_origin = 0;
 };
 struct SetQueued { int32_t sample; int64_t first, n; std::shared_ptr<SetChunk> data; };   // what is left of a segment
 struct SetPart { int32_t sample; int64_t first, n, at; std::shared_ptr<SetChunk> data; }; // units [first, first + n) of
@@ -2640,6 +2647,17 @@ struct skm_sample_set {
     // one row of observed hexamers per sample (skm_sample_set_keep_bias): [rows][4096], kept as `hist` is
     bool keep_bias = false;
     DBuf<unsigned long long> bias_rows;
+    // UMI collapse (skm_sample_set_keep_umis; skm_umi.hip): the molecule set -- umi_n_slots slots, a power of two,
+    // sized ahead of every launch to at least twice (molecules so far + the launch's records) --, its two counters,
+    // the units removed per sample (rows kept as `hist` is) and the segments' UMIs of the launch under way;
+    // touched under m->mu.  SKM_TEST_UMI_SLOTS: the set starts at that many slots and grows only when a launch
+    // finds it full.
+    int umi_bases = 0;                            // 0: the set keeps no UMIs
+    DBuf<UmiSlot> umi_slots;
+    uint64_t umi_n_slots = 0, umi_test_slots = 0;
+    int64_t umi_entries = 0;
+    DBuf<unsigned long long> umi_ctl, umi_removed;
+    DBuf<UmiSegment> umi_segs;
     // ---- under mu
     std::mutex mu;
     std::condition_variable work_cv, done_cv;
@@ -2656,7 +2674,8 @@ struct skm_sample_set {
     struct View {
         bool valid = false;
         std::vector<int64_t> start, len, count, local, order, sample_class_offsets, sample_rows, sample_aligned;
-        std::vector<int64_t> units;               // sample_units as the view was made: all of them mapped
+        std::vector<int64_t> units;               // sample_units as the view was made, all of them mapped, less `removed`
+        std::vector<int64_t> removed;             // the units UMI collapse has removed, per sample (zeros without it)
         std::vector<int32_t> arena;
         // the classes where class_compact and sample_assign left them in HBM (registry order), kept with the view
         // for the calls that pass over the table on the device (skm_sample_set_gene_counts)
@@ -2668,6 +2687,31 @@ struct skm_sample_set {
 
 namespace {
 
+// the molecule set in `n_slots` slots (a power of two): a fresh set, or the molecules of the old one rehashed
+// (m->mu is held; the stream drains before the old slots go back to the pool)
+int set_umi_grow(skm_sample_set *s, uint64_t n_slots)
+{
+    skm_mapper *m = s->m;
+    if (n_slots > (1ULL << 36)) return fail(SKM_ERR_STATE, "a molecule set of %llu slots", (unsigned long long)n_slots);
+    DBuf<UmiSlot> fresh;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });
+    if (fresh.ensure((size_t)n_slots) != SKM_OK) {
+        const std::string why = g_error;
+        return fail(SKM_ERR_HIP, "UMI collapse: no device memory for a molecule set of %llu slots, %llu MB (64 bytes a molecule "
+                    "at load 1/2; %lld molecules so far): %s", (unsigned long long)n_slots,
+                    (unsigned long long)(n_slots * sizeof(UmiSlot) >> 20), (long long)s->umi_entries, why.c_str());
+    }
+    const UmiSet to{fresh.p, n_slots - 1, s->umi_ctl.p, m->error.p};
+    if (s->umi_n_slots) launch_umi_rehash(UmiSet{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, m->error.p}, to, m->stream);
+    else launch_umi_init(to, m->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    drain.dismiss();
+    s->umi_slots = std::move(fresh);
+    s->umi_n_slots = n_slots;
+    return SKM_OK;
+}
+
 int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_units, int64_t global_first)
 {
     skm_mapper *m = s->m;
@@ -2677,6 +2721,7 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
     const int n_parts = (int)parts.size();
     if (n_parts > SAMPLE_LAUNCH_SEGMENTS) return fail(SKM_ERR_STATE, "%d segments in one launch", n_parts);
     std::vector<int32_t> table(2 * (size_t)n_parts);
+    std::vector<UmiSegment> umi_segments;         // (a set that keeps UMIs)
     std::vector<PackedSegment> segments;          // `first` = place in the launch
     int max_cw = 0, max_len = 0;
     for (int i = 0; i < n_parts; ++i) {
@@ -2728,8 +2773,62 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
         if (s->bias_rows.cap > held)
             HIP_TRY(hipMemsetAsync(s->bias_rows.p + held, 0, (s->bias_rows.cap - held) * sizeof(unsigned long long), m->stream));
     }
+    // UMI collapse: the launch's segments with their UMIs, room in the molecule set, rows of removed[]; then claim and
+    // resolve between the strand filter and everything that counts
+    const BatchStage collapse = [&](const MapBatch &b) -> int {
+        for (;;) {
+            const UmiSet set{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, m->error.p};
+            HIP_TRY(hipMemsetAsync(s->umi_ctl.p + UMI_CTL_LOST, 0, sizeof(unsigned long long), m->stream));
+            launch_umi_claim(set, b, salt, s->umi_segs.p, m->stream);
+            HIP_TRY(hipGetLastError());
+            if (!s->umi_test_slots) break;        // (sized ahead: a full set is reported after the launch)
+            unsigned long long *lost = m->pinned + 48;
+            HIP_TRY(hipMemcpyAsync(lost, s->umi_ctl.p + UMI_CTL_LOST, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+            HIP_TRY(hipStreamSynchronize(m->stream));
+            if (*lost == 0) break;
+            // full under test: four times the slots, and the pass again -- find-or-claim and a minimum, so a
+            // record that had its turn changes nothing by a second one
+            SKM_TRY(set_umi_grow(s, s->umi_n_slots * 4));
+        }
+        const UmiSet set{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, m->error.p};
+        launch_umi_resolve(set, b, salt, s->umi_segs.p, s->umi_removed.p, m->stream);
+        HIP_TRY(hipGetLastError());
+        return SKM_OK;
+    };
+    if (s->umi_bases) {
+        int32_t largest = 0;
+        umi_segments.reserve(n_parts);
+        for (const SetPart &part : parts) {
+            largest = std::max(largest, part.sample);
+            if (!part.data->umis) return fail(SKM_ERR_STATE, "a segment without UMIs in a set that keeps them");
+            umi_segments.push_back(UmiSegment{part.first, part.data->umis.get() + (part.first - part.data->umi_origin)});
+        }
+        SKM_TRY(s->umi_segs.ensure(SAMPLE_LAUNCH_SEGMENTS));
+        HIP_TRY(hipMemcpyAsync(s->umi_segs.p, umi_segments.data(), umi_segments.size() * sizeof(UmiSegment), hipMemcpyHostToDevice, m->stream));
+        const size_t held = s->umi_removed.cap;
+        SKM_TRY(s->umi_removed.ensure((size_t)largest + 1, true, m->stream));
+        if (s->umi_removed.cap > held)
+            HIP_TRY(hipMemsetAsync(s->umi_removed.p + held, 0, (s->umi_removed.cap - held) * sizeof(unsigned long long), m->stream));
+        if (!s->umi_ctl.p) {
+            SKM_TRY(s->umi_ctl.ensure(UMI_CTL_WORDS));
+            HIP_TRY(hipMemsetAsync(s->umi_ctl.p, 0, UMI_CTL_WORDS * sizeof(unsigned long long), m->stream));
+        }
+        uint64_t want = s->umi_test_slots ? s->umi_test_slots : 1024;
+        if (!s->umi_test_slots)
+            while (want < 2 * (uint64_t)(s->umi_entries + n_units)) want *= 2;
+        if (s->umi_n_slots == 0 || (!s->umi_test_slots && want > s->umi_n_slots)) SKM_TRY(set_umi_grow(s, want));
+    }
     SKM_TRY(map_batch_resident(m, nullptr, nullptr, n_units, s->paired, max_len, global_first, &fill, &salt,
-                               s->keep_bias ? s->bias_rows.p : nullptr));
+                               s->keep_bias ? s->bias_rows.p : nullptr, s->umi_bases ? &collapse : nullptr));
+    if (s->umi_bases) {                           // (the stream has drained)
+        unsigned long long *ctl = m->pinned + 48;
+        HIP_TRY(hipMemcpyAsync(ctl, s->umi_ctl.p, UMI_CTL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        if (ctl[UMI_CTL_LOST])
+            return fail(SKM_ERR_STATE, "the molecule set of %llu slots was full for %llu records", (unsigned long long)s->umi_n_slots,
+                        ctl[UMI_CTL_LOST]);
+        s->umi_entries = (int64_t)ctl[UMI_CTL_ENTRIES];
+    }
     if (s->keep_hist) {
         // the spans of the attempt that stood (an overflowing entry arena runs the map kernel again), after
         // the pair rule; they stay until this mapper's next launch, which the set's worker starts after this one
@@ -2862,6 +2961,19 @@ int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
     v.sample_class_offsets.assign(n_samples + 1, 0);
     v.sample_rows.assign(n_samples, 0); v.sample_aligned.assign(n_samples, 0);
     v.units = s->sample_units;
+    v.removed.assign(n_samples, 0);
+    int64_t removed_total = 0;
+    if (s->umi_bases && s->umi_removed.cap && n_samples) {      // (a sample that no launch has held may lie past the rows)
+        const int64_t rows = std::min<int64_t>(n_samples, (int64_t)s->umi_removed.cap);
+        HIP_TRY(hipMemcpyAsync(v.removed.data(), s->umi_removed.p, (size_t)rows * 8, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        for (int64_t i = 0; i < n_samples; ++i) {
+            if (v.removed[i] < 0 || v.removed[i] > v.units[i])
+                return fail(SKM_ERR_STATE, "sample %lld: %lld of %lld units removed", (long long)i, (long long)v.removed[i], (long long)v.units[i]);
+            v.units[i] -= v.removed[i];               // a removed unit was never in the files
+            removed_total += v.removed[i];
+        }
+    }
     std::vector<int32_t> cls_sample(C);
     if (C) {
         if (n_log == 0) return fail(SKM_ERR_STATE, "classes without a launch");
@@ -2894,14 +3006,16 @@ int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
         }
     }
     set_split_order(n_samples, C, cls_sample.data(), v.local.data(), v.order.data(), v.sample_class_offsets.data());
-    // (units_s - aligned_s is each sample's unaligned count; their sum is what the table counted)
+    // (units_s - aligned_s is each sample's unaligned count; their sum is what the table counted -- less the units
+    // that UMI collapse removed, which reached class counting looking unaligned)
     int64_t unaligned = 0;
     for (int64_t i = 0; i < n_samples; ++i) {
-        if (v.sample_aligned[i] > s->sample_units[i]) return fail(SKM_ERR_STATE, "sample %lld counts more units than it has", (long long)i);
-        unaligned += s->sample_units[i] - v.sample_aligned[i];
+        if (v.sample_aligned[i] > v.units[i]) return fail(SKM_ERR_STATE, "sample %lld counts more units than it has", (long long)i);
+        unaligned += v.units[i] - v.sample_aligned[i];
     }
-    if (m->host_totals_valid && unaligned != (int64_t)m->host_unaligned)
-        return fail(SKM_ERR_STATE, "the samples' unaligned units (%lld) are not the table's (%llu)", (long long)unaligned, m->host_unaligned);
+    if (m->host_totals_valid && unaligned != (int64_t)m->host_unaligned - removed_total)
+        return fail(SKM_ERR_STATE, "the samples' unaligned units (%lld) are not the table's (%llu less %lld removed)", (long long)unaligned,
+                    m->host_unaligned, (long long)removed_total);
     v.valid = true;
     return SKM_OK;
 }
@@ -2928,6 +3042,12 @@ extern "C" int skm_sample_set_create(skm_index *ix, int paired, skm_sample_set *
     HIP_TRY(hipStreamCreateWithFlags(s->copy_stream.out(), hipStreamNonBlocking));
     if (const char *v = getenv("SKM_SAMPLE_SET_MAX_UNITS"))
         if (atoll(v) > 0) s->max_units = std::min<int64_t>(atoll(v), PACKED_MAX_UNITS);
+    if (const char *v = getenv("SKM_TEST_UMI_SLOTS")) {          // test hook: a molecule set that has to grow under a launch
+        const long long n = atoll(v);
+        if (n < 2 || n > (1LL << 30) || (n & (n - 1)))
+            return fail(SKM_ERR_ARG, "SKM_TEST_UMI_SLOTS must be a power of two from 2 to 2^30, not '%s'", v);
+        s->umi_test_slots = (uint64_t)n;
+    }
     *out = s.release();
     return SKM_OK;
 }
@@ -2963,6 +3083,7 @@ extern "C" int skm_sample_set_keep_histograms(skm_sample_set *s, int enable)
     std::lock_guard<std::mutex> hold(s->mu);
     for (const int64_t units : s->sample_units)
         if (units) return fail(SKM_ERR_STATE, "histograms per sample can only be switched on an empty sample set");
+    if (!enable && s->umi_bases) return fail(SKM_ERR_STATE, "a set that keeps UMIs keeps its histograms per sample");
     SKM_TRY(skm_mapper_keep_spans(s->m, enable));
     s->keep_hist = enable != 0;
     return SKM_OK;
@@ -2978,10 +3099,30 @@ extern "C" int skm_sample_set_keep_bias(skm_sample_set *s, int enable)
     return SKM_OK;
 }
 
-extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit,
-                                         const skm_packed_reads *mate1, const skm_packed_reads *mate2)
+extern "C" int skm_sample_set_keep_umis(skm_sample_set *s, int umi_bases)
 {
-    if (!s || !mate1) return fail(SKM_ERR_ARG, "NULL argument");
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    if (umi_bases < 0 || umi_bases > 16) return fail(SKM_ERR_ARG, "UMIs of %d bases: 1 to 16 are possible (0: none)", umi_bases);
+    std::lock_guard<std::mutex> hold(s->mu);
+    if (!s->sample_units.empty()) return fail(SKM_ERR_STATE, "UMIs can only be switched before the set's first segment");
+    if (umi_bases && !s->keep_hist)
+        return fail(SKM_ERR_STATE, "a set that keeps UMIs keeps a histogram per sample: call skm_sample_set_keep_histograms(set, 1) "
+                    "first (the pooled histogram is counted inside the map kernel and cannot leave a unit out)");
+    s->umi_bases = umi_bases;
+    return SKM_OK;
+}
+
+namespace {
+
+int set_umi_bases(skm_sample_set *s)
+{
+    std::lock_guard<std::mutex> hold(s->mu);
+    return s->umi_bases;
+}
+
+int set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit, const skm_packed_reads *mate1,
+                   const skm_packed_reads *mate2, const uint32_t *umis)
+{
     if ((mate2 != nullptr) != (s->paired != 0)) return fail(SKM_ERR_ARG, "a %s set takes %s", s->paired ? "paired" : "single-ended",
                                                            s->paired ? "both mates" : "mate 1 alone");
     const int64_t n = mate1->n_reads;
@@ -3000,16 +3141,50 @@ extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int6
             SKM_TRY(packed_upload(&piece, s->bytes, s->copy_stream, &held));
             data->pieces[k].push_back(std::move(held));
         }
+        if (umis) {                                    // the UMIs go with the chunk
+            uint32_t *raw = nullptr;
+            const int64_t block_bytes = (int64_t)packed_round((size_t)n * 4);
+            HIP_TRY(pool_alloc((void **)&raw, (size_t)block_bytes));
+            std::shared_ptr<std::atomic<int64_t>> counter = s->bytes;
+            counter->fetch_add(block_bytes);
+            data->umis = std::shared_ptr<uint32_t>(raw, [counter, block_bytes](uint32_t *q) { pool_free(q); counter->fetch_sub(block_bytes); });
+            data->umi_origin = first_unit;
+            HIP_TRY(hipMemcpyAsync(raw, umis, (size_t)n * 4, hipMemcpyHostToDevice, s->copy_stream));
+        }
         drain.dismiss();
         HIP_TRY(hipStreamSynchronize(s->copy_stream));
     }
     return set_enqueue(s, sample, first_unit, n, std::move(data));
 }
 
+}  // namespace
+
+extern "C" int skm_sample_set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit,
+                                         const skm_packed_reads *mate1, const skm_packed_reads *mate2)
+{
+    if (!s || !mate1) return fail(SKM_ERR_ARG, "NULL argument");
+    if (set_umi_bases(s)) return fail(SKM_ERR_ARG, "a set that keeps UMIs takes its reads with them: skm_sample_set_add_packed_umis");
+    return set_add_packed(s, sample, first_unit, mate1, mate2, nullptr);
+}
+
+extern "C" int skm_sample_set_add_packed_umis(skm_sample_set *s, int64_t sample, int64_t first_unit, const skm_packed_reads *mate1,
+                                              const skm_packed_reads *mate2, const uint32_t *umis)
+{
+    if (!s || !mate1) return fail(SKM_ERR_ARG, "NULL argument");
+    const int umi_bases = set_umi_bases(s);
+    if (!umi_bases) return fail(SKM_ERR_ARG, "the set keeps no UMIs: call skm_sample_set_keep_umis before the first segment");
+    if (mate1->n_reads > 0 && !umis) return fail(SKM_ERR_ARG, "NULL UMIs");
+    if (umi_bases < 16)
+        for (int64_t u = 0; u < mate1->n_reads; ++u)
+            if (umis[u] >> (2 * umi_bases)) return fail(SKM_ERR_ARG, "UMI %lld (%u) does not fit %d bases", (long long)u, umis[u], umi_bases);
+    return set_add_packed(s, sample, first_unit, mate1, mate2, mate1->n_reads > 0 ? umis : nullptr);
+}
+
 extern "C" int skm_sample_set_add_batch(skm_sample_set *s, int64_t sample, int64_t first_unit, const char *bases,
                                         const int64_t *offsets, int64_t n_units)
 {
     if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    if (set_umi_bases(s)) return fail(SKM_ERR_ARG, "a set that keeps UMIs takes its reads with them: skm_sample_set_add_packed_umis");
     if (n_units > 0 && (!bases || !offsets)) return fail(SKM_ERR_ARG, "NULL reads");
     SKM_TRY(set_admit(s, sample, first_unit, n_units));
     auto data = std::make_shared<SetChunk>();
@@ -3149,6 +3324,18 @@ extern "C" int skm_sample_set_bias_observed(skm_sample_set *s, int64_t cap_sampl
         HIP_TRY(hipMemcpyAsync(out, s->bias_rows.p, (size_t)rows * BIAS_BINS * 8, hipMemcpyDeviceToHost, m->stream));
         HIP_TRY(hipStreamSynchronize(m->stream));
     }
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_umi_removed(skm_sample_set *s, int64_t cap_samples, int64_t *removed)
+{
+    if (!s || cap_samples < 0 || (cap_samples && !removed)) return fail(SKM_ERR_ARG, "bad argument");
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    const skm_sample_set::View &v = s->view;
+    const int64_t n_samples = (int64_t)v.removed.size();
+    if (cap_samples < n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)n_samples);
+    std::copy(v.removed.begin(), v.removed.end(), removed);
     return SKM_OK;
 }
 
@@ -3515,6 +3702,73 @@ extern "C" int skm_barcodes_assign(skm_barcodes *b, const skm_packed_reads *read
     drain.dismiss();                          // (the copies home have waited for the kernels)
     for (int64_t c = 0; c < b->n; ++c) cell_units[c] += (int64_t)counted[c];
     for (int k = 0; k < BARCODE_STATS; ++k) stats[k] += (int64_t)counted[b->n + k];
+    return SKM_OK;
+}
+
+// The scratch lives for the call; all work is on the default stream with blocking copies, as skm_barcodes_assign.
+extern "C" int skm_umi_windows(int device, const skm_packed_reads *reads, int start, int length, int32_t *cell, uint32_t *umi,
+                               int64_t *n_unreadable)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    if (!reads || !n_unreadable) return fail(SKM_ERR_ARG, "bad argument");
+    if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a UMI that starts at base %d", start);
+    if (length < 1 || length > 16) return fail(SKM_ERR_ARG, "UMIs of %d bases: 1 to 16 are possible", length);
+    const int64_t n = reads->n_reads, n_exc = reads->n_exceptions;
+    if (n < 0 || n >= (1LL << 31) || n_exc < 0 || n_exc > n) return fail(SKM_ERR_ARG, "a piece of %lld reads", (long long)n);
+    if (n == 0) return SKM_OK;
+    const int64_t code_words = reads->code_words;
+    if (!umi || code_words < 0 || reads->read_stride < code_words || (code_words && !reads->codes) ||
+        (!reads->lengths && reads->uniform_len < 0) || (n_exc && (!reads->exception_reads || !reads->exception_masks)))
+        return fail(SKM_ERR_ARG, "not a piece of packed reads");
+    for (int64_t e = 0; e < n_exc; ++e)
+        if (reads->exception_reads[e] >= (uint64_t)n) return fail(SKM_ERR_ARG, "exception %lld names read %u of %lld", (long long)e, reads->exception_reads[e], (long long)n);
+    // the one or two words of every read that hold the window, as far as the piece has them
+    const int64_t first_word = start / 32;
+    const int offset = start % 32;
+    const int words = (int)std::max<int64_t>(0, std::min<int64_t>(code_words - first_word, offset + length > 32 ? 2 : 1));
+    SKM_TRY(set_device(device));
+    DBuf<uint64_t> d_codes; DBuf<uint32_t> d_lengths, d_clean, d_exc_reads, d_exc_masks, d_umi; DBuf<int32_t> d_cell;
+    DBuf<unsigned long long> d_count;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_codes.ensure((size_t)std::max<int64_t>(n * words, 1))); SKM_TRY(d_clean.ensure(n)); SKM_TRY(d_umi.ensure(n));
+    SKM_TRY(d_count.ensure(1));
+    if (words) {
+        std::vector<uint64_t> window((size_t)(n * words));
+        for (int64_t r = 0; r < n; ++r)
+            for (int k = 0; k < words; ++k) window[r * words + k] = reads->codes[r * reads->read_stride + first_word + k];
+        HIP_TRY(hipMemcpy(d_codes.p, window.data(), window.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (reads->lengths) {
+        SKM_TRY(d_lengths.ensure(n));
+        HIP_TRY(hipMemcpy(d_lengths.p, reads->lengths, n * 4, hipMemcpyHostToDevice));
+    }
+    if (cell) {
+        SKM_TRY(d_cell.ensure(n));
+        HIP_TRY(hipMemcpy(d_cell.p, cell, n * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(d_clean.p, 0xff, n * 4, nullptr));
+    HIP_TRY(hipMemsetAsync(d_count.p, 0, 8, nullptr));
+    if (n_exc && words) {
+        SKM_TRY(d_exc_reads.ensure(n_exc)); SKM_TRY(d_exc_masks.ensure(n_exc * words));
+        HIP_TRY(hipMemcpy(d_exc_reads.p, reads->exception_reads, n_exc * 4, hipMemcpyHostToDevice));
+        std::vector<uint32_t> planes((size_t)(n_exc * words));
+        for (int64_t e = 0; e < n_exc; ++e)
+            for (int k = 0; k < words; ++k) planes[e * words + k] = reads->exception_masks[e * code_words + first_word + k];
+        HIP_TRY(hipMemcpy(d_exc_masks.p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice));
+        launch_barcode_clean(d_exc_reads.p, d_exc_masks.p, n_exc, words, offset, d_clean.p, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    const BarcodeWindows w{n, d_codes.p, words, offset, reads->lengths ? d_lengths.p : nullptr, reads->uniform_len, start, d_clean.p};
+    launch_umi_windows(w, length, cell ? d_cell.p : nullptr, d_umi.p, d_count.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    unsigned long long counted = 0;
+    HIP_TRY(hipMemcpy(umi, d_umi.p, n * 4, hipMemcpyDeviceToHost));
+    if (cell) HIP_TRY(hipMemcpy(cell, d_cell.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&counted, d_count.p, 8, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    *n_unreadable += (int64_t)counted;
     return SKM_OK;
 }
 

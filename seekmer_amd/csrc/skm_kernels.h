@@ -555,6 +555,52 @@ void launch_group_keys(const int32_t *sample, int64_t n, int64_t n_samples, uint
 // offsets[s] (s <= n_samples) = the first place of the ascending keys[0 .. n) whose key is >= s
 void launch_group_offsets(const uint32_t *sorted_keys, int64_t n, int64_t n_samples, int64_t *offsets, hipStream_t stream);
 
+// ---- UMI collapse (skm_umi.hip; DESIGN.md section 4, "UMI collapse")
+// umi[r] = the 2 L code bits of bases [w.start, w.start + length) of read r (first base in the top bits of the 2 L used
+// bits; 1 <= length <= 16), 0 where the read is too short for the window or holds a position there that is not an
+// upper-case ACGT; such a read gets cell[r] = -1 (cell may be nullptr) and adds one to *n_unreadable
+void launch_umi_windows(const BarcodeWindows &w, int length, int32_t *cell, uint32_t *umi, unsigned long long *n_unreadable,
+                        hipStream_t stream);
+struct alignas(32) UmiSlot {      // 32 B: one molecule (sample, class, UMI) of a sample set
+    unsigned long long tag;       // umi_tag(class_key, umi); 0 = empty
+    unsigned long long class_key; // sample_key(the tuple's key, sample)
+    uint32_t umi;
+    uint32_t unused;
+    unsigned long long min_unit;  // the smallest sample-local unit number seen of the molecule (~0: none yet)
+};
+// the tag of a molecule: a mix of its salted class key and its UMI.  Only where the probe starts and what it compares
+// first: resolve compares key and UMI in full.
+__host__ __device__ __forceinline__ uint64_t umi_tag(uint64_t class_key, uint32_t umi)
+{
+    uint64_t h = class_key ^ (((uint64_t)umi + 1) * 0x9E3779B97F4A7C15ULL);
+    h ^= h >> 32;
+    h *= 0xD6E8FEB86659FD93ULL;
+    h ^= h >> 29;
+    h *= 0x9E3779B97F4A7C15ULL;
+    h ^= h >> 32;
+    return h;
+}
+enum { UMI_CTL_ENTRIES = 0, UMI_CTL_LOST = 1, UMI_CTL_WORDS = 2 };
+struct UmiSet {
+    UmiSlot *slots;
+    uint64_t slot_mask;           // slots - 1, a power of two of them
+    unsigned long long *ctl;      // [UMI_CTL_ENTRIES] molecules in the set, [UMI_CTL_LOST] probes that found the set full
+    int *error;                   // SKM_ERR_* raised by a kernel
+};
+struct UmiSegment {               // beside SampleSalt's arrays, for the same segments of a launch
+    int64_t local_first;          // the sample-local unit number of the segment's first unit
+    const uint32_t *umi;          // the UMIs of the segment's units, in unit order
+};
+void launch_umi_init(const UmiSet &t, hipStream_t stream);
+// pass 1 and pass 2 over the records of a launch (after the strand filter, before anything counts); removed[sample]
+// += the records that pass 2 made unaligned.  A full set adds to ctl[UMI_CTL_LOST] and changes no record wrongly: what
+// it removes had an earlier copy.
+void launch_umi_claim(const UmiSet &t, const MapBatch &b, const SampleSalt &salt, const UmiSegment *segs, hipStream_t stream);
+void launch_umi_resolve(const UmiSet &t, const MapBatch &b, const SampleSalt &salt, const UmiSegment *segs,
+                        unsigned long long *removed, hipStream_t stream);
+// `to` (any slots' contents) becomes a set that holds the molecules of `from`
+void launch_umi_rehash(const UmiSet &from, const UmiSet &to, hipStream_t stream);
+
 // one hipFuncGetAttributes per translation unit: its code object is loaded now, not by a sample's first launch
 void warm_code_map();
 void warm_code_classes();

@@ -427,7 +427,7 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
-             barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, **__):
+             barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -465,7 +465,14 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     `barcode_mismatches` (0 or 1) substitutions).  All cells go through one sample set; every folder holds what
     it would for a FASTQ pair of the cell's reads alone.  output/barcodes.tsv lists every whitelist entry
     (barcode, name, assigned units, kept 0/1) and output/barcodes.json the demultiplexing summary.  Plain FASTQ
-    files only; `names` is refused."""
+    files only; `names` is refused.
+
+    umi_length: --umi-length L (1..16, with barcodes only).  The UMI of a unit is bases [umi_start, umi_start + L) of
+    its barcode read; a unit without a readable one belongs to no cell, and inside a cell every unit whose UMI and
+    class an earlier unit has shown is removed on the GPU as if it had never been in the files (mapper.SampleSet with
+    umi_bases; DESIGN.md section 4, "UMI collapse").  Every folder then holds what it would for a FASTQ pair of the
+    cell's surviving units; barcodes.tsv gains two columns (units with a readable UMI, units left after collapse) and
+    barcodes.json the keys umi_start, umi_length, umi_unreadable, umi_duplicates.  No mismatch correction."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -476,13 +483,15 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     if barcodes is None:
         if barcode_file is not None:
             raise ValueError('--barcode-file goes with --barcodes')
+        if umi_length or umi_start:
+            raise ValueError('--umi-length and --umi-start go with --barcodes')
         groups = sample_groups(fastq_paths, single_ended)
         if not groups:
             raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
         names = sample_names(groups, names)
     else:
         whitelist = barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start,
-                                    barcode_mismatches, min_units)
+                                    barcode_mismatches, min_units, umi_start, umi_length)
         groups = [tuple(fastq_paths)]
     ranks = parallel.Ranks.from_env()
     if ranks.world > 1:
@@ -523,10 +532,13 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
             index, table, common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads),
             common.PackedReadFeeder(list(fastq_paths), paired=paired, threads=parse_threads), paired, start=barcode_start,
             mismatches=barcode_mismatches, min_units=min_units, device=device, strand=strand, per_sample_lengths=True,
-            length_model=length_model, bias=bias)
+            length_model=length_model, bias=bias, umi_start=umi_start, umi_length=umi_length)
         _LOG.info('Barcodes of %d units: %d exact, %d corrected, %d ambiguous, %d without a match, %d short or unreadable',
                   demux['units'], *[demux[name] for name in mapper.BARCODE_STATS])
-        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units)
+        if umi_length:
+            _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed', umi_length,
+                      demux['umi_unreadable'], demux['umi_duplicates'])
+        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units, umi_start, umi_length)
         if not kept.size:
             raise ValueError('no cell has %d units or more (see %s)' % (min_units, output_path / 'barcodes.tsv'))
         names = [table.names[c] for c in kept]
@@ -633,7 +645,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
 
 
 def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start, barcode_mismatches,
-                    min_units):
+                    min_units, umi_start=0, umi_length=0):
     """The checks of `infer-many --barcodes` that need no read file -> the whitelist (barcodes, names) of
     mapper.read_whitelist.  ValueError for a combination that cannot be and for a malformed whitelist."""
     if barcode_file is None:
@@ -649,21 +661,36 @@ def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, ba
         raise ValueError('--barcode-mismatches must be 0 or 1, not %r' % (barcode_mismatches,))
     if int(min_units) < 1:
         raise ValueError('--min-units must be 1 or more, not %r' % (min_units,))
+    if int(umi_length) and not 1 <= int(umi_length) <= mapper.MAX_UMI_LENGTH:
+        raise ValueError('--umi-length must be 1 to %d, not %r' % (mapper.MAX_UMI_LENGTH, umi_length))
+    if int(umi_start) < 0:
+        raise ValueError('--umi-start must be 0 or more, not %r' % (umi_start,))
+    if int(umi_start) and not int(umi_length):
+        raise ValueError('--umi-start goes with --umi-length')
     return mapper.read_whitelist(barcodes)
 
 
-def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units):
-    """output/barcodes.tsv: barcode, name, assigned units, kept 0/1 per whitelist entry; output/barcodes.json: the
+def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units, umi_start=0, umi_length=0):
+    """output/barcodes.tsv: barcode, name, assigned units, kept 0/1 per whitelist entry -- with UMIs also the units
+    with a readable UMI (what `kept` looks at) and the units left after collapse; output/barcodes.json: the
     demultiplexing summary."""
     is_kept = numpy.zeros(len(table), dtype=bool)
     is_kept[kept] = True
     with (output_path / 'barcodes.tsv').open('w') as f:
-        for barcode, name, units, flag in zip(table.barcodes, table.names, demux['cell_units'], is_kept):
-            f.write('%s\t%s\t%d\t%d\n' % (barcode, name, units, flag))
+        if umi_length:
+            for row in zip(table.barcodes, table.names, demux['cell_assigned'], is_kept, demux['cell_units'],
+                           demux['cell_survivors']):
+                f.write('%s\t%s\t%d\t%d\t%d\t%d\n' % row)
+        else:
+            for barcode, name, units, flag in zip(table.barcodes, table.names, demux['cell_units'], is_kept):
+                f.write('%s\t%s\t%d\t%d\n' % (barcode, name, units, flag))
     summary = {name: demux[name] for name in mapper.BARCODE_STATS}
     summary.update(units=demux['units'], records=demux['records'], whitelist=len(table), barcode_length=table.length,
                    barcode_start=int(start), barcode_mismatches=int(mismatches), min_units=int(min_units),
                    cells=int(len(kept)), assigned=int(demux['exact'] + demux['corrected']))
+    if umi_length:
+        summary.update(umi_start=int(umi_start), umi_length=int(umi_length), umi_unreadable=demux['umi_unreadable'],
+                       umi_duplicates=demux['umi_duplicates'])
     with (output_path / 'barcodes.json').open('w') as f:
         json.dump(summary, f, indent=4)
         f.write('\n')
@@ -1367,7 +1394,7 @@ def add_many_subcommand_parser(subparsers):
 
 def add_barcode_arguments(parser):
     """--barcodes and its companions: dest 'barcodes', 'barcode_file', 'barcode_start', 'barcode_mismatches',
-    'min_units' (barcode_option checks the combinations once the arguments are parsed)."""
+    'min_units', 'umi_start', 'umi_length' (barcode_option checks the combinations once the arguments are parsed)."""
     parser.add_argument('--barcodes', type=pathlib.Path, dest='barcodes', default=None, metavar='WHITELIST',
                         help='the FASTQ files are ONE pooled sample: split it into the cells of this whitelist (a '
                              'barcode per line, optionally a tab and the cell\'s name) on the GPU; needs --barcode-file')
@@ -1379,12 +1406,18 @@ def add_barcode_arguments(parser):
                         help='substitutions a barcode may differ from its whitelist entry by (default 1)')
     parser.add_argument('--min-units', type=int, dest='min_units', default=None, metavar='N',
                         help='keep the cells with at least N assigned units (default 1)')
+    parser.add_argument('--umi-length', type=int, dest='umi_length', default=None, metavar='L',
+                        help='the barcode reads carry a UMI of L bases (1 to 16): inside a cell, count the reads of one '
+                             'UMI and one equivalence class once (with --barcodes; no mismatch correction)')
+    parser.add_argument('--umi-start', type=int, dest='umi_start', default=None, metavar='N',
+                        help='the UMI begins at base N of a barcode read (default 0; with --umi-length)')
 
 
 def barcode_option(parser, opts):
     """The parsed barcode options: a combination that cannot be is an argparse error; the defaults are filled in."""
     given = [flag for flag, key in (('--barcode-file', 'barcode_file'), ('--barcode-start', 'barcode_start'),
-                                    ('--barcode-mismatches', 'barcode_mismatches'), ('--min-units', 'min_units'))
+                                    ('--barcode-mismatches', 'barcode_mismatches'), ('--min-units', 'min_units'),
+                                    ('--umi-length', 'umi_length'), ('--umi-start', 'umi_start'))
              if opts.get(key) is not None]
     if opts.get('barcodes') is None:
         if given:
@@ -1400,7 +1433,13 @@ def barcode_option(parser, opts):
         parser.error('--barcode-start must be 0 or more')
     if opts.get('min_units') is not None and opts['min_units'] < 1:
         parser.error('--min-units must be 1 or more')
-    for key, default in (('barcode_start', 0), ('barcode_mismatches', 1), ('min_units', 1)):
+    if opts.get('umi_length') is not None and not 1 <= opts['umi_length'] <= mapper.MAX_UMI_LENGTH:
+        parser.error('--umi-length must be 1 to %d' % mapper.MAX_UMI_LENGTH)
+    if opts.get('umi_start') is not None and opts['umi_start'] < 0:
+        parser.error('--umi-start must be 0 or more')
+    if opts.get('umi_start') is not None and opts.get('umi_length') is None:
+        parser.error('--umi-start goes with --umi-length')
+    for key, default in (('barcode_start', 0), ('barcode_mismatches', 1), ('min_units', 1), ('umi_start', 0), ('umi_length', 0)):
         if opts.get(key) is None:
             opts[key] = default
     return opts

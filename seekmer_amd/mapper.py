@@ -727,13 +727,22 @@ class SampleSet:
     With ``bias`` the set also counts, per sample, the hexamer every aligned unit starts with
     (skm_sample_set_keep_bias), for the sequence-bias correction of infer.bias_correct_many:
     bias_observed().  Such a set numbers its samples below 2^15.
+    With ``umi_bases`` (1..16; needs per_sample_lengths) every unit comes with a UMI and the set collapses
+    duplicates on the device (skm_sample_set_keep_umis; DESIGN.md section 4, "UMI collapse"): inside a sample
+    only the first unit of every (UMI, class) stays, and every table, total, histogram per sample and hexamer row
+    is that of a set fed the surviving units alone; umi_removed() says how many went.  Such a set takes its reads
+    through add_packed(..., umis=) only, and its POOLED histogram still holds the removed units.
 
     Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
     where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
 
-    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None, bias=False):
+    def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None, bias=False,
+                 umi_bases=0):
         mode = strand_mode(strand)
         self.length_model, self._length_weights = length_model_weights(length_model)
+        self.umi_bases = int(umi_bases)
+        if not 0 <= self.umi_bases <= MAX_UMI_LENGTH:
+            raise ValueError('UMIs of %r bases: 1 to %d are possible' % (umi_bases, MAX_UMI_LENGTH))
         self.index = index
         self.paired = bool(paired)
         self.device = device
@@ -752,6 +761,20 @@ class SampleSet:
                 self._handle, _native.ptr(self._length_weights, _native.c_f64p)))
         if self.bias:
             _native.check(_native.hip().skm_sample_set_keep_bias(self._handle, 1))
+        if self.umi_bases:
+            _native.check(_native.hip().skm_sample_set_keep_umis(self._handle, self.umi_bases))
+
+    def umi_removed(self):
+        """int64[n_samples]: the units UMI collapse has removed from every sample (zeros in a set without UMIs)."""
+        # (samples may be added meanwhile: the call says when there are more than the rows it was given)
+        while True:
+            out = numpy.zeros(len(self), dtype=numpy.int64)
+            code = _native.hip().skm_sample_set_umi_removed(self._handle, out.size,
+                                                            _native.ptr(out, _native.c_i64p) if out.size else None)
+            if code == _native.SKM_ERR_ARG and len(self) > out.size:
+                continue
+            _native.check(code)
+            return out
 
     def bias_observed(self):
         """int64[n_samples, 4096]: row i is MapResult.bias_observed() of sample i mapped alone (zeros for a sample
@@ -797,10 +820,19 @@ class SampleSet:
                 pass
             self._handle = None
 
-    def add_packed(self, sample, first_unit, mate1, mate2=None):
-        """Units [first_unit, first_unit + n) of `sample` as common.PackedReads (mate2: paired sets)."""
+    def add_packed(self, sample, first_unit, mate1, mate2=None, umis=None):
+        """Units [first_unit, first_unit + n) of `sample` as common.PackedReads (mate2: paired sets); umis: uint32[n],
+        the units' UMIs, in a set made with umi_bases and only there."""
         if (mate2 is not None) != self.paired:
             raise ValueError('a %s set takes %s' % (('paired', 'both mates') if self.paired else ('single-ended', 'mate 1 alone')))
+        if umis is not None:
+            umis = numpy.ascontiguousarray(umis, dtype=numpy.uint32)
+            if umis.shape != (mate1.n_reads,):
+                raise ValueError('%d UMIs for %d units' % (umis.size, mate1.n_reads))
+            _native.check(_native.hip().skm_sample_set_add_packed_umis(
+                self._handle, int(sample), int(first_unit), ctypes.byref(mate1.raw),
+                ctypes.byref(mate2.raw) if mate2 is not None else None, _native.ptr(umis, _native.c_u32p) if umis.size else None))
+            return
         _native.check(_native.hip().skm_sample_set_add_packed(
             self._handle, int(sample), int(first_unit), ctypes.byref(mate1.raw),
             ctypes.byref(mate2.raw) if mate2 is not None else None))
@@ -1031,6 +1063,7 @@ def map_sample_set(index, read_feeders, job_count=1, device=0, strand=None, per_
 DEMUX_CHUNK_UNITS = 1 << 22         # units grouped and gathered at a time (SKM_DEMUX_CHUNK_UNITS: fewer, for tests)
 BARCODE_STATS = ('exact', 'corrected', 'ambiguous', 'no_match', 'unreadable')    # skm_barcodes_assign's stats[5]
 MAX_BARCODE_LENGTH = 32
+MAX_UMI_LENGTH = 16
 
 
 def check_whitelist(barcodes, names=None):
@@ -1139,6 +1172,24 @@ def group_units(sample, n_samples, device=0):
     return order[:offsets[-1]], offsets
 
 
+def umi_windows(piece, start, length, cell=None, device=0):
+    """The UMIs of a piece of barcode reads on the GPU (skm_umi_windows): bases [start, start + length) of every
+    read, 1 <= length <= 16, as uint32 (2 bits a base, first base in the top bits of the 2 * length used) ->
+    (umi uint32[n], n_unreadable).  A read too short for the window, or with a position there that is not an
+    upper-case ACGT, has UMI 0 and is counted; with `cell` (int32[n], changed in place) it also gets cell -1."""
+    n = piece.n_reads
+    umi = numpy.zeros(max(n, 1), dtype=numpy.uint32)
+    unreadable = ctypes.c_int64(0)
+    if cell is not None and (cell.dtype != numpy.int32 or cell.shape != (n,) or not cell.flags.c_contiguous
+                             or not cell.flags.writeable):
+        raise ValueError('cell: a writeable contiguous int32 array of the piece\'s %d reads' % n)
+    _native.check(_native.hip().skm_umi_windows(
+        device, ctypes.byref(piece.raw), int(start), int(length),
+        _native.ptr(cell, _native.c_i32p) if cell is not None and n else None, _native.ptr(umi, _native.c_u32p),
+        ctypes.byref(unreadable)))
+    return umi[:n], unreadable.value
+
+
 class _Gathered:
     """One mate's reads of a chunk in grouped order (skm_packed_gather): arrays of its own, cut into the cells'
     segments without another copy."""
@@ -1173,15 +1224,16 @@ class _Gathered:
                                        paired=self.paired)
 
 
-def demux_chunks(pieces, paired, sample, n_samples, chunk_units, group, add):
+def demux_chunks(pieces, paired, sample, n_samples, chunk_units, group, add, umi=None):
     """Phase 2 of map_barcoded: the cDNA pieces of a pooled run, as a packed reader hands them out (one stream
     single-ended, two paired, each numbered by unit), against sample[u] for the run's units (int32, negative =
     dropped).  The streams are paired by unit as sample_segments pairs them; every `chunk_units` units that all
     streams cover are grouped -- group(sample[a:b], n_samples) -> (order, offsets), mapper.group_units -- each
     mate is gathered once into that order (skm_packed_gather), and every sample present gets one
     add(sample, first_unit, mate1, mate2 or None) with first_unit = its units so far.  The chunks are
-    [0, c), [c, 2c), ... whatever the pieces' sizes; reads beyond sample.size units are dropped.  Returns
-    (int64[n_samples] units added per sample, units walked)."""
+    [0, c), [c, 2c), ... whatever the pieces' sizes; reads beyond sample.size units are dropped.  With umi (one
+    value per unit of the run) every add also gets umis=, the values of exactly the segment's units in their
+    order.  Returns (int64[n_samples] units added per sample, units walked)."""
     n_units = int(sample.size)
     chunk_units = max(1, int(chunk_units))
     streams = ([], []) if paired else ([],)
@@ -1196,10 +1248,14 @@ def demux_chunks(pieces, paired, sample, n_samples, chunk_units, group, add):
             order, offsets = group(sample[done:end], n_samples)
             if len(order):
                 mates = [_Gathered(held, done, order) for held in streams]
+                umis = umi[done:end][order] if umi is not None else None
                 for s in numpy.flatnonzero(numpy.diff(offsets)):
                     lo, hi = int(offsets[s]), int(offsets[s + 1])
                     segments = [mate.segment(lo, hi) for mate in mates]
-                    add(int(s), int(added[s]), segments[0], segments[1] if paired else None)
+                    if umis is not None:
+                        add(int(s), int(added[s]), segments[0], segments[1] if paired else None, umis=umis[lo:hi])
+                    else:
+                        add(int(s), int(added[s]), segments[0], segments[1] if paired else None)
                     added[s] += hi - lo
             done = end
             for held in streams:          # (a piece that ends at or below `done` is not needed again)
@@ -1261,7 +1317,7 @@ def _demux_chunk_units():
 
 
 def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mismatches=1, min_units=1, device=0,
-                 strand=None, per_sample_lengths=False, length_model=None, bias=False):
+                 strand=None, per_sample_lengths=False, length_model=None, bias=False, umi_start=0, umi_length=0):
     """One pooled run -> a SampleSet with one sample per kept cell.  table: a BarcodeTable; barcode_feeder: a
     single-ended PackedReadFeeder over the barcode file; read_feeder: a PackedReadFeeder over the pooled cDNA
     file (or pair of files).  The run holds min(records) units over these files (zip of the reference's feeders);
@@ -1273,8 +1329,23 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
     (demux_chunks: at most DEMUX_CHUNK_UNITS units a chunk, SKM_DEMUX_CHUNK_UNITS in the environment for fewer)
     and adds every cell's reads of a chunk as one in-order segment.  Every kept cell goes through the set whatever
     its size.  Returns (SampleSet, kept int64[n_kept], stats): stats maps BARCODE_STATS to counts over the run's
-    units, 'units' to their number and 'records' to the files' record counts (barcode file, cDNA files)."""
+    units, 'units' to their number and 'records' to the files' record counts (barcode file, cDNA files).
+
+    umi_length (1..16; needs per_sample_lengths): the UMI of a unit is bases [umi_start, umi_start + umi_length) of its
+    barcode read (umi_windows, on every barcode piece after its assign; umi[] of the run stays on the host beside
+    cell[], 4 bytes a unit).  A unit without a readable UMI belongs to no cell; the cells' units -- stats['cell_units'],
+    what min_units looks at -- are counted again from the final cell[] (stats['cell_assigned'] keeps the barcodes'
+    count), and stats gains 'umi_unreadable', the units of the run without a readable UMI.  The set is made with
+    umi_bases=umi_length and collapses duplicates (SampleSet); stats['cell_survivors'] int64[whitelist] are the units
+    it left every kept cell (0 for a cell that is not kept) and stats['umi_duplicates'] those it removed."""
     strand_mode(strand)
+    umi_start, umi_length = int(umi_start), int(umi_length)
+    if umi_length and not 1 <= umi_length <= MAX_UMI_LENGTH:
+        raise ValueError('a UMI of %d bases: 1 to %d are possible' % (umi_length, MAX_UMI_LENGTH))
+    if umi_start < 0 or (umi_start and not umi_length):
+        raise ValueError('umi_start %d with umi_length %d' % (umi_start, umi_length))
+    if umi_length and not per_sample_lengths:
+        raise ValueError('UMI collapse needs per_sample_lengths')
     if int(min_units) < 1:
         raise ValueError('min_units must be at least 1, not %r' % (min_units,))
     if barcode_feeder.paired or len(barcode_feeder.paths) != 1:
@@ -1291,6 +1362,8 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
         raise ValueError('a run of %d units' % n_units)
     # phase 1: the cell of every unit
     cell = numpy.full(n_units, -1, dtype=numpy.int32)
+    umi = numpy.zeros(n_units, dtype=numpy.uint32) if umi_length else None
+    umi_unreadable = 0
     units = 0
     units_before, stats_before = table.cell_units.copy(), table.stats.copy()       # (the table's counters run on)
     for piece in barcode_feeder:
@@ -1301,10 +1374,16 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
         if units + piece.n_reads > n_units:
             piece = _slice_piece(piece, 0, n_units - units)
         cell[units:units + piece.n_reads] = table.assign(piece, start=start, mismatches=mismatches)
+        if umi_length:
+            umi[units:units + piece.n_reads], unreadable = umi_windows(piece, umi_start, umi_length,
+                                                                       cell=cell[units:units + piece.n_reads], device=device)
+            umi_unreadable += unreadable
         units += piece.n_reads
     if units != n_units:
         raise ValueError('the barcode file gave %d reads, its lines said %d' % (units, n_units))
-    cell_units = table.cell_units - units_before
+    cell_units = cell_assigned = table.cell_units - units_before
+    if umi_length:                    # (the units that enter the set: those of the final cell[])
+        cell_units = numpy.bincount(cell[cell >= 0], minlength=len(table)).astype(numpy.int64)
     kept = numpy.flatnonzero(cell_units >= int(min_units))
     limit = 1 << 15 if bias else 1 << 16 if per_sample_lengths else 1 << 24
     if kept.size > limit:
@@ -1315,13 +1394,19 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
     sample = number[cell]
     # phase 2: the reads, cell by cell, into the set
     sample_set = SampleSet(index, paired, device=device, strand=strand, per_sample_lengths=per_sample_lengths,
-                           length_model=length_model, bias=bias)
+                           length_model=length_model, bias=bias, umi_bases=umi_length)
     if kept.size:
         added, walked = demux_chunks(read_feeder, paired, sample, kept.size, chunk_units,
-                                     lambda part, n: group_units(part, n, device=device), sample_set.add_packed)
+                                     lambda part, n: group_units(part, n, device=device), sample_set.add_packed, umi=umi)
         if walked != n_units or not numpy.array_equal(added, cell_units[kept]):
             raise ValueError('the cDNA files gave %d units, their lines said %d' % (walked, n_units))
         sample_set.sync()
     stats = {name: int(value) for name, value in zip(BARCODE_STATS, table.stats - stats_before)}
     stats.update(units=n_units, records=records, cells=int(kept.size), cell_units=cell_units)
+    if umi_length:
+        survivors = numpy.zeros_like(cell_units)
+        removed = sample_set.umi_removed() if kept.size else numpy.zeros(0, dtype=numpy.int64)
+        survivors[kept] = cell_units[kept] - removed
+        stats.update(umi_unreadable=int(umi_unreadable), umi_duplicates=int(removed.sum()), cell_assigned=cell_assigned,
+                     cell_survivors=survivors)
     return sample_set, kept, stats
