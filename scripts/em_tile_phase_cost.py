@@ -71,17 +71,34 @@ def child(args):
         x0 = 1.0 / lengths
         x0 /= x0.sum()
         quant.em(x0, lengths, fixed_iters=CHUNK)                     # (warm-up: first launches, allocations)
-        best = None
-        for _ in range(args.repeats):
-            before = quant.timing()
-            _, steps = quant.em(x0, lengths, fixed_iters=args.steps)
-            after = quant.timing()
-            assert steps == args.steps
-            us = (after['em_ns'] - before['em_ns']) * 1e-3 / (args.steps / CHUNK)
-            best = us if best is None else min(best, us)
+
+        def fastest():
+            best = None
+            for _ in range(args.repeats):
+                before = quant.timing()
+                _, steps = quant.em(x0, lengths, fixed_iters=args.steps)
+                after = quant.timing()
+                assert steps == args.steps
+                us = (after['em_ns'] - before['em_ns']) * 1e-3 / (args.steps / CHUNK)
+                best = us if best is None else min(best, us)
+            return best
+
+        best = fastest()
         n_tiles = info['tiles']
         lens = np.diff(offsets)
         inside, cls_inside = tile < n_tx, class_tile < n_tx
+        if args.orders:
+            # the launch orders of the tiles (SKM_EM_TILE_ORDER is looked up at every run) and the sizes they sort
+            by_order = {'largest first': best}
+            for form in ('identity', 'reverse'):
+                os.environ['SKM_EM_TILE_ORDER'] = form
+                by_order[form] = fastest()
+            del os.environ['SKM_EM_TILE_ORDER']
+            pairs = np.bincount(class_tile[cls_inside], weights=lens[cls_inside], minlength=n_tiles)
+            print(json.dumps({'us_per_chunk_by_order': by_order, 'tiles': n_tiles, 'capacity': info['capacity'],
+                              'tiles_below_half_fill': int((pairs < info['capacity'][0] / 2).sum()),
+                              'pairs_quartiles': [float(q) for q in np.percentile(pairs, (0, 25, 50, 75, 100))]}), flush=True)
+            return
         fill = [float(np.bincount(class_tile[cls_inside], weights=lens[cls_inside], minlength=n_tiles).mean()),
                 float(np.bincount(class_tile[cls_inside], minlength=n_tiles).mean()),
                 float(np.bincount(tile[inside], minlength=n_tiles).mean())] if n_tiles else [0.0, 0.0, 0.0]
@@ -101,6 +118,9 @@ def main():
     ap.add_argument('--repeats', type=int, default=3, help='timed runs per build; the fastest is reported')
     ap.add_argument('--timeout', type=int, default=600, help='seconds per build')
     ap.add_argument('--index-cache', default='', help='load the index from this file / store it there')
+    ap.add_argument('--orders', action='store_true',
+                    help='the product library alone: the chunk under the three launch orders of the tiles '
+                         '(SKM_EM_TILE_ORDER) and the distribution of the tiles\' pair counts, one JSON line')
     ap.add_argument('--child', default='', help='(internal) measure the library in SKM_HIP_LIB on the table in this file')
     args = ap.parse_args()
     if args.steps % CHUNK:
@@ -111,7 +131,7 @@ def main():
     table = os.path.join(folder, 'table.npz')
     rows = []
     try:
-        for name, lib in BUILDS:
+        for name, lib in BUILDS[:1] if args.orders else BUILDS:
             path = os.path.join(ROOT, 'seekmer_amd', lib)
             if not os.path.exists(path):
                 raise SystemExit('%s is missing: build it first (see the top of this file)' % path)
@@ -119,11 +139,15 @@ def main():
             cmd = ['timeout', '-k', '10', str(args.timeout), sys.executable, os.path.abspath(__file__), '--child', table,
                    '--genes', str(args.genes), '--pairs', str(args.pairs), '--seed', str(args.seed), '--steps', str(args.steps),
                    '--repeats', str(args.repeats)] + (['--index-cache', args.index_cache] if args.index_cache else [])
+            cmd += ['--orders'] if args.orders else []
             t0 = time.perf_counter()
             done = subprocess.run(cmd, stdout=subprocess.PIPE, env=env)
             if done.returncode:
                 raise SystemExit('%s: exit status %d after %.0f s; nothing further is run'
                                  % (name, done.returncode, time.perf_counter() - t0))
+            if args.orders:
+                print(done.stdout.decode().strip().splitlines()[-1])
+                return
             rows.append((name, json.loads(done.stdout.decode().strip().splitlines()[-1])))
     finally:
         for f in (table,):

@@ -333,6 +333,7 @@ struct skm_quant {
     struct Tiles {
         DBuf<int64_t> tile_tx, tile_cls, cls_pair, tx_pair;
         DBuf<int32_t> tx_list, cls_list, tx_label, tx_tile, cls_tile;
+        DBuf<int32_t> order;                  // [T + 1] the tiles by descending pair count: the launch order
         DBuf<uint16_t> cls_tx, tx_cls;
         DBuf<double> snap, step_max;          // snap: [EM_CHUNK_MAX][T] every step's abundances of the chunk in flight
         DBuf<unsigned int> step_flags;
@@ -3939,7 +3940,7 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
     SKM_TRY(q->x0.ensure(T));
     SKM_TRY(q->x1.ensure(T));
     SKM_TRY(q->acc.ensure(T));
-    SKM_TRY(q->ctl.ensure(16));
+    SKM_TRY(q->ctl.ensure(EM_CTL_WORDS + EM_JUDGE_WORDS));       // (the tile judge's words lie behind the control block)
     SKM_TRY(q->part_max.ensure(EM_FINAL_BLOCKS));
     SKM_TRY(q->part_flags.ensure(EM_FINAL_BLOCKS));
     SKM_TRY(q->arrivals.ensure(T));
@@ -3951,6 +3952,7 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
         SKM_TRY(t.tx_list.ensure(T)); SKM_TRY(t.cls_list.ensure(C));
         SKM_TRY(t.tx_label.ensure(T)); SKM_TRY(t.tx_tile.ensure(T)); SKM_TRY(t.cls_tile.ensure(C));
         SKM_TRY(t.cls_tx.ensure(M)); SKM_TRY(t.tx_cls.ensure(M));
+        SKM_TRY(t.order.ensure(T + 1));
     }
     STALE_CHECK("quant_alloc exit");
     return SKM_OK;
@@ -3977,6 +3979,7 @@ QuantBuild quant_build_view(skm_quant *q)
         b.cls_pair = t.cls_pair.p; b.tx_pair = t.tx_pair.p;
         b.tile_cls_tx = t.cls_tx.p; b.tile_tx_cls = t.tx_cls.p;
         b.tx_label = t.tx_label.p; b.tx_tile = t.tx_tile.p; b.cls_tile = t.cls_tile.p;
+        b.tile_order = t.order.p;
     }
     return b;
 }
@@ -4142,9 +4145,9 @@ bool em_ctl_done(const unsigned long long *ctl) { return ctl[CTL_DONE] != 0; }
 
 // The component form of em_run's loop (after its preamble: control block cleared, ev[0] recorded).  Every
 // chunk is ONE launch that steps all the tiles `chunk` times in LDS and leaves every step's abundances in
-// the snapshot buffer -- the next chunk starts from the last of them -- plus the one-block launch that
-// judges the chunk's steps in order.  The host stays one chunk ahead as before; the look-ahead chunk that
-// finds the EM stopped (at step K) copies the tiles' entries of step K from the snapshots to x[K & 1],
+// the snapshot buffer -- the next chunk starts from the last of them -- and judges the chunk's steps in order
+// itself (beside a residual problem: that problem's judge does).  The host stays one chunk ahead as before;
+// the look-ahead chunk that finds the EM stopped (at step K) copies the tiles' entries of step K from the snapshots to x[K & 1],
 // where the callers look for the result: no step runs twice and the stop costs no launch of its own.
 int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters_out)
 {
@@ -4157,10 +4160,20 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
     tl.cls_tx = t.cls_tx.p; tl.tx_cls = t.tx_cls.p;
     tl.step_max = t.step_max.p; tl.step_flags = t.step_flags.p;
     tl.snap = t.snap.p;
+    // SKM_EM_TILE_ORDER (tuning aid, looked up at every run as SKM_EM_NO_COMPONENTS is): `identity` launches the
+    // tiles in tile order, `reverse` smallest first; unset: largest first.  The results are the same bits.
+    tl.order = t.order.p;
+    if (const char *form = getenv("SKM_EM_TILE_ORDER")) {
+        if (!strcmp(form, "identity")) tl.order = nullptr;
+        else if (!strcmp(form, "reverse")) tl.order_reversed = 1;
+        else return fail(SKM_ERR_ARG, "SKM_EM_TILE_ORDER is identity or reverse, not '%s'", form);
+    }
     // With components above the capacity the residual problem runs beside the tiles, step by step with
     // the whole-table kernels on its own classes and rows (its transcripts' entries of x0 / x1; the
     // tiles' entries are the tiles' alone), and ITS judge takes the tiles' partials of the step along.
     const bool mixed = t.n_oversize > 0;
+    // Tiles alone: the chunk launch judges its own steps (the workgroup that finishes last does), one launch a chunk.
+    if (!mixed && !SKM_EM_JUDGE_LAUNCH) tl.judge = q->ctl.p + EM_CTL_WORDS;
     EmProblem pr = p;
     if (mixed) {
         auto &r = t.residual;
@@ -4184,8 +4197,11 @@ int em_run_tiles(skm_quant *q, const EmProblem &p, int64_t chunk, int64_t *iters
             launch_em_decide(pr, (queued + 1) * chunk, q->stream);
             q->launches += 2 * chunk + 2;
         } else {
+#if SKM_EM_JUDGE_LAUNCH
             launch_em_local_decide(p, tl, queued * chunk, (int)chunk, q->stream);
-            q->launches += 2;
+            q->launches += 1;
+#endif
+            q->launches += 1;
         }
         ++queued;
         HIP_TRY(hipGetLastError());
@@ -4228,7 +4244,9 @@ int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int6
     }
     EmProblem p = em_problem(q, rel_tol, x_floor, max_iters, fixed_iters);
     p.n_total = n_total;
-    HIP_TRY(hipMemsetAsync(q->ctl.p, 0, 16 * 8, q->stream));
+    // (with the control block the tile judge's words behind it: a run that ended in a tile fault or an error
+    // leaves nothing there)
+    HIP_TRY(hipMemsetAsync(q->ctl.p, 0, (EM_CTL_WORDS + EM_JUDGE_WORDS) * sizeof(unsigned long long), q->stream));
     int64_t k = 0;
     const int64_t chunk = fixed_iters > 0 ? std::min<int64_t>(fixed_iters, chunk_steps) : chunk_steps;
     HIP_TRY(hipEventRecord(q->ev[0], q->stream));

@@ -158,8 +158,10 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 //                number of such batches, so the 64 classes of a wave take like numbers of turns.
 //   row phase    eight lanes per transcript, its rows of <= EM_ROW_CAP entries one after the other, the
 //                row sums added in row order from 0.0, then the finalize (skm_em_core.h)
-// with two workgroup barriers and nothing that crosses workgroups.  Each step's partials of the stopping
-// rule go to step_max / step_flags [step][tile]; em_local_decide_kernel judges the steps in order.
+// with two workgroup barriers and nothing that crosses workgroups but the stopping rule's partials.  Tiles
+// alone: each workgroup adds its partials of the chunk's steps to the judge's words and the one that arrives
+// last judges the steps in order (em_tile_arrive, em_tiles_judge).  Beside a residual problem they go to
+// step_max / step_flags [step][tile], which that problem's judge reads (em_evaluate).
 // Every step's abundances also go to tl.snap[step][transcript]: the next chunk starts from the last of
 // them, and the launch that finds the EM stopped -- the look-ahead chunk, which would otherwise do
 // nothing -- copies its tile's entries of the step the rule was met at to p.x[steps & 1], where the
@@ -178,6 +180,62 @@ em_decide_kernel(EmProblem p, int n_parts, int64_t steps_done)
 constexpr int EM_CLASS_BATCH = SKM_EM_CLASS_BATCH;
 static_assert(EM_CLASS_BATCH == EM_TILE_CLASS_BATCH || EM_CLASS_BATCH == 1, "the set-up orders classes by turns of this width");
 
+// ---- the chunk's verdict without a launch of its own (tiles alone; the words of EmTiles::judge)
+// Called by wave 0 of a tile's workgroup, whose lane s (`has`: s < n_steps) holds the tile's partials (m, f) of
+// step s.  They are a maximum over doubles that are +0.0 or above and never NaN (em_note_change sends a NaN to
+// the flags) -- the bits of such doubles order as unsigned integers -- and an OR, so whatever order the tiles
+// arrive in, the words end up as the pair that a pass over step_max / step_flags gives.  The XCDs' L2s are not
+// coherent, so the words are touched by agent-scope accesses alone, as the row sums of skm_em_core.h are:
+//   * a lane first reads its words (agent-scope load) and issues the atomic only where its value would change the
+//     word: the maximum settles after a few arrivals, and thousands of atomics on 32 words would queue
+//     (a word read too low costs a needless atomic, never a wrong one: between launches the words are zero,
+//     and inside one they only grow);
+//   * the wave's atomics are complete (vmcnt) before lane 0 counts the tile's arrival;
+//   * the workgroup that counts the last arrival reads the words by atomic exchange, which clears them for the
+//     next launch, and clears the counter.
+// Nothing waits for another workgroup.  Returns the tiles arrived, this one included, in every lane.
+__device__ __forceinline__ unsigned long long em_tile_arrive(unsigned long long *judge, bool has, double m, unsigned int f)
+{
+    if (has) {
+        unsigned long long *word_max = judge + EM_JUDGE_MAX + threadIdx.x, *word_flags = judge + EM_JUDGE_FLAGS + threadIdx.x;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(m);
+        if (__hip_atomic_load(word_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < bits)
+            __hip_atomic_fetch_max(word_max, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (f & ~(unsigned int)__hip_atomic_load(word_flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            __hip_atomic_fetch_or(word_flags, (unsigned long long)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned long long arrived = 0;
+    if (threadIdx.x == 0)
+        arrived = __hip_atomic_fetch_add(judge + EM_JUDGE_ARRIVED, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ULL;
+    return __shfl(arrived, 0, 64);
+}
+// By wave 0 of the workgroup that arrived last: the stopping rule for steps first_step + 1 .. first_step + n_steps
+// in order, the first that stops latched in the control block.
+__device__ __forceinline__ void em_tiles_judge(const EmProblem &p, unsigned long long *judge, bool has, int64_t first_step, int n_steps)
+{
+    double m = 0.0;
+    unsigned int f = 0;
+    if (has) {
+        m = __longlong_as_double((long long)__hip_atomic_exchange(judge + EM_JUDGE_MAX + threadIdx.x, 0ULL, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT));
+        f = (unsigned int)__hip_atomic_exchange(judge + EM_JUDGE_FLAGS + threadIdx.x, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(judge + EM_JUDGE_ARRIVED, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    bool undefined = false, done = false;
+    int64_t steps_done = first_step;
+    for (int s = 0; s < n_steps && !done; ++s) {        // (wave-uniform: every lane walks the same pairs)
+        steps_done = first_step + s + 1;
+        const EmVerdict verdict = em_stop_rule(__shfl(f, s, 64), __shfl(m, s, 64), p.rel_tol, steps_done, p.max_iters, p.fixed_iters);
+        undefined |= verdict.undefined;
+        done = verdict.done;
+    }
+    if (threadIdx.x != 0) return;
+    if (undefined) p.ctl[CTL_UNDEFINED] = 1;
+    p.ctl[CTL_ITERS] = (unsigned long long)steps_done;
+    p.ctl[CTL_DONE] = done ? 1ULL : 0ULL;
+}
+
 __global__ void __launch_bounds__(256)
 em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, int n_steps, int64_t first_step)
 {
@@ -191,7 +249,8 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, int n_steps, 
     __shared__ int32_t s_tx[EM_TILE_TX];
     __shared__ uint16_t s_cls_tx[EM_TILE_PAIRS], s_tx_cls[EM_TILE_PAIRS];
     __shared__ uint16_t s_cls_off[EM_TILE_CLASSES + 1], s_tx_off[EM_TILE_TX + 1];
-    const int64_t tile = blockIdx.x;
+    // (the launch order: the set-up's largest tiles first, see EmTiles::order)
+    const int64_t tile = tl.order ? tl.order[tl.order_reversed ? tl.n_tiles - 1 - blockIdx.x : blockIdx.x] : blockIdx.x;
     const int64_t tx0 = tl.tile_tx[tile], cls0 = tl.tile_cls[tile];
     const int n_tx = (int)(tl.tile_tx[tile + 1] - tx0), n_cls = (int)(tl.tile_cls[tile + 1] - cls0);
     const int64_t cp0 = tl.cls_pair[cls0], tp0 = tl.tx_pair[tx0];
@@ -299,15 +358,24 @@ em_local_chunk_kernel(EmProblem p, EmTiles tl, const double *x_in, int n_steps, 
         if ((tid & 63) == 0) { s_max[step][wave] = local_max; s_flags[step][wave] = flags; }
         __syncthreads();
     }
-    if (tid < n_steps) {
-        double m;
-        unsigned int f;
-        em_fold_waves(s_max[tid], s_flags[tid], 1, m, f);
-        tl.step_max[tid * tl.n_tiles + tile] = m;
-        tl.step_flags[tid * tl.n_tiles + tile] = f;
+    if (tid >= 64) return;                      // (lane s of wave 0 holds the tile's partials of step s)
+    double m = 0.0;
+    unsigned int f = 0;
+    if (tid < n_steps) em_fold_waves(s_max[tid], s_flags[tid], 1, m, f);
+    if (tl.judge == nullptr) {                  // a residual problem beside the tiles: its judge reads these
+        if (tid < n_steps) {
+            tl.step_max[tid * tl.n_tiles + tile] = m;
+            tl.step_flags[tid * tl.n_tiles + tile] = f;
+        }
+        return;
     }
+    if (em_tile_arrive(tl.judge, tid < n_steps, m, f) != (unsigned long long)tl.n_tiles) return;
+    em_tiles_judge(p, tl.judge, tid < n_steps, first_step, n_steps);
 }
 
+#if SKM_EM_JUDGE_LAUNCH
+// (tuning builds only: the judge of a chunk of tiles alone as a launch of its own, as it was before
+// em_tiles_judge; the A/B of profiles/em_tile_order_ab.log prices the two against each other)
 // The stopping rule (em_evaluate) for the n_steps steps of a chunk, in order: wave s takes the maximum and
 // the flags of step s over the tiles (max and or: the order does not matter), lane 0 then walks the steps
 // and latches the first that stops.
@@ -351,6 +419,7 @@ em_local_decide_kernel(EmProblem p, EmTiles tl, int64_t first_step, int n_steps)
         if (verdict.done) break;
     }
 }
+#endif
 
 // MapResult.effective_lengths, mapper.py:134-141: p = fld / fld.sum();
 // eff_t = sum_i max(len_t - i, 1) * p_i accumulated for i = 0..1999 in order
@@ -738,11 +807,13 @@ void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const doubl
                        std::min(n_steps, EM_CHUNK_MAX), first_step);
 }
 
+#if SKM_EM_JUDGE_LAUNCH
 void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream)
 {
     hipLaunchKernelGGL(em_local_decide_kernel, dim3(1), dim3(64 * EM_CHUNK_MAX), 0, stream, p, tiles, first_step,
                        std::min(n_steps, EM_CHUNK_MAX));
 }
+#endif
 
 void launch_em_rows_to_acc(const EmProblem &p, hipStream_t stream)
 {

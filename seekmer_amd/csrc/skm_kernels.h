@@ -297,15 +297,38 @@ struct EmTiles {
     double *step_max;             // [EM_CHUNK_MAX][n_tiles] the tiles' partials of the stopping rule, per step
     unsigned int *step_flags;     // [EM_CHUNK_MAX][n_tiles] bit0 = any, bit1 = nan
     double *snap;                 // [EM_CHUNK_MAX][T] the tiles' abundances after every step of the chunk in flight
+    // the launch order: workgroup b of a chunk launch works on tile order[b], or order[n_tiles - 1 - b] with
+    // order_reversed set; nullptr: on tile b.  A permutation of the tiles by descending pair count
+    // (skm_quant_setup.hip: tile_order_kernel); no result depends on it.
+    const int32_t *order;
+    int32_t order_reversed;
+    // tiles alone (no residual problem beside them): the chunk kernel judges its own steps and step_max /
+    // step_flags are not written.  EM_JUDGE_WORDS words that are zero between launches (em_run clears them with
+    // the control block; the workgroup that judges leaves them clear): [EM_JUDGE_MAX + s] the largest relative
+    // change of step s over the tiles arrived so far (the bits of a double >= +0.0: they order as integers),
+    // [EM_JUDGE_FLAGS + s] their flags, [EM_JUDGE_ARRIVED] the tiles arrived.  nullptr: step_max / step_flags.
+    unsigned long long *judge;
 };
+// (each group of words in a 128-byte line of its own: the arrivals do not queue behind the partials)
+enum { EM_JUDGE_MAX = 0, EM_JUDGE_FLAGS = 16, EM_JUDGE_ARRIVED = 32, EM_JUDGE_WORDS = 48 };
+static_assert(EM_CHUNK_MAX <= 16, "a step's word of each kind");
+constexpr int EM_CTL_WORDS = 16;         // EmProblem::ctl; a handle keeps the judge's words right behind them
+// (tuning aid, scripts/build_variant.sh with skm_abi.hip and skm_em.hip: 1 keeps the one-block launch that
+// judged a chunk of tiles alone before the chunk kernel did)
+#ifndef SKM_EM_JUDGE_LAUNCH
+#define SKM_EM_JUDGE_LAUNCH 0
+#endif
 // Steps first_step + 1 .. first_step + n_steps (n_steps <= EM_CHUNK_MAX, the same for every chunk of a run) of
 // every tile, from x_in (a tile reads its own transcripts only) to tiles.snap[0 .. n_steps).  Once the control
 // block says stopped, the launch instead copies the tiles' entries of the step the EM stopped at -- one of the
 // chunk before, still in tiles.snap -- to p.x[steps & 1].
 void launch_em_local_chunk(const EmProblem &p, const EmTiles &tiles, const double *x_in, int n_steps, int64_t first_step,
                            hipStream_t stream);
-// the stopping rule for steps first_step + 1 .. first_step + n_steps in order: latches the first that stops
+// the stopping rule for steps first_step + 1 .. first_step + n_steps in order, from step_max / step_flags: latches
+// the first that stops (SKM_EM_JUDGE_LAUNCH builds only)
+#if SKM_EM_JUDGE_LAUNCH
 void launch_em_local_decide(const EmProblem &p, const EmTiles &tiles, int64_t first_step, int n_steps, hipStream_t stream);
+#endif
 
 // ---- the EM for EM_BATCH problems of one class structure side by side (skm_em_batch.hip):
 // the bootstrap replicates, count vectors of the caller's, the blended tables of the second round of `impute`.
@@ -433,6 +456,7 @@ struct QuantBuild {
     int64_t *cls_pair, *tx_pair;  // [C + 1], [T + 1] out
     uint16_t *tile_cls_tx, *tile_tx_cls;   // [M], [M] out
     int32_t *tx_label, *tx_tile, *cls_tile;   // [T], [T], [C] out: component (smallest id), tile of each
+    int32_t *tile_order;          // [T + 1] out: the tiles by descending pair count (EmTiles::order)
     int64_t tile_info[2];
 };
 // One asynchronous pipeline: classes (from a mapper's table when `table` is given, the caller's

@@ -1020,6 +1020,43 @@ tile_fill_tx_kernel(const int32_t *tx_list, int64_t n_tx, const int64_t *tx_row,
     }
 }
 
+// EmTiles::order: the tiles by descending pair count (the row phase of the chunk kernel walks the pairs), so that
+// a chunk launch starts its large tiles first and fills its last, thinly occupied round with the small ones.  A
+// counting sort over TILE_ORDER_BINS size bins by ONE workgroup: a few thousand tiles, n_tx at the most.  The
+// tiles of a bin stand in the order their lanes drew their places in: not stable, and no result depends on it.
+constexpr int TILE_ORDER_BINS = 256;
+__global__ void __launch_bounds__(1024)
+tile_order_kernel(const int64_t *__restrict__ tile_cls, const int64_t *__restrict__ cls_pair, const int64_t *n_tiles,
+                  int32_t *__restrict__ order)
+{
+    __shared__ unsigned int at[TILE_ORDER_BINS];      // tiles of the bin, then the next free place of the bin
+    const int64_t tiles = *n_tiles;
+    auto bin_of = [&](int64_t i) {
+        const int64_t pairs = cls_pair[tile_cls[i + 1]] - cls_pair[tile_cls[i]];
+        const int64_t fill = min(max(pairs, (int64_t)0), (int64_t)EM_TILE_PAIRS) * (TILE_ORDER_BINS - 1) / EM_TILE_PAIRS;
+        return TILE_ORDER_BINS - 1 - (int)fill;       // (the fullest tiles in bin 0)
+    };
+    for (int d = threadIdx.x; d < TILE_ORDER_BINS; d += 1024) at[d] = 0;
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < tiles; i += 1024) atomicAdd(&at[bin_of(i)], 1u);
+    __syncthreads();
+    if (threadIdx.x < 64) {                           // exclusive scan over the bins: four per lane of one wave
+        constexpr int PER = TILE_ORDER_BINS / 64;
+        unsigned int n[PER], sum = 0;
+        for (int k = 0; k < PER; ++k) { n[k] = at[threadIdx.x * PER + k]; sum += n[k]; }
+        unsigned int incl = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int o = __shfl_up(incl, d, 64);
+            if ((int)threadIdx.x >= d) incl += o;
+        }
+        unsigned int first = incl - sum;
+        for (int k = 0; k < PER; ++k) { at[threadIdx.x * PER + k] = first; first += n[k]; }
+    }
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < tiles; i += 1024) order[atomicAdd(&at[bin_of(i)], 1u)] = (int32_t)i;
+}
+static_assert(TILE_ORDER_BINS % 64 == 0, "the scan gives every lane of a wave the same number of bins");
+
 int build_tiles(Scratch &scratch, QuantBuild &q)
 {
     hipStream_t stream = scratch.stream;
@@ -1072,6 +1109,8 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
                        q.ids, tx_local, q.cls_pair, q.cls_tile, (int32_t)T, q.tile_cls_tx);
     hipLaunchKernelGGL(tile_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_list, T, q.tx_row,
                        q.row_start, q.tx_cls, cls_local, q.tx_pair, q.tx_tile, q.tile_tx_cls);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, q.tile_cls, q.cls_pair, seg_base + n_segments,
+                       q.tile_order);
     QB_TRY(hipMemcpyAsync(&q.tile_info[0], seg_base + n_segments, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     QB_TRY(hipMemcpyAsync(&q.tile_info[1], oversize, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     return 0;
