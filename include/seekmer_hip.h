@@ -109,13 +109,31 @@ int skm_index_info(const skm_index *index, int64_t info[8]);
  * ask for when it leaves the contig, computed once at upload, so that a hop reads its answer
  * from the record instead of visiting the k-mer table (results identical by construction;
  * off for a table probed in the reference's layout).  A junction k-mer that is neither the
- * first nor the last k-mer of its contig -- none in a built index -- is marked "look it up".
+ * first nor the last k-mer of its contig -- rare in a built index, but they exist: 39 of the 66 848
+ * junction slots of the reference's chr21 test transcriptome, where a contig's extension by one base
+ * spells a k-mer from the inside of another contig -- is marked "look it up".
  * [7]=slots of the signature table (0: none): per minimizer of the table's k-mers a 64-bit word
  * that says which k-mers it has; the roll past a sequencing error (_find_first_kmer,
  * seekmer/_mapper.pyx:207-216) asks it before the table -- a k-mer whose bit is clear is not in
  * the table, and a run of the read's k-mers shares a minimizer.  Results identical by
  * construction (no false negatives); SKM_NO_SIGNATURES=1 leaves it out. */
 int skm_index_layout(const skm_index *index, int64_t layout[8]);
+/* A download of the junction words of the contig records, for tests: succ[n_contigs * 8] and kept[n_contigs * 8]
+ * in the order [contig][side][b], side 0 = the contig's end (k-mer: its tail k-mer with base b appended),
+ * side 1 = its start (first k-mer with base b prepended), copied out of the records as they stand.  A word is
+ * entry << 4 | 8 (the merge on the landing contig keeps what `kept` names of this contig's list) | 4 (it keeps
+ * the whole running list) | kind, kind 0 = the k-mer is not in the table, 1 = it is the first k-mer of contig
+ * `entry` (complemented: on the other strand), 2 = the last one, 3 = look it up; the entry is 0 for kinds 0 and 3.
+ * SKM_ERR_STATE when layout[6] == 0. */
+int skm_index_junctions(const skm_index *index, int32_t *succ, uint8_t *kept);
+/* The lookups the mapper and the junction words are built from, one per query, for tests: (entry, offset)[n] of
+ * kmers[n] (2k bits each) through mode 0 = map_kmer over the reference's layout, 1 = the bucket table's chain,
+ * 2 = the bucket table with the home bucket's positions fetched with its keys; a k-mer that is not in the table
+ * gives (0, -1).  Mode 3 = the signature table's verdict: entry = 1 when the k-mer may be in the table, 0 when
+ * it is turned away (offset = 0).  SKM_ERR_STATE when the index has no bucket table (modes 1, 2) or no
+ * signature table (mode 3). */
+int skm_index_probe(const skm_index *index, int mode, const uint64_t *kmers, int64_t n, int32_t *entry,
+                    int32_t *offset);
 /* The transcripts' own sequences, for the sequence-bias correction (skm_bias_correct): rebuilt in HBM from
  * the index alone -- a target row (e, o) of a contig of length L with pooled bases S says T_e[o .. o + L) = S
  * for e >= 0 and T_~e[o + 25 - L .. o + 25) = revcomp(S) for e < 0 -- as 2-bit codes plus one "known" bit per

@@ -71,6 +71,8 @@ HIP_SYMBOLS = {
     'skm_index_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_index_info': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_index_layout': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_index_junctions': (ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
+    'skm_index_probe': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_u64p, c_i64, c_i32p, c_i32p]),
     'skm_index_build_transcripts': (ctypes.c_int, [ctypes.c_void_p, c_f64p, c_i64]),
     'skm_index_transcript_bases': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'skm_mapper_create': (ctypes.c_int, [ctypes.c_void_p, c_void_pp]),

@@ -84,6 +84,27 @@ class KMerIndex:
                         'slots_unreached', 'successors', 'signature_slots'), layout))
         return out
 
+    def device_junctions(self, device=0):
+        """skm_index_junctions of the device copy (for tests): the junction words of the contig records as
+        (succ int32[n_contigs, 2, 4], kept uint8[n_contigs, 2, 4]), side 0 = the contig's end.  NativeError
+        SKM_ERR_STATE when the records carry none."""
+        n = self.contigs.size
+        succ = numpy.zeros((n, 2, 4), dtype=numpy.int32)
+        kept = numpy.zeros((n, 2, 4), dtype=numpy.uint8)
+        _native.check(_native.hip().skm_index_junctions(self.device_handle(device), _native.ptr(succ, _native.c_i32p),
+                                                        kept.ctypes.data))
+        return succ, kept
+
+    def device_probe(self, mode, kmers, device=0):
+        """skm_index_probe of the device copy (for tests): (entry, offset) int32[n] of the encoded k-mers."""
+        kmers = numpy.ascontiguousarray(kmers, dtype=numpy.uint64)
+        entry = numpy.zeros(kmers.size, dtype=numpy.int32)
+        offset = numpy.zeros(kmers.size, dtype=numpy.int32)
+        _native.check(_native.hip().skm_index_probe(self.device_handle(device), int(mode), _native.ptr(kmers, _native.c_u64p),
+                                                    kmers.size, _native.ptr(entry, _native.c_i32p),
+                                                    _native.ptr(offset, _native.c_i32p)))
+        return entry, offset
+
     def release(self):
         with self._lock:
             for handle in self._handles.values():

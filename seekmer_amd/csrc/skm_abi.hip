@@ -860,6 +860,48 @@ extern "C" int skm_index_layout(const skm_index *ix, int64_t layout[8])
     return SKM_OK;
 }
 
+extern "C" int skm_index_junctions(const skm_index *ix, int32_t *succ, uint8_t *kept)
+{
+    if (!ix || !succ || !kept) return fail(SKM_ERR_ARG, "NULL argument");
+    if (!ix->layout[6]) return fail(SKM_ERR_STATE, "the contig records of this index carry no junction successors");
+    SKM_TRY(set_device(ix->device));
+    const int64_t n_contigs = ix->d.n_contigs;
+    std::vector<DevContig> rows((size_t)n_contigs);
+    if (n_contigs)
+        HIP_TRY(hipMemcpy(rows.data(), ix->contigs, (size_t)n_contigs * sizeof(DevContig), hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < n_contigs; ++c)
+        for (int s = 0; s < 2; ++s)
+            for (int b = 0; b < 4; ++b) {
+                succ[c * 8 + s * 4 + b] = rows[(size_t)c].side[s].succ[b];
+                kept[c * 8 + s * 4 + b] = rows[(size_t)c].side[s].kept[b];
+            }
+    return SKM_OK;
+}
+
+extern "C" int skm_index_probe(const skm_index *ix, int mode, const uint64_t *kmers, int64_t n, int32_t *entry,
+                               int32_t *offset)
+{
+    if (!ix || n < 0 || (n && (!kmers || !entry || !offset))) return fail(SKM_ERR_ARG, "NULL array or negative size");
+    if (mode < 0 || mode > 3) return fail(SKM_ERR_ARG, "unknown probe mode %d", mode);
+    for (int64_t i = 0; i < n; ++i)
+        if (kmers[i] & ~KMER_MASK) return fail(SKM_ERR_ARG, "query %lld has bits above the %d a k-mer has", (long long)i, 2 * K);
+    if ((mode == 1 || mode == 2) && !ix->d.buckets) return fail(SKM_ERR_STATE, "this index is probed in the reference's layout: no buckets");
+    if (mode == 3 && !ix->d.signatures) return fail(SKM_ERR_STATE, "this index has no signature table");
+    if (n == 0) return SKM_OK;
+    SKM_TRY(set_device(ix->device));
+    DevMem d_kmers, d_entry, d_offset;
+    HIP_TRY(hipMalloc(d_kmers.out(), (size_t)n * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(d_entry.out(), (size_t)n * sizeof(int32_t)));
+    HIP_TRY(hipMalloc(d_offset.out(), (size_t)n * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(d_kmers, kmers, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    launch_index_probe(ix->d, mode, (const uint64_t *)d_kmers.get(), n, (int32_t *)d_entry.get(), (int32_t *)d_offset.get(),
+                       nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(entry, d_entry, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(offset, d_offset, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return SKM_OK;
+}
+
 // ---- the transcript pool and the sequence-bias correction (skm_bias.hip) ----------------------------
 extern "C" int skm_index_build_transcripts(skm_index *ix, const double *lengths, int64_t n_tx)
 {

@@ -44,8 +44,9 @@ struct ContigEntry {                                             // _common.pxd:
 //     answer is the stored one with the entry complemented (map_kmer, _common.pyx:84-87).  Their
 //     map_kmer results are computed once at upload, with the device's own lookup, and a hop reads
 //     its answer from the record of the contig it is leaving: no visit to the k-mer table.  In a
-//     built index such a k-mer is the first k-mer of the contig it belongs to or the last one (that
-//     is what makes it a junction), so a successor is one word: the signed contig entry and, in the
+//     built index such a k-mer is nearly always the first k-mer of the contig it belongs to or the
+//     last one (that is what makes it a junction; 39 of the 20 271 that exist on the reference's
+//     chr21 transcriptome lie inside a contig), so a successor is one word: the signed contig entry and, in the
 //     two low bits, SUCC_ABSENT (not in the table: a miss, _mapper.pyx:250, :312), SUCC_AT_START
 //     (offset 0), SUCC_AT_END (offset = that contig's length - k, filled in when the hop lands
 //     there and its record has arrived) or SUCC_LOOKUP (any other offset, or a k-mer stored without

@@ -80,6 +80,10 @@ void launch_signature_build(const DevBucket *buckets, uint64_t n_buckets, uint64
                             hipStream_t stream);
 void launch_successor_build(const DevIndex &ix, DevContig *records, int64_t n_contigs, int force_lookup,
                             hipStream_t stream);
+// one lookup per k-mer through the device functions of the index (skm_index_probe, tests); the caller has checked
+// that the structure `mode` asks exists
+void launch_index_probe(const DevIndex &ix, int mode, const uint64_t *kmers, int64_t n, int32_t *entry, int32_t *offset,
+                        hipStream_t stream);
 // stats: 0 production, 1 counting build, 2 census build (skm_map.hip)
 void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, int stats,
                       hipStream_t stream);

@@ -413,8 +413,37 @@ successor_build_kernel(DevIndex ix, DevContig *records, int64_t n_contigs, int f
     }
 }
 
+// The lookups of this file asked one k-mer at a time, for tests (skm_index_probe): a lane per query,
+// read-only, through the device functions the kernels above and the mapper call.  mode 0: map_kmer
+// over the reference's layout; 1: map_kmer_buckets; 2: map_kmer_buckets_whole; 3: entry = 1 when the
+// signature of the k-mer's minimizer lets it through to the table, 0 when it turns it away.
+__global__ void __launch_bounds__(256)
+index_probe_kernel(DevIndex ix, int mode, const uint64_t *__restrict__ kmers, int64_t n, int32_t *__restrict__ entry,
+                   int32_t *__restrict__ offset)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t kmer = kmers[i];
+        Coord pos{0, 0};
+        if (mode == 0) {
+            pos = map_kmer<false>(ix, kmer, nullptr);
+        } else if (mode == 1) {
+            pos = map_kmer_buckets(ix, kmer);
+        } else if (mode == 2) {
+            pos = map_kmer_buckets_whole(ix, kmer);
+        } else {
+            const uint64_t rc = kmer_revcomp(kmer);
+            const uint64_t canonical = kmer < rc ? kmer : rc;
+            const Signature wanted = signature_bits(bucket_hash(canonical));
+            const uint64_t *slot = ix.signatures + 2 * (size_t)signature_slot(kmer_min_hash(canonical), ix.signature_shift);
+            pos.entry = (slot[0] & wanted.lo) == wanted.lo && (slot[1] & wanted.hi) == wanted.hi ? 1 : 0;
+        }
+        entry[i] = pos.entry;
+        offset[i] = pos.offset;
+    }
+}
+
 // ------------------------------------------------------------------- mapper
-// Running target list of a context.  KMerIndex.map_contig (_common.pyx:143-179)
+// Running target list of a context. KMerIndex.map_contig (_common.pyx:143-179)
 // copies the first contig's target slice (reversed and complemented for a
 // reverse hit) and every later step only deletes entries from it
 // (_filter_on_contig, _intersect).  So the list is kept as
@@ -1717,6 +1746,15 @@ void launch_successor_build(const DevIndex &ix, DevContig *records, int64_t n_co
                             hipStream_t stream)
 {
     hipLaunchKernelGGL(successor_build_kernel, dim3(2048), dim3(256), 0, stream, ix, records, n_contigs, force_lookup);
+}
+
+void launch_index_probe(const DevIndex &ix, int mode, const uint64_t *kmers, int64_t n, int32_t *entry, int32_t *offset,
+                        hipStream_t stream)
+{
+    if (n <= 0) return;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(index_probe_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix, mode, kmers, n, entry, offset);
 }
 
 void launch_offsets_scan(int64_t *offsets, int64_t n_reads, int64_t base, unsigned long long *out,

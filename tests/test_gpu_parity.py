@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import make_product_index
+from junction_reference import segment_chain_transcripts
 from quant_reference import check_multinomial_dispersion as _check_multinomial_dispersion
 
 pytestmark = pytest.mark.gpu
@@ -149,17 +150,7 @@ def test_repeats_inside_transcripts_and_segments_shared_in_both_orientations(ora
     from seekmer_amd import index_builder
     rng = np.random.default_rng(2024)
     comp = bytes.maketrans(b'ACGT', b'TGCA')
-    letters = np.frombuffer(b'ACGT', dtype=np.uint8)
-    segments = [bytes(rng.choice(letters, int(rng.integers(26, 140)))) for _ in range(40)]
-    transcripts = []
-    for _ in range(90):
-        parts = []
-        for _ in range(int(rng.integers(3, 10))):
-            seg = segments[int(rng.integers(len(segments)))]
-            parts.append(seg.translate(comp)[::-1] if rng.random() < 0.35 else seg)
-        if rng.random() < 0.5:                      # a segment twice in the same transcript, some way apart
-            parts.insert(int(rng.integers(len(parts) + 1)), parts[0])
-        transcripts.append(b''.join(parts))
+    transcripts = segment_chain_transcripts(rng)
     ids = [b'R%04d' % i for i in range(len(transcripts))]
     tx_offsets = np.concatenate([[0], np.cumsum([len(t) for t in transcripts])]).astype(np.int64)
     pool = np.frombuffer(b''.join(transcripts) + b'\0', dtype=np.uint8).copy()
