@@ -12,7 +12,8 @@
  * Two shared libraries implement it:
  *   libseekmer_hip.so   -- everything that touches the GPU (skm_index_*,
  *                          skm_mapper_*, skm_sample_set_*, skm_quant_*, skm_bias_*,
- *                          skm_gene_*, skm_barcodes_*, skm_umi_windows, skm_units_group, skm_comm_*, skm_device_*)
+ *                          skm_gene_*, skm_barcodes_*, skm_umi_windows, skm_units_group, skm_barcode_census_*,
+ *                          skm_comm_*, skm_device_*)
  *   libseekmer_host.so  -- host-side native code with no GPU dependency
  *                          (skm_build_*, skm_fastq_*, skm_fastq_packed_*, skm_pack_*, skm_packed_gather,
  *                          skm_synth_*)
@@ -576,6 +577,38 @@ int skm_umi_windows(int device, const skm_packed_reads *reads, int start, int le
  * views (skm_quant_setup.hip), dropped units under key n_samples.  SKM_ERR_ARG for a sample >= n_samples. */
 int skm_units_group(int device, const int32_t *sample, int64_t n, int64_t n_samples, int32_t *order,
                     int64_t *offsets /* [n_samples + 1] */);
+
+/* ---------------------------------------------------------------- cell discovery
+ * ("Cell discovery".)  A whitelist made from the barcode reads themselves: an exact count of
+ * every distinct barcode, and from it the barcodes that are cells.  The handle owns the census table in HBM (open
+ * addressing, 16 bytes a slot: key and count; a power of two slots, sized ahead of every add to at most half full;
+ * an empty slot holds the key of the all-T 32-mer, which is counted in a counter of its own).  `length` is 1 .. 32:
+ * SKM_ERR_ARG otherwise.  SKM_TEST_CENSUS_SLOTS=N (a power of two >= 2, read by _create) starts the table at N slots;
+ * it then grows only when a launch finds it full.  A handle that found no memory for its table stays failed
+ * (SKM_ERR_STATE from then on).  Calls on one handle run one after the other. */
+typedef struct skm_barcode_census skm_barcode_census;
+int skm_barcode_census_create(int device, int length, skm_barcode_census **out);
+int skm_barcode_census_destroy(skm_barcode_census *census);
+/* A piece of barcode reads (a host piece, as for skm_barcodes_assign).  The window of read r is its bases
+ * [start, start + length): a read shorter than that is short; a window with any position that is not an upper-case
+ * ACGT is unreadable (no tolerance, unlike skm_barcodes_assign); every other window is counted under its 2 x length
+ * code bits (A0 C1 G2 T3, first base in the top bits).  stats[3] += counted, short, unreadable (they add up to
+ * n_reads).  SKM_ERR_ARG for a negative start. */
+int skm_barcode_census_add(skm_barcode_census *census, const skm_packed_reads *reads, int start,
+                           int64_t stats[3] /* counted, short, unreadable; added to */);
+int skm_barcode_census_size(skm_barcode_census *census, int64_t *n_distinct, int64_t *n_counted);
+/* The census in ranked order -- count descending, then key ascending -- ranked on the device: the first
+ * min(cap, n_distinct) entries. */
+int skm_barcode_census_ranked(skm_barcode_census *census, int64_t cap, uint64_t *keys, int64_t *counts);
+/* The cells.  rank = min((expect_cells + 99) / 100, n_distinct), m = the count at that rank (from 1),
+ * threshold = max((m + 9) / 10, 1); the candidates are the entries with count >= threshold; with drop_neighbours a
+ * candidate is dropped when a candidate earlier in ranked order differs from it in exactly one position (whether or
+ * not that one is dropped itself); the picked barcodes are the candidates not dropped, in ranked order.
+ * info[6] = rank, m, threshold, candidates, dropped, picked.  SKM_ERR_ARG for expect_cells < 1; SKM_ERR_STATE for a
+ * census without a counted barcode, and when picked > cap (info is filled, nothing is copied, the handle stays
+ * usable). */
+int skm_barcode_census_pick(skm_barcode_census *census, int64_t expect_cells, int drop_neighbours, int64_t cap,
+                            uint64_t *keys, int64_t *counts, int64_t info[6]);
 
 /* ------------------------------------------------------------ quantification
  * MapResult.effective_lengths (seekmer/mapper.py:134-141). */

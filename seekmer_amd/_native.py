@@ -151,6 +151,12 @@ HIP_SYMBOLS = {
     'skm_barcodes_assign': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PackedReads), ctypes.c_int, ctypes.c_int,
                                            c_i32p, c_i64p, c_i64p]),
     'skm_units_group': (ctypes.c_int, [ctypes.c_int, c_i32p, c_i64, c_i64, c_i32p, c_i64p]),
+    'skm_barcode_census_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_void_pp]),
+    'skm_barcode_census_destroy': (ctypes.c_int, [ctypes.c_void_p]),
+    'skm_barcode_census_add': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PackedReads), ctypes.c_int, c_i64p]),
+    'skm_barcode_census_size': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p]),
+    'skm_barcode_census_ranked': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_u64p, c_i64p]),
+    'skm_barcode_census_pick': (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_int, c_i64, c_u64p, c_i64p, c_i64p]),
     'skm_quant_create': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64p, c_i32p, c_f64p,
                                         c_void_pp]),
     'skm_quant_create_from_mapper': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_void_pp]),

@@ -51,18 +51,6 @@ namespace {
 
 enum { BC_EXACT = 0, BC_CORRECTED = 1, BC_AMBIGUOUS = 2, BC_NO_MATCH = 3, BC_UNREADABLE = 4 };
 
-// candidate j of a window: with a non-clean position (bad != 0) base j of 4 there, else substitution j of 3 L
-__device__ inline uint64_t barcode_candidate(uint64_t key, uint32_t bad, int length, int j)
-{
-    if (bad) {
-        const int shift = 2 * (length - 1 - __clz(bad));
-        return (key & ~(3ULL << shift)) | ((uint64_t)j << shift);
-    }
-    const int shift = 2 * (length - 1 - j / 3);
-    const uint64_t base = (key >> shift) & 3;
-    return key ^ ((base ^ ((base + 1 + j % 3) & 3)) << shift);
-}
-
 template <bool LDS>
 __global__ void __launch_bounds__(256)
 barcode_assign_kernel(BarcodeTable t, BarcodeWindows w, int max_mismatches, int32_t *__restrict__ cell,

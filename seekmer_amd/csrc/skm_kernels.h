@@ -560,6 +560,17 @@ inline __host__ __device__ uint32_t barcode_slot(uint64_t key, uint32_t slot_bit
 {
     return (uint32_t)((key * 0x9E3779B97F4A7C15ULL) >> 32) >> (32 - slot_bits);       // slot_bits >= 1
 }
+// candidate j of a window: with a non-clean position (bad != 0) base j of 4 there, else substitution j of 3 L
+__device__ inline uint64_t barcode_candidate(uint64_t key, uint32_t bad, int length, int j)
+{
+    if (bad) {
+        const int shift = 2 * (length - 1 - __clz(bad));
+        return (key & ~(3ULL << shift)) | ((uint64_t)j << shift);
+    }
+    const int shift = 2 * (length - 1 - j / 3);
+    const uint64_t base = (key >> shift) & 3;
+    return key ^ ((base ^ ((base + 1 + j % 3) & 3)) << shift);
+}
 struct BarcodeWindows {           // the window words of a piece's reads, compacted: what the assign kernel reads
     int64_t n_reads;
     const uint64_t *codes;        // [n_reads][words] the code words that hold the window (words = 0: no read reaches it)
@@ -628,6 +639,56 @@ void launch_umi_resolve(const UmiSet &t, const MapBatch &b, const SampleSalt &sa
                         unsigned long long *removed, hipStream_t stream);
 // `to` (any slots' contents) becomes a set that holds the molecules of `from`
 void launch_umi_rehash(const UmiSet &from, const UmiSet &to, hipStream_t stream);
+
+// ---- cell discovery (skm_census.hip; DESIGN.md section 4, "Cell discovery")
+constexpr unsigned long long CENSUS_EMPTY = ~0ULL;    // the key of an empty slot; its one preimage (32 T) is counted in ctl[]
+struct alignas(16) CensusSlot {   // 16 B: one distinct barcode
+    unsigned long long key;       // the 2 L code bits, CENSUS_EMPTY = empty
+    unsigned long long count;     // the clean windows seen with this key
+};
+enum { CENSUS_CTL_ENTRIES = 0,    // occupied slots (the sentinel's barcode is not among them)
+       CENSUS_CTL_SENTINEL = 1,   // windows whose key is CENSUS_EMPTY: the all-T 32-mer
+       CENSUS_CTL_DEFERRED = 2,   // (key, count) pairs a launch could not place: the table was full
+       CENSUS_CTL_COUNTED = 3, CENSUS_CTL_SHORT = 4, CENSUS_CTL_UNREADABLE = 5,      // the launch's units by kind
+       CENSUS_CTL_WORDS = 8,      // what an add resets and reads back
+       CENSUS_CTL_OUT = 6,        // [OUT .. OUT + 2] what the ranking kernels count: compacted entries, candidates, dropped
+       CENSUS_CTL_ROOM = 16 };    // words of the block
+struct CensusTable {
+    CensusSlot *slots;            // [1 << slot_bits] open addressing, linear probing from barcode_slot(key, slot_bits)
+    uint32_t slot_bits;           // 1 .. 31
+    int32_t length;               // L
+    unsigned long long *ctl;      // [CENSUS_CTL_ROOM]
+    unsigned long long *deferred; // [deferred_cap][2] key, count of what found the table full (nullptr: only counted)
+    int64_t deferred_cap;
+};
+// every slot empty
+void launch_census_init(const CensusTable &t, hipStream_t stream);
+// `to` (any slots' contents; room for all of them) becomes a table that holds the entries of `from`
+void launch_census_rehash(const CensusTable &from, const CensusTable &to, hipStream_t stream);
+// the clean windows of a piece are counted under their keys; ctl[COUNTED, SHORT, UNREADABLE] += the piece's units by
+// kind (they add up to w.n_reads), ctl[ENTRIES] += the slots claimed, ctl[SENTINEL] += the all-T 32-mers.  What finds
+// the table full is appended to t.deferred and counted in ctl[DEFERRED]
+void launch_census_count(const CensusTable &t, const BarcodeWindows &w, hipStream_t stream);
+// the n pairs of `pairs` ([n][2] key, count), none with the sentinel's key, are added to the table
+void launch_census_replay(const CensusTable &t, const unsigned long long *pairs, int64_t n, hipStream_t stream);
+// the occupied slots, and the sentinel's barcode if it was seen, as keys[] / counts[] in any order (room for
+// ctl[ENTRIES] + 1), iota[i] = i beside them; ctl[OUT] += their number
+void launch_census_compact(const CensusTable &t, unsigned long long *keys, unsigned long long *counts, int32_t *iota,
+                           hipStream_t stream);
+// word[i] = the 32 bits from `shift` on of (keys or counts)[perm[i]], XOR flip: what one stable sort pass orders by
+void launch_census_sort_word(const unsigned long long *values, const int32_t *perm, int64_t n, int shift, uint32_t flip,
+                             uint32_t *word, hipStream_t stream);
+// out_keys[i] = keys[perm[i]], out_counts[i] = counts[perm[i]] for i < n
+void launch_census_gather(const unsigned long long *keys, const unsigned long long *counts, const int32_t *perm, int64_t n,
+                          unsigned long long *out_keys, unsigned long long *out_counts, hipStream_t stream);
+// counts[] descending: ctl[OUT + 1] = the number of entries with counts[i] >= threshold (written only if there is one)
+void launch_census_candidates(const unsigned long long *counts, int64_t n, unsigned long long threshold,
+                              unsigned long long *ctl, hipStream_t stream);
+// dropped[i] (i < n_candidates, entries in ranked order, all with count >= threshold) = 1 when one of the 3 L single
+// substitutions of keys[i] is in the table with count >= threshold and ranks earlier, else 0; ctl[OUT + 2] += the ones
+void launch_census_pick(const CensusTable &t, const unsigned long long *keys, const unsigned long long *counts,
+                        int64_t n_candidates, unsigned long long threshold, uint32_t *dropped, int32_t *iota,
+                        hipStream_t stream);
 
 // one hipFuncGetAttributes per translation unit: its code object is loaded now, not by a sample's first launch
 void warm_code_map();

@@ -427,7 +427,8 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
-             barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0, **__):
+             barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
+             discover_cells=None, barcode_length=None, discover_keep_neighbours=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -472,7 +473,15 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     class an earlier unit has shown is removed on the GPU as if it had never been in the files (mapper.SampleSet with
     umi_bases; DESIGN.md section 4, "UMI collapse").  Every folder then holds what it would for a FASTQ pair of the
     cell's surviving units; barcodes.tsv gains two columns (units with a readable UMI, units left after collapse) and
-    barcodes.json the keys umi_start, umi_length, umi_unreadable, umi_duplicates.  No mismatch correction."""
+    barcodes.json the keys umi_start, umi_length, umi_unreadable, umi_duplicates.  No mismatch correction.
+
+    discover_cells: --discover-cells N with barcode_length L (1..32), instead of barcodes: there is no whitelist, the
+    cells are found in the barcode reads (mapper.discover_barcodes; DESIGN.md section 4, "Cell discovery": an exact
+    count of every distinct clean window on the GPU, a tenth of the count at rank ceil(N / 100) as threshold, and --
+    unless discover_keep_neighbours -- no candidate one substitution away from an earlier one).  The picked barcodes
+    go to output/barcodes.discovered.txt, a valid whitelist, every candidate to output/barcodes.census.tsv (barcode,
+    count, picked 0/1), and barcodes.json gains the key "discovery".  From there the run is `barcodes` on that list,
+    which reads the barcode file a second time."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -480,34 +489,44 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     mapper.strand_mode(strand)
     length_model, _ = mapper.length_model_weights(length_model)
     whitelist = None
-    if barcodes is None:
+    pooled = barcodes is not None or discover_cells is not None
+    if not pooled:
         if barcode_file is not None:
             raise ValueError('--barcode-file goes with --barcodes')
         if umi_length or umi_start:
             raise ValueError('--umi-length and --umi-start go with --barcodes')
+        if barcode_length is not None:
+            raise ValueError('--barcode-length goes with --discover-cells')
+        if discover_keep_neighbours:
+            raise ValueError('--discover-keep-neighbours goes with --discover-cells')
         groups = sample_groups(fastq_paths, single_ended)
         if not groups:
             raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
         names = sample_names(groups, names)
     else:
         whitelist = barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start,
-                                    barcode_mismatches, min_units, umi_start, umi_length)
+                                    barcode_mismatches, min_units, umi_start, umi_length, discover_cells=discover_cells,
+                                    barcode_length=barcode_length, discover_keep_neighbours=discover_keep_neighbours)
         groups = [tuple(fastq_paths)]
     ranks = parallel.Ranks.from_env()
     if ranks.world > 1:
         ranks.close()
         raise ValueError('infer-many runs in one process on one GPU: start it without a launcher')
-    for path in list(fastq_paths) + ([barcode_file] if whitelist is not None else []):
+    for path in list(fastq_paths) + ([barcode_file] if pooled else []):
         if not pathlib.Path(path).exists():
             raise ValueError(f'invalid FastQ file: {path}')
-        if whitelist is not None and not common.PackedReadFeeder.eligible([path]):
-            raise ValueError(f'--barcodes reads plain FASTQ files: decompress {path} first')
+        if pooled and not common.PackedReadFeeder.eligible([path]):
+            raise ValueError('%s reads plain FASTQ files: decompress %s first'
+                             % ('--barcodes' if barcodes is not None else '--discover-cells', path))
     try:
         output_path.mkdir(parents=True)
     except FileExistsError:
         _LOG.warning('The output folder exists. Overriding...')
-    if whitelist is None:
+    if not pooled:
         _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    elif whitelist is None:
+        _LOG.info('Inferring transcript abundance of the cells of one pooled run (about %d cells, found in the barcode reads)',
+                  discover_cells)
     else:
         _LOG.info('Inferring transcript abundance of the cells of one pooled run (%d barcodes)', len(whitelist[0]))
     _log_length_model(length_model, single_ended)
@@ -524,10 +543,25 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     set_estimates = {}
     trace('index load')
     sample_set = None
-    if whitelist is not None:
+    if pooled:
         # the cells of the pooled run are the samples, all of them in one set
-        table = mapper.BarcodeTable(*whitelist, device=device)
         parse_threads = 0 if debug or job_count <= 1 else min(int(job_count), 8)     # (one large file: -j parses it)
+        discovery = None
+        if whitelist is None:
+            # no whitelist: the census of the barcode reads gives one (the barcode file is read again below)
+            n_units = min(mapper.fastq_records(path) for path in [barcode_file] + list(fastq_paths))
+            picked, _, found = mapper.discover_barcodes(
+                common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads), barcode_length, discover_cells,
+                start=barcode_start, drop_neighbours=not discover_keep_neighbours, device=device, n_units=n_units)
+            discovery = _output_discovery(output_path, picked, found, discover_cells, barcode_length, barcode_start,
+                                          discover_keep_neighbours)
+            _LOG.info('Barcodes of %d units: %d counted, %d short, %d unreadable, %d distinct; rank %d has %d, threshold %d: '
+                      '%d candidates, %d dropped as neighbours, %d picked', found['units'], found['counted'], found['short'],
+                      found['unreadable'], found['distinct'], found['rank'], found['rank_count'], found['threshold'],
+                      found['candidates'], found['dropped'], found['picked'])
+            whitelist = mapper.check_whitelist(picked)
+            trace('cell discovery')
+        table = mapper.BarcodeTable(*whitelist, device=device)
         sample_set, kept, demux = mapper.map_barcoded(
             index, table, common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads),
             common.PackedReadFeeder(list(fastq_paths), paired=paired, threads=parse_threads), paired, start=barcode_start,
@@ -538,7 +572,8 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         if umi_length:
             _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed', umi_length,
                       demux['umi_unreadable'], demux['umi_duplicates'])
-        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units, umi_start, umi_length)
+        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units, umi_start, umi_length,
+                         discovery=discovery)
         if not kept.size:
             raise ValueError('no cell has %d units or more (see %s)' % (min_units, output_path / 'barcodes.tsv'))
         names = [table.names[c] for c in kept]
@@ -645,16 +680,34 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
 
 
 def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start, barcode_mismatches,
-                    min_units, umi_start=0, umi_length=0):
-    """The checks of `infer-many --barcodes` that need no read file -> the whitelist (barcodes, names) of
-    mapper.read_whitelist.  ValueError for a combination that cannot be and for a malformed whitelist."""
+                    min_units, umi_start=0, umi_length=0, discover_cells=None, barcode_length=None,
+                    discover_keep_neighbours=False):
+    """The checks of `infer-many --barcodes` and `infer-many --discover-cells` that need no read file -> the whitelist
+    (barcodes, names) of mapper.read_whitelist, or None where the cells are to be discovered.  ValueError for a
+    combination that cannot be and for a malformed whitelist."""
+    if barcodes is not None and discover_cells is not None:
+        raise ValueError('one of --barcodes and --discover-cells: a whitelist, or cells found in the barcode reads')
+    flag = '--barcodes' if discover_cells is None else '--discover-cells'
+    if discover_cells is None:
+        if barcode_length is not None:
+            raise ValueError('--barcode-length does not go with --barcodes: the whitelist gives the length')
+        if discover_keep_neighbours:
+            raise ValueError('--discover-keep-neighbours goes with --discover-cells')
+    else:
+        if int(discover_cells) < 1:
+            raise ValueError('--discover-cells must be 1 or more, not %r' % (discover_cells,))
+        if barcode_length is None:
+            raise ValueError('--discover-cells needs the length of a barcode: --barcode-length L')
+        if not 1 <= int(barcode_length) <= mapper.MAX_BARCODE_LENGTH:
+            raise ValueError('--barcode-length must be 1 to %d, not %r' % (mapper.MAX_BARCODE_LENGTH, barcode_length))
     if barcode_file is None:
-        raise ValueError('--barcodes needs the barcode reads: --barcode-file FASTQ')
+        raise ValueError('%s needs the barcode reads: --barcode-file FASTQ' % flag)
     if names is not None:
-        raise ValueError('--names does not go with --barcodes: the cells are named by the whitelist')
+        raise ValueError('--names does not go with %s: the cells are named by %s'
+                         % (flag, 'the whitelist' if discover_cells is None else 'their barcodes'))
     if len(fastq_paths) != (1 if single_ended else 2):
-        raise ValueError('--barcodes takes ONE pooled sample: %s, not %d'
-                         % ('one FASTQ file with -s' if single_ended else 'two FASTQ files (one with -s)', len(fastq_paths)))
+        raise ValueError('%s takes ONE pooled sample: %s, not %d'
+                         % (flag, 'one FASTQ file with -s' if single_ended else 'two FASTQ files (one with -s)', len(fastq_paths)))
     if int(barcode_start) < 0:
         raise ValueError('--barcode-start must be 0 or more, not %r' % (barcode_start,))
     if barcode_mismatches not in (0, 1):
@@ -667,10 +720,31 @@ def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, ba
         raise ValueError('--umi-start must be 0 or more, not %r' % (umi_start,))
     if int(umi_start) and not int(umi_length):
         raise ValueError('--umi-start goes with --umi-length')
-    return mapper.read_whitelist(barcodes)
+    return mapper.read_whitelist(barcodes) if discover_cells is None else None
 
 
-def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units, umi_start=0, umi_length=0):
+def _output_discovery(output_path, picked, found, expect_cells, length, start, keep_neighbours):
+    """output/barcodes.discovered.txt: the picked barcodes in ranked order under '#' lines that say how they were
+    found -- a whitelist as `--barcodes` reads it; output/barcodes.census.tsv: barcode, count, picked 0/1 of every
+    candidate in ranked order.  Returns the "discovery" entry of barcodes.json."""
+    with (output_path / 'barcodes.discovered.txt').open('w') as f:
+        f.write('# cells discovered from the barcode reads: --discover-cells %d --barcode-length %d --barcode-start %d%s\n'
+                % (expect_cells, length, start, ' --discover-keep-neighbours' if keep_neighbours else ''))
+        f.write('# threshold %d (a tenth of the count %d at rank %d)\n' % (found['threshold'], found['rank_count'], found['rank']))
+        f.write('# distinct %d, candidates %d, dropped %d\n' % (found['distinct'], found['candidates'], found['dropped']))
+        for barcode in picked:
+            f.write(barcode + '\n')
+    stays = set(picked)
+    with (output_path / 'barcodes.census.tsv').open('w') as f:
+        for barcode, count in zip(found['candidate_barcodes'], found['candidate_counts']):
+            f.write('%s\t%d\t%d\n' % (barcode, count, barcode in stays))
+    return dict(expect_cells=int(expect_cells), barcode_length=int(length), units_counted=found['counted'], short=found['short'],
+                unreadable=found['unreadable'], distinct=found['distinct'], rank=found['rank'], rank_count=found['rank_count'],
+                threshold=found['threshold'], candidates=found['candidates'], dropped_neighbours=found['dropped'],
+                picked=found['picked'], keep_neighbours=bool(keep_neighbours))
+
+
+def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units, umi_start=0, umi_length=0, discovery=None):
     """output/barcodes.tsv: barcode, name, assigned units, kept 0/1 per whitelist entry -- with UMIs also the units
     with a readable UMI (what `kept` looks at) and the units left after collapse; output/barcodes.json: the
     demultiplexing summary."""
@@ -691,6 +765,8 @@ def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_uni
     if umi_length:
         summary.update(umi_start=int(umi_start), umi_length=int(umi_length), umi_unreadable=demux['umi_unreadable'],
                        umi_duplicates=demux['umi_duplicates'])
+    if discovery is not None:
+        summary.update(discovery=discovery)
     with (output_path / 'barcodes.json').open('w') as f:
         json.dump(summary, f, indent=4)
         f.write('\n')
@@ -1394,7 +1470,8 @@ def add_many_subcommand_parser(subparsers):
 
 def add_barcode_arguments(parser):
     """--barcodes and its companions: dest 'barcodes', 'barcode_file', 'barcode_start', 'barcode_mismatches',
-    'min_units', 'umi_start', 'umi_length' (barcode_option checks the combinations once the arguments are parsed)."""
+    'min_units', 'umi_start', 'umi_length', and --discover-cells with 'discover_cells', 'barcode_length',
+    'discover_keep_neighbours' (barcode_option checks the combinations once the arguments are parsed)."""
     parser.add_argument('--barcodes', type=pathlib.Path, dest='barcodes', default=None, metavar='WHITELIST',
                         help='the FASTQ files are ONE pooled sample: split it into the cells of this whitelist (a '
                              'barcode per line, optionally a tab and the cell\'s name) on the GPU; needs --barcode-file')
@@ -1411,6 +1488,15 @@ def add_barcode_arguments(parser):
                              'UMI and one equivalence class once (with --barcodes; no mismatch correction)')
     parser.add_argument('--umi-start', type=int, dest='umi_start', default=None, metavar='N',
                         help='the UMI begins at base N of a barcode read (default 0; with --umi-length)')
+    parser.add_argument('--discover-cells', type=int, dest='discover_cells', default=None, metavar='N',
+                        help='instead of --barcodes: there is no whitelist, find the barcodes of about N expected cells in '
+                             'the barcode reads on the GPU (a tenth of the count at rank N/100 is the threshold); needs '
+                             '--barcode-length and --barcode-file')
+    parser.add_argument('--barcode-length', type=int, dest='barcode_length', default=None, metavar='L',
+                        help='a barcode is L bases long (1 to 32; with --discover-cells)')
+    parser.add_argument('--discover-keep-neighbours', action='store_true', dest='discover_keep_neighbours',
+                        help='keep a discovered barcode that is one substitution away from a larger one (default: it is '
+                             'taken for a misreading, and its reads are corrected into the larger one)')
 
 
 def barcode_option(parser, opts):
@@ -1419,16 +1505,34 @@ def barcode_option(parser, opts):
                                     ('--barcode-mismatches', 'barcode_mismatches'), ('--min-units', 'min_units'),
                                     ('--umi-length', 'umi_length'), ('--umi-start', 'umi_start'))
              if opts.get(key) is not None]
-    if opts.get('barcodes') is None:
+    discover = opts.get('discover_cells') is not None
+    if opts.get('barcodes') is not None and discover:
+        parser.error('one of --barcodes and --discover-cells: a whitelist, or cells found in the barcode reads')
+    if not discover:
+        if opts.get('barcodes') is not None and opts.get('barcode_length') is not None:
+            parser.error('--barcode-length does not go with --barcodes: the whitelist gives the length')
+        if opts.get('barcode_length') is not None:
+            parser.error('--barcode-length goes with --discover-cells')
+        if opts.get('discover_keep_neighbours'):             # (a flag: False when it is not given)
+            parser.error('--discover-keep-neighbours goes with --discover-cells')
+    if opts.get('barcodes') is None and not discover:
         if given:
             parser.error('%s goes with --barcodes' % given[0])
     else:
+        flag = '--discover-cells' if discover else '--barcodes'
+        if discover and opts['discover_cells'] < 1:
+            parser.error('--discover-cells must be 1 or more')
+        if discover and opts.get('barcode_length') is None:
+            parser.error('--discover-cells needs the length of a barcode: --barcode-length L')
+        if discover and not 1 <= opts['barcode_length'] <= mapper.MAX_BARCODE_LENGTH:
+            parser.error('--barcode-length must be 1 to %d' % mapper.MAX_BARCODE_LENGTH)
         if opts.get('barcode_file') is None:
-            parser.error('--barcodes needs the barcode reads: --barcode-file FASTQ')
+            parser.error('%s needs the barcode reads: --barcode-file FASTQ' % flag)
         if opts.get('names') is not None:
-            parser.error('--names does not go with --barcodes: the cells are named by the whitelist')
+            parser.error('--names does not go with %s: the cells are named by %s'
+                         % (flag, 'their barcodes' if discover else 'the whitelist'))
         if len(opts['fastq_paths']) != (1 if opts['single_ended'] else 2):
-            parser.error('--barcodes takes ONE pooled sample: two FASTQ files, or one with -s')
+            parser.error('%s takes ONE pooled sample: two FASTQ files, or one with -s' % flag)
     if opts.get('barcode_start') is not None and opts['barcode_start'] < 0:
         parser.error('--barcode-start must be 0 or more')
     if opts.get('min_units') is not None and opts['min_units'] < 1:

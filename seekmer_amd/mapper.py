@@ -26,8 +26,8 @@ import numpy
 from . import _native
 from .common import PackedReadFeeder, PackedReads, ReadBatch, decompress_and_open
 
-__all__ = ('BarcodeTable', 'DEMUX_CHUNK_UNITS', 'MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet',
-           'SummarizedResult', 'fragment_length_weights', 'group_units', 'map_barcoded', 'map_reads',
+__all__ = ('BarcodeCensus', 'BarcodeTable', 'DEMUX_CHUNK_UNITS', 'MAX_FRAGMENT_LENGTH', 'MapResult', 'ReadMapper', 'SampleSet',
+           'SummarizedResult', 'discover_barcodes', 'fragment_length_weights', 'group_units', 'map_barcoded', 'map_reads',
            'map_multiple_samples', 'map_sample_set', 'read_whitelist')
 
 _LOG = logging.getLogger(__name__)
@@ -1188,6 +1188,127 @@ def umi_windows(piece, start, length, cell=None, device=0):
         _native.ptr(cell, _native.c_i32p) if cell is not None and n else None, _native.ptr(umi, _native.c_u32p),
         ctypes.byref(unreadable)))
     return umi[:n], unreadable.value
+
+
+# ---- cell discovery: a whitelist from the barcode reads themselves (include/seekmer_hip.h, skm_barcode_census_*) ----
+
+CENSUS_STATS = ('counted', 'short', 'unreadable')           # skm_barcode_census_add's stats[3]
+CENSUS_INFO = ('rank', 'rank_count', 'threshold', 'candidates', 'dropped', 'picked')      # skm_barcode_census_pick's info[6]
+MAX_DISCOVERED_CELLS = 1 << 24      # what skm_units_group takes
+
+
+def barcode_strings(keys, length):
+    """The 2 * length code bits of barcodes (uint64; A0 C1 G2 T3, first base in the top bits) as a list of str."""
+    keys = numpy.asarray(keys, dtype=numpy.uint64)
+    if keys.size == 0:
+        return []
+    shifts = (2 * numpy.arange(length - 1, -1, -1)).astype(numpy.uint64)
+    letters = numpy.frombuffer(b'ACGT', dtype=numpy.uint8)[((keys[:, None] >> shifts) & numpy.uint64(3)).astype(numpy.intp)]
+    return [row.tobytes().decode() for row in letters]
+
+
+class BarcodeCensus:
+    """An exact count of every distinct barcode of the pieces added, in HBM (skm_barcode_census; DESIGN.md section 4,
+    "Cell discovery").  The window of a read is its bases [start, start + length); a shorter read is short, a window
+    with any position that is not an upper-case ACGT unreadable, every other window counted.  ``stats`` int64[3]
+    (CENSUS_STATS) runs over all pieces added so far; len() is the number of distinct barcodes."""
+
+    def __init__(self, length, device=0):
+        self.length = int(length)
+        self.device = device
+        self.stats = numpy.zeros(len(CENSUS_STATS), dtype=numpy.int64)
+        self._handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_barcode_census_create(device, self.length, ctypes.byref(self._handle)))
+
+    def __del__(self):
+        handle = getattr(self, '_handle', None)
+        if handle:
+            try:
+                _native.hip().skm_barcode_census_destroy(handle)
+            except Exception:
+                pass
+            self._handle = None
+
+    def add(self, piece, start=0):
+        _native.check(_native.hip().skm_barcode_census_add(self._handle, ctypes.byref(piece.raw), int(start),
+                                                           _native.ptr(self.stats, _native.c_i64p)))
+
+    def _size(self):
+        distinct, counted = ctypes.c_int64(), ctypes.c_int64()
+        _native.check(_native.hip().skm_barcode_census_size(self._handle, ctypes.byref(distinct), ctypes.byref(counted)))
+        return distinct.value, counted.value
+
+    def __len__(self):
+        return self._size()[0]
+
+    def ranked(self, limit=None):
+        """(barcodes as str, counts int64): the census by count descending, then barcode ascending (A < C < G < T) --
+        the first `limit` entries, or all of them.  Ranked on the device."""
+        n = len(self) if limit is None else min(int(limit), len(self))
+        keys, counts = numpy.zeros(max(n, 1), dtype=numpy.uint64), numpy.zeros(max(n, 1), dtype=numpy.int64)
+        _native.check(_native.hip().skm_barcode_census_ranked(self._handle, n, _native.ptr(keys, _native.c_u64p),
+                                                              _native.ptr(counts, _native.c_i64p)))
+        return barcode_strings(keys[:n], self.length), counts[:n]
+
+    def pick(self, expect_cells, drop_neighbours=True):
+        """The cells by the rule of DESIGN.md section 4, "Cell discovery" -> (barcodes as str, counts int64, info):
+        the picked barcodes in ranked order; info maps CENSUS_INFO to numbers.  ValueError for expect_cells < 1 and for
+        a census without a counted barcode."""
+        if int(expect_cells) < 1:
+            raise ValueError('%r expected cells: 1 at least' % (expect_cells,))
+        if len(self) == 0:
+            raise ValueError('no readable barcode')
+        info = numpy.zeros(len(CENSUS_INFO), dtype=numpy.int64)
+        cap = min(len(self), max(4 * int(expect_cells), 1024))
+        while True:
+            keys, counts = numpy.zeros(cap, dtype=numpy.uint64), numpy.zeros(cap, dtype=numpy.int64)
+            code = _native.hip().skm_barcode_census_pick(
+                self._handle, int(expect_cells), 1 if drop_neighbours else 0, cap, _native.ptr(keys, _native.c_u64p),
+                _native.ptr(counts, _native.c_i64p), _native.ptr(info, _native.c_i64p))
+            if code == _native.SKM_ERR_STATE and info[5] > cap:
+                cap = int(info[5])                    # (more than the first guess: the call has said how many)
+                continue
+            _native.check(code)
+            n = int(info[5])
+            return barcode_strings(keys[:n], self.length), counts[:n], dict(zip(CENSUS_INFO, info.tolist()))
+
+
+def discover_barcodes(barcode_feeder, length, expect_cells, start=0, drop_neighbours=True, device=0, n_units=None):
+    """The cell barcodes of a pooled run from its barcode reads alone -> (barcodes, counts, info), as
+    BarcodeCensus.pick, info also holding CENSUS_STATS over the run's units, 'distinct', 'units' and every candidate in
+    ranked order ('candidate_barcodes', 'candidate_counts').  barcode_feeder:
+    a single-ended PackedReadFeeder over the barcode file, drained here (map_barcoded reads the file again with a
+    feeder of its own); n_units: the units of the run where the cDNA files hold fewer records than the barcode file
+    (map_barcoded's cut; default: all the barcode file's)."""
+    if not 1 <= int(length) <= MAX_BARCODE_LENGTH:
+        raise ValueError('barcodes of %d bases: 1 to %d are possible' % (length, MAX_BARCODE_LENGTH))
+    if int(expect_cells) < 1:
+        raise ValueError('%r expected cells: 1 at least' % (expect_cells,))
+    if int(start) < 0:
+        raise ValueError('a barcode that starts at base %d' % start)
+    if barcode_feeder.paired or len(barcode_feeder.paths) != 1:
+        raise ValueError('one barcode file, read single-ended')
+    if n_units is None:
+        n_units = fastq_records(barcode_feeder.paths[0])
+    census = BarcodeCensus(length, device=device)
+    units = 0
+    for piece in barcode_feeder:
+        if piece.is_cut or piece.n_reads == 0 or units >= n_units:
+            continue
+        if piece.first_read != units:
+            raise ValueError('the barcode reads do not follow each other (read %d after %d)' % (piece.first_read, units))
+        if units + piece.n_reads > n_units:
+            piece = _slice_piece(piece, 0, n_units - units)
+        census.add(piece, start=start)
+        units += piece.n_reads
+    if units != n_units:
+        raise ValueError('the barcode file gave %d reads, its lines said %d' % (units, n_units))
+    barcodes, counts, info = census.pick(expect_cells, drop_neighbours=drop_neighbours)
+    if len(barcodes) > MAX_DISCOVERED_CELLS:
+        raise ValueError('%d barcodes picked, %d are possible: lower --discover-cells' % (len(barcodes), MAX_DISCOVERED_CELLS))
+    info.update(zip(CENSUS_STATS, census.stats.tolist()), distinct=len(census), units=int(n_units))
+    info['candidate_barcodes'], info['candidate_counts'] = census.ranked(info['candidates'])
+    return barcodes, counts, info
 
 
 class _Gathered:
