@@ -10,7 +10,7 @@ cd "$(dirname "$0")/../seekmer_amd/csrc"
 make -s ../libseekmer_hip.so
 mkdir -p build_$name
 objs=""
-for src in skm_abi.hip skm_map.hip skm_classes.hip skm_em.hip skm_em_batch.hip skm_em_set.hip skm_quant_setup.hip skm_pool.hip skm_strand.hip skm_samples.hip skm_bias.hip skm_genes.hip skm_barcodes.hip skm_umi.hip skm_census.hip; do
+for src in $(make -s --no-print-directory print-hip-src); do          # (the Makefile's HIP_SRC: the units are named there only)
   if [[ " $files " == *" $src "* ]]; then
     # (the compiler's resource remarks beside the object, as the product build keeps them)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wall -Wno-unused-function $flags \

@@ -1,13 +1,17 @@
-// skm_barcode_census_* (the host glue of cell discovery in skm_abi.hip, with the pool) under AddressSanitizer + UBSan,
+// skm_barcode_census_* (the host glue of cell discovery in skm_abi_cells.hip, with the pool) under AddressSanitizer + UBSan,
 // as a program of its own: CPU only, no GPU, no Python.  The HIP runtime calls the glue makes are stand-ins over
 // host memory (below); the launchers are sequential CPU versions with the same table layout and probing
 // (census_host_asan_kernels.hip).  From the repository's root:
 //   F="--offload-arch=gfx950 --cuda-host-only -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer"
-//   hipcc $F -c seekmer_amd/csrc/skm_abi.hip -o /tmp/ca_abi.o && hipcc $F -c seekmer_amd/csrc/skm_pool.hip -o /tmp/ca_pool.o
+//   hipcc $F -c seekmer_amd/csrc/skm_abi_cells.hip -o /tmp/ca_cells.o && hipcc $F -c seekmer_amd/csrc/skm_abi_core.hip -o /tmp/ca_core.o
+//   hipcc $F -c seekmer_amd/csrc/skm_pool.hip -o /tmp/ca_pool.o
 //   hipcc $F -Iinclude -Iseekmer_amd/csrc -c scripts/micro/census_host_asan_kernels.hip -o /tmp/ca_kernels.o
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude -c scripts/micro/census_host_asan.cpp -o /tmp/ca_main.o
-//   /opt/rocm/llvm/bin/clang++ -fsanitize=address,undefined -o /tmp/census_host_asan /tmp/ca_main.o /tmp/ca_abi.o /tmp/ca_pool.o \
-//       /tmp/ca_kernels.o -Wl,--unresolved-symbols=ignore-all -ldl -lpthread      (the other families' launchers are never called)
+//   /opt/rocm/llvm/bin/clang++ -fsanitize=address,undefined -o /tmp/census_host_asan /tmp/ca_main.o /tmp/ca_cells.o /tmp/ca_core.o \
+//       /tmp/ca_pool.o /tmp/ca_kernels.o -Wl,--unresolved-symbols=ignore-all -ldl -lpthread
+//   (only the units the census glue needs: skm_abi_cells.hip and, for the error message and set_device, skm_abi_core.hip.
+//   The flag stays: the cells unit also holds the barcode, UMI-window and unit-grouping glue and the core unit the
+//   gather probe, whose five launchers the stand-ins do not define and the program never calls)
 //   ASAN_OPTIONS=detect_leaks=0 /tmp/census_host_asan        (the pool parks its blocks for the life of the process: no leak)
 // 120 censuses: L in {1, 5, 16, 31, 32} x start in {0, 3, 20, 40}, ragged and uniform pieces (every other uniform piece
 // without a lengths array), strided codes, empty pieces, exception planes, SKM_TEST_CENSUS_SLOTS unset, 2 and 64; size,

@@ -1,9 +1,7 @@
 // C ABI of libseekmer_hip.so (declared in include/seekmer_hip.h): handle
 // management, HBM buffers, stream/event plumbing and the launch sequences.
 // No torch types, no exceptions across the boundary.
-#include "../../include/seekmer_hip.h"
-#include "skm_kernels.h"
-#include "skm_pool.h"
+#include "skm_abi.h"
 #include "skm_bias.h"
 #include "skm_bias_weights.h"
 
@@ -30,135 +28,7 @@
 #include <vector>
 
 using namespace skm;
-
-namespace {
-
-thread_local std::string g_error;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_error = buf;
-    return code;
-}
-
-#define HIP_TRY(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(SKM_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                               \
-    } while (0)
-
-// SKM_TRACE_STALE=1: report (and clear) a HIP error that some earlier call left behind (tuning aid)
-#define STALE_CHECK(where)                                                                           \
-    do {                                                                                             \
-        static const bool trace_stale_ = getenv("SKM_TRACE_STALE") != nullptr;                       \
-        if (trace_stale_) {                                                                          \
-            const hipError_t s_ = hipGetLastError();                                                 \
-            if (s_ != hipSuccess) fprintf(stderr, "[skm] stale HIP error at %s: %s\n", where, hipGetErrorString(s_)); \
-        }                                                                                            \
-    } while (0)
-
-#define SKM_TRY(call)          \
-    do {                       \
-        int rc_ = (call);      \
-        if (rc_ != SKM_OK) return rc_; \
-    } while (0)
-
-// device buffer that only ever grows; its block goes back to the pool with it (a block that a
-// stream may still use: drain that stream before the buffer goes)
-template <class T>
-struct DBuf {
-    T *p = nullptr;
-    size_t cap = 0;      // elements
-    DBuf() = default;
-    DBuf(const DBuf &) = delete;
-    DBuf &operator=(const DBuf &) = delete;
-    DBuf(DBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
-    DBuf &operator=(DBuf &&o) noexcept
-    {
-        if (this != &o) { pool_free(p); p = std::exchange(o.p, nullptr); cap = std::exchange(o.cap, 0); }
-        return *this;
-    }
-    ~DBuf() { pool_free(p); }
-    int ensure(size_t n, bool keep = false, hipStream_t stream = nullptr)
-    {
-        if (n <= cap) return SKM_OK;
-        size_t want = std::max(n, cap + cap / 2);
-        T *q = nullptr;
-        HIP_TRY(pool_alloc((void **)&q, want * sizeof(T)));
-        want = pool_round(want * sizeof(T)) / sizeof(T);
-        if (keep && p && cap) {
-            HIP_TRY(hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        }
-        pool_free(p);
-        p = q;
-        cap = want;
-        return SKM_OK;
-    }
-};
-
-// One HIP resource of another kind -- a stream, an event, a pinned block, hipMalloc'd memory --
-// handed back by `Free` (to the pool or to the runtime) when its owner goes.  Reads as the handle.
-template <class H, auto Free>
-class Own {
-public:
-    Own() = default;
-    explicit Own(H h) : h_(h) {}
-    Own(const Own &) = delete;
-    Own &operator=(const Own &) = delete;
-    ~Own() { reset(); }
-    operator H() const { return h_; }
-    H get() const { return h_; }
-    H operator->() const { return h_; }
-    H *out() { reset(); return &h_; }          // for the call that acquires a new one
-    void reset(H h = nullptr) { if (h_) (void)Free(h_); h_ = h; }
-    H release() { return std::exchange(h_, nullptr); }     // hand the resource to another owner
-
-private:
-    H h_ = nullptr;
-};
-
-void pool_event_release_plain(hipEvent_t e) { pool_event_release(e, false); }
-void pool_event_release_timing(hipEvent_t e) { pool_event_release(e, true); }
-
-using PoolStream = Own<hipStream_t, pool_stream_release>;
-using PoolEvent = Own<hipEvent_t, pool_event_release_plain>;
-using PoolTimingEvent = Own<hipEvent_t, pool_event_release_timing>;
-using PoolPinned = Own<unsigned long long *, pool_pinned_release>;
-using Stream = Own<hipStream_t, hipStreamDestroy>;
-using Event = Own<hipEvent_t, hipEventDestroy>;
-using HostPinned = Own<unsigned long long *, hipHostFree>;
-using DevMem = Own<void *, hipFree>;
-
-// runs a clean-up on every exit of the enclosing scope unless dismissed (the HIP_TRY / SKM_TRY
-// macros return from the middle of a function)
-template <class F>
-struct ScopeGuard {
-    F f;
-    bool armed = true;
-    explicit ScopeGuard(F fn) : f(fn) {}
-    ~ScopeGuard() { if (armed) f(); }
-    void dismiss() { armed = false; }
-};
-template <class F> ScopeGuard<F> on_exit(F f) { return ScopeGuard<F>(f); }
-// (scratch that kernels on a stream use goes back to the pool, where another stream may get it at
-// once, only after that stream has drained: a function declares its scratch BEFORE the guard that
-// synchronises the stream on an early return -- destroyed in reverse order, the guard runs first)
-
-int set_device(int device)
-{
-    HIP_TRY(hipSetDevice(device));
-    return SKM_OK;
-}
-
-}  // namespace
+using namespace skm::abi;
 
 struct skm_index {
     ~skm_index() { (void)hipSetDevice(device); }     // (then the members free the device copy)
@@ -361,208 +231,6 @@ struct skm_comm {
     void *comm = nullptr;
     int rank = 0, world = 1;
 };
-
-// ------------------------------------------------------------------- errors
-extern "C" const char *skm_last_error(void) { return g_error.c_str(); }
-
-extern "C" int skm_device_count(int *count)
-{
-    if (!count) return fail(SKM_ERR_ARG, "count is NULL");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        *count = 0;
-        return fail(SKM_ERR_NO_DEVICE, "no HIP device: %s", hipGetErrorString(e));
-    }
-    *count = n;
-    return SKM_OK;
-}
-
-extern "C" int skm_device_malloc(int device, int64_t bytes, void **out)
-{
-    if (!out || bytes < 0) return fail(SKM_ERR_ARG, "bad argument");
-    SKM_TRY(set_device(device));
-    HIP_TRY(hipMalloc(out, (size_t)std::max<int64_t>(bytes, 1)));
-    return SKM_OK;
-}
-
-extern "C" int skm_device_free(int device, void *ptr)
-{
-    SKM_TRY(set_device(device));
-    if (ptr) HIP_TRY(hipFree(ptr));
-    return SKM_OK;
-}
-
-extern "C" int skm_device_upload(int device, void *dst, const void *src, int64_t bytes)
-{
-    if (!dst || !src || bytes < 0) return fail(SKM_ERR_ARG, "bad argument");
-    SKM_TRY(set_device(device));
-    HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyHostToDevice));
-    return SKM_OK;
-}
-
-extern "C" int skm_device_download(int device, void *dst, const void *src, int64_t bytes)
-{
-    if (!dst || !src || bytes < 0) return fail(SKM_ERR_ARG, "bad argument");
-    SKM_TRY(set_device(device));
-    HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
-    return SKM_OK;
-}
-
-extern "C" int skm_device_synchronize(int device)
-{
-    SKM_TRY(set_device(device));
-    HIP_TRY(hipDeviceSynchronize());
-    return SKM_OK;
-}
-
-// Page-locked host memory: a batch handed over from it crosses the link at the full PCIe rate
-// and asynchronously (no staging copy by the runtime).  Plain C allocator signatures so that
-// libseekmer_host.so's FASTQ reader can take them as its slab allocator (skm_fastq_set_allocator).
-namespace {
-
-std::atomic<int> g_pinned_device{0};
-
-void *pinned_direct(size_t bytes)
-{
-    void *p = nullptr;
-    const int want = g_pinned_device.load();
-    int current = 0;
-    if (hipGetDevice(&current) != hipSuccess) return nullptr;
-    if (current != want && hipSetDevice(want) != hipSuccess) return nullptr;
-    const hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable);
-    if (current != want) (void)hipSetDevice(current);
-    return e == hipSuccess ? p : nullptr;
-}
-
-// One page-locked arena per process for the FASTQ readers' pieces.  Page-locking is slow
-// (hipHostMalloc: about a millisecond per megabyte, one call at a time inside the driver) and a
-// reader asks for a few dozen pieces of a megabyte or two in its first milliseconds -- measured: 19
-// concurrent calls that end 15 ms later, the parse waiting behind them.  The arena is page-locked
-// ONCE, by a helper thread that skm_pinned_set_device starts (infer.run calls it before it loads the
-// index, so the reservation runs under the index upload), and handed out first-fit; a request it
-// cannot serve (too large, arena full, no arena) is page-locked on its own as before.
-struct PinnedArena {
-    std::mutex mu;
-    std::condition_variable cv;
-    bool started = false, ready = false;
-    std::thread helper;
-    char *base = nullptr;
-    size_t bytes = 0;
-    std::map<size_t, size_t> free_at;          // offset -> length of every free range
-    std::unordered_map<size_t, size_t> live;   // offset -> length handed out
-    ~PinnedArena() { if (helper.joinable()) helper.join(); }
-} g_arena;
-
-size_t arena_size()
-{
-    size_t mb = 128;
-    if (const char *v = getenv("SKM_PINNED_ARENA_MB")) mb = (size_t)std::max(0L, atol(v));
-    return mb << 20;
-}
-
-}  // namespace
-
-extern "C" int skm_pinned_set_device(int device)
-{
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(SKM_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= count) return fail(SKM_ERR_ARG, "no GPU %d", device);
-    g_pinned_device.store(device);
-    std::lock_guard<std::mutex> hold(g_arena.mu);
-    if (!g_arena.started && arena_size() > 0) {
-        g_arena.started = true;
-        g_arena.helper = std::thread([device]() {
-            const size_t want = arena_size();
-            void *p = nullptr;
-            if (hipSetDevice(device) != hipSuccess || hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) p = nullptr;
-            std::lock_guard<std::mutex> hold(g_arena.mu);
-            g_arena.base = (char *)p;
-            g_arena.bytes = p ? want : 0;
-            if (p) g_arena.free_at[0] = want;
-            g_arena.ready = true;
-            g_arena.cv.notify_all();
-        });
-    }
-    return SKM_OK;
-}
-
-// (called from the FASTQ readers' worker threads, which never chose a device: page-lock against the
-// process's GPU, not against GPU 0, and portably, so that any device of the process may copy from it)
-extern "C" void *skm_pinned_alloc(size_t bytes)
-{
-    const size_t need = (std::max<size_t>(bytes, 1) + 4095) & ~(size_t)4095;
-    {
-        std::unique_lock<std::mutex> hold(g_arena.mu);
-        if (g_arena.started && need <= arena_size() / 8) {
-            // (a reservation in progress is worth waiting for: a call of our own would queue behind it)
-            g_arena.cv.wait(hold, [] { return g_arena.ready; });
-            for (auto it = g_arena.free_at.begin(); it != g_arena.free_at.end(); ++it) {
-                if (it->second < need) continue;
-                const size_t at = it->first, rest = it->second - need;
-                g_arena.free_at.erase(it);
-                if (rest) g_arena.free_at[at + need] = rest;
-                g_arena.live[at] = need;
-                return g_arena.base + at;
-            }
-        }
-    }
-    return pinned_direct(bytes);
-}
-
-extern "C" void skm_pinned_free(void *p)
-{
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> hold(g_arena.mu);
-        if (g_arena.base && (char *)p >= g_arena.base && (char *)p < g_arena.base + g_arena.bytes) {
-            const size_t at = (size_t)((char *)p - g_arena.base);
-            auto it = g_arena.live.find(at);
-            if (it == g_arena.live.end()) return;
-            size_t len = it->second, from = at;
-            g_arena.live.erase(it);
-            auto next = g_arena.free_at.lower_bound(from);          // merge with the free neighbours
-            if (next != g_arena.free_at.end() && next->first == from + len) { len += next->second; next = g_arena.free_at.erase(next); }
-            if (next != g_arena.free_at.begin()) {
-                auto prev = std::prev(next);
-                if (prev->first + prev->second == from) { from = prev->first; len += prev->second; g_arena.free_at.erase(prev); }
-            }
-            g_arena.free_at[from] = len;
-            return;
-        }
-    }
-    (void)hipHostFree(p);
-}
-
-// Diagnostic: random 16-byte gathers over a zero-filled table of `table_bytes`
-// (power of two).  chain=0: independent gathers (throughput); chain=1: each
-// address depends on the previous slot (latency under load).
-extern "C" int skm_device_gather_ceiling(int device, int64_t table_bytes, int blocks, int per_lane,
-                                         int chain, double *gathers_per_second)
-{
-    if (!gathers_per_second || table_bytes < 4096 || (table_bytes & (table_bytes - 1)) || blocks < 1
-            || per_lane < 4)
-        return fail(SKM_ERR_ARG, "bad argument");
-    SKM_TRY(set_device(device));
-    DevMem table, sink;
-    HIP_TRY(hipMalloc(table.out(), (size_t)table_bytes));
-    HIP_TRY(hipMalloc(sink.out(), 8));
-    HIP_TRY(hipMemset(table, 0, (size_t)table_bytes));
-    Event e0, e1;
-    HIP_TRY(hipEventCreate(e0.out()));
-    HIP_TRY(hipEventCreate(e1.out()));
-    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, (unsigned long long *)sink.get(),
-                        nullptr);   // warm-up
-    HIP_TRY(hipEventRecord(e0, nullptr));
-    launch_gather_probe(table, (uint64_t)table_bytes / 16, blocks, per_lane, chain, (unsigned long long *)sink.get(),
-                        nullptr);
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *gathers_per_second = (double)blocks * 256.0 * per_lane / (ms * 1e-3);
-    return SKM_OK;
-}
 
 // -------------------------------------------------------------------- index
 extern "C" int skm_index_create(const void *kmers, int64_t n_slots, const void *contigs,
@@ -1751,7 +1419,7 @@ void worker_main(skm_mapper *m)
         if (packed) {
             rc = run_packed_job(m, lo, hi, paired, segments, max_cw);
             if (rc != SKM_OK) {
-                message = g_error;
+                message = last_message();
                 // kernels that read the pieces' blocks may still be queued: nothing is handed back
                 // to the pool (and from there to the next pusher's copy) before the stream has drained
                 (void)hipStreamSynchronize(m->stream);
@@ -1776,7 +1444,7 @@ void worker_main(skm_mapper *m)
         }
         if (!skip) {
             rc = run_job(m, job);
-            if (rc != SKM_OK) message = g_error;  // (this thread's message)
+            if (rc != SKM_OK) message = last_message();  // (this thread's message)
         }
         {
             std::lock_guard<std::mutex> hold(m->q_mu);
@@ -1814,7 +1482,7 @@ int wait_jobs(skm_mapper *m, uint64_t ticket, bool consume)
         const int rc = m->job_error;
         const std::string message = m->job_error_msg;
         if (consume) { m->job_error = SKM_OK; m->job_error_ticket = 0; m->job_error_msg.clear(); }
-        g_error = message;
+        set_message(message);
         return rc;
     }
     return SKM_OK;
@@ -2739,7 +2407,7 @@ int set_umi_grow(skm_sample_set *s, uint64_t n_slots)
     DBuf<UmiSlot> fresh;
     auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });
     if (fresh.ensure((size_t)n_slots) != SKM_OK) {
-        const std::string why = g_error;
+        const std::string why = last_message();
         return fail(SKM_ERR_HIP, "UMI collapse: no device memory for a molecule set of %llu slots, %llu MB (64 bytes a molecule "
                     "at load 1/2; %lld molecules so far): %s", (unsigned long long)n_slots,
                     (unsigned long long)(n_slots * sizeof(UmiSlot) >> 20), (long long)s->umi_entries, why.c_str());
@@ -2908,7 +2576,7 @@ void set_worker(skm_sample_set *s)
             s->busy = true;
         }
         const int rc = set_launch(s, parts, n_units, global_first);
-        const std::string message = rc != SKM_OK ? g_error : std::string();
+        const std::string message = rc != SKM_OK ? last_message() : std::string();
         if (rc != SKM_OK) (void)hipStreamSynchronize(s->m->stream);   // (before the parts' blocks go back to the pool)
         parts.clear();
         {
@@ -2928,7 +2596,7 @@ int set_wait(skm_sample_set *s)
     s->work_cv.notify_all();
     s->done_cv.wait(hold, [&] { return !s->busy && s->queue.empty(); });
     s->flush--;
-    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    if (s->error != SKM_OK) { set_message(s->error_msg); return s->error; }
     return SKM_OK;
 }
 
@@ -2946,7 +2614,7 @@ int set_admit(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n_u
         return fail(SKM_ERR_ARG, "sample %lld: a set that counts hexamers per sample numbers its samples below %lld",
                     (long long)sample, (long long)SET_MAX_BIAS_SAMPLES);
     s->done_cv.wait(hold, [&] { return s->error != SKM_OK || s->queued_units <= SET_MAX_QUEUED; });
-    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    if (s->error != SKM_OK) { set_message(s->error_msg); return s->error; }
     return SKM_OK;
 }
 
@@ -2955,7 +2623,7 @@ int set_enqueue(skm_sample_set *s, int64_t sample, int64_t first_unit, int64_t n
 {
     {
         std::lock_guard<std::mutex> hold(s->mu);
-        if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+        if (s->error != SKM_OK) { set_message(s->error_msg); return s->error; }
         if ((int64_t)s->sample_units.size() <= sample) s->sample_units.resize((size_t)sample + 1, 0);
         if (first_unit != s->sample_units[sample])
             return fail(SKM_ERR_STATE, "sample %lld: a segment from unit %lld after %lld units (segments are added in order)",
@@ -2985,7 +2653,7 @@ int set_hold(skm_sample_set *s, std::unique_lock<std::mutex> &hold)
     s->work_cv.notify_all();
     s->done_cv.wait(hold, [&] { return !s->busy && s->queue.empty(); });
     s->flush--;
-    if (s->error != SKM_OK) { g_error = s->error_msg; return s->error; }
+    if (s->error != SKM_OK) { set_message(s->error_msg); return s->error; }
     return SKM_OK;
 }
 
@@ -3623,514 +3291,6 @@ extern "C" int skm_sample_set_split(int64_t n_entries, const int64_t *entry_glob
         class_local[k] = entry_local[e] + (first_seen[k] - entry_global[e]);
     }
     set_split_order(n_samples, n_classes, class_sample, class_local, order, sample_class_offsets);
-    return SKM_OK;
-}
-
-// ------------------------------------------------------------ cell barcodes (skm_barcodes.hip)
-// The whitelist's table is built here, on the host, once per handle, and uploaded; the scratch of the assign calls
-// lives in the handle and grows with the largest piece.  All work is on the default stream with blocking copies.
-// What the window kernels (barcode_assign_kernel, umi_window_kernel, census_count_kernel) read of a host piece: only
-// the one or two code words of every read that hold bases [start, start + length), the lengths unless uniform, and
-// the dense clean word that barcode_clean_kernel scatters from the exception list.
-struct WindowScratch {
-    DBuf<uint64_t> codes;
-    DBuf<uint32_t> lengths, clean, exception_reads, exception_masks;
-};
-
-namespace {
-
-// a piece of packed reads as the window kernels take it (n_reads > 0 pieces are looked at in full)
-int window_piece_check(const skm_packed_reads *reads)
-{
-    const int64_t n = reads->n_reads, n_exc = reads->n_exceptions;
-    if (n < 0 || n >= (1LL << 31) || n_exc < 0 || n_exc > n) return fail(SKM_ERR_ARG, "a piece of %lld reads", (long long)n);
-    if (n == 0) return SKM_OK;
-    const int64_t code_words = reads->code_words;
-    if (code_words < 0 || reads->read_stride < code_words || (code_words && !reads->codes) ||
-        (!reads->lengths && reads->uniform_len < 0) || (n_exc && (!reads->exception_reads || !reads->exception_masks)))
-        return fail(SKM_ERR_ARG, "not a piece of packed reads");
-    for (int64_t e = 0; e < n_exc; ++e)
-        if (reads->exception_reads[e] >= (uint64_t)n) return fail(SKM_ERR_ARG, "exception %lld names read %u of %lld", (long long)e, reads->exception_reads[e], (long long)n);
-    return SKM_OK;
-}
-
-// the windows of a checked piece of n_reads > 0 reads go up (default stream; the copies block, the clean kernel is
-// queued): *w is what the kernels take.  The caller drains the stream before the scratch goes.
-int window_piece_upload(WindowScratch &s, const skm_packed_reads *reads, int start, int length, BarcodeWindows *w)
-{
-    const int64_t n = reads->n_reads, n_exc = reads->n_exceptions, code_words = reads->code_words;
-    // the one or two words of every read that hold the window, as far as the piece has them
-    const int64_t first_word = start / 32;
-    const int offset = start % 32;
-    const int words = (int)std::max<int64_t>(0, std::min<int64_t>(code_words - first_word, offset + length > 32 ? 2 : 1));
-    SKM_TRY(s.codes.ensure((size_t)std::max<int64_t>(n * words, 1))); SKM_TRY(s.clean.ensure(n));
-    if (words && reads->read_stride == words) {
-        HIP_TRY(hipMemcpy(s.codes.p, reads->codes, (size_t)(n * words) * 8, hipMemcpyHostToDevice));
-    } else if (words) {
-        std::vector<uint64_t> window((size_t)(n * words));
-        for (int64_t r = 0; r < n; ++r)
-            for (int k = 0; k < words; ++k) window[r * words + k] = reads->codes[r * reads->read_stride + first_word + k];
-        HIP_TRY(hipMemcpy(s.codes.p, window.data(), window.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (reads->lengths) {
-        SKM_TRY(s.lengths.ensure(n));
-        HIP_TRY(hipMemcpy(s.lengths.p, reads->lengths, n * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemsetAsync(s.clean.p, 0xff, n * 4, nullptr));
-    if (n_exc && words) {
-        SKM_TRY(s.exception_reads.ensure(n_exc)); SKM_TRY(s.exception_masks.ensure(n_exc * words));
-        HIP_TRY(hipMemcpy(s.exception_reads.p, reads->exception_reads, n_exc * 4, hipMemcpyHostToDevice));
-        std::vector<uint32_t> planes((size_t)(n_exc * words));
-        for (int64_t e = 0; e < n_exc; ++e)
-            for (int k = 0; k < words; ++k) planes[e * words + k] = reads->exception_masks[e * code_words + first_word + k];
-        HIP_TRY(hipMemcpy(s.exception_masks.p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice));
-        launch_barcode_clean(s.exception_reads.p, s.exception_masks.p, n_exc, words, offset, s.clean.p, nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    *w = BarcodeWindows{n, s.codes.p, words, offset, reads->lengths ? s.lengths.p : nullptr, reads->uniform_len, start, s.clean.p};
-    return SKM_OK;
-}
-
-}  // namespace
-
-struct skm_barcodes {
-    ~skm_barcodes() { (void)hipSetDevice(device); }  // (then the members free the device memory)
-    int device = 0;
-    int length = 0;
-    int64_t n = 0;
-    uint32_t slot_bits = 1;
-    std::mutex mu;                                   // one assign call at a time: they share the scratch
-    DBuf<uint64_t> keys;
-    DBuf<int32_t> cells, cell;
-    WindowScratch windows;
-    DBuf<unsigned long long> units;                  // [n] + the five counters
-};
-
-extern "C" int skm_barcodes_create(int device, const char *barcodes, int64_t n, int length, skm_barcodes **out)
-{
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
-    if (!out || !barcodes) return fail(SKM_ERR_ARG, "bad argument");
-    if (length < 1 || length > 32) return fail(SKM_ERR_ARG, "barcodes of %d bases: 1 to 32 are possible", length);
-    if (n < 1 || n > (1LL << 28)) return fail(SKM_ERR_ARG, "a whitelist of %lld barcodes", (long long)n);
-    uint32_t slot_bits = 1;
-    while ((1LL << slot_bits) < 2 * n) ++slot_bits;
-    const uint32_t mask = (uint32_t)((1ULL << slot_bits) - 1);
-    std::vector<uint64_t> keys((size_t)mask + 1, 0);
-    std::vector<int32_t> cells((size_t)mask + 1, -1);
-    for (int64_t i = 0; i < n; ++i) {
-        uint64_t key = 0;
-        for (int j = 0; j < length; ++j) {
-            const char c = barcodes[i * length + j];
-            const int code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-            if (code < 0) return fail(SKM_ERR_ARG, "barcode %lld holds a character other than A, C, G, T", (long long)i);
-            key = key << 2 | (uint64_t)code;
-        }
-        uint32_t s = barcode_slot(key, slot_bits);
-        while (cells[s] >= 0) {
-            if (keys[s] == key) return fail(SKM_ERR_ARG, "barcodes %d and %lld are the same", cells[s], (long long)i);
-            s = (s + 1) & mask;
-        }
-        keys[s] = key;
-        cells[s] = (int32_t)i;
-    }
-    SKM_TRY(set_device(device));
-    auto b = std::make_unique<skm_barcodes>();
-    b->device = device; b->length = length; b->n = n; b->slot_bits = slot_bits;
-    SKM_TRY(b->keys.ensure(keys.size())); SKM_TRY(b->cells.ensure(cells.size()));
-    HIP_TRY(hipMemcpy(b->keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->cells.p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice));
-    *out = b.release();
-    return SKM_OK;
-}
-
-extern "C" int skm_barcodes_destroy(skm_barcodes *barcodes)
-{
-    delete barcodes;
-    return SKM_OK;
-}
-
-extern "C" int skm_barcodes_assign(skm_barcodes *b, const skm_packed_reads *reads, int start, int max_mismatches,
-                                   int32_t *cell, int64_t *cell_units, int64_t stats[5])
-{
-    if (!b || !reads || !cell_units || !stats) return fail(SKM_ERR_ARG, "bad argument");
-    if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a barcode that starts at base %d", start);
-    if (max_mismatches != 0 && max_mismatches != 1) return fail(SKM_ERR_ARG, "%d mismatches: 0 or 1", max_mismatches);
-    SKM_TRY(window_piece_check(reads));
-    const int64_t n = reads->n_reads;
-    if (n == 0) return SKM_OK;
-    if (!cell) return fail(SKM_ERR_ARG, "not a piece of packed reads");
-    std::lock_guard<std::mutex> hold(b->mu);
-    SKM_TRY(set_device(b->device));
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: the scratch is in use)
-    SKM_TRY(b->cell.ensure(n));
-    SKM_TRY(b->units.ensure(b->n + BARCODE_STATS));
-    BarcodeWindows w{};
-    SKM_TRY(window_piece_upload(b->windows, reads, start, b->length, &w));
-    HIP_TRY(hipMemsetAsync(b->units.p, 0, (b->n + BARCODE_STATS) * 8, nullptr));
-    BarcodeTable table{b->keys.p, b->cells.p, b->slot_bits, b->length, b->n};
-    launch_barcode_assign(table, w, max_mismatches, b->cell.p, b->units.p, b->units.p + b->n, nullptr);
-    HIP_TRY(hipGetLastError());
-    std::vector<unsigned long long> counted((size_t)b->n + BARCODE_STATS);
-    HIP_TRY(hipMemcpy(cell, b->cell.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(counted.data(), b->units.p, counted.size() * 8, hipMemcpyDeviceToHost));
-    drain.dismiss();                          // (the copies home have waited for the kernels)
-    for (int64_t c = 0; c < b->n; ++c) cell_units[c] += (int64_t)counted[c];
-    for (int k = 0; k < BARCODE_STATS; ++k) stats[k] += (int64_t)counted[b->n + k];
-    return SKM_OK;
-}
-
-// The scratch lives for the call; all work is on the default stream with blocking copies, as skm_barcodes_assign.
-extern "C" int skm_umi_windows(int device, const skm_packed_reads *reads, int start, int length, int32_t *cell, uint32_t *umi,
-                               int64_t *n_unreadable)
-{
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
-    if (!reads || !n_unreadable) return fail(SKM_ERR_ARG, "bad argument");
-    if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a UMI that starts at base %d", start);
-    if (length < 1 || length > 16) return fail(SKM_ERR_ARG, "UMIs of %d bases: 1 to 16 are possible", length);
-    SKM_TRY(window_piece_check(reads));
-    const int64_t n = reads->n_reads;
-    if (n == 0) return SKM_OK;
-    if (!umi) return fail(SKM_ERR_ARG, "not a piece of packed reads");
-    SKM_TRY(set_device(device));
-    WindowScratch windows; DBuf<uint32_t> d_umi; DBuf<int32_t> d_cell;
-    DBuf<unsigned long long> d_count;
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
-    SKM_TRY(d_umi.ensure(n));
-    SKM_TRY(d_count.ensure(1));
-    if (cell) {
-        SKM_TRY(d_cell.ensure(n));
-        HIP_TRY(hipMemcpy(d_cell.p, cell, n * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemsetAsync(d_count.p, 0, 8, nullptr));
-    BarcodeWindows w{};
-    SKM_TRY(window_piece_upload(windows, reads, start, length, &w));
-    launch_umi_windows(w, length, cell ? d_cell.p : nullptr, d_umi.p, d_count.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    unsigned long long counted = 0;
-    HIP_TRY(hipMemcpy(umi, d_umi.p, n * 4, hipMemcpyDeviceToHost));
-    if (cell) HIP_TRY(hipMemcpy(cell, d_cell.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&counted, d_count.p, 8, hipMemcpyDeviceToHost));
-    drain.dismiss();                          // (the copies home have waited for the kernels)
-    *n_unreadable += (int64_t)counted;
-    return SKM_OK;
-}
-
-extern "C" int skm_units_group(int device, const int32_t *sample, int64_t n, int64_t n_samples, int32_t *order,
-                               int64_t *offsets)
-{
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
-    if (n < 0 || n >= (1LL << 31) || n_samples < 1 || n_samples > (1LL << 24) || !offsets || (n && (!sample || !order)))
-        return fail(SKM_ERR_ARG, "bad argument");
-    SKM_TRY(set_device(device));
-    DBuf<int32_t> d_sample, d_iota, d_order; DBuf<uint32_t> d_keys, d_sorted; DBuf<int64_t> d_offsets; DBuf<int> d_error;
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
-    const size_t room = (size_t)std::max<int64_t>(n, 1);
-    SKM_TRY(d_sample.ensure(room)); SKM_TRY(d_iota.ensure(room)); SKM_TRY(d_order.ensure(room)); SKM_TRY(d_keys.ensure(room));
-    SKM_TRY(d_sorted.ensure(room)); SKM_TRY(d_offsets.ensure(n_samples + 1)); SKM_TRY(d_error.ensure(1));
-    HIP_TRY(hipMemsetAsync(d_error.p, 0, sizeof(int), nullptr));
-    if (n) HIP_TRY(hipMemcpy(d_sample.p, sample, n * 4, hipMemcpyHostToDevice));
-    launch_group_keys(d_sample.p, n, n_samples, d_keys.p, d_iota.p, d_error.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    int end_bit = 1;
-    while ((1LL << end_bit) <= n_samples) ++end_bit;      // (the keys go up to n_samples itself: the dropped units)
-    if (sort_pairs_u32(d_keys.p, d_sorted.p, d_iota.p, d_order.p, n, end_bit, nullptr) != 0)
-        return fail(SKM_ERR_HIP, "grouping %lld units: %s", (long long)n, quant_setup_failure());
-    launch_group_offsets(d_sorted.p, n, n_samples, d_offsets.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    int error = 0;
-    HIP_TRY(hipMemcpy(&error, d_error.p, sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(offsets, d_offsets.p, (n_samples + 1) * 8, hipMemcpyDeviceToHost));
-    drain.dismiss();                          // (the copies home have waited for the kernels)
-    if (error) return fail(SKM_ERR_ARG, "a unit names a sample not below n_samples = %lld", (long long)n_samples);
-    if (offsets[n_samples]) HIP_TRY(hipMemcpy(order, d_order.p, offsets[n_samples] * 4, hipMemcpyDeviceToHost));
-    return SKM_OK;
-}
-
-// ------------------------------------------------------------ cell discovery (skm_census.hip)
-// The census table lives in the handle and is sized ahead of every add to at least twice (distinct keys so far + the
-// piece's reads); SKM_TEST_CENSUS_SLOTS starts it at that many slots instead, and it then grows only when a launch
-// finds it full (the deferred pairs are replayed after the rehash).  The ranking is made by the first call that
-// needs it after the last add and kept on the device.  All work is on the default stream with blocking copies.
-struct skm_barcode_census {
-    ~skm_barcode_census() { (void)hipSetDevice(device); }  // (then the members free the device memory)
-    int device = 0;
-    int length = 0;
-    std::mutex mu;                                   // calls on one handle run one after the other
-    uint32_t slot_bits = 0;
-    bool test_slots = false;
-    int64_t entries = 0, sentinel = 0, counted = 0;  // occupied slots, all-T 32-mers seen, clean windows counted
-    bool failed = false;                             // no memory for the table, or a launch that lost units
-    std::string failed_msg;
-    DBuf<CensusSlot> slots;
-    DBuf<unsigned long long> ctl, deferred;
-    WindowScratch windows;                           // the windows of the piece at hand
-    bool ranked = false;                             // ranked_keys / ranked_counts hold the census in ranked order
-    int64_t n_ranked = 0;
-    DBuf<unsigned long long> keys, counts, ranked_keys, ranked_counts, picked_keys, picked_counts;
-    DBuf<int32_t> perm, perm_sorted;
-    DBuf<uint32_t> word, word_sorted;
-    CensusTable table(unsigned long long *list = nullptr, int64_t list_cap = 0) const
-    {
-        return CensusTable{slots.p, slot_bits, length, ctl.p, list, list_cap};
-    }
-};
-
-namespace {
-
-int census_fail(skm_barcode_census *c, int code, const std::string &msg)
-{
-    c->failed = true;
-    c->failed_msg = msg;
-    return fail(code, "%s", msg.c_str());
-}
-
-// the census in 1 << bits slots: a fresh table, or the entries of the old one rehashed (c->mu is held)
-int census_grow(skm_barcode_census *c, uint32_t bits)
-{
-    char text[320];
-    if (bits > 31) {
-        snprintf(text, sizeof(text), "a census table of 2^%u slots (%lld distinct barcodes so far)", bits, (long long)c->entries);
-        return census_fail(c, SKM_ERR_STATE, text);
-    }
-    DBuf<CensusSlot> fresh;
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });
-    if (fresh.ensure((size_t)1 << bits) != SKM_OK) {
-        const std::string why = g_error;
-        snprintf(text, sizeof(text), "cell discovery: no device memory for a census table of %llu slots, %llu MB (32 bytes a "
-                 "distinct barcode at load 1/2; %lld distinct keys so far): ", 1ULL << bits,
-                 (unsigned long long)(((1ULL << bits) * sizeof(CensusSlot)) >> 20), (long long)c->entries);
-        return census_fail(c, SKM_ERR_HIP, text + why);
-    }
-    const CensusTable to{fresh.p, bits, c->length, c->ctl.p, nullptr, 0};
-    if (c->slot_bits) {
-        HIP_TRY(hipMemsetAsync(c->ctl.p + CENSUS_CTL_DEFERRED, 0, 8, nullptr));
-        launch_census_rehash(c->table(), to, nullptr);
-    } else {
-        launch_census_init(to, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    unsigned long long lost = 0;                     // (the copy home waits for the kernels: the old slots can go)
-    HIP_TRY(hipMemcpy(&lost, c->ctl.p + CENSUS_CTL_DEFERRED, 8, hipMemcpyDeviceToHost));
-    drain.dismiss();
-    if (c->slot_bits && lost) {
-        snprintf(text, sizeof(text), "%llu barcodes found no slot in a census table of 2^%u slots", lost, bits);
-        return census_fail(c, SKM_ERR_STATE, text);
-    }
-    c->slots = std::move(fresh);
-    c->slot_bits = bits;
-    return SKM_OK;
-}
-
-// the census in ranked order on the device: count descending, then key ascending (c->mu is held)
-int census_rank(skm_barcode_census *c)
-{
-    if (c->ranked) return SKM_OK;
-    const int64_t D = c->entries + (c->sentinel ? 1 : 0);
-    if (D >= (1LL << 31)) return fail(SKM_ERR_STATE, "%lld distinct barcodes: fewer than 2^31 can be ranked", (long long)D);
-    c->n_ranked = D;
-    if (D == 0) { c->ranked = true; return SKM_OK; }
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });
-    const size_t room = (size_t)c->entries + 1;
-    SKM_TRY(c->keys.ensure(room)); SKM_TRY(c->counts.ensure(room)); SKM_TRY(c->ranked_keys.ensure(room));
-    SKM_TRY(c->ranked_counts.ensure(room)); SKM_TRY(c->perm.ensure(room)); SKM_TRY(c->perm_sorted.ensure(room));
-    SKM_TRY(c->word.ensure(room)); SKM_TRY(c->word_sorted.ensure(room));
-    HIP_TRY(hipMemsetAsync(c->ctl.p + CENSUS_CTL_OUT, 0, 2 * 8, nullptr));
-    launch_census_compact(c->table(), c->keys.p, c->counts.p, c->perm.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    unsigned long long found = 0;
-    HIP_TRY(hipMemcpy(&found, c->ctl.p + CENSUS_CTL_OUT, 8, hipMemcpyDeviceToHost));
-    if ((int64_t)found != D) return fail(SKM_ERR_STATE, "the census table holds %llu barcodes, its counter says %lld", found, (long long)D);
-    // stable passes from the last criterion to the first: key low and high words, then the complemented count words
-    int count_bits = 1;
-    while (count_bits < 63 && (1LL << count_bits) <= c->counted) ++count_bits;
-    struct Pass { const unsigned long long *values; int shift; uint32_t flip; int bits; };
-    std::vector<Pass> passes;
-    passes.push_back({c->keys.p, 0, 0u, std::min(32, 2 * c->length)});
-    if (c->length > 16) passes.push_back({c->keys.p, 32, 0u, 2 * c->length - 32});
-    passes.push_back({c->counts.p, 0, count_bits >= 32 ? ~0u : (1u << count_bits) - 1u, std::min(32, count_bits)});
-    if (count_bits > 32) passes.push_back({c->counts.p, 32, (uint32_t)((1ULL << (count_bits - 32)) - 1ULL), count_bits - 32});
-    for (const Pass &p : passes) {
-        launch_census_sort_word(p.values, c->perm.p, D, p.shift, p.flip, c->word.p, nullptr);
-        HIP_TRY(hipGetLastError());
-        if (sort_pairs_u32(c->word.p, c->word_sorted.p, c->perm.p, c->perm_sorted.p, D, p.bits, nullptr) != 0)
-            return fail(SKM_ERR_HIP, "ranking %lld barcodes: %s", (long long)D, quant_setup_failure());
-        std::swap(c->perm, c->perm_sorted);
-    }
-    launch_census_gather(c->keys.p, c->counts.p, c->perm.p, D, c->ranked_keys.p, c->ranked_counts.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    drain.dismiss();
-    c->ranked = true;
-    return SKM_OK;
-}
-
-}  // namespace
-
-extern "C" int skm_barcode_census_create(int device, int length, skm_barcode_census **out)
-{
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
-    if (!out) return fail(SKM_ERR_ARG, "bad argument");
-    if (length < 1 || length > 32) return fail(SKM_ERR_ARG, "barcodes of %d bases: 1 to 32 are possible", length);
-    uint32_t bits = 10;
-    bool test_slots = false;
-    if (const char *v = getenv("SKM_TEST_CENSUS_SLOTS")) {       // test hook: a census table that has to grow under a launch
-        const long long n = atoll(v);
-        if (n < 2 || n > (1LL << 30) || (n & (n - 1)))
-            return fail(SKM_ERR_ARG, "SKM_TEST_CENSUS_SLOTS must be a power of two from 2 to 2^30, not '%s'", v);
-        bits = 1;
-        while ((1LL << bits) < n) ++bits;
-        test_slots = true;
-    }
-    SKM_TRY(set_device(device));
-    auto c = std::make_unique<skm_barcode_census>();
-    c->device = device; c->length = length; c->test_slots = test_slots;
-    SKM_TRY(c->ctl.ensure(CENSUS_CTL_ROOM));
-    HIP_TRY(hipMemsetAsync(c->ctl.p, 0, CENSUS_CTL_ROOM * 8, nullptr));
-    SKM_TRY(census_grow(c.get(), bits));
-    *out = c.release();
-    return SKM_OK;
-}
-
-extern "C" int skm_barcode_census_destroy(skm_barcode_census *census)
-{
-    delete census;
-    return SKM_OK;
-}
-
-extern "C" int skm_barcode_census_add(skm_barcode_census *c, const skm_packed_reads *reads, int start, int64_t stats[3])
-{
-    if (!c || !reads || !stats) return fail(SKM_ERR_ARG, "bad argument");
-    if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a barcode that starts at base %d", start);
-    SKM_TRY(window_piece_check(reads));
-    const int64_t n = reads->n_reads;
-    std::lock_guard<std::mutex> hold(c->mu);
-    if (c->failed) return fail(SKM_ERR_STATE, "the census has failed: %s", c->failed_msg.c_str());
-    if (n == 0) return SKM_OK;
-    SKM_TRY(set_device(c->device));
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: the scratch is in use)
-    if (!c->test_slots) {
-        uint32_t bits = c->slot_bits;
-        while ((1LL << bits) < 2 * (c->entries + n)) ++bits;
-        if (bits > c->slot_bits) SKM_TRY(census_grow(c, bits));
-    }
-    SKM_TRY(c->deferred.ensure((size_t)(2 * n)));
-    HIP_TRY(hipMemsetAsync(c->ctl.p + CENSUS_CTL_DEFERRED, 0, (CENSUS_CTL_WORDS - CENSUS_CTL_DEFERRED) * 8, nullptr));
-    BarcodeWindows w{};
-    SKM_TRY(window_piece_upload(c->windows, reads, start, c->length, &w));
-    c->ranked = false;
-    launch_census_count(c->table(c->deferred.p, n), w, nullptr);
-    HIP_TRY(hipGetLastError());
-    unsigned long long ctl[CENSUS_CTL_WORDS];
-    HIP_TRY(hipMemcpy(ctl, c->ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
-    c->entries = (int64_t)ctl[CENSUS_CTL_ENTRIES];
-    const int64_t deferred = (int64_t)ctl[CENSUS_CTL_DEFERRED];
-    char text[200];
-    if (deferred > n) {
-        snprintf(text, sizeof(text), "a launch deferred %lld pairs of a piece of %lld reads", (long long)deferred, (long long)n);
-        return census_fail(c, SKM_ERR_STATE, text);
-    }
-    if (deferred) {
-        // the table was full: room for everything deferred, then the pairs again
-        uint32_t bits = c->slot_bits + 1;
-        while ((1LL << bits) < 2 * (c->entries + deferred)) ++bits;
-        SKM_TRY(census_grow(c, bits));               // (leaves ctl[CENSUS_CTL_DEFERRED] at 0)
-        launch_census_replay(c->table(), c->deferred.p, deferred, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(ctl, c->ctl.p, 3 * 8, hipMemcpyDeviceToHost));
-        c->entries = (int64_t)ctl[CENSUS_CTL_ENTRIES];
-        if (ctl[CENSUS_CTL_DEFERRED]) {
-            snprintf(text, sizeof(text), "%llu barcodes found no slot in a table grown for them", ctl[CENSUS_CTL_DEFERRED]);
-            return census_fail(c, SKM_ERR_STATE, text);
-        }
-    }
-    drain.dismiss();                          // (the copies home have waited for the kernels)
-    c->sentinel = (int64_t)ctl[CENSUS_CTL_SENTINEL];
-    c->counted += (int64_t)ctl[CENSUS_CTL_COUNTED];
-    for (int k = 0; k < 3; ++k) stats[k] += (int64_t)ctl[CENSUS_CTL_COUNTED + k];
-    return SKM_OK;
-}
-
-extern "C" int skm_barcode_census_size(skm_barcode_census *c, int64_t *n_distinct, int64_t *n_counted)
-{
-    if (!c || !n_distinct || !n_counted) return fail(SKM_ERR_ARG, "bad argument");
-    std::lock_guard<std::mutex> hold(c->mu);
-    if (c->failed) return fail(SKM_ERR_STATE, "the census has failed: %s", c->failed_msg.c_str());
-    *n_distinct = c->entries + (c->sentinel ? 1 : 0);
-    *n_counted = c->counted;
-    return SKM_OK;
-}
-
-extern "C" int skm_barcode_census_ranked(skm_barcode_census *c, int64_t cap, uint64_t *keys, int64_t *counts)
-{
-    if (!c || cap < 0 || (cap && (!keys || !counts))) return fail(SKM_ERR_ARG, "bad argument");
-    std::lock_guard<std::mutex> hold(c->mu);
-    if (c->failed) return fail(SKM_ERR_STATE, "the census has failed: %s", c->failed_msg.c_str());
-    SKM_TRY(set_device(c->device));
-    SKM_TRY(census_rank(c));
-    const int64_t n = std::min(cap, c->n_ranked);
-    if (n) {
-        HIP_TRY(hipMemcpy(keys, c->ranked_keys.p, n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(counts, c->ranked_counts.p, n * 8, hipMemcpyDeviceToHost));
-    }
-    return SKM_OK;
-}
-
-extern "C" int skm_barcode_census_pick(skm_barcode_census *c, int64_t expect_cells, int drop_neighbours, int64_t cap,
-                                       uint64_t *keys, int64_t *counts, int64_t info[6])
-{
-    if (!c || !info || cap < 0 || (cap && (!keys || !counts))) return fail(SKM_ERR_ARG, "bad argument");
-    if (expect_cells < 1) return fail(SKM_ERR_ARG, "%lld expected cells: 1 at least", (long long)expect_cells);
-    std::lock_guard<std::mutex> hold(c->mu);
-    if (c->failed) return fail(SKM_ERR_STATE, "the census has failed: %s", c->failed_msg.c_str());
-    SKM_TRY(set_device(c->device));
-    SKM_TRY(census_rank(c));
-    const int64_t D = c->n_ranked;
-    if (D == 0) return fail(SKM_ERR_STATE, "no readable barcode");
-    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });
-    const int64_t rank = std::min(expect_cells / 100 + (expect_cells % 100 ? 1 : 0), D);
-    unsigned long long m = 0, found[2] = {0, 0};
-    HIP_TRY(hipMemcpy(&m, c->ranked_counts.p + (rank - 1), 8, hipMemcpyDeviceToHost));
-    const unsigned long long threshold = std::max<unsigned long long>((m + 9) / 10, 1);
-    HIP_TRY(hipMemsetAsync(c->ctl.p + CENSUS_CTL_OUT + 1, 0, 8, nullptr));
-    launch_census_candidates(c->ranked_counts.p, D, threshold, c->ctl.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(found, c->ctl.p + CENSUS_CTL_OUT + 1, 8, hipMemcpyDeviceToHost));
-    const int64_t n_candidates = (int64_t)found[0];
-    if (n_candidates < rank || n_candidates > D) return fail(SKM_ERR_STATE, "%lld candidates of %lld barcodes", (long long)n_candidates, (long long)D);
-    int64_t n_dropped = 0;
-    const unsigned long long *from_keys = c->ranked_keys.p, *from_counts = c->ranked_counts.p;
-    if (drop_neighbours) {
-        HIP_TRY(hipMemsetAsync(c->ctl.p + CENSUS_CTL_OUT + 2, 0, 8, nullptr));
-        launch_census_pick(c->table(), c->ranked_keys.p, c->ranked_counts.p, n_candidates, threshold, c->word.p, c->perm.p, nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(found + 1, c->ctl.p + CENSUS_CTL_OUT + 2, 8, hipMemcpyDeviceToHost));
-        n_dropped = (int64_t)found[1];
-        if (n_dropped < 0 || n_dropped >= n_candidates) return fail(SKM_ERR_STATE, "%lld of %lld candidates dropped", (long long)n_dropped, (long long)n_candidates);
-        if (n_dropped) {
-            // the stable sort on the one flag bit is the compaction: the candidates that stay come first, in ranked order
-            if (sort_pairs_u32(c->word.p, c->word_sorted.p, c->perm.p, c->perm_sorted.p, n_candidates, 1, nullptr) != 0)
-                return fail(SKM_ERR_HIP, "picking from %lld candidates: %s", (long long)n_candidates, quant_setup_failure());
-            SKM_TRY(c->picked_keys.ensure(n_candidates - n_dropped)); SKM_TRY(c->picked_counts.ensure(n_candidates - n_dropped));
-            launch_census_gather(c->ranked_keys.p, c->ranked_counts.p, c->perm_sorted.p, n_candidates - n_dropped, c->picked_keys.p,
-                                 c->picked_counts.p, nullptr);
-            HIP_TRY(hipGetLastError());
-            from_keys = c->picked_keys.p; from_counts = c->picked_counts.p;
-        }
-    }
-    const int64_t n_picked = n_candidates - n_dropped;
-    info[0] = rank; info[1] = (int64_t)m; info[2] = (int64_t)threshold; info[3] = n_candidates; info[4] = n_dropped; info[5] = n_picked;
-    if (n_picked > cap) return fail(SKM_ERR_STATE, "%lld barcodes picked, room for %lld", (long long)n_picked, (long long)cap);
-    HIP_TRY(hipMemcpy(keys, from_keys, n_picked * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(counts, from_counts, n_picked * 8, hipMemcpyDeviceToHost));
-    drain.dismiss();                          // (the copies home have waited for the kernels)
     return SKM_OK;
 }
 

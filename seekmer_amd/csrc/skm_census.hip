@@ -19,7 +19,7 @@
 // the exception read numbers), slots by the mask, probe walks by the number of slots.
 //
 // (c) ranking: the occupied slots are compacted to (key, count) and ordered by the stable radix sort of
-// skm_quant_setup.hip over a permutation, one pass per 32-bit word (the host drives it: skm_abi.hip).
+// skm_quant_setup.hip over a permutation, one pass per 32-bit word (the host drives it: skm_abi_cells.hip).
 //
 // (d) census_pick_kernel.  One lane per candidate (count >= threshold): its 3 L single substitutions are looked up
 // in the census table; a neighbour that is a candidate too and ranks earlier (a larger count, or an equal count and
