@@ -251,6 +251,18 @@ int skm_mapper_last_batch(skm_mapper *mapper, int32_t *begin, int32_t *end,
                           int32_t *counts, int32_t *entries,
                           int64_t cap_entries, int64_t *n_entries);
 int skm_mapper_keep_spans(skm_mapper *mapper, int enable);
+/* The read records of the LAST batch as the map kernel read them (tests): records first_read ..
+ * first_read + n_reads of its n_units (single-ended) or 2 * n_units (paired: 2u, 2u + 1) records, copied
+ * to out[n_reads][*record_words] u32 words.  A record is W = *words_per_read code words (u64: 32 bases a
+ * word, 2 bits a base, A0 C1 G2 T3 in either case, anything else 0, the first base in the top bits),
+ * then W flag words (u32: bit 31 - i of word w set = base 32 w + i is an upper-case A, C, G or T), then
+ * the read's length, then zeros; codes and flags are zero beyond the read's end.  out may be NULL (the
+ * two sizes only).  SKM_ERR_STATE before the first batch.
+ * skm_pack_stage_reads: how many consecutive reads a workgroup of the packing kernel stages in LDS for
+ * this W; 0 = reads too long for the stage, such launches take the kernel with one lane per word. */
+int skm_mapper_copy_records(skm_mapper *mapper, int64_t first_read, int64_t n_reads, uint32_t *out,
+                            int32_t *record_words, int32_t *words_per_read);
+int skm_pack_stage_reads(int32_t words_per_read, int32_t *reads_per_block);
 /* Strand-specific libraries (kallisto's --fr-stranded / --rf-stranded).  Every target entry of a
  * unit is signed: e >= 0 means mate 1 (or the single read) lies in transcript e's own orientation,
  * e < 0 that it lies antisense to transcript ~e.  SKM_STRAND_FR keeps a unit's entries with

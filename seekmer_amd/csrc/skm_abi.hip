@@ -96,6 +96,8 @@ struct skm_mapper {
     int64_t units_done = 0;
     int64_t first_seen_bound = 0;     // every first_seen in the table is below this
     int64_t last_units = 0, last_ids = 0;
+    int64_t last_reads = 0;           // skm_mapper_copy_records: the records of the last batch ...
+    int last_words = 0, last_record_words = 0;   // ... W and u32 words per record
     int64_t host_classes = 0, host_arena_used = 0;
     // the table's unit totals as the last mapped batch read them back (valid: nothing else -- a merge
     // of a foreign table -- has changed the device counters since): spares skm_quant_infer a
@@ -952,10 +954,14 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
     const int words = (max_len + 31) / 32 + 1;
     m->last_units = n_units;
     m->last_ids = 0;
+    m->last_reads = 0;
     if (n_units == 0) return SKM_OK;
 
     const int record_words = ((3 * words + 1 + 15) / 16) * 16;      // 64-byte records
     SKM_TRY(m->records.ensure((size_t)n_reads * record_words + 16));
+    m->last_reads = n_reads;
+    m->last_words = words;
+    m->last_record_words = record_words;
     if (n_units >= (1LL << 31)) return fail(SKM_ERR_ARG, "more than 2^31 - 1 units in one batch");
     if (m->keep_spans) {
         SKM_TRY(m->unit_begin.ensure(n_units));
@@ -1896,6 +1902,34 @@ extern "C" int skm_mapper_last_batch(skm_mapper *m, int32_t *begin, int32_t *end
     return SKM_OK;
 }
 
+extern "C" int skm_mapper_copy_records(skm_mapper *m, int64_t first_read, int64_t n_reads, uint32_t *out,
+                                       int32_t *record_words, int32_t *words_per_read)
+{
+    if (!m) return fail(SKM_ERR_ARG, "NULL mapper");
+    SKM_TRY(wait_jobs(m, 0, false));           // queued host batches first
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    if (m->last_reads == 0) return fail(SKM_ERR_STATE, "no batch has been mapped since the handle was made or reset");
+    if (first_read < 0 || n_reads < 0 || first_read > m->last_reads || n_reads > m->last_reads - first_read)
+        return fail(SKM_ERR_ARG, "reads %lld .. +%lld of a batch of %lld", (long long)first_read, (long long)n_reads,
+                    (long long)m->last_reads);
+    if (record_words) *record_words = m->last_record_words;
+    if (words_per_read) *words_per_read = m->last_words;
+    if (out && n_reads) {
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipMemcpy(out, m->records.p + first_read * (int64_t)m->last_record_words,
+                          (size_t)n_reads * m->last_record_words * 4, hipMemcpyDeviceToHost));
+    }
+    return SKM_OK;
+}
+
+extern "C" int skm_pack_stage_reads(int32_t words_per_read, int32_t *reads_per_block)
+{
+    if (words_per_read < 1 || !reads_per_block) return fail(SKM_ERR_ARG, "bad argument");
+    *reads_per_block = pack_stage_reads(words_per_read);
+    return SKM_OK;
+}
+
 extern "C" int skm_mapper_keep_spans(skm_mapper *m, int enable)
 {
     if (!m) return fail(SKM_ERR_ARG, "NULL mapper");
@@ -2221,6 +2255,7 @@ extern "C" int skm_mapper_reset(skm_mapper *m)
     HIP_TRY(hipStreamSynchronize(m->stream));         // (readers of the table use streams of their own)
     m->last_units = 0;
     m->last_ids = 0;
+    m->last_reads = 0;
     return SKM_OK;
 }
 

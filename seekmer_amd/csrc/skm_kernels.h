@@ -54,8 +54,11 @@ constexpr int MAP_BLOCKS_PER_CU = 4;
 constexpr int MAP_CONTEXTS = SKM_MAP_CONTEXTS;   // unit contexts per block: 16 words + 7 ring entries each, 4 blocks in 160 KB of LDS
 constexpr int MAP_ARENA_CHUNK = 2048;            // ids a wave takes from the entry arena per atomic
 
+// ASCII reads -> records.  Blocks of pack_stage_reads(words_per_read) consecutive reads go through LDS
+// (pack_reads_staged_kernel); 0 = reads too long for the stage, the launch takes pack_reads_kernel.
 void launch_pack_reads(const uint8_t *bases, const int64_t *offsets, int64_t n_reads,
                        int words_per_read, int record_words, uint32_t *records, hipStream_t stream);
+int pack_stage_reads(int words_per_read);
 // host-packed reads (skm_packed_reads) -> records: `n_reads` reads whose code words lie `stride`
 // u64 words apart go to dst, dst + dst_stride, ... (u32 words); *error = SKM_ERR_ARG when a length
 // exceeds 32 * code_words.  Then the bit planes of the exception reads (indices relative to

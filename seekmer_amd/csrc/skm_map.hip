@@ -135,6 +135,186 @@ pack_reads_kernel(const uint8_t *__restrict__ bases, const int64_t *__restrict__
     }
 }
 
+// ------------------------------------------------------- pack_reads, staged
+// The same records with both sides of the stream coalesced, through the block's LDS.  A block takes
+// `reads_per_block` consecutive reads: their bases are one span of the batch.
+//   phase 1  lane k loads the k-th 16-byte aligned chunk of the span and leaves its 32 bits of codes and
+//            its 16 flags in two bit streams in LDS (first base in the top bits; a stream position is a
+//            byte's distance from the aligned chunk that holds the span's first byte);
+//   phase 2  lane i makes the i-th 16 bytes of the block's records: every one of its four words is a
+//            32-bit window of a stream (two LDS words and a shift), cut to the read's length, and
+//            the lanes of a wave store 1 KiB of consecutive record bytes.
+// Only the chunks that hold the first and the last byte of the LAUNCH can reach outside
+// [offsets[0], offsets[n_reads]); they are loaded byte by byte, the bytes outside as zeros.
+// LDS: [reads_per_block + 1] stream positions of the reads, then the code stream, then the flag stream.
+// Bases and records pass once: both sides carry the nontemporal hint (0.62 -> 0.59 ms per 10 M pairs).
+// Measured beside this geometry, none faster (profiles/pack_staged_ab.log): 64 and 255 reads a block; 128 and
+// 512 lanes a block; 64 lanes for 32 reads, 128 for 64; eight loads a lane.
+constexpr int PACK_STAGE_BYTES = 8192;          // budget of the two streams: 12 bytes per 32 bases
+constexpr int PACK_STAGE_MAX_READS = 128;
+constexpr int PACK_STAGE_MIN_READS = 16;        // longer reads than leave room for these: pack_reads_kernel
+constexpr int PACK_STAGE_LOADS = 4;             // 16-byte loads a lane has in flight
+constexpr int PACK_STAGE_THREADS = 256;
+static_assert(PACK_STAGE_MAX_READS < PACK_STAGE_THREADS, "a lane per read of the block, and one more");
+typedef uint32_t PackVec4 __attribute__((ext_vector_type(4)));
+#ifndef SKM_PACK_NONTEMPORAL
+#define SKM_PACK_NONTEMPORAL 3                  // tuning builds: bit 0 the loads, bit 1 the stores
+#endif
+#if SKM_PACK_NONTEMPORAL & 1
+#define PACK_LOAD(p) __builtin_nontemporal_load(p)
+#else
+#define PACK_LOAD(p) (*(p))
+#endif
+#if SKM_PACK_NONTEMPORAL & 2
+#define PACK_STORE(v, p) __builtin_nontemporal_store(v, p)
+#else
+#define PACK_STORE(v, p) (*(p) = (v))
+#endif
+
+struct PackStage {
+    int reads_per_block;       // 0: the launch takes pack_reads_kernel
+    int code_words;            // u32 words of the code stream (16 bases each) ...
+    int flag_words;            // ... and of the flag stream (32 bases each), slack included
+    uint32_t chunk_magic;      // ceil(2^32 / (record_words / 4)): 16-byte piece of the block -> its record
+    size_t lds_bytes() const { return 4 * (size_t)(reads_per_block + 1 + code_words + flag_words); }
+};
+static PackStage pack_stage(int words_per_read, int record_words)
+{
+    PackStage s{};
+    const int base_words = words_per_read > 1 ? words_per_read - 1 : 1;     // 32 * this bounds a read's length
+    int reads = PACK_STAGE_BYTES / (12 * base_words);
+    if (reads > PACK_STAGE_MAX_READS) reads = PACK_STAGE_MAX_READS;
+#if defined(SKM_PACK_STAGED) && !SKM_PACK_STAGED
+    reads = 0;                                  // tuning build: the A/B partner
+#endif
+    if (reads < PACK_STAGE_MIN_READS) return s;
+    s.reads_per_block = reads;
+    // a span is at most 15 bytes of head + reads * 32 * base_words bases; a window reads one word past its first,
+    // and the window of a pad word starts up to 32 bases past the span's end
+    s.code_words = reads * 2 * base_words + 5;
+    s.flag_words = reads * base_words + 4;
+    s.chunk_magic = 0xffffffffu / (uint32_t)(record_words / 4) + 1u;
+    return s;
+}
+int pack_stage_reads(int words_per_read)
+{
+    return pack_stage(words_per_read, 16).reads_per_block;
+}
+
+// the 32 bits from bit `shift` (0 .. 31) of word `word` on, of a stream of 32-bit words, most significant bit
+// first (`last`: the last word a window may start in -- what lies past a read's end is cut by the caller,
+// wherever it came from)
+__device__ __forceinline__ uint32_t stream_window(const uint32_t *stream, uint32_t word, uint32_t shift, uint32_t last)
+{
+    const uint32_t i = min(word, last);
+    const uint32_t a = stream[i], b = stream[i + 1];
+    return shift ? __builtin_amdgcn_alignbit(a, b, 32u - shift) : a;
+}
+
+__global__ void __launch_bounds__(PACK_STAGE_THREADS)
+pack_reads_staged_kernel(const uint8_t *__restrict__ bases, const int64_t *__restrict__ offsets,
+                         int64_t n_reads, int words_per_read, int record_words, PackStage stage,
+                         uint32_t *__restrict__ records)
+{
+    extern __shared__ uint32_t pack_lds[];
+    int32_t *at = reinterpret_cast<int32_t *>(pack_lds);                  // [reads + 1]
+    uint32_t *codes = pack_lds + stage.reads_per_block + 1;
+    uint32_t *flags = codes + stage.code_words;
+
+    const int64_t r0 = blockIdx.x * (int64_t)stage.reads_per_block;
+    const int reads = n_reads - r0 < stage.reads_per_block ? (int)(n_reads - r0) : stage.reads_per_block;
+    const int64_t first_of_bases = offsets[0], end_of_bases = offsets[n_reads];
+    const int64_t span_begin = offsets[r0], span_end = offsets[r0 + reads];
+    const int head = (int)(reinterpret_cast<uintptr_t>(bases + span_begin) & 15u);
+    const int64_t chunk0 = span_begin - head;                             // offset of the first chunk from `bases`
+    // (a span longer than the caller's bound on the read length allows is cut to what the stage holds)
+    const int64_t span_chunks = span_end > span_begin ? (span_end - chunk0 + 15) >> 4 : 0;
+    const int n_chunks = span_chunks < stage.code_words - 4 ? (int)span_chunks : stage.code_words - 4;
+    // chunks [first_whole, end_whole) lie inside the launch's bases: all but its first and its last, at the most
+    const int64_t whole_from = first_of_bases > chunk0 ? (first_of_bases - chunk0 + 15) >> 4 : 0;
+    const int64_t whole_to = (end_of_bases - chunk0) >> 4;
+    const int first_whole = whole_from < n_chunks ? (int)whole_from : n_chunks;
+    const int end_whole = whole_to < n_chunks ? (whole_to > 0 ? (int)whole_to : 0) : n_chunks;
+
+    // every load of the block is issued before the first is waited for: the reads' places for phase 2, then
+    // PACK_STAGE_LOADS chunks a lane
+    const int64_t my_offset = (int)threadIdx.x <= reads ? offsets[r0 + threadIdx.x] : 0;
+    for (int k0 = threadIdx.x; k0 < n_chunks; k0 += PACK_STAGE_LOADS * PACK_STAGE_THREADS) {
+        PackVec4 v[PACK_STAGE_LOADS];
+        bool whole[PACK_STAGE_LOADS];
+#pragma unroll
+        for (int u = 0; u < PACK_STAGE_LOADS; ++u) {
+            const int k = k0 + PACK_STAGE_THREADS * u;
+            whole[u] = k >= first_whole && k < end_whole;
+            if (whole[u]) v[u] = PACK_LOAD(reinterpret_cast<const PackVec4 *>(bases + chunk0) + k);
+        }
+#pragma unroll
+        for (int u = 0; u < PACK_STAGE_LOADS; ++u) {
+            const int k = k0 + PACK_STAGE_THREADS * u;
+            if (k >= n_chunks) break;
+            uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            if (!whole[u]) {                               // the first or the last chunk of the launch
+                const int64_t pos = chunk0 + 16 * (int64_t)k;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    w[d] = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int64_t p = pos + 4 * d + i;
+                        if (p >= first_of_bases && p < end_of_bases) w[d] |= (uint32_t)bases[p] << (8 * i);
+                    }
+                }
+            }
+            uint32_t bad = 0;
+            uint32_t code = top_bytes(pack_dword_plain(w[0], bad), pack_dword_plain(w[1], bad),
+                                      pack_dword_plain(w[2], bad), pack_dword_plain(w[3], bad));
+            uint32_t flag = 0xffffu;
+            if (bad != 0) {                                // N, lower case, anything else: the full rule
+                uint64_t c = 0;
+                uint32_t m = 0;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) pack_dword(w[d], 4 * d, 16, c, m);
+                code = (uint32_t)(c >> 32);
+                flag = m >> 16;
+            }
+            codes[k] = code;
+            reinterpret_cast<uint16_t *>(flags)[k ^ 1] = (uint16_t)flag;      // (the first of two chunks in the top half)
+        }
+    }
+    if ((int)threadIdx.x <= reads) at[threadIdx.x] = (int32_t)(my_offset - chunk0);
+    __syncthreads();
+
+    const int chunks_per_record = record_words >> 2;
+    const int total = reads * chunks_per_record;
+    const uint32_t last_code = (uint32_t)stage.code_words - 2u, last_flag = (uint32_t)stage.flag_words - 2u;
+    PackVec4 *out = reinterpret_cast<PackVec4 *>(records + r0 * (int64_t)record_words);
+    for (int i = threadIdx.x; i < total; i += PACK_STAGE_THREADS) {
+        const int r = (int)__umulhi((uint32_t)i, stage.chunk_magic);
+        const int first_word = 4 * (i - r * chunks_per_record);
+        const int begin = at[r];
+        const int len = at[r + 1] - begin;
+        // the read's first bit in either stream: every window of the read starts a whole number of words behind it
+        const uint32_t code_at = (uint32_t)begin >> 4, code_shift = 2u * ((uint32_t)begin & 15u);
+        const uint32_t flag_at = (uint32_t)begin >> 5, flag_shift = (uint32_t)begin & 31u;
+        uint32_t v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = first_word + t;
+            // word j of the record: 16-base half j ^ 1 of the codes (a u64 code word has its low half, bases 16-31,
+            // first), 32-base word j - 2 W of the flags, the length, or padding
+            const bool is_code = j < 2 * words_per_read;
+            const int k = is_code ? j ^ 1 : j - 2 * words_per_read;
+            const int bits = min(max(is_code ? 2 * len - 32 * k : j < 3 * words_per_read ? len - 32 * k : 0, 0), 32);
+            v[t] = stream_window(is_code ? codes : flags, (is_code ? code_at : flag_at) + (uint32_t)k,
+                                 is_code ? code_shift : flag_shift, is_code ? last_code : last_flag);
+            v[t] = bits >= 32 ? v[t] : v[t] & ~(0xffffffffu >> bits);      // (zero beyond the read's end)
+            if (j == 3 * words_per_read) v[t] = (uint32_t)len;
+        }
+        const PackVec4 piece = {v[0], v[1], v[2], v[3]};
+        PACK_STORE(piece, out + i);
+    }
+}
+
 // ------------------------------------------------------------- unpack_reads
 // Reads that arrive already packed by the host (skm_packed_reads: code words only): one lane per
 // (read, record word) writes the 64-byte record the map kernel reads -- codes as they came, the
@@ -1782,6 +1962,13 @@ void launch_pack_reads(const uint8_t *bases, const int64_t *offsets, int64_t n_r
 {
     const int64_t total = n_reads * (int64_t)words_per_read;
     if (total == 0) return;
+    const PackStage stage = pack_stage(words_per_read, record_words);
+    const int64_t staged_blocks = stage.reads_per_block ? (n_reads + stage.reads_per_block - 1) / stage.reads_per_block : 0;
+    if (stage.reads_per_block && staged_blocks <= 0x7fffffffLL) {
+        hipLaunchKernelGGL(pack_reads_staged_kernel, dim3((unsigned)staged_blocks), dim3(PACK_STAGE_THREADS), stage.lds_bytes(), stream,
+                           bases, offsets, n_reads, words_per_read, record_words, stage, records);
+        return;
+    }
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(pack_reads_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
