@@ -131,6 +131,8 @@ template <class F> ScopeGuard<F> on_exit(F f) { return ScopeGuard<F>(f); }
 // synchronises the stream on an early return -- destroyed in reverse order, the guard runs first)
 
 int set_device(int device);
+// SKM_ERR_NO_DEVICE without a GPU, SKM_ERR_ARG for a `device` outside [0, skm_device_count)
+int check_device(int device);
 
 }  // namespace abi
 }  // namespace skm

@@ -95,9 +95,7 @@ struct skm_barcodes {
 
 extern "C" int skm_barcodes_create(int device, const char *barcodes, int64_t n, int length, skm_barcodes **out)
 {
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(check_device(device));
     if (!out || !barcodes) return fail(SKM_ERR_ARG, "bad argument");
     if (length < 1 || length > 32) return fail(SKM_ERR_ARG, "barcodes of %d bases: 1 to 32 are possible", length);
     if (n < 1 || n > (1LL << 28)) return fail(SKM_ERR_ARG, "a whitelist of %lld barcodes", (long long)n);
@@ -172,9 +170,7 @@ extern "C" int skm_barcodes_assign(skm_barcodes *b, const skm_packed_reads *read
 extern "C" int skm_umi_windows(int device, const skm_packed_reads *reads, int start, int length, int32_t *cell, uint32_t *umi,
                                int64_t *n_unreadable)
 {
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(check_device(device));
     if (!reads || !n_unreadable) return fail(SKM_ERR_ARG, "bad argument");
     if (start < 0 || start > (1 << 24)) return fail(SKM_ERR_ARG, "a UMI that starts at base %d", start);
     if (length < 1 || length > 16) return fail(SKM_ERR_ARG, "UMIs of %d bases: 1 to 16 are possible", length);
@@ -209,9 +205,7 @@ extern "C" int skm_umi_windows(int device, const skm_packed_reads *reads, int st
 extern "C" int skm_units_group(int device, const int32_t *sample, int64_t n, int64_t n_samples, int32_t *order,
                                int64_t *offsets)
 {
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(check_device(device));
     if (n < 0 || n >= (1LL << 31) || n_samples < 1 || n_samples > (1LL << 24) || !offsets || (n && (!sample || !order)))
         return fail(SKM_ERR_ARG, "bad argument");
     SKM_TRY(set_device(device));
@@ -361,9 +355,7 @@ int census_rank(skm_barcode_census *c)
 
 extern "C" int skm_barcode_census_create(int device, int length, skm_barcode_census **out)
 {
-    int n_dev = 0;
-    SKM_TRY(skm_device_count(&n_dev));
-    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    SKM_TRY(check_device(device));
     if (!out) return fail(SKM_ERR_ARG, "bad argument");
     if (length < 1 || length > 32) return fail(SKM_ERR_ARG, "barcodes of %d bases: 1 to 32 are possible", length);
     uint32_t bits = 10;

@@ -47,6 +47,14 @@ int set_device(int device)
     return SKM_OK;
 }
 
+int check_device(int device)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (device < 0 || device >= n_dev) return fail(SKM_ERR_ARG, "device %d out of range", device);
+    return SKM_OK;
+}
+
 }  // namespace abi
 }  // namespace skm
 

@@ -1,0 +1,182 @@
+// The index and mapper handles of the C ABI glue, for the units that look into them (skm_abi.hip, which owns
+// both, and skm_abi_quant.hip), with the words of the mapper's counter blocks and the two calls of the mapper that
+// other families make.  The handles are the C ABI's global types and their members are types of `skm` and
+// `skm::abi`, so this header names both namespaces as the units that include it do.
+#pragma once
+#include "skm_abi.h"
+#include "skm_bias.h"
+
+#include <atomic>
+#include <condition_variable>
+#include <cstdint>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+using namespace skm;
+using namespace skm::abi;
+
+struct skm_index {
+    ~skm_index() { (void)hipSetDevice(device); }     // (then the members free the device copy)
+    int device = 0;
+    DevIndex d{};
+    DevMem kmers, contigs, seq2, buckets, edge_kmers, signatures;
+    int64_t n_slots = 0, bytes = 0;
+    int64_t layout[8] = {0};          // skm_index_layout
+    int cu_count = 256;
+    // the caller's handle + one per mapper that maps against it: skm_index_destroy only gives up the
+    // caller's, the device copy goes with the last one (garbage collectors finalise a mapper and
+    // its index in any order; a mapper destroyed after its index used to read freed memory here)
+    std::atomic<int> holders{1};
+    // ---- the transcript pool of the sequence-bias correction (skm_bias.h), built by
+    // skm_index_build_transcripts from the host rows below, which are dropped once it stands (all under pool_mu)
+    std::mutex pool_mu;
+    std::vector<PoolContig> pool_contigs;
+    std::vector<Coord> pool_targets;
+    bool pool_built = false;
+    TxPool pool{};
+    DevMem pool_codes, pool_known, pool_tx_word, pool_tx_len, pool_tx_windows;
+    std::vector<int64_t> pool_tx_base;        // [n_tx + 1] first base of every transcript in a download
+    std::vector<int32_t> pool_windows;        // [n_tx] n_t, host copy
+};
+
+struct skm_mapper {
+    explicit skm_mapper(skm_index *index) : ix(index) { index->holders.fetch_add(1); }
+    ~skm_mapper();
+    Own<skm_index *, skm_index_destroy> ix;   // a hold on the index (declared first: given up last)
+    PoolStream stream;
+    Event ev[4];
+    std::mutex mu;
+    // class table
+    ClassTable t{};
+    DBuf<ClassSlot> slots;
+    DBuf<int32_t> arena;
+    DBuf<int64_t> class_list;
+    DBuf<unsigned long long> counters;   // [0]=arena_cursor [1]=n_classes [2]=n_unaligned [3]=n_units [8..2007]=fld
+    DBuf<int> error;
+    // batch buffers
+    DBuf<uint8_t> bases;
+    DBuf<int64_t> offsets;
+    DBuf<uint32_t> records;
+    DBuf<int32_t> workspace;
+    DBuf<int32_t> unit_begin, unit_end, rec_unit;
+    DBuf<Coord> unit_anchor;
+    DBuf<int64_t> unit_slot;
+    DBuf<unsigned long long> rec_tuple;
+    HostPinned pinned;                      // host-pinned readback words
+    DBuf<uint64_t> rec_key;
+    bool keep_spans = false, last_spans = false;   // spans wanted / written by the last batch
+    int strand = SKM_STRAND_NONE;                  // skm_mapper_set_strand (under mu)
+    bool bias = false;                             // skm_mapper_set_bias (under mu): count the aligned units' first hexamers
+    DBuf<unsigned long long> bias_observed;        // [4096], zeroed where the histogram is
+    // skm_mapper_set_length_weights (under mu): p[2000] of a fragment-length model; while it is in use the
+    // quantification calls take the effective lengths from it and not from the histogram
+    DBuf<double> length_weights;
+    bool use_length_weights = false;
+    DBuf<int32_t> unit_entries;
+    DBuf<unsigned long long> batch_ctl;  // [0]=ids_cursor [8..2007]=fld [2048..2063]=stats
+    int grid_blocks = 0;
+    // (both under mu)
+    int64_t expected_units = 0;       // skm_mapper_expect_units: the sample's size, announced before its reads
+    bool packed_sized = false;        // the batch buffers hold a run of PACKED_MAX_UNITS already
+    int64_t units_done = 0;
+    int64_t first_seen_bound = 0;     // every first_seen in the table is below this
+    int64_t last_units = 0, last_ids = 0;
+    int64_t last_reads = 0;           // skm_mapper_copy_records: the records of the last batch ...
+    int last_words = 0, last_record_words = 0;   // ... W and u32 words per record
+    int64_t host_classes = 0, host_arena_used = 0;
+    // the table's unit totals as the last mapped batch read them back (valid: nothing else -- a merge
+    // of a foreign table -- has changed the device counters since): spares skm_quant_infer a
+    // synchronous read of two words
+    bool host_totals_valid = false;
+    unsigned long long host_units = 0, host_unaligned = 0;
+    int want_stats = 0;               // 0 production, 1 counting build, 2 census build
+    double t_pack_ns = 0, t_map_ns = 0, t_class_ns = 0, batches = 0;
+    double t_em_ns = 0, em_iters = 0;          // skm_quant_infer calls on this mapper
+    bool test_class_slots = false;             // SKM_TEST_CLASS_SLOTS: table_reserve[_for_sample] leave the slot count alone
+    int64_t deferred_grows = 0;                // table_grow calls with units in flight (after a pass that deferred units)
+    int test_map_blocks = 0;                   // SKM_TEST_MAP_BLOCKS: a cap on the map kernel's grid (0: none)
+    int64_t map_relaunches = 0;                // map kernel launches repeated because the entry arena overflowed
+    unsigned long long stats_total[48] = {0};
+    // ---- host batches: staging lanes + one worker (skm_mapper_map_batch[_async])
+    // A host batch is copied to HBM on a lane's own stream by the thread that submits it (the
+    // copy of batch i+1 runs under the kernels of batch i) and then queued; the worker maps
+    // the queued batches in submission order on the mapper's stream, holding `mu` only for its
+    // batch.  Every call that reads or changes the table first waits for the queue to drain.
+    struct Lane {
+        DBuf<uint8_t> bases;
+        DBuf<int64_t> offsets;
+        Stream stream;
+        bool busy = false;
+    };
+    static constexpr int N_LANES = 3;
+    Lane lanes[N_LANES];
+    struct Job { int lane; int64_t n_units; int paired; int64_t offset_base; int64_t first_unit; uint64_t ticket; };
+    std::mutex q_mu;
+    std::condition_variable q_cv;             // job queued / stop
+    std::condition_variable done_cv;          // job finished, lane released
+    std::deque<Job> jobs;
+    std::thread worker;
+    bool worker_started = false, stop = false;
+    uint64_t next_ticket = 1, done_ticket = 0;
+    int job_error = SKM_OK;                   // first failure of a queued batch (sticky until reported)
+    uint64_t job_error_ticket = 0;
+    std::string job_error_msg;
+    DBuf<unsigned long long> scan_out;        // device-side max read length / monotonicity of a batch
+    // ---- packed pieces (skm_mapper_push_packed): reads that arrive as 2-bit code words wait in HBM,
+    // one ascending list of pieces per stream, until the worker maps a run of units that every
+    // stream covers.  All of it under q_mu.
+    struct Piece {
+        int64_t first = 0, n = 0;             // units [first, first + n) of the stream (what is left of the piece)
+        int64_t origin = 0;                   // first_read of the piece as pushed: the arrays start there
+        int cw = 1;
+        int64_t uniform_len = -1;
+        std::shared_ptr<char> block;          // one HBM allocation: codes | lengths | exception reads | masks
+        uint64_t *codes = nullptr;            // [n as pushed][cw]
+        uint32_t *lengths = nullptr;          // or NULL (uniform_len)
+        uint32_t *exc_reads_dev = nullptr, *exc_masks = nullptr;
+        std::vector<uint32_t> exc_reads;      // host copy (indices relative to origin), for cutting runs
+        bool in_job = false;
+    };
+    std::deque<Piece> pending[2];
+    Stream packed_stream;
+    int packed_paired = -1;                   // -1 until the first piece
+    int packed_flush = 0;                     // callers waiting for everything mappable to be mapped
+    int packed_waiters = 0;                   // pushers held back by the byte limit: whatever run there is gets mapped
+    int64_t packed_max_pending = 8LL << 30;   // bytes of HBM that pieces may hold before a pusher waits
+    bool packed_busy = false;
+    int64_t packed_dropped = 0;               // reads that never got a mate
+    // HBM held by pieces that wait to be mapped; a pusher that is ahead of the GPU by more than
+    // PACKED_MAX_PENDING bytes waits (only while the worker has something to map: a caller that
+    // pushes one stream long before the other is never blocked on itself)
+    std::shared_ptr<std::atomic<int64_t>> packed_bytes = std::make_shared<std::atomic<int64_t>>(0);
+    int vote[8] = {1, 1, 1, 1, 1, 1, 1, 0};   // quorum per action (start, lookup, merge, left, right, emit, scan)
+    // skm_mapper_device_table: the classes in registry order, as class_compact leaves them
+    DBuf<int64_t> view_start, view_len;
+    DBuf<double> view_count;
+    DBuf<unsigned long long> view_first_seen;
+};
+
+namespace skm {
+namespace abi __attribute__((visibility("hidden"))) {
+
+// words of skm_mapper::counters (CTR_*) and skm_mapper::batch_ctl (BC_*)
+constexpr int CTR_ARENA = 0, CTR_CLASSES = 1, CTR_UNALIGNED = 2, CTR_UNITS = 3, CTR_LISTED = 4,
+              CTR_DEFERRED = 5, CTR_COMMITTED = 6, CTR_FLD = 8;
+constexpr int CTR_WORDS = 8 + MAX_FRAGMENT_LENGTH;
+constexpr int BC_IDS = 0, BC_FLD = 8, BC_STATS = 2048, BC_WORDS = 2096;
+constexpr int64_t PACKED_MIN_UNITS = 1 << 15;      // smaller runs wait for more (or for a flush)
+constexpr int64_t PACKED_MAX_UNITS = 1 << 21;      // one launch
+
+// (both defined in skm_abi.hip)
+// wait until every queued batch up to `ticket` (0: all of them) has been mapped; reports (and, with `consume`,
+// forgets) the first failure among them
+int wait_jobs(skm_mapper *m, uint64_t ticket, bool consume);
+// the weights of a fragment-length model: every one finite and >= 0
+bool length_weights_valid(const double *p, int64_t count);
+
+}  // namespace abi
+}  // namespace skm

@@ -1,6 +1,6 @@
 // The EM of /root/reference/seekmer/infer.py:133-168 for EM_BATCH problems at once that share
 // their class structure and differ only in the class counts (and with them the total) and the
-// abundance vector.  Three callers have problems of that shape (skm_abi.hip: em_group_run):
+// abundance vector.  Three callers have problems of that shape (skm_abi_quant.hip: em_group_run):
 //   - the bootstrap replicates of `-b N` (infer.py:79-82, 108-111 -- every replicate resamples the
 //     counts of the SAME class table and starts from the same estimate; all totals are equal),
 //   - K count vectors of the caller's on one class table (skm_quant_em_many),

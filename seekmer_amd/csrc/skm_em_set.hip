@@ -1,6 +1,6 @@
 // The EM of /root/reference/seekmer/infer.py:133-168 for many class tables over the same transcripts
 // in shared launches: the first-round quantification of the samples of a sample set, or of K tables of
-// the caller's (skm_abi.hip: set_quant_group).
+// the caller's (skm_abi_quant.hip: set_quant_group).
 //
 // S tables over T transcripts are ONE block-diagonal problem: transcript t of table s is stacked
 // transcript s * T + t, the classes are concatenated with their ids rebased by s * T, and no class

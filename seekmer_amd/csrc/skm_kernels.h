@@ -269,7 +269,7 @@ void launch_em_result(const unsigned long long *ctl, const double *x0, const dou
 // transcript id) are packed into TILES of at most EM_TILE_PAIRS pairs, EM_TILE_CLASSES classes and
 // EM_TILE_TX transcripts; one workgroup keeps a tile's two views, `inner` and both abundance vectors in
 // LDS and runs a whole chunk of steps with workgroup barriers only.
-// (the four values are sweep aids, scripts/build_variant.sh with skm_abi.hip, skm_em.hip and
+// (the four values are sweep aids, scripts/build_variant.sh with skm_abi_quant.hip, skm_em.hip and
 // skm_quant_setup.hip: results do not depend on them)
 #ifndef SKM_EM_TILE_PAIRS
 #define SKM_EM_TILE_PAIRS 2048
@@ -320,7 +320,7 @@ struct EmTiles {
 enum { EM_JUDGE_MAX = 0, EM_JUDGE_FLAGS = 16, EM_JUDGE_ARRIVED = 32, EM_JUDGE_WORDS = 48 };
 static_assert(EM_CHUNK_MAX <= 16, "a step's word of each kind");
 constexpr int EM_CTL_WORDS = 16;         // EmProblem::ctl; a handle keeps the judge's words right behind them
-// (tuning aid, scripts/build_variant.sh with skm_abi.hip and skm_em.hip: 1 keeps the one-block launch that
+// (tuning aid, scripts/build_variant.sh with skm_abi_quant.hip and skm_em.hip: 1 keeps the one-block launch that
 // judged a chunk of tiles alone before the chunk kernel did)
 #ifndef SKM_EM_JUDGE_LAUNCH
 #define SKM_EM_JUDGE_LAUNCH 0
