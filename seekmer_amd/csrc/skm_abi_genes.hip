@@ -1,0 +1,201 @@
+// C ABI of libseekmer_hip.so: gene-level tables -- sums of transcript values by gene, and the unique counts of a
+// class table given on the host, held by a mapper or held by a sample set.
+#include "skm_abi_samples.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <mutex>
+#include <vector>
+
+using namespace skm;
+using namespace skm::abi;
+
+// ------------------------------------------------------------------ gene-level tables (skm_genes.hip)
+namespace {
+
+// SKM_GENE_GROUP (tests): rows of values per group of skm_gene_sums, samples per range of the gene counts
+int64_t gene_group(int64_t fitting, int64_t n)
+{
+    int64_t group = fitting;
+    if (const char *v = getenv("SKM_GENE_GROUP"))
+        if (atoll(v) > 0) group = std::min<int64_t>(group, atoll(v));
+    return std::max<int64_t>(1, std::min(group, n));
+}
+
+int gene_map_check(int64_t n_tx, int64_t n_genes, const int32_t *tx_gene)
+{
+    if (n_tx < 0 || n_genes < 0 || n_tx > INT32_MAX || n_genes > INT32_MAX || (n_tx && !tx_gene))
+        return fail(SKM_ERR_ARG, "bad gene map");
+    for (int64_t t = 0; t < n_tx; ++t)
+        if (tx_gene[t] < -1 || tx_gene[t] >= n_genes)
+            return fail(SKM_ERR_ARG, "transcript %lld has gene %d of %lld", (long long)t, tx_gene[t], (long long)n_genes);
+    return SKM_OK;
+}
+
+// unique[n_samples][n_genes], other[n_samples][2] of a class table in HBM (stream drained on return).  Device rows
+// exist for a range of samples at a time: 1 GiB of them at most.
+int gene_counts_device(const GeneClasses &t, int64_t n_samples, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                       int64_t *unique, int64_t *other, hipStream_t stream)
+{
+    std::fill(unique, unique + n_samples * n_genes, (int64_t)0);
+    std::fill(other, other + n_samples * 2, (int64_t)0);
+    if (t.n_classes == 0 || n_samples == 0) return SKM_OK;
+    if (n_tx == 0) return fail(SKM_ERR_ARG, "classes over no transcripts");
+    const int64_t range = gene_group((int64_t)(1LL << 27) / std::max<int64_t>(n_genes, 1), n_samples);
+    DBuf<int32_t> d_gene; DBuf<unsigned long long> d_rows; DBuf<int> d_error;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    const size_t row_words = (size_t)range * (size_t)(n_genes + 2);             // unique rows | other rows
+    SKM_TRY(d_gene.ensure(n_tx)); SKM_TRY(d_rows.ensure(row_words)); SKM_TRY(d_error.ensure(1));
+    HIP_TRY(hipMemcpyAsync(d_gene.p, tx_gene, n_tx * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_error.p, 0, sizeof(int), stream));
+    for (int64_t first = 0; first < n_samples; first += range) {
+        const int64_t here = std::min(range, n_samples - first);
+        unsigned long long *d_other = d_rows.p + here * n_genes;
+        HIP_TRY(hipMemsetAsync(d_rows.p, 0, (size_t)here * (size_t)(n_genes + 2) * 8, stream));
+        launch_gene_unique(t, d_gene.p, n_tx, n_genes, first, first + here, d_rows.p, d_other, d_error.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (n_genes)
+            HIP_TRY(hipMemcpyAsync(unique + first * n_genes, d_rows.p, (size_t)(here * n_genes) * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(other + first * 2, d_other, (size_t)here * 16, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    int error = 0;
+    HIP_TRY(hipMemcpyAsync(&error, d_error.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.dismiss();
+    if (error) return fail(SKM_ERR_ARG, "a class names a transcript not below n_tx = %lld", (long long)n_tx);
+    return SKM_OK;
+}
+
+}  // namespace
+
+// Rows in groups, so that the rows staged in HBM stay within 256 MB; the gene list goes up once.
+extern "C" int skm_gene_sums(int device, int64_t n_rows, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                             const double *values, double *out)
+{
+    SKM_TRY(check_device(device));
+    if (n_rows < 0 || (n_rows && ((n_tx && !values) || (n_genes && !out)))) return fail(SKM_ERR_ARG, "bad argument");
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    if (n_rows == 0 || n_genes == 0) return SKM_OK;
+    // the transcripts by gene, ascending inside a gene: a stable counting sort
+    std::vector<int64_t> gene_off(n_genes + 1, 0);
+    for (int64_t t = 0; t < n_tx; ++t)
+        if (tx_gene[t] >= 0) gene_off[tx_gene[t] + 1]++;
+    for (int64_t g = 0; g < n_genes; ++g) gene_off[g + 1] += gene_off[g];
+    std::vector<int32_t> gene_tx((size_t)std::max<int64_t>(gene_off[n_genes], 1));
+    {
+        std::vector<int64_t> next(gene_off.begin(), gene_off.end() - 1);
+        for (int64_t t = 0; t < n_tx; ++t)
+            if (tx_gene[t] >= 0) gene_tx[next[tx_gene[t]]++] = (int32_t)t;
+    }
+    SKM_TRY(set_device(device));
+    const int64_t group = gene_group(std::min<int64_t>((int64_t)(1LL << 25) / std::max<int64_t>(std::max(n_tx, n_genes), 1), 65535), n_rows);
+    DBuf<int64_t> d_off; DBuf<int32_t> d_tx; DBuf<double> d_values, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_off.ensure(n_genes + 1)); SKM_TRY(d_tx.ensure(gene_tx.size()));
+    SKM_TRY(d_values.ensure((size_t)std::max<int64_t>(group * n_tx, 1))); SKM_TRY(d_out.ensure((size_t)(group * n_genes)));
+    HIP_TRY(hipMemcpy(d_off.p, gene_off.data(), (n_genes + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tx.p, gene_tx.data(), gene_tx.size() * 4, hipMemcpyHostToDevice));
+    for (int64_t first = 0; first < n_rows; first += group) {
+        const int64_t here = std::min(group, n_rows - first);
+        if (n_tx) HIP_TRY(hipMemcpy(d_values.p, values + first * n_tx, (size_t)(here * n_tx) * 8, hipMemcpyHostToDevice));
+        launch_gene_sums(d_values.p, here, n_tx, d_off.p, d_tx.p, n_genes, d_out.p, nullptr);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out + first * n_genes, d_out.p, (size_t)(here * n_genes) * 8, hipMemcpyDeviceToHost));
+    }
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    return SKM_OK;
+}
+
+extern "C" int skm_gene_unique_counts(int device, int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets,
+                                      const int64_t *class_counts, const int32_t *class_sample, int64_t n_samples,
+                                      int64_t n_tx, int64_t n_genes, const int32_t *tx_gene, int64_t *unique, int64_t *other)
+{
+    SKM_TRY(check_device(device));
+    if (n_classes < 0 || n_samples < 0 || (n_samples && (!other || (n_genes > 0 && !unique))))
+        return fail(SKM_ERR_ARG, "bad argument");
+    if (n_classes && (!class_offsets || !class_counts || n_samples < 1)) return fail(SKM_ERR_ARG, "NULL class arrays");
+    if (n_classes && !class_sample && n_samples > 1) return fail(SKM_ERR_ARG, "%lld samples without class_sample", (long long)n_samples);
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    const int64_t M = n_classes ? class_offsets[n_classes] : 0;
+    for (int64_t c = 0; c < n_classes; ++c) {
+        if (class_offsets[c] < 0 || class_offsets[c + 1] < class_offsets[c] || class_offsets[c + 1] - class_offsets[c] > INT32_MAX)
+            return fail(SKM_ERR_ARG, "class_offsets are not those of a table");
+        if (class_counts[c] < 0) return fail(SKM_ERR_ARG, "class %lld has a negative count", (long long)c);
+        if (class_sample && (class_sample[c] < 0 || class_sample[c] >= n_samples))
+            return fail(SKM_ERR_ARG, "class %lld belongs to sample %d of %lld", (long long)c, class_sample[c], (long long)n_samples);
+    }
+    if (M && !class_targets) return fail(SKM_ERR_ARG, "NULL class arrays");
+    for (int64_t k = 0; k < M; ++k)
+        if (class_targets[k] < 0 || class_targets[k] >= n_tx)
+            return fail(SKM_ERR_ARG, "a class names transcript %d of %lld", class_targets[k], (long long)n_tx);
+    SKM_TRY(set_device(device));
+    DBuf<int64_t> d_off, d_cnt; DBuf<int32_t> d_ids, d_sample;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    GeneClasses t{};
+    t.n_classes = n_classes;
+    if (n_classes) {
+        SKM_TRY(d_off.ensure(n_classes + 1)); SKM_TRY(d_cnt.ensure(n_classes)); SKM_TRY(d_ids.ensure((size_t)std::max<int64_t>(M, 1)));
+        HIP_TRY(hipMemcpy(d_off.p, class_offsets, (n_classes + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_cnt.p, class_counts, n_classes * 8, hipMemcpyHostToDevice));
+        if (M) HIP_TRY(hipMemcpy(d_ids.p, class_targets, M * 4, hipMemcpyHostToDevice));
+        if (class_sample) {
+            SKM_TRY(d_sample.ensure(n_classes));
+            HIP_TRY(hipMemcpy(d_sample.p, class_sample, n_classes * 4, hipMemcpyHostToDevice));
+            t.sample = d_sample.p;
+        }
+        t.start = d_off.p; t.count_i64 = d_cnt.p; t.ids = d_ids.p;
+    }
+    SKM_TRY(gene_counts_device(t, n_samples, n_tx, n_genes, tx_gene, unique, other, nullptr));
+    drain.dismiss();
+    return SKM_OK;
+}
+
+extern "C" int skm_mapper_gene_counts(skm_mapper *m, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                      int64_t *unique, int64_t other[2])
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!m || !other || (n_genes > 0 && !unique)) return fail(SKM_ERR_ARG, "NULL argument");
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    SKM_TRY(wait_jobs(m, 0, false));           // queued host batches first
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    const int64_t C = m->host_classes;
+    DBuf<int64_t> d_off, d_len; DBuf<double> d_cnt; DBuf<unsigned long long> d_fs;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(m->stream); });   // (an early return: before they go)
+    GeneClasses t{};
+    t.n_classes = C;
+    if (C) {
+        SKM_TRY(d_off.ensure(C)); SKM_TRY(d_len.ensure(C)); SKM_TRY(d_cnt.ensure(C)); SKM_TRY(d_fs.ensure(C));
+        launch_class_compact(m->t, C, d_off.p, d_len.p, d_cnt.p, d_fs.p, m->stream);
+        HIP_TRY(hipGetLastError());
+        t.start = d_off.p; t.len = d_len.p; t.count_f64 = d_cnt.p; t.ids = m->arena.p;
+    }
+    SKM_TRY(gene_counts_device(t, 1, n_tx, n_genes, tx_gene, unique, other, m->stream));
+    drain.dismiss();
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_gene_counts(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                          int64_t cap_samples, int64_t *unique, int64_t *other)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!s || cap_samples < 0 || (cap_samples && (!other || (n_genes > 0 && !unique)))) return fail(SKM_ERR_ARG, "bad argument");
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    skm_sample_set::View &v = s->view;
+    const int64_t n_samples = (int64_t)v.units.size();
+    if (cap_samples < n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)n_samples);
+    if (n_samples == 0) return SKM_OK;
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    GeneClasses t{};
+    t.n_classes = (int64_t)v.start.size();
+    if (t.n_classes) { t.start = v.d_start.p; t.len = v.d_len.p; t.count_f64 = v.d_count.p; t.sample = v.d_sample.p; t.ids = m->arena.p; }
+    return gene_counts_device(t, n_samples, n_tx, n_genes, tx_gene, unique, other, m->stream);
+}

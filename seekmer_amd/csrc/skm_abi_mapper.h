@@ -1,7 +1,8 @@
-// The index and mapper handles of the C ABI glue, for the units that look into them (skm_abi.hip, which owns
-// both, and skm_abi_quant.hip), with the words of the mapper's counter blocks and the two calls of the mapper that
-// other families make.  The handles are the C ABI's global types and their members are types of `skm` and
-// `skm::abi`, so this header names both namespaces as the units that include it do.
+// The index and mapper handles of the C ABI glue, for the units that look into them (skm_abi_index.hip and
+// skm_abi.hip, which own them, skm_abi_samples.hip, skm_abi_genes.hip and skm_abi_quant.hip), with the words of the
+// mapper's counter blocks and the calls of the mapper that other families make.  The handles are the C ABI's global
+// types and their members are types of `skm` and `skm::abi`, so this header names both namespaces as the units that
+// include it do.
 #pragma once
 #include "skm_abi.h"
 #include "skm_bias.h"
@@ -10,6 +11,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -171,12 +173,54 @@ constexpr int BC_IDS = 0, BC_FLD = 8, BC_STATS = 2048, BC_WORDS = 2096;
 constexpr int64_t PACKED_MIN_UNITS = 1 << 15;      // smaller runs wait for more (or for a flush)
 constexpr int64_t PACKED_MAX_UNITS = 1 << 21;      // one launch
 
-// (both defined in skm_abi.hip)
+// (all defined in skm_abi.hip)
 // wait until every queued batch up to `ticket` (0: all of them) has been mapped; reports (and, with `consume`,
 // forgets) the first failure among them
 int wait_jobs(skm_mapper *m, uint64_t ticket, bool consume);
 // the weights of a fragment-length model: every one finite and >= 0
 bool length_weights_valid(const double *p, int64_t count);
+
+// ---- what a sample set, which drives its mapper's launches itself, uses of the mapper
+// map_batch_resident (m->mu held) -- first_unit: global index of the batch's first unit (first-seen values count from it), or -1
+// to continue after the units mapped so far
+// fill_records: what makes the read records of the batch (records, words per read, u32 words per
+// record); nullptr = pack_reads_kernel over ASCII bases + offsets
+// salt: the batch is a launch of a sample set -- the segments whose samples go into the records' keys
+// before class counting (skm_samples.hip); nullptr = one sample, keys as the map kernel made them
+// collapse: a sample set that keeps UMIs -- what removes the duplicate units' records (skm_umi.hip) once the map
+// attempt that stood and the strand filter have run, before anything counts; nullptr = nothing is launched
+typedef std::function<int(uint32_t *, int, int)> RecordStage;
+typedef std::function<int(const MapBatch &)> BatchStage;
+int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_offsets,
+                       int64_t n_units, int paired, int max_len, int64_t first_unit = -1,
+                       const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr,
+                       unsigned long long *sample_bias_rows = nullptr, const BatchStage *collapse = nullptr);
+
+struct PackedSegment {               // part of one piece inside a run
+    int mate;
+    int64_t first, n;                // units
+    const uint64_t *codes;
+    const uint32_t *lengths;
+    int cw;
+    uint32_t uniform_len;
+    const uint32_t *exc_reads, *exc_masks;   // device, already offset to the segment's first exception
+    int64_t n_exc;
+    int64_t exc_base;                // index (relative to the piece as pushed) of the segment's first read
+};
+// the parts of a stream's pieces that lie in units [lo, hi), as segments of a launch
+void packed_segments(std::deque<skm_mapper::Piece> &pieces, int mate, int64_t lo, int64_t hi, bool mark_in_job,
+                     std::vector<PackedSegment> *segments, int *max_cw);
+// the read records of a launch's packed segments (`first_unit`: the unit that stands at record 0)
+void packed_unpack(const std::vector<PackedSegment> &segments, int64_t first_unit, int mates, uint32_t *records, int words,
+                   int record_words, int *error, hipStream_t stream);
+// the arrays of a piece that holds reads
+int packed_check_arrays(const skm_packed_reads *piece);
+inline size_t packed_round(size_t b) { return (b + 255) & ~(size_t)255; }
+// `bytes` of HBM from the pool, counted in *counter while the block lives
+int packed_block(int64_t bytes, const std::shared_ptr<std::atomic<int64_t>> &counter, std::shared_ptr<char> *block);
+// take the block (counted in *counter while it lives) and QUEUE the copies of the piece's arrays on `stream`
+int packed_upload(const skm_packed_reads *piece, const std::shared_ptr<std::atomic<int64_t>> &counter, hipStream_t stream,
+                  skm_mapper::Piece *out);
 
 }  // namespace abi
 }  // namespace skm

@@ -1,5 +1,6 @@
 // The sample-set handle of the C ABI glue with the types of its members, for the units that look into it
-// (skm_abi.hip, which owns it, and skm_abi_quant.hip), and the call that makes its tables by sample.
+// (skm_abi_samples.hip, which owns it, skm_abi_genes.hip and skm_abi_quant.hip), and the call that makes its tables
+// by sample.
 #pragma once
 #include "skm_abi_mapper.h"
 
@@ -108,7 +109,7 @@ struct skm_sample_set {
 namespace skm {
 namespace abi __attribute__((visibility("hidden"))) {
 
-// (defined in skm_abi.hip) waits for the set's launches and makes s->view if it is not valid; `hold` then holds s->mu
+// (defined in skm_abi_samples.hip) waits for the set's launches and makes s->view if it is not valid; `hold` then holds s->mu
 int set_view(skm_sample_set *s, std::unique_lock<std::mutex> &hold);
 
 }  // namespace abi

@@ -1,6 +1,6 @@
 // The host's half of the expected hexamer counts of the sequence-bias correction (DESIGN.md section 4,
 // "Sequence bias"): the abundances as 96-bit fixed-point weights.  Plain C++, no GPU: skm_bias_correct and
-// skm_bias_correct_many (skm_abi.hip) and skm_bias_fixed_weights (libseekmer_host.so) all call this one function.
+// skm_bias_correct_many (skm_abi_index.hip) and skm_bias_fixed_weights (libseekmer_host.so) all call this one function.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -35,6 +35,34 @@ def test_every_declared_symbol_is_exported_and_bound(native_libs):
     native_libs.host()
 
 
+def _defined_dynamic_symbols(path):
+    """`nm -D --defined-only` of a shared library: binutils' nm, or else the llvm-nm that stands beside hipcc."""
+    import shutil
+    import subprocess
+    import pytest
+    hipcc = shutil.which(os.environ.get('HIPCC', 'hipcc')) or '/opt/rocm/bin/hipcc'
+    beside = os.path.dirname(os.path.realpath(hipcc))
+    tools = [shutil.which('nm'), os.path.join(beside, 'llvm-nm'), os.path.join(beside, '..', 'lib', 'llvm', 'bin', 'llvm-nm'),
+             os.path.join(beside, '..', 'llvm', 'bin', 'llvm-nm')]
+    tools = [t for t in tools if t and os.path.exists(t)]
+    if not tools:
+        pytest.skip('neither nm nor llvm-nm')
+    lines = subprocess.check_output([tools[0], '-D', '--defined-only', path], text=True).splitlines()
+    return [line.split()[-1].split('@')[0] for line in lines if line.strip()]
+
+
+def test_the_gpu_library_exports_the_c_abi_and_nothing_of_the_glue(native_libs):
+    """The glue's units share their helpers through the hidden namespace skm::abi: none of them is a dynamic symbol,
+    and the library's skm_* symbols are exactly the header's declarations that the host library does not export."""
+    hip = _defined_dynamic_symbols(native_libs.HIP_LIB_PATH)
+    host = _defined_dynamic_symbols(native_libs.HOST_LIB_PATH)
+    assert hip and host
+    assert [name for name in hip if '3skm3abi' in name] == []
+    exported = sorted(name for name in hip if name.startswith('skm_'))
+    assert len(exported) == len(set(exported))
+    assert exported == sorted(set(_declared_symbols()) - set(host))
+
+
 def test_no_gpu_fails_loudly(native_libs):
     """Without a GPU every device entry point must fail, never fall back."""
     import numpy as np

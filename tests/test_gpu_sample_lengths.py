@@ -319,3 +319,27 @@ def test_summaries_carry_their_own_lengths(oracle, native_libs, product_index, c
         plain, middle = summaries[PLAIN].effective_lengths, summaries[MIDDLE].effective_lengths
         assert not np.array_equal(plain, middle)
         assert not np.array_equal(plain, pooled) and not np.array_equal(middle, pooled)
+
+
+def test_a_sample_without_units_past_the_rows_reads_as_zero(oracle, chr21, product_index):
+    """A set that keeps histograms and hexamer counts, two samples of 300 pairs, and sample 40 named by a segment
+    without units: no launch held it, so its rows lie past the set's buffers (rows 0 to 1 exist).  Its histogram
+    and hexamer rows are zero, its sizes (0, 0, 0, 0); the rows of the two others are those of the same reads
+    mapped alone."""
+    from seekmer_amd import mapper
+    rng = np.random.default_rng(40)
+    cells = [_cell_reads(chr21[1], rng, 300, True, 150, 400, 450) for _ in range(2)]
+    sample_set = mapper.SampleSet(product_index, True, per_sample_lengths=True, bias=True)
+    for i, reads in enumerate(cells):
+        _add(oracle, sample_set, i, reads, True, packed=i == 0)
+    _add(oracle, sample_set, 40, [], True, packed=False)
+    histograms, hexamers, sizes = sample_set.sample_fragment_length_counts, sample_set.bias_observed(), sample_set.sizes()
+    assert histograms.shape == (41, 2000) and hexamers.shape == (41, 4096) and sizes.shape == (41, 4)
+    assert not histograms[2:].any() and not hexamers[2:].any() and not sizes[2:].any()
+    for i, reads in enumerate(cells):
+        alone = mapper.MapResult(product_index, bias=True)
+        mapper.ReadMapper(product_index, alone).map_batch(_batch(oracle, reads, True))
+        assert alone.fragment_length_counts.sum() > 100 and alone.bias_observed().sum() > 100
+        np.testing.assert_array_equal(histograms[i], alone.fragment_length_counts, err_msg='histogram of sample %d' % i)
+        np.testing.assert_array_equal(hexamers[i], alone.bias_observed(), err_msg='hexamers of sample %d' % i)
+        assert tuple(sizes[i]) == alone.sizes(), i
