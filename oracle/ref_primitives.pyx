@@ -6,8 +6,9 @@ _sequence.pxd from /root/reference where they lie (include path only; nothing
 is copied) so that the reference's own compiled code can be called from
 Python.  Built by oracle/build_ref.py into oracle/_ref/ (git-ignored).  Used
 only to pin the oracle's primitives and to generate tests/golden/primitives.json.
-The reference's .pyx modules (mapper, index, builder) are NOT built: they
-import `logbook`/`tables`, which this image lacks, and no stand-ins are written.
+The reference's .pyx modules (_common, _mapper, _index_builder) are built by the
+same script into oracle/_ref/seekmer/, with the stand-ins of oracle/ref_stubs/
+for `logbook` and `tables`; they do not go through this harness.
 """
 cimport libc.stdint
 cimport libc.stdlib

@@ -56,9 +56,12 @@ def test_builder_edge_inputs(native_libs, oracle):
 
 
 def test_builder_never_leaves_an_occupied_slot_unassigned(native_libs, oracle):
-    """SURVEY.md (finding 3 / row a9) records, for the reference's 3-transcript FASTA, one
+    """SURVEY.md (rows a9, (f)1) records, for the reference's 3-transcript FASTA, one
     occupied k-mer slot whose position was never assigned and a 24-base contig without
-    targets.  Neither can come out of _assemble_contigs (_index_builder.pyx:428-487): links are
+    targets: the compiled reference's "no link" value is 0, the number of a slot (SURVEY.md
+    section 0, finding 8; tests/test_reference_recordings.py pins that relation).  With a value
+    that is no slot number, as our builders have it, neither can come out of _assemble_contigs
+    (_index_builder.pyx:428-487): links are
     only ever made between two consecutive NEW k-mers (:283-288), so the graph is a set of
     disjoint simple paths, every path has an end that starts a walk (:436-445), a walk covers its
     whole path (:458-471), and a contig of n k-mers is 25*ceil(n/25) + (n-1)%25 = n + 24 >= 25
