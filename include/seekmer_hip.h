@@ -72,6 +72,18 @@ int skm_pinned_set_device(int device);
  * (latency under load).  The ceiling the index probes are priced against. */
 int skm_device_gather_ceiling(int device, int64_t table_bytes, int blocks, int per_lane,
                               int chain, double *gathers_per_second);
+/* Diagnostics, tests: the engine's own prefix sum and stable radix sort (the class views of skm_quant_*, skm_units_group
+ * and the ranking of skm_barcode_census_* rest on them) on the caller's host arrays -- upload, the production call,
+ * download.  SKM_ERR_ARG for n < 0 or n >= 2^31, for NULL arrays with n > 0 (`out` of the scan: always needed), for a
+ * key_kind or an end_bit outside what is listed below.
+ * skm_device_scan_probe: out[0 .. n) = the exclusive prefix sums of in[0 .. n), out[n] = the total (n = 0: out[0] = 0);
+ * in_place != 0 scans with input and output in ONE device buffer of n + 1 entries, the input in its first n.
+ * skm_device_sort_probe: the (key, value) pairs in stable order of key & (2^min(width, 9 p) - 1), p =
+ * max(1, ceil(end_bit / 9)) whole 9-bit passes, the full keys carried; key_kind 0 = uint32_t keys, 1 = uint64_t
+ * (end_bit 0 .. 64), 2 = non-negative int32_t; end_bit 0 .. 32 for kinds 0 and 2.  n = 0 writes nothing. */
+int skm_device_scan_probe(int device, const int64_t *in, int64_t n, int in_place, int64_t *out);
+int skm_device_sort_probe(int device, int key_kind, const void *keys, const int32_t *vals, int64_t n, int end_bit,
+                          void *keys_out, int32_t *vals_out);
 
 /* ------------------------------------------------------------------ index
  * Replaces the memoryview binding of KMerIndex.__init__

@@ -62,6 +62,9 @@ HIP_SYMBOLS = {
     'skm_device_synchronize': (ctypes.c_int, [ctypes.c_int]),
     'skm_device_gather_ceiling': (ctypes.c_int, [ctypes.c_int, c_i64, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, c_f64p]),
+    'skm_device_scan_probe': (ctypes.c_int, [ctypes.c_int, c_i64p, c_i64, ctypes.c_int, c_i64p]),
+    'skm_device_sort_probe': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_i32p, c_i64, ctypes.c_int,
+                                             ctypes.c_void_p, c_i32p]),
     'skm_pinned_alloc': (ctypes.c_void_p, [ctypes.c_size_t]),
     'skm_pinned_free': (None, [ctypes.c_void_p]),
     'skm_pinned_set_device': (ctypes.c_int, [ctypes.c_int]),

@@ -1,5 +1,5 @@
 // C ABI of libseekmer_hip.so: this thread's error message, the device calls, the page-locked arena
-// and the gather probe.
+// and the diagnostic probes (gathers, scan, sort).
 #include "skm_abi.h"
 
 #include <algorithm>
@@ -260,3 +260,65 @@ extern "C" int skm_device_gather_ceiling(int device, int64_t table_bytes, int bl
     return SKM_OK;
 }
 
+// Diagnostics: the scan and the stable radix sort of skm_quant_setup.hip on the caller's arrays, as the class
+// views, the unit grouping and the census run them -- upload, the production call, download (tests pin them to numpy).
+// The device outputs are filled with 0xff first: an entry the kernels fail to write then shows as that, not as whatever
+// the pool's block held before (the right answer of an earlier call, perhaps).
+extern "C" int skm_device_scan_probe(int device, const int64_t *in, int64_t n, int in_place, int64_t *out)
+{
+    SKM_TRY(check_device(device));
+    if (n < 0 || n >= (1LL << 31) || !out || (n && !in)) return fail(SKM_ERR_ARG, "bad argument");
+    SKM_TRY(set_device(device));
+    DBuf<int64_t> d_in, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_out.ensure((size_t)n + 1));
+    if (!in_place) SKM_TRY(d_in.ensure((size_t)std::max<int64_t>(n, 1)));
+    int64_t *src = in_place ? d_out.p : d_in.p;
+    HIP_TRY(hipMemsetAsync(d_out.p, 0xff, ((size_t)n + 1) * 8, nullptr));
+    if (n) HIP_TRY(hipMemcpy(src, in, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (exclusive_scan_total_i64(src, d_out.p, n, nullptr) != 0)
+        return fail(SKM_ERR_HIP, "scanning %lld values: %s", (long long)n, quant_setup_failure());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copy home has waited for the kernels)
+    return SKM_OK;
+}
+
+namespace {
+
+template <class K>
+int sort_probe(int (*sort)(const K *, K *, const int32_t *, int32_t *, int64_t, int, hipStream_t), const void *keys,
+               const int32_t *vals, int64_t n, int end_bit, void *keys_out, int32_t *vals_out)
+{
+    DBuf<K> d_keys, d_keys_out; DBuf<int32_t> d_vals, d_vals_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    const size_t room = (size_t)n;
+    SKM_TRY(d_keys.ensure(room)); SKM_TRY(d_keys_out.ensure(room)); SKM_TRY(d_vals.ensure(room)); SKM_TRY(d_vals_out.ensure(room));
+    HIP_TRY(hipMemsetAsync(d_keys_out.p, 0xff, room * sizeof(K), nullptr));
+    HIP_TRY(hipMemsetAsync(d_vals_out.p, 0xff, room * 4, nullptr));
+    HIP_TRY(hipMemcpy(d_keys.p, keys, room * sizeof(K), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_vals.p, vals, room * 4, hipMemcpyHostToDevice));
+    if (sort(d_keys.p, d_keys_out.p, d_vals.p, d_vals_out.p, n, end_bit, nullptr) != 0)
+        return fail(SKM_ERR_HIP, "sorting %lld pairs: %s", (long long)n, quant_setup_failure());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(keys_out, d_keys_out.p, room * sizeof(K), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vals_out, d_vals_out.p, room * 4, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copies home have waited for the kernels)
+    return SKM_OK;
+}
+
+}  // namespace
+
+extern "C" int skm_device_sort_probe(int device, int key_kind, const void *keys, const int32_t *vals, int64_t n, int end_bit,
+                                     void *keys_out, int32_t *vals_out)
+{
+    SKM_TRY(check_device(device));
+    if (n < 0 || n >= (1LL << 31) || key_kind < 0 || key_kind > 2 || end_bit < 0 || end_bit > (key_kind == 1 ? 64 : 32)
+            || (n && (!keys || !vals || !keys_out || !vals_out)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    if (n == 0) return SKM_OK;
+    SKM_TRY(set_device(device));
+    if (key_kind == 0) return sort_probe<uint32_t>(sort_pairs_u32, keys, vals, n, end_bit, keys_out, vals_out);
+    if (key_kind == 1) return sort_probe<unsigned long long>(sort_pairs_u64, keys, vals, n, end_bit, keys_out, vals_out);
+    return sort_probe<int32_t>(sort_pairs_i32, keys, vals, n, end_bit, keys_out, vals_out);
+}

@@ -546,10 +546,19 @@ void launch_gene_unique(const GeneClasses &t, const int32_t *tx_gene, int64_t n_
                         hipStream_t stream);
 
 // ---- cell barcodes (skm_barcodes.hip; DESIGN.md section 4, "Cell barcodes")
-// The stable radix sort of skm_quant_setup.hip for (uint32 key, int32 value) pairs on key bits [0, end_bit):
+// The stable radix sort of skm_quant_setup.hip for (uint32 key, int32 value) pairs, in max(1, ceil(end_bit / 9))
+// whole 9-bit passes (the order is by the key bits those passes cover; keys below 2^end_bit: by the key):
 // 0 = done (the stream has drained), < 0 = no memory or n >= 2^32 (quant_setup_failure() says which).
 int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *vals_in, int32_t *vals_out, int64_t n,
                    int end_bit, hipStream_t stream);
+// Its other two instantiations in use (non-negative int32 keys), and the exclusive scan of the same file -- out[0 .. n)
+// the prefix sums of in[0 .. n), out[n] the total, in == out allowed -- for skm_device_sort_probe and
+// skm_device_scan_probe (diagnostics, tests).  Same results; the stream has drained on return.
+int sort_pairs_u64(const unsigned long long *keys_in, unsigned long long *keys_out, const int32_t *vals_in,
+                   int32_t *vals_out, int64_t n, int end_bit, hipStream_t stream);
+int sort_pairs_i32(const int32_t *keys_in, int32_t *keys_out, const int32_t *vals_in, int32_t *vals_out, int64_t n,
+                   int end_bit, hipStream_t stream);
+int exclusive_scan_total_i64(const int64_t *in, int64_t *out, int64_t n, hipStream_t stream);
 constexpr int BARCODE_LDS_MAX_ENTRIES = 1024;     // whitelists up to this size are probed from a copy in LDS
 constexpr int BARCODE_STATS = 5;                  // exact, corrected, ambiguous, no match, short or unreadable
 struct BarcodeTable {             // the whitelist in HBM: open addressing, linear probing, at most half full

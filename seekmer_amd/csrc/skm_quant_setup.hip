@@ -370,8 +370,9 @@ int exclusive_scan_with_total(Scratch &scratch, const int64_t *in, int64_t *out,
     return exclusive_scan<int64_t>(scratch, in, out, n, out + n);
 }
 
-// Stable least-significant-digit radix sort of (key, value) pairs on key bits [0, end_bit), 9 bits
-// (512 bins) per pass: the 18-bit keys of the class views take two passes.  A pass: a histogram per
+// Stable least-significant-digit radix sort of (key, value) pairs in whole passes of 9 key bits
+// (512 bins), as many as cover end_bit (sort_pairs below says what that orders by): the 18-bit keys
+// of the class views take two passes.  A pass: a histogram per
 // tile of 4096 pairs (digit-major, so that ONE exclusive scan over it gives every (digit, tile) its
 // place), then the scatter -- a tile's four waves each own a quarter of it in order; a wave ranks 64
 // pairs at a time with nine ballots (the lanes that share my digit) against its running per-digit
@@ -540,7 +541,15 @@ radix_scatter_kernel(const K *__restrict__ keys_in, const int32_t *__restrict__ 
     }
 }
 
-// Stable radix sort of (key, value) pairs on bits [0, end_bit); the result lands in keys_out / vals_out.
+// Stable radix sort of (key, value) pairs; the result lands in keys_out / vals_out.  It runs
+// max(1, ceil(end_bit / 9)) WHOLE 9-bit passes, so the pairs come out ordered by
+// key & (2^(9 passes) - 1), or by the whole key where K is no wider than that -- NOT by the bits
+// below end_bit alone: key bits in [end_bit, 9 passes) take part.  Bits above are ignored, and the full
+// keys are carried.  localize relies on this: it sorts with end_bit = the bits of n_tx - 1 and gives
+// an empty class the key 0xffffffff, all ones in every whole pass (no transcript id is above that),
+// so that these classes come out last.  A caller that wants bits [0, end_bit) alone keeps its keys
+// below 2^end_bit, as all the others do.
+// (tests/test_gpu_scan_sort.py pins this against tests/sort_scan_reference.py)
 template <class K>
 int sort_pairs(Scratch &scratch, const K *keys_in, K *keys_out, const int32_t *vals_in, int32_t *vals_out,
                int64_t n, int end_bit)
@@ -584,6 +593,28 @@ int sort_pairs_u32(const uint32_t *keys_in, uint32_t *keys_out, const int32_t *v
 {
     Scratch scratch(stream);
     return sort_pairs<uint32_t>(scratch, keys_in, keys_out, vals_in, vals_out, n, end_bit);
+}
+
+// the other two instantiations in use and the scan, as they stand, for the diagnostic entry points
+// (skm_device_sort_probe, skm_device_scan_probe: tests); the stream has drained on return
+int sort_pairs_u64(const unsigned long long *keys_in, unsigned long long *keys_out, const int32_t *vals_in,
+                   int32_t *vals_out, int64_t n, int end_bit, hipStream_t stream)
+{
+    Scratch scratch(stream);
+    return sort_pairs<unsigned long long>(scratch, keys_in, keys_out, vals_in, vals_out, n, end_bit);
+}
+
+int sort_pairs_i32(const int32_t *keys_in, int32_t *keys_out, const int32_t *vals_in, int32_t *vals_out, int64_t n,
+                   int end_bit, hipStream_t stream)
+{
+    Scratch scratch(stream);
+    return sort_pairs<int32_t>(scratch, keys_in, keys_out, vals_in, vals_out, n, end_bit);
+}
+
+int exclusive_scan_total_i64(const int64_t *in, int64_t *out, int64_t n, hipStream_t stream)
+{
+    Scratch scratch(stream);
+    return exclusive_scan_with_total(scratch, in, out, n);
 }
 
 int64_t quant_rows_upper_bound(int64_t n_tx, int64_t n_ids)

@@ -188,7 +188,7 @@ def test_barcodes_create_refuses_bad_whitelists(native_libs):
 
 
 # ---- grouping -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('n_samples', [1, 2, 513, 65536])
+@pytest.mark.parametrize('n_samples', [1, 2, 513, 65536, 262145])         # (262145: 19 key bits, three passes of the sort)
 @pytest.mark.parametrize('n', [0, 1, 4095, 4096, 4097, 3 * 4096 + 5])
 def test_group_units_is_a_stable_argsort(native_libs, n, n_samples):
     from seekmer_amd import mapper
