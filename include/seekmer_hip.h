@@ -501,8 +501,23 @@ int skm_sample_set_bias_observed(skm_sample_set *set, int64_t cap_samples, int64
  * add (_add_packed and _add_batch return SKM_ERR_ARG), in any other set it returns SKM_ERR_ARG.
  * skm_sample_set_umi_removed: removed[n_samples], the units removed so far per sample (zeros in a set that keeps no
  * UMIs); every unit total the set reports (_summary, _export, the samples' unaligned counts) is the units added less
- * these.  Waits and holds adders as _summary; SKM_ERR_ARG if cap_samples is below the samples named so far. */
+ * these.  Waits and holds adders as _summary; SKM_ERR_ARG if cap_samples is below the samples named so far.
+ * skm_sample_set_set_umi_mismatches ("UMI mismatches"): mismatches = 1 also takes a UMI one
+ * substitution away for a sequencing error.  Inside a sample a unit with a class is then removed when an EARLIER unit
+ * of the sample (a lower unit number) has the same class and a UMI at Hamming distance 0 or 1 over the umi_bases
+ * bases -- whether or not that earlier unit was itself removed; everything else is as above (unaligned units are never
+ * removed, the class is the tuple after the strand filter, two samples or two classes are separate molecules).  The
+ * rule is arrival-ordered and exact: a chain m0 - m1 - m2 with d(m0, m2) = 2 leaves one unit in the order m0, m1, m2
+ * and two (m0, m2) in the order m0, m2, m1; it is neither a count-based nor a "directional" rule.  The result does
+ * not depend on the grid, the cut into launches or the order in which samples are added.  0 (the default) is the
+ * exact rule above and launches what it always has.  SKM_ERR_ARG for any other value; SKM_ERR_STATE in a set that
+ * keeps no UMIs (skm_sample_set_keep_umis first) and after the set's first segment.
+ * skm_sample_set_umi_near_removed: *n = the units removed so far ONLY because of such a neighbour (each the first
+ * unit of its own exact molecule), over all samples; they are part of _umi_removed's counts.  0 in any other set.
+ * Waits for the set's launches. */
 int skm_sample_set_keep_umis(skm_sample_set *set, int umi_bases);
+int skm_sample_set_set_umi_mismatches(skm_sample_set *set, int mismatches);
+int skm_sample_set_umi_near_removed(skm_sample_set *set, int64_t *n);
 int skm_sample_set_add_packed_umis(skm_sample_set *set, int64_t sample, int64_t first_unit, const skm_packed_reads *mate1,
                                    const skm_packed_reads *mate2, const uint32_t *umis);
 int skm_sample_set_umi_removed(skm_sample_set *set, int64_t cap_samples, int64_t *removed);

@@ -4,6 +4,8 @@ molecules drawn at random, so that a molecule appears C times on average; the ce
 permutation, 85 % of the barcodes exact, 10 % with one substitution, 5 % unreadable.  The same files are quantified
     (plain) by `infer-many --barcodes`, every read counted, and
     (umi)   by `infer-many --barcodes --umi-start L --umi-length 12`, duplicates collapsed on the GPU,
+    (near)  with --mismatches 1 also by the same command with `--umi-mismatches 1`: every surviving unit then looks up
+            its 36 one-substitution neighbours in the molecule set (with --only umi this form alone),
 with SKM_TRACE_INFER's phase times of both printed: "demultiplexing" (which holds the UMI windows, the UMIs' way
 through the chunks and the set's launches that ran meanwhile) and "mapping (set)" (what was left of the set's
 mapping, and its summaries) separately.  The yardstick for the option's cost is the same command without it.
@@ -38,6 +40,8 @@ ap.add_argument('--read-len', type=int, default=75)
 ap.add_argument('--barcode-len', type=int, default=16)
 ap.add_argument('--jobs', type=int, default=4)
 ap.add_argument('--only', choices=('umi', 'plain'), default=None)
+ap.add_argument('--mismatches', type=int, choices=(0, 1), default=0,
+                help='1: also run the UMI form with --umi-mismatches 1 (with --only umi: that form alone)')
 ap.add_argument('--cache', default='', help='keep the index in this file between invocations')
 ap.add_argument('--step-limit', type=int, default=300, help='seconds one child process may take')
 ap.add_argument('--work', default='', help='folder for the files (default: a temporary one)')
@@ -126,16 +130,25 @@ def main():
         took, trace = step('infer-many --barcodes', pooled)
         print('infer-many --barcodes, every read counted:   %.2f s' % took, flush=True)
         print('\n'.join('    ' + line for line in trace), flush=True)
-    if args.only in (None, 'umi'):
-        pooled[2] = str(work / 'out_umi')
-        took, trace = step('infer-many --barcodes --umi-length',
-                           pooled + ['--umi-start', str(args.barcode_len), '--umi-length', str(UMI_LENGTH)])
-        print('infer-many --barcodes --umi-length %d:      %.2f s' % (UMI_LENGTH, took), flush=True)
+    forms = [args.mismatches]                    # the UMI forms to run: --umi-mismatches 0 and / or 1
+    if args.only == 'plain':
+        forms = []
+    if args.only is None and args.mismatches:
+        forms = [0, 1]
+    for mismatches in forms:
+        out = work / ('out_near' if mismatches else 'out_umi')
+        pooled[2] = str(out)
+        extra = ['--umi-mismatches', '1'] if mismatches else []
+        took, trace = step('infer-many --barcodes --umi-length' + ' --umi-mismatches 1' * mismatches,
+                           pooled + ['--umi-start', str(args.barcode_len), '--umi-length', str(UMI_LENGTH)] + extra)
+        print('infer-many --barcodes --umi-length %d%s:      %.2f s' % (UMI_LENGTH, ' --umi-mismatches 1' * mismatches, took), flush=True)
         print('\n'.join('    ' + line for line in trace), flush=True)
-        summary = json.loads((work / 'out_umi' / 'barcodes.json').read_text())
-        units = sum(int(line.split('\t')[4]) for line in (work / 'out_umi' / 'barcodes.tsv').read_text().splitlines())
-        print('%d units with a cell and a UMI, %d removed as duplicates (%.1f %%)'
-              % (units, summary['umi_duplicates'], 100.0 * summary['umi_duplicates'] / max(units, 1)), flush=True)
+        summary = json.loads((out / 'barcodes.json').read_text())
+        units = sum(int(line.split('\t')[4]) for line in (out / 'barcodes.tsv').read_text().splitlines())
+        print('%d units with a cell and a UMI, %d removed as duplicates (%.1f %%)%s'
+              % (units, summary['umi_duplicates'], 100.0 * summary['umi_duplicates'] / max(units, 1),
+                 ', %d of them only for a UMI one substitution away' % summary['umi_near_duplicates'] if mismatches else ''),
+              flush=True)
 
 
 if __name__ == '__main__':

@@ -141,6 +141,8 @@ HIP_SYMBOLS = {
     'skm_sample_set_add_packed_umis': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.POINTER(PackedReads),
                                                       ctypes.POINTER(PackedReads), c_u32p]),
     'skm_sample_set_umi_removed': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64p]),
+    'skm_sample_set_set_umi_mismatches': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'skm_sample_set_umi_near_removed': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
     'skm_umi_windows': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(PackedReads), ctypes.c_int, ctypes.c_int, c_i32p, c_u32p,
                                        c_i64p]),
     'skm_sample_set_plan': (ctypes.c_int, [c_i64, c_i32p, c_i64p, c_i64, c_i64, c_i64p, c_i64p, c_i64p, c_i32p]),

@@ -69,11 +69,14 @@ struct skm_sample_set {
     bool keep_bias = false;
     DBuf<unsigned long long> bias_rows;
     // UMI collapse (skm_sample_set_keep_umis; skm_umi.hip): the molecule set -- umi_n_slots slots, a power of two,
-    // sized ahead of every launch to at least twice (molecules so far + the launch's records) --, its two counters,
+    // sized ahead of every launch to at least twice (molecules so far + the launch's records) --, its counters,
     // the units removed per sample (rows kept as `hist` is) and the segments' UMIs of the launch under way;
     // touched under m->mu.  SKM_TEST_UMI_SLOTS: the set starts at that many slots and grows only when a launch
-    // finds it full.
+    // finds it full.  umi_mismatches (skm_sample_set_set_umi_mismatches, under mu like umi_bases): 1 = resolve also
+    // removes a unit that an earlier unit with a UMI one substitution away precedes; umi_near = those removed so.
     int umi_bases = 0;                            // 0: the set keeps no UMIs
+    int umi_mismatches = 0;
+    int64_t umi_near = 0;
     DBuf<UmiSlot> umi_slots;
     uint64_t umi_n_slots = 0, umi_test_slots = 0;
     int64_t umi_entries = 0;

@@ -154,7 +154,7 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
             SKM_TRY(set_umi_grow(s, s->umi_n_slots * 4));
         }
         const UmiSet set{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, m->error.p};
-        launch_umi_resolve(set, b, salt, s->umi_segs.p, s->umi_removed.p, m->stream);
+        launch_umi_resolve(set, b, salt, s->umi_segs.p, s->umi_removed.p, s->umi_bases, s->umi_mismatches, m->stream);
         HIP_TRY(hipGetLastError());
         return SKM_OK;
     };
@@ -186,6 +186,7 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
             return fail(SKM_ERR_STATE, "the molecule set of %llu slots was full for %llu records", (unsigned long long)s->umi_n_slots,
                         ctl[UMI_CTL_LOST]);
         s->umi_entries = (int64_t)ctl[UMI_CTL_ENTRIES];
+        s->umi_near = (int64_t)ctl[UMI_CTL_NEAR];
     }
     if (s->keep_hist) {
         // the spans of the attempt that stood (an overflowing entry arena runs the map kernel again), after
@@ -489,6 +490,18 @@ extern "C" int skm_sample_set_keep_umis(skm_sample_set *s, int umi_bases)
         return fail(SKM_ERR_STATE, "a set that keeps UMIs keeps a histogram per sample: call skm_sample_set_keep_histograms(set, 1) "
                     "first (the pooled histogram is counted inside the map kernel and cannot leave a unit out)");
     s->umi_bases = umi_bases;
+    if (!umi_bases) s->umi_mismatches = 0;
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_set_umi_mismatches(skm_sample_set *s, int mismatches)
+{
+    if (!s) return fail(SKM_ERR_ARG, "NULL sample set");
+    if (mismatches != 0 && mismatches != 1) return fail(SKM_ERR_ARG, "%d UMI mismatches: 0 or 1 are possible", mismatches);
+    std::lock_guard<std::mutex> hold(s->mu);
+    if (!s->umi_bases) return fail(SKM_ERR_STATE, "the set keeps no UMIs: call skm_sample_set_keep_umis first");
+    if (!s->sample_units.empty()) return fail(SKM_ERR_STATE, "UMI mismatches can only be switched before the set's first segment");
+    s->umi_mismatches = mismatches;
     return SKM_OK;
 }
 
@@ -690,6 +703,16 @@ extern "C" int skm_sample_set_umi_removed(skm_sample_set *s, int64_t cap_samples
     const int64_t n_samples = (int64_t)v.removed.size();
     if (cap_samples < n_samples) return fail(SKM_ERR_ARG, "room for %lld samples of %lld", (long long)cap_samples, (long long)n_samples);
     std::copy(v.removed.begin(), v.removed.end(), removed);
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_umi_near_removed(skm_sample_set *s, int64_t *n)
+{
+    if (!s || !n) return fail(SKM_ERR_ARG, "bad argument");
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_hold(s, hold));                   // (every launch has read its counters back)
+    std::lock_guard<std::mutex> lock(s->m->mu);
+    *n = s->umi_near;
     return SKM_OK;
 }
 

@@ -631,11 +631,12 @@ __host__ __device__ __forceinline__ uint64_t umi_tag(uint64_t class_key, uint32_
     h ^= h >> 32;
     return h;
 }
-enum { UMI_CTL_ENTRIES = 0, UMI_CTL_LOST = 1, UMI_CTL_WORDS = 2 };
+enum { UMI_CTL_ENTRIES = 0, UMI_CTL_LOST = 1, UMI_CTL_NEAR = 2, UMI_CTL_WORDS = 3 };
 struct UmiSet {
     UmiSlot *slots;
     uint64_t slot_mask;           // slots - 1, a power of two of them
-    unsigned long long *ctl;      // [UMI_CTL_ENTRIES] molecules in the set, [UMI_CTL_LOST] probes that found the set full
+    unsigned long long *ctl;      // [UMI_CTL_ENTRIES] molecules in the set, [UMI_CTL_LOST] probes that found the set full,
+                                  // [UMI_CTL_NEAR] units removed only because of a neighbour (mismatches = 1)
     int *error;                   // SKM_ERR_* raised by a kernel
 };
 struct UmiSegment {               // beside SampleSalt's arrays, for the same segments of a launch
@@ -645,10 +646,12 @@ struct UmiSegment {               // beside SampleSalt's arrays, for the same se
 void launch_umi_init(const UmiSet &t, hipStream_t stream);
 // pass 1 and pass 2 over the records of a launch (after the strand filter, before anything counts); removed[sample]
 // += the records that pass 2 made unaligned.  A full set adds to ctl[UMI_CTL_LOST] and changes no record wrongly: what
-// it removes had an earlier copy.
+// it removes had an earlier copy.  mismatches = 1 (UMIs of umi_bases <= 16 bases): pass 2 also removes the first unit
+// of a molecule when a molecule of the same class and a UMI one substitution away has an earlier unit, and adds the
+// units that only this removed to ctl[UMI_CTL_NEAR]; mismatches = 0 launches the kernel it always has.
 void launch_umi_claim(const UmiSet &t, const MapBatch &b, const SampleSalt &salt, const UmiSegment *segs, hipStream_t stream);
 void launch_umi_resolve(const UmiSet &t, const MapBatch &b, const SampleSalt &salt, const UmiSegment *segs,
-                        unsigned long long *removed, hipStream_t stream);
+                        unsigned long long *removed, int umi_bases, int mismatches, hipStream_t stream);
 // `to` (any slots' contents) becomes a set that holds the molecules of `from`
 void launch_umi_rehash(const UmiSet &from, const UmiSet &to, hipStream_t stream);
 

@@ -17,7 +17,10 @@
 //              again, compares key and UMI in FULL (a mismatch is a collision of two molecules' tags and fails the
 //              call: exact or fail, like the class table) and, if min_unit is not its own unit, removes itself:
 //              key 0, tuple length 0, a span that gives no fragment length -- from here on an unaligned unit,
-//              which the set subtracts again (removed[sample]).
+//              which the set subtracts again (removed[sample]).  With one mismatch allowed (umi_resolve_kernel<true>)
+//              the first unit of a molecule also looks up its 3 L one-substitution neighbours and removes itself
+//              when one of them has a smaller min_unit; it reads the set only, with plain loads, for the same
+//              reason: claim has finished.  The units removed by a neighbour alone are counted in ctl[UMI_CTL_NEAR].
 // Units of earlier launches have smaller local numbers (a sample's segments are added in order), so an entry of an
 // earlier launch always wins; inside a launch the minimum does not depend on the order of arrival.  No lane waits
 // for another; nothing a lane stores with a plain store is read in the same launch.
@@ -187,15 +190,84 @@ umi_claim_kernel(UmiSet t, const int32_t *__restrict__ rec_unit, const uint64_t 
 // a mixed tile adds straight to HBM.  Integer adds: any order gives the same counts.
 constexpr int UMI_RESOLVE_RUN = 1024;
 
+// The neighbour step (skm_sample_set_set_umi_mismatches(set, 1); DESIGN.md section 4, "UMI mismatches").  A record
+// that is the first unit of its own molecule is still removed when one of the 3 L molecules (same salted class key,
+// UMI one substitution away) is in the set with a min_unit below the record's unit: an EARLIER unit of the cell showed
+// a UMI at distance 1, whether or not that unit stayed itself -- so one lane decides from the set alone, waits for
+// nobody and stores nothing into the set.  Everything claim stored (tags by CAS, keys and UMIs by plain stores,
+// min_unit by atomicMin), in this launch and in every one before it, is visible: resolve is a launch of its own, and
+// claim of the same launch has finished -- also where the test hook grew the set and claimed again.  So all reads
+// here are plain loads, and a min_unit is final for every unit below the launch's end: a later launch only brings
+// larger units, which never decide about this record.
+//   The 3 L probe chains of a record are independent random 32-byte sectors: UMI_NEAR_WIDTH home slots (two
+// positions' three substitutions) are fetched whole before any is looked at, as umi_claim_kernel does with its
+// records; a chain that goes past its home slot walks on alone (at load 1/2 mostly inside the 128-byte line its
+// home slot brought).  A probe ends at an empty slot, at a slot with the neighbour's tag, or after n_slots steps.
+// A tag match whose key or UMI differs is another molecule with the neighbour's tag: the neighbour itself cannot
+// be stored beside it, so it is not in the set -- no collision is raised for a molecule no record has shown (the
+// records of a real collision report it themselves above).  A neighbour whose tag is 0 cannot be stored: skipped.
+//   Bounds: shifts are 2 * position <= 30 (L <= 16), slots go through the mask, walks end after n_slots steps.
+constexpr int UMI_NEAR_WIDTH = 6;
+
+// true: an earlier unit of the record's cell and class has a UMI one substitution away
+__device__ __forceinline__ bool umi_near_earlier(const UmiSet &t, const UmiRecord &rec, int L, uint64_t n_slots)
+{
+    const unsigned long long mine = (unsigned long long)rec.local;
+    bool earlier = false;
+    for (int p = 0; p < L && !earlier; p += UMI_NEAR_WIDTH / 3) {
+        uint32_t near[UMI_NEAR_WIDTH], home_umi[UMI_NEAR_WIDTH];
+        uint64_t tag[UMI_NEAR_WIDTH];
+        unsigned long long home_tag[UMI_NEAR_WIDTH], home_key[UMI_NEAR_WIDTH], home_min[UMI_NEAR_WIDTH];
+#pragma unroll
+        for (int k = 0; k < UMI_NEAR_WIDTH; ++k) {
+            const int at = p + k / 3;                                  // the position, counted from the UMI's last base
+            near[k] = rec.umi ^ ((uint32_t)(k % 3 + 1) << (2 * (at & 15)));
+            tag[k] = at < L ? umi_tag(rec.key, near[k]) : 0;           // (0: nothing to look for)
+        }
+#pragma unroll
+        for (int k = 0; k < UMI_NEAR_WIDTH; ++k) {
+            const UmiSlot *home = &t.slots[tag[k] & t.slot_mask];      // (tag 0: slot 0, unused)
+            home_tag[k] = home->tag;
+            home_key[k] = home->class_key;
+            home_umi[k] = home->umi;
+            home_min[k] = home->min_unit;
+        }
+#pragma unroll
+        for (int k = 0; k < UMI_NEAR_WIDTH; ++k) {
+            if (tag[k] == 0) continue;
+            if (home_tag[k] == tag[k]) {
+                earlier |= home_key[k] == rec.key && home_umi[k] == near[k] && home_min[k] < mine;
+                continue;
+            }
+            unsigned long long cur = home_tag[k];
+            uint64_t slot = tag[k] & t.slot_mask;
+            for (uint64_t n = 1; cur != tag[k] && cur != 0 && n < n_slots; ++n) {
+                slot = (slot + 1) & t.slot_mask;
+                cur = t.slots[slot].tag;
+            }
+            if (cur != tag[k]) continue;
+            const UmiSlot *entry = &t.slots[slot];
+            earlier |= entry->class_key == rec.key && entry->umi == near[k] && entry->min_unit < mine;
+        }
+    }
+    return earlier;
+}
+
+// NEAR: with the neighbour step, and then with one more argument, the bases of a UMI; without it the kernel has the
+// arguments and the code it always had
+template <bool NEAR, typename... Bases>
 __global__ void __launch_bounds__(256)
 umi_resolve_kernel(UmiSet t, MapBatch b, const int32_t *__restrict__ seg_first, const int32_t *__restrict__ seg_sample,
-                   const UmiSegment *__restrict__ segs, int n_segments, unsigned long long *__restrict__ removed)
+                   const UmiSegment *__restrict__ segs, int n_segments, unsigned long long *__restrict__ removed, Bases... bases)
 {
+    static_assert(sizeof...(Bases) == (NEAR ? 1 : 0), "the UMI's length goes with the neighbour step");
+    const int L = (0 + ... + bases);
     __shared__ int32_t s_first[SAMPLE_LAUNCH_SEGMENTS], s_sample[SAMPLE_LAUNCH_SEGMENTS];
-    __shared__ unsigned int s_removed;
+    __shared__ unsigned int s_removed, s_near;    // (s_near: touched by the neighbour form alone, the other has none)
     __shared__ int32_t s_ref;
     for (int i = threadIdx.x; i < n_segments; i += blockDim.x) { s_first[i] = seg_first[i]; s_sample[i] = seg_sample[i]; }
     if (threadIdx.x == 0) s_removed = 0;
+    if constexpr (NEAR) { if (threadIdx.x == 0) s_near = 0; }
     __syncthreads();
     const int64_t run_first = (int64_t)blockIdx.x * UMI_RESOLVE_RUN;
     const int64_t run_end = run_first + UMI_RESOLVE_RUN < b.n_units ? run_first + UMI_RESOLVE_RUN : b.n_units;
@@ -210,6 +282,7 @@ umi_resolve_kernel(UmiSet t, MapBatch b, const int32_t *__restrict__ seg_first, 
         __syncthreads();
     };
     int fault = 0;
+    unsigned int near = 0;                        // removed by a neighbour alone
     for (int64_t tile = run_first; tile < run_end; tile += blockDim.x) {
         const int64_t r = tile + threadIdx.x;
         const uint64_t key = r < run_end ? b.rec_key[r] : 0;
@@ -241,7 +314,11 @@ umi_resolve_kernel(UmiSet t, MapBatch b, const int32_t *__restrict__ seg_first, 
         if (!found) { fault = SKM_ERR_STATE; continue; }              // (claim has reported it: the set was full)
         const UmiSlot entry = t.slots[slot];
         if (entry.class_key != rec.key || entry.umi != rec.umi) { fault = SKM_ERR_COLLISION; continue; }
-        if (entry.min_unit == (unsigned long long)rec.local) continue;                   // the molecule's first unit stays
+        if (entry.min_unit == (unsigned long long)rec.local) {        // the molecule's first unit stays
+            if (!NEAR) continue;
+            if (!umi_near_earlier(t, rec, L, n_slots)) continue;      // ... unless an earlier unit was one substitution away
+            ++near;
+        }
         b.rec_key[r] = 0;
         b.rec_tuple[r] &= (1ULL << 40) - 1;       // tuple length 0: unaligned to everything that follows
         if (b.keep_spans) { b.unit_begin[unit] = 0; b.unit_end[unit] = -K; }             // fragment length rule: 0, not counted
@@ -250,6 +327,11 @@ umi_resolve_kernel(UmiSet t, MapBatch b, const int32_t *__restrict__ seg_first, 
     }
     if (held >= 0) flush();
     if (fault) atomicExch(t.error, fault);
+    if constexpr (NEAR) {
+        if (near) atomicAdd(&s_near, near);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_near) atomicAdd(t.ctl + UMI_CTL_NEAR, (unsigned long long)s_near);
+    }
 }
 
 // one lane per old slot: the 32 bytes move to the slot their tag finds in the new table
@@ -303,12 +385,16 @@ void launch_umi_claim(const UmiSet &t, const MapBatch &b, const SampleSalt &salt
 }
 
 void launch_umi_resolve(const UmiSet &t, const MapBatch &b, const SampleSalt &salt, const UmiSegment *segs,
-                        unsigned long long *removed, hipStream_t stream)
+                        unsigned long long *removed, int umi_bases, int mismatches, hipStream_t stream)
 {
     if (b.n_units <= 0 || salt.n_segments <= 0) return;
     const int64_t blocks = (b.n_units + UMI_RESOLVE_RUN - 1) / UMI_RESOLVE_RUN;       // (at most 2^21 units a launch)
-    hipLaunchKernelGGL(umi_resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, t, b, salt.seg_first, salt.seg_sample,
-                       segs, (int)salt.n_segments, removed);
+    if (mismatches)
+        hipLaunchKernelGGL((umi_resolve_kernel<true, int>), dim3((unsigned)blocks), dim3(256), 0, stream, t, b, salt.seg_first,
+                           salt.seg_sample, segs, (int)salt.n_segments, removed, std::min(std::max(umi_bases, 0), 16));
+    else
+        hipLaunchKernelGGL(umi_resolve_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, t, b, salt.seg_first,
+                           salt.seg_sample, segs, (int)salt.n_segments, removed);
 }
 
 void launch_umi_rehash(const UmiSet &from, const UmiSet &to, hipStream_t stream)

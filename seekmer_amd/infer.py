@@ -428,7 +428,7 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
              barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
-             discover_cells=None, barcode_length=None, discover_keep_neighbours=False, **__):
+             discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -473,7 +473,14 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     class an earlier unit has shown is removed on the GPU as if it had never been in the files (mapper.SampleSet with
     umi_bases; DESIGN.md section 4, "UMI collapse").  Every folder then holds what it would for a FASTQ pair of the
     cell's surviving units; barcodes.tsv gains two columns (units with a readable UMI, units left after collapse) and
-    barcodes.json the keys umi_start, umi_length, umi_unreadable, umi_duplicates.  No mismatch correction.
+    barcodes.json the keys umi_start, umi_length, umi_unreadable, umi_duplicates.
+
+    umi_mismatches: --umi-mismatches 0 or 1 (1 with umi_length only).  0, the default, collapses UMIs that are equal
+    letter for letter.  With 1 a unit is also removed when an EARLIER unit of its cell has the same class and a UMI
+    one substitution away, whether or not that earlier unit stayed ("UMI mismatches": an
+    arrival-ordered rule, neither Cell Ranger's nor UMI-tools' "directional" one).  barcodes.json then gains
+    "umi_mismatches": 1 and "umi_near_duplicates" (the units that only a neighbour removed; umi_duplicates stays the
+    total), and the last column of barcodes.tsv counts what is left after both kinds of removal.
 
     discover_cells: --discover-cells N with barcode_length L (1..32), instead of barcodes: there is no whitelist, the
     cells are found in the barcode reads (mapper.discover_barcodes; DESIGN.md section 4, "Cell discovery": an exact
@@ -488,6 +495,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     trace = _phase_trace()
     mapper.strand_mode(strand)
     length_model, _ = mapper.length_model_weights(length_model)
+    umi_mismatches = mapper.check_umi_mismatches(umi_mismatches, umi_length)
     whitelist = None
     pooled = barcodes is not None or discover_cells is not None
     if not pooled:
@@ -566,14 +574,19 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
             index, table, common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads),
             common.PackedReadFeeder(list(fastq_paths), paired=paired, threads=parse_threads), paired, start=barcode_start,
             mismatches=barcode_mismatches, min_units=min_units, device=device, strand=strand, per_sample_lengths=True,
-            length_model=length_model, bias=bias, umi_start=umi_start, umi_length=umi_length)
+            length_model=length_model, bias=bias, umi_start=umi_start, umi_length=umi_length,
+            umi_mismatches=umi_mismatches)
         _LOG.info('Barcodes of %d units: %d exact, %d corrected, %d ambiguous, %d without a match, %d short or unreadable',
                   demux['units'], *[demux[name] for name in mapper.BARCODE_STATS])
-        if umi_length:
+        if umi_length and umi_mismatches:
+            _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed, %d of them only for a UMI '
+                      'one substitution away', umi_length, demux['umi_unreadable'], demux['umi_duplicates'],
+                      demux['umi_near_duplicates'])
+        elif umi_length:
             _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed', umi_length,
                       demux['umi_unreadable'], demux['umi_duplicates'])
         _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units, umi_start, umi_length,
-                         discovery=discovery)
+                         discovery=discovery, umi_mismatches=umi_mismatches)
         if not kept.size:
             raise ValueError('no cell has %d units or more (see %s)' % (min_units, output_path / 'barcodes.tsv'))
         names = [table.names[c] for c in kept]
@@ -744,10 +757,12 @@ def _output_discovery(output_path, picked, found, expect_cells, length, start, k
                 picked=found['picked'], keep_neighbours=bool(keep_neighbours))
 
 
-def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units, umi_start=0, umi_length=0, discovery=None):
+def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_units, umi_start=0, umi_length=0, discovery=None,
+                     umi_mismatches=0):
     """output/barcodes.tsv: barcode, name, assigned units, kept 0/1 per whitelist entry -- with UMIs also the units
-    with a readable UMI (what `kept` looks at) and the units left after collapse; output/barcodes.json: the
-    demultiplexing summary."""
+    with a readable UMI (what `kept` looks at) and the units left after collapse (with umi_mismatches=1: after both
+    kinds of removal); output/barcodes.json: the demultiplexing summary, with umi_mismatches=1 also that key and
+    umi_near_duplicates."""
     is_kept = numpy.zeros(len(table), dtype=bool)
     is_kept[kept] = True
     with (output_path / 'barcodes.tsv').open('w') as f:
@@ -765,6 +780,8 @@ def _output_barcodes(output_path, table, kept, demux, start, mismatches, min_uni
     if umi_length:
         summary.update(umi_start=int(umi_start), umi_length=int(umi_length), umi_unreadable=demux['umi_unreadable'],
                        umi_duplicates=demux['umi_duplicates'])
+        if umi_mismatches:
+            summary.update(umi_mismatches=int(umi_mismatches), umi_near_duplicates=demux['umi_near_duplicates'])
     if discovery is not None:
         summary.update(discovery=discovery)
     with (output_path / 'barcodes.json').open('w') as f:
@@ -1470,7 +1487,7 @@ def add_many_subcommand_parser(subparsers):
 
 def add_barcode_arguments(parser):
     """--barcodes and its companions: dest 'barcodes', 'barcode_file', 'barcode_start', 'barcode_mismatches',
-    'min_units', 'umi_start', 'umi_length', and --discover-cells with 'discover_cells', 'barcode_length',
+    'min_units', 'umi_start', 'umi_length', 'umi_mismatches', and --discover-cells with 'discover_cells', 'barcode_length',
     'discover_keep_neighbours' (barcode_option checks the combinations once the arguments are parsed)."""
     parser.add_argument('--barcodes', type=pathlib.Path, dest='barcodes', default=None, metavar='WHITELIST',
                         help='the FASTQ files are ONE pooled sample: split it into the cells of this whitelist (a '
@@ -1485,7 +1502,11 @@ def add_barcode_arguments(parser):
                         help='keep the cells with at least N assigned units (default 1)')
     parser.add_argument('--umi-length', type=int, dest='umi_length', default=None, metavar='L',
                         help='the barcode reads carry a UMI of L bases (1 to 16): inside a cell, count the reads of one '
-                             'UMI and one equivalence class once (with --barcodes; no mismatch correction)')
+                             'UMI and one equivalence class once (with --barcodes or --discover-cells; UMIs must be '
+                             'equal letter for letter unless --umi-mismatches 1)')
+    parser.add_argument('--umi-mismatches', type=int, dest='umi_mismatches', default=None, choices=(0, 1),
+                        help='1: also remove a read when an EARLIER read of its cell has the same equivalence class and a '
+                             'UMI one substitution away (default 0; with --umi-length)')
     parser.add_argument('--umi-start', type=int, dest='umi_start', default=None, metavar='N',
                         help='the UMI begins at base N of a barcode read (default 0; with --umi-length)')
     parser.add_argument('--discover-cells', type=int, dest='discover_cells', default=None, metavar='N',
@@ -1503,7 +1524,8 @@ def barcode_option(parser, opts):
     """The parsed barcode options: a combination that cannot be is an argparse error; the defaults are filled in."""
     given = [flag for flag, key in (('--barcode-file', 'barcode_file'), ('--barcode-start', 'barcode_start'),
                                     ('--barcode-mismatches', 'barcode_mismatches'), ('--min-units', 'min_units'),
-                                    ('--umi-length', 'umi_length'), ('--umi-start', 'umi_start'))
+                                    ('--umi-length', 'umi_length'), ('--umi-start', 'umi_start'),
+                                    ('--umi-mismatches', 'umi_mismatches'))
              if opts.get(key) is not None]
     discover = opts.get('discover_cells') is not None
     if opts.get('barcodes') is not None and discover:
@@ -1543,7 +1565,10 @@ def barcode_option(parser, opts):
         parser.error('--umi-start must be 0 or more')
     if opts.get('umi_start') is not None and opts.get('umi_length') is None:
         parser.error('--umi-start goes with --umi-length')
-    for key, default in (('barcode_start', 0), ('barcode_mismatches', 1), ('min_units', 1), ('umi_start', 0), ('umi_length', 0)):
+    if opts.get('umi_mismatches') is not None and opts.get('umi_length') is None:
+        parser.error('--umi-mismatches goes with --umi-length')
+    for key, default in (('barcode_start', 0), ('barcode_mismatches', 1), ('min_units', 1), ('umi_start', 0), ('umi_length', 0),
+                         ('umi_mismatches', 0)):
         if opts.get(key) is None:
             opts[key] = default
     return opts

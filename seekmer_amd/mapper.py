@@ -732,17 +732,22 @@ class SampleSet:
     only the first unit of every (UMI, class) stays, and every table, total, histogram per sample and hexamer row
     is that of a set fed the surviving units alone; umi_removed() says how many went.  Such a set takes its reads
     through add_packed(..., umis=) only, and its POOLED histogram still holds the removed units.
+    With ``umi_mismatches=1`` (needs umi_bases; skm_sample_set_set_umi_mismatches; DESIGN.md section 4, "UMI
+    mismatches") a unit is also removed when an earlier unit of its sample has the same class and a UMI one
+    substitution away, whether or not that earlier unit stayed; umi_near_removed() counts the units that only this
+    removed.  0, the default, is the exact rule.
 
     Samples are numbered from 0.  A sample's reads are added as segments, each beginning at the unit
     where the sample's units so far end (NativeError SKM_ERR_STATE otherwise); any thread may add."""
 
     def __init__(self, index, paired, device=0, strand=None, per_sample_lengths=False, length_model=None, bias=False,
-                 umi_bases=0):
+                 umi_bases=0, umi_mismatches=0):
         mode = strand_mode(strand)
         self.length_model, self._length_weights = length_model_weights(length_model)
         self.umi_bases = int(umi_bases)
         if not 0 <= self.umi_bases <= MAX_UMI_LENGTH:
             raise ValueError('UMIs of %r bases: 1 to %d are possible' % (umi_bases, MAX_UMI_LENGTH))
+        self.umi_mismatches = check_umi_mismatches(umi_mismatches, self.umi_bases)
         self.index = index
         self.paired = bool(paired)
         self.device = device
@@ -763,6 +768,15 @@ class SampleSet:
             _native.check(_native.hip().skm_sample_set_keep_bias(self._handle, 1))
         if self.umi_bases:
             _native.check(_native.hip().skm_sample_set_keep_umis(self._handle, self.umi_bases))
+        if self.umi_mismatches:
+            _native.check(_native.hip().skm_sample_set_set_umi_mismatches(self._handle, self.umi_mismatches))
+
+    def umi_near_removed(self):
+        """The units removed so far only because an earlier unit of their sample and class had a UMI one substitution
+        away (each the first of its own UMI): part of umi_removed()'s counts; 0 in a set without umi_mismatches=1."""
+        n = ctypes.c_int64(0)
+        _native.check(_native.hip().skm_sample_set_umi_near_removed(self._handle, ctypes.byref(n)))
+        return int(n.value)
 
     def umi_removed(self):
         """int64[n_samples]: the units UMI collapse has removed from every sample (zeros in a set without UMIs)."""
@@ -1064,6 +1078,15 @@ DEMUX_CHUNK_UNITS = 1 << 22         # units grouped and gathered at a time (SKM_
 BARCODE_STATS = ('exact', 'corrected', 'ambiguous', 'no_match', 'unreadable')    # skm_barcodes_assign's stats[5]
 MAX_BARCODE_LENGTH = 32
 MAX_UMI_LENGTH = 16
+
+
+def check_umi_mismatches(umi_mismatches, umi_length):
+    """umi_mismatches as an int: 0 or 1, and 1 only with UMIs (umi_length > 0); ValueError otherwise"""
+    if isinstance(umi_mismatches, bool) or umi_mismatches not in (0, 1):
+        raise ValueError('UMI mismatches must be 0 or 1, not %r' % (umi_mismatches,))
+    if umi_mismatches and not int(umi_length):
+        raise ValueError('UMI mismatches go with UMIs: give their length (--umi-length L)')
+    return int(umi_mismatches)
 
 
 def check_whitelist(barcodes, names=None):
@@ -1438,7 +1461,8 @@ def _demux_chunk_units():
 
 
 def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mismatches=1, min_units=1, device=0,
-                 strand=None, per_sample_lengths=False, length_model=None, bias=False, umi_start=0, umi_length=0):
+                 strand=None, per_sample_lengths=False, length_model=None, bias=False, umi_start=0, umi_length=0,
+                 umi_mismatches=0):
     """One pooled run -> a SampleSet with one sample per kept cell.  table: a BarcodeTable; barcode_feeder: a
     single-ended PackedReadFeeder over the barcode file; read_feeder: a PackedReadFeeder over the pooled cDNA
     file (or pair of files).  The run holds min(records) units over these files (zip of the reference's feeders);
@@ -1458,9 +1482,13 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
     what min_units looks at -- are counted again from the final cell[] (stats['cell_assigned'] keeps the barcodes'
     count), and stats gains 'umi_unreadable', the units of the run without a readable UMI.  The set is made with
     umi_bases=umi_length and collapses duplicates (SampleSet); stats['cell_survivors'] int64[whitelist] are the units
-    it left every kept cell (0 for a cell that is not kept) and stats['umi_duplicates'] those it removed."""
+    it left every kept cell (0 for a cell that is not kept) and stats['umi_duplicates'] those it removed.
+    umi_mismatches (0 or 1; 1 needs umi_length): the set's umi_mismatches.  With 1 a unit also goes when an earlier unit
+    of its cell and class has a UMI one substitution away; stats['umi_near_duplicates'] are the units that only this
+    removed (0 with umi_mismatches=0), part of stats['umi_duplicates']."""
     strand_mode(strand)
     umi_start, umi_length = int(umi_start), int(umi_length)
+    umi_mismatches = check_umi_mismatches(umi_mismatches, umi_length)
     if umi_length and not 1 <= umi_length <= MAX_UMI_LENGTH:
         raise ValueError('a UMI of %d bases: 1 to %d are possible' % (umi_length, MAX_UMI_LENGTH))
     if umi_start < 0 or (umi_start and not umi_length):
@@ -1515,7 +1543,8 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
     sample = number[cell]
     # phase 2: the reads, cell by cell, into the set
     sample_set = SampleSet(index, paired, device=device, strand=strand, per_sample_lengths=per_sample_lengths,
-                           length_model=length_model, bias=bias, umi_bases=umi_length)
+                           length_model=length_model, bias=bias, umi_bases=umi_length,
+                           umi_mismatches=umi_mismatches)
     if kept.size:
         added, walked = demux_chunks(read_feeder, paired, sample, kept.size, chunk_units,
                                      lambda part, n: group_units(part, n, device=device), sample_set.add_packed, umi=umi)
@@ -1529,5 +1558,6 @@ def map_barcoded(index, table, barcode_feeder, read_feeder, paired, start=0, mis
         removed = sample_set.umi_removed() if kept.size else numpy.zeros(0, dtype=numpy.int64)
         survivors[kept] = cell_units[kept] - removed
         stats.update(umi_unreadable=int(umi_unreadable), umi_duplicates=int(removed.sum()), cell_assigned=cell_assigned,
-                     cell_survivors=survivors)
+                     cell_survivors=survivors,
+                     umi_near_duplicates=sample_set.umi_near_removed() if umi_mismatches and kept.size else 0)
     return sample_set, kept, stats
