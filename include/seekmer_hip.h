@@ -572,6 +572,27 @@ int skm_mapper_gene_counts(skm_mapper *mapper, int64_t n_tx, int64_t n_genes, co
  * ranges of samples, 1 GiB of them at most (SKM_GENE_GROUP, for tests: fewer samples per range). */
 int skm_sample_set_gene_counts(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
                                int64_t cap_samples, int64_t *unique /*[n_samples][n_genes]*/, int64_t *other);
+/* The count matrix ("Count matrix"): the same counts, by the same rule, as a CSR over
+ * samples that is made and kept in HBM -- indptr int64[n_samples + 1]; indices int32[nnz], the gene numbers,
+ * strictly ascending inside a sample; data int64[nnz], every one > 0 (a class inside one gene with a count
+ * of 0 makes no entry); other int64[n_samples][2] as above.  Densified, row i is row i of
+ * skm_sample_set_gene_counts / skm_gene_unique_counts, whatever the grid: the sums are 64-bit integers.
+ * No dense row exists anywhere: the cost is that of sorting the classes by (sample, gene).
+ * SKM_ERR_ARG for a table of 2^32 classes or more and for more than 2^31 - 2 samples; on any failure *out is NULL.
+ * skm_sample_set_gene_matrix works from the set's resident table and waits and locks as skm_sample_set_gene_counts
+ * does; skm_gene_matrix_from_classes takes the table of skm_gene_unique_counts, with that call's checks.
+ * _shape: any pointer may be NULL.  _read copies the arrays home; any pointer may be NULL to skip that array.
+ * The handle owns its device buffers until _destroy (NULL is allowed there). */
+typedef struct skm_gene_matrix skm_gene_matrix;
+int skm_sample_set_gene_matrix(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                               skm_gene_matrix **out);
+int skm_gene_matrix_from_classes(int device, int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets,
+                                 const int64_t *class_counts, const int32_t *class_sample, int64_t n_samples,
+                                 int64_t n_tx, int64_t n_genes, const int32_t *tx_gene, skm_gene_matrix **out);
+int skm_gene_matrix_shape(const skm_gene_matrix *matrix, int64_t *n_samples, int64_t *n_genes, int64_t *nnz);
+int skm_gene_matrix_read(const skm_gene_matrix *matrix, int64_t *indptr /*[n_samples + 1]*/, int32_t *indices /*[nnz]*/,
+                         int64_t *data /*[nnz]*/, int64_t *other /*[n_samples][2]*/);
+int skm_gene_matrix_destroy(skm_gene_matrix *matrix);
 
 /* ---------------------------------------------------------------- cell barcodes
  * ("Cell barcodes".)  A pooled run -- one barcode read per unit beside the cDNA reads --

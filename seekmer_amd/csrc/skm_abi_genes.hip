@@ -1,10 +1,12 @@
 // C ABI of libseekmer_hip.so: gene-level tables -- sums of transcript values by gene, and the unique counts of a
-// class table given on the host, held by a mapper or held by a sample set.
+// class table given on the host, held by a mapper or held by a sample set -- as dense rows, or as the sparse count
+// matrix (skm_gene_matrix: a CSR over samples that stays in HBM until it is read).
 #include "skm_abi_samples.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -68,6 +70,50 @@ int gene_counts_device(const GeneClasses &t, int64_t n_samples, int64_t n_tx, in
     return SKM_OK;
 }
 
+// a class table given on the host as the CSR of skm_mapper_export, with a sample per class or none
+int host_classes_check(int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets, const int64_t *class_counts,
+                       const int32_t *class_sample, int64_t n_samples, int64_t n_tx)
+{
+    if (n_classes && (!class_offsets || !class_counts || n_samples < 1)) return fail(SKM_ERR_ARG, "NULL class arrays");
+    if (n_classes && !class_sample && n_samples > 1) return fail(SKM_ERR_ARG, "%lld samples without class_sample", (long long)n_samples);
+    const int64_t M = n_classes ? class_offsets[n_classes] : 0;
+    for (int64_t c = 0; c < n_classes; ++c) {
+        if (class_offsets[c] < 0 || class_offsets[c + 1] < class_offsets[c] || class_offsets[c + 1] - class_offsets[c] > INT32_MAX)
+            return fail(SKM_ERR_ARG, "class_offsets are not those of a table");
+        if (class_counts[c] < 0) return fail(SKM_ERR_ARG, "class %lld has a negative count", (long long)c);
+        if (class_sample && (class_sample[c] < 0 || class_sample[c] >= n_samples))
+            return fail(SKM_ERR_ARG, "class %lld belongs to sample %d of %lld", (long long)c, class_sample[c], (long long)n_samples);
+    }
+    if (M && !class_targets) return fail(SKM_ERR_ARG, "NULL class arrays");
+    for (int64_t k = 0; k < M; ++k)
+        if (class_targets[k] < 0 || class_targets[k] >= n_tx)
+            return fail(SKM_ERR_ARG, "a class names transcript %d of %lld", class_targets[k], (long long)n_tx);
+    return SKM_OK;
+}
+
+struct HostClasses {              // that table in HBM (copies on the null stream)
+    DBuf<int64_t> d_off, d_cnt; DBuf<int32_t> d_ids, d_sample;
+    GeneClasses t{};
+    int upload(int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets, const int64_t *class_counts,
+               const int32_t *class_sample)
+    {
+        t.n_classes = n_classes;
+        if (!n_classes) return SKM_OK;
+        const int64_t M = class_offsets[n_classes];
+        SKM_TRY(d_off.ensure(n_classes + 1)); SKM_TRY(d_cnt.ensure(n_classes)); SKM_TRY(d_ids.ensure((size_t)std::max<int64_t>(M, 1)));
+        HIP_TRY(hipMemcpy(d_off.p, class_offsets, (n_classes + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_cnt.p, class_counts, n_classes * 8, hipMemcpyHostToDevice));
+        if (M) HIP_TRY(hipMemcpy(d_ids.p, class_targets, M * 4, hipMemcpyHostToDevice));
+        if (class_sample) {
+            SKM_TRY(d_sample.ensure(n_classes));
+            HIP_TRY(hipMemcpy(d_sample.p, class_sample, n_classes * 4, hipMemcpyHostToDevice));
+            t.sample = d_sample.p;
+        }
+        t.start = d_off.p; t.count_i64 = d_cnt.p; t.ids = d_ids.p;
+        return SKM_OK;
+    }
+};
+
 }  // namespace
 
 // Rows in groups, so that the rows staged in HBM stay within 256 MB; the gene list goes up once.
@@ -115,38 +161,13 @@ extern "C" int skm_gene_unique_counts(int device, int64_t n_classes, const int64
     SKM_TRY(check_device(device));
     if (n_classes < 0 || n_samples < 0 || (n_samples && (!other || (n_genes > 0 && !unique))))
         return fail(SKM_ERR_ARG, "bad argument");
-    if (n_classes && (!class_offsets || !class_counts || n_samples < 1)) return fail(SKM_ERR_ARG, "NULL class arrays");
-    if (n_classes && !class_sample && n_samples > 1) return fail(SKM_ERR_ARG, "%lld samples without class_sample", (long long)n_samples);
     SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
-    const int64_t M = n_classes ? class_offsets[n_classes] : 0;
-    for (int64_t c = 0; c < n_classes; ++c) {
-        if (class_offsets[c] < 0 || class_offsets[c + 1] < class_offsets[c] || class_offsets[c + 1] - class_offsets[c] > INT32_MAX)
-            return fail(SKM_ERR_ARG, "class_offsets are not those of a table");
-        if (class_counts[c] < 0) return fail(SKM_ERR_ARG, "class %lld has a negative count", (long long)c);
-        if (class_sample && (class_sample[c] < 0 || class_sample[c] >= n_samples))
-            return fail(SKM_ERR_ARG, "class %lld belongs to sample %d of %lld", (long long)c, class_sample[c], (long long)n_samples);
-    }
-    if (M && !class_targets) return fail(SKM_ERR_ARG, "NULL class arrays");
-    for (int64_t k = 0; k < M; ++k)
-        if (class_targets[k] < 0 || class_targets[k] >= n_tx)
-            return fail(SKM_ERR_ARG, "a class names transcript %d of %lld", class_targets[k], (long long)n_tx);
+    SKM_TRY(host_classes_check(n_classes, class_offsets, class_targets, class_counts, class_sample, n_samples, n_tx));
     SKM_TRY(set_device(device));
-    DBuf<int64_t> d_off, d_cnt; DBuf<int32_t> d_ids, d_sample;
+    HostClasses up;
     auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
-    GeneClasses t{};
-    t.n_classes = n_classes;
-    if (n_classes) {
-        SKM_TRY(d_off.ensure(n_classes + 1)); SKM_TRY(d_cnt.ensure(n_classes)); SKM_TRY(d_ids.ensure((size_t)std::max<int64_t>(M, 1)));
-        HIP_TRY(hipMemcpy(d_off.p, class_offsets, (n_classes + 1) * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_cnt.p, class_counts, n_classes * 8, hipMemcpyHostToDevice));
-        if (M) HIP_TRY(hipMemcpy(d_ids.p, class_targets, M * 4, hipMemcpyHostToDevice));
-        if (class_sample) {
-            SKM_TRY(d_sample.ensure(n_classes));
-            HIP_TRY(hipMemcpy(d_sample.p, class_sample, n_classes * 4, hipMemcpyHostToDevice));
-            t.sample = d_sample.p;
-        }
-        t.start = d_off.p; t.count_i64 = d_cnt.p; t.ids = d_ids.p;
-    }
+    SKM_TRY(up.upload(n_classes, class_offsets, class_targets, class_counts, class_sample));
+    const GeneClasses &t = up.t;
     SKM_TRY(gene_counts_device(t, n_samples, n_tx, n_genes, tx_gene, unique, other, nullptr));
     drain.dismiss();
     return SKM_OK;
@@ -198,4 +219,144 @@ extern "C" int skm_sample_set_gene_counts(skm_sample_set *s, int64_t n_tx, int64
     t.n_classes = (int64_t)v.start.size();
     if (t.n_classes) { t.start = v.d_start.p; t.len = v.d_len.p; t.count_f64 = v.d_count.p; t.sample = v.d_sample.p; t.ids = m->arena.p; }
     return gene_counts_device(t, n_samples, n_tx, n_genes, tx_gene, unique, other, m->stream);
+}
+
+// ------------------------------------------------------------------ count matrix (skm_gene_matrix.hip)
+struct skm_gene_matrix {
+    ~skm_gene_matrix() { (void)hipSetDevice(device); }  // (then the members free the device memory)
+    int device = 0;
+    int64_t n_samples = 0, n_genes = 0, nnz = 0;
+    DBuf<int64_t> indptr;                            // [n_samples + 1]
+    DBuf<int32_t> indices;                           // [nnz]
+    DBuf<unsigned long long> data, other;            // [nnz], [n_samples][2]
+};
+
+namespace {
+
+// what a key and the sort can number: never wrapped silently
+int gene_matrix_limits(int64_t n_classes, int64_t n_samples)
+{
+    if (n_classes >= (1LL << 32))
+        return fail(SKM_ERR_ARG, "a count matrix of %lld classes: fewer than 2^32 are possible", (long long)n_classes);
+    if (n_samples > (int64_t)INT32_MAX - 1)
+        return fail(SKM_ERR_ARG, "a count matrix of %lld samples: 2^31 - 2 at most are possible", (long long)n_samples);
+    return SKM_OK;
+}
+
+// The CSR of a class table in HBM (stream drained on return): keys, the sort, run heads and their scan, fill.  nnz
+// comes home between the scan and the fill: indices and data are made as long as they have to be.
+int gene_matrix_device(const GeneClasses &t, int device, int64_t n_samples, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                       hipStream_t stream, skm_gene_matrix **out)
+{
+    const int64_t n = t.n_classes;
+    SKM_TRY(gene_matrix_limits(n, n_samples));
+    if (n && n_samples && n_tx == 0) return fail(SKM_ERR_ARG, "classes over no transcripts");
+    std::unique_ptr<skm_gene_matrix> m(new skm_gene_matrix);
+    m->device = device; m->n_samples = n_samples; m->n_genes = n_genes;
+    DBuf<int32_t> d_gene, d_vals, d_order; DBuf<unsigned long long> d_keys, d_sorted; DBuf<int64_t> d_runs; DBuf<int> d_error;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    SKM_TRY(m->indptr.ensure((size_t)n_samples + 1)); SKM_TRY(m->other.ensure((size_t)std::max<int64_t>(2 * n_samples, 1)));
+    HIP_TRY(hipMemsetAsync(m->indptr.p, 0, (size_t)(n_samples + 1) * 8, stream));
+    HIP_TRY(hipMemsetAsync(m->other.p, 0, (size_t)std::max<int64_t>(2 * n_samples, 1) * 8, stream));
+    int error = 0;
+    if (n && n_samples) {
+        SKM_TRY(d_gene.ensure(n_tx)); SKM_TRY(d_error.ensure(1));
+        SKM_TRY(d_keys.ensure(n)); SKM_TRY(d_sorted.ensure(n)); SKM_TRY(d_vals.ensure(n)); SKM_TRY(d_order.ensure(n));
+        SKM_TRY(d_runs.ensure((size_t)n + 1));
+        HIP_TRY(hipMemcpyAsync(d_gene.p, tx_gene, n_tx * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_error.p, 0, sizeof(int), stream));
+        launch_gene_matrix_keys(t, d_gene.p, n_tx, n_samples, d_keys.p, d_vals.p, m->other.p, d_error.p, stream);
+        HIP_TRY(hipGetLastError());
+        int end_bit = 33;
+        while ((1LL << (end_bit - 32)) <= n_samples) ++end_bit;   // (the keys go up to n_samples << 32 itself: the other classes)
+        if (sort_pairs_u64(d_keys.p, d_sorted.p, d_vals.p, d_order.p, n, end_bit, stream) != 0)
+            return fail(SKM_ERR_HIP, "sorting %lld classes by sample and gene: %s", (long long)n, quant_setup_failure());
+        launch_gene_matrix_heads(d_sorted.p, n, n_samples, d_runs.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (exclusive_scan_total_i64(d_runs.p, d_runs.p, n, stream) != 0)
+            return fail(SKM_ERR_HIP, "numbering the entries of %lld classes: %s", (long long)n, quant_setup_failure());
+        HIP_TRY(hipMemcpyAsync(&m->nnz, d_runs.p + n, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&error, d_error.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (error) return fail(SKM_ERR_ARG, "a class names a transcript not below n_tx = %lld", (long long)n_tx);
+        if (m->nnz < 0 || m->nnz > n) return fail(SKM_ERR_HIP, "%lld entries from %lld classes", (long long)m->nnz, (long long)n);
+    }
+    SKM_TRY(m->indices.ensure((size_t)std::max<int64_t>(m->nnz, 1))); SKM_TRY(m->data.ensure((size_t)std::max<int64_t>(m->nnz, 1)));
+    if (n && n_samples) {
+        HIP_TRY(hipMemsetAsync(m->data.p, 0, (size_t)std::max<int64_t>(m->nnz, 1) * 8, stream));
+        launch_gene_matrix_fill(t, d_sorted.p, d_order.p, d_runs.p, n, n_samples, m->indptr.p, m->indices.p, m->data.p, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.dismiss();
+    *out = m.release();
+    return SKM_OK;
+}
+
+}  // namespace
+
+extern "C" int skm_sample_set_gene_matrix(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                          skm_gene_matrix **out)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!s || !out) return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    skm_sample_set::View &v = s->view;
+    const int64_t n_samples = (int64_t)v.units.size();
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    GeneClasses t{};
+    t.n_classes = (int64_t)v.start.size();
+    if (t.n_classes) { t.start = v.d_start.p; t.len = v.d_len.p; t.count_f64 = v.d_count.p; t.sample = v.d_sample.p; t.ids = m->arena.p; }
+    return gene_matrix_device(t, m->ix->device, n_samples, n_tx, n_genes, tx_gene, m->stream, out);
+}
+
+extern "C" int skm_gene_matrix_from_classes(int device, int64_t n_classes, const int64_t *class_offsets, const int32_t *class_targets,
+                                            const int64_t *class_counts, const int32_t *class_sample, int64_t n_samples,
+                                            int64_t n_tx, int64_t n_genes, const int32_t *tx_gene, skm_gene_matrix **out)
+{
+    SKM_TRY(check_device(device));
+    if (n_classes < 0 || n_samples < 0 || !out) return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(gene_matrix_limits(n_classes, n_samples));
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    SKM_TRY(host_classes_check(n_classes, class_offsets, class_targets, class_counts, class_sample, n_samples, n_tx));
+    SKM_TRY(set_device(device));
+    HostClasses up;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(up.upload(n_classes, class_offsets, class_targets, class_counts, class_sample));
+    SKM_TRY(gene_matrix_device(up.t, device, n_samples, n_tx, n_genes, tx_gene, nullptr, out));
+    drain.dismiss();
+    return SKM_OK;
+}
+
+extern "C" int skm_gene_matrix_shape(const skm_gene_matrix *m, int64_t *n_samples, int64_t *n_genes, int64_t *nnz)
+{
+    if (!m) return fail(SKM_ERR_ARG, "NULL argument");
+    if (n_samples) *n_samples = m->n_samples;
+    if (n_genes) *n_genes = m->n_genes;
+    if (nnz) *nnz = m->nnz;
+    return SKM_OK;
+}
+
+extern "C" int skm_gene_matrix_read(const skm_gene_matrix *m, int64_t *indptr, int32_t *indices, int64_t *data, int64_t *other)
+{
+    if (!m) return fail(SKM_ERR_ARG, "NULL argument");
+    SKM_TRY(set_device(m->device));
+    if (indptr) HIP_TRY(hipMemcpy(indptr, m->indptr.p, (size_t)(m->n_samples + 1) * 8, hipMemcpyDeviceToHost));
+    if (indices && m->nnz) HIP_TRY(hipMemcpy(indices, m->indices.p, (size_t)m->nnz * 4, hipMemcpyDeviceToHost));
+    if (data && m->nnz) HIP_TRY(hipMemcpy(data, m->data.p, (size_t)m->nnz * 8, hipMemcpyDeviceToHost));
+    if (other && m->n_samples) HIP_TRY(hipMemcpy(other, m->other.p, (size_t)m->n_samples * 16, hipMemcpyDeviceToHost));
+    return SKM_OK;
+}
+
+extern "C" int skm_gene_matrix_destroy(skm_gene_matrix *m)
+{
+    delete m;
+    return SKM_OK;
 }

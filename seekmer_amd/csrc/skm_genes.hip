@@ -19,12 +19,13 @@
 // first, one atomic per distinct word.  unique[sample][gene] is wide and rarely shared: one atomic per class.
 // All state is a handful of registers: no scratch, no recursion.  Every id is checked against n_tx before it
 // indexes tx_gene (*error otherwise); tx_gene's values and the classes' samples are checked by the host.
+// The rule itself -- the head / whole-wave walk and the wave reduction of `other` -- is in skm_gene_rule.h, shared
+// with the sparse rows of skm_gene_matrix.hip.
 #include "../../include/seekmer_hip.h"
+#include "skm_gene_rule.h"
 #include "skm_kernels.h"
 
 namespace skm {
-
-constexpr int GENE_HEAD = 8;              // ids of a class that its own lane compares
 
 __global__ void __launch_bounds__(256)
 gene_sums_kernel(const double *values, int64_t n_tx, const int64_t *gene_off, const int32_t *gene_tx,
@@ -47,74 +48,16 @@ void launch_gene_sums(const double *values, int64_t n_rows, int64_t n_tx, const 
                        values, n_tx, gene_off, gene_tx, n_genes, out);
 }
 
-enum { GENE_KIND_NONE = 0, GENE_KIND_UNIQUE = 1, GENE_KIND_AMBIGUOUS = 2, GENE_KIND_UNNAMED = 3 };
-
 __global__ void __launch_bounds__(256)
 gene_unique_kernel(GeneClasses t, const int32_t *tx_gene, int64_t n_tx, int64_t n_genes, int64_t sample_first,
                    int64_t sample_end, unsigned long long *unique, unsigned long long *other, int *error)
 {
     const int lane = threadIdx.x & 63;
     const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    int64_t start = 0, sample = 0;
-    int len = 0, gene = -1, kind = GENE_KIND_NONE;
-    unsigned long long count = 0;
-    bool undecided = false;
-    // (no lane leaves before the wave's shared part below: a lane without a class just has nothing to add)
-    if (c < t.n_classes) {
-        sample = t.sample ? t.sample[c] : 0;
-        if (sample >= sample_first && sample < sample_end) {
-            start = t.start[c];
-            len = (int)(t.len ? t.len[c] : t.start[c + 1] - start);
-            count = t.count_f64 ? (unsigned long long)t.count_f64[c] : (unsigned long long)t.count_i64[c];
-            kind = GENE_KIND_AMBIGUOUS;                       // (what a class without ids stays)
-            const int head = len < GENE_HEAD ? len : GENE_HEAD;
-            bool same = head > 0;
-            for (int j = 0; j < head && same; ++j) {
-                const uint32_t id = (uint32_t)t.ids[start + j];
-                if (id >= (uint64_t)n_tx) { *error = SKM_ERR_ARG; same = false; break; }
-                const int g = tx_gene[id];
-                if (j == 0) gene = g;
-                same = g == gene;
-            }
-            if (same) {
-                kind = gene >= 0 ? GENE_KIND_UNIQUE : GENE_KIND_UNNAMED;
-                undecided = len > GENE_HEAD;
-            }
-        }
-    }
-    // the rest of the long classes, by the whole wave
-    unsigned long long todo = __ballot(undecided);
-    while (todo) {
-        const int src = __ffsll(todo) - 1;
-        todo &= todo - 1;
-        const int64_t src_start = __shfl(start, src);
-        const int src_len = __shfl(len, src), src_gene = __shfl(gene, src);
-        int differs = 0;
-        for (int base = GENE_HEAD; base < src_len && !differs; base += 64) {
-            bool bad = false;
-            if (base + lane < src_len) {
-                const uint32_t id = (uint32_t)t.ids[src_start + base + lane];
-                if (id >= (uint64_t)n_tx) { *error = SKM_ERR_ARG; bad = true; }
-                else bad = tx_gene[id] != src_gene;
-            }
-            differs = __any(bad);
-        }
-        if (lane == src && differs) kind = GENE_KIND_AMBIGUOUS;
-    }
-    if (kind == GENE_KIND_UNIQUE)
-        atomicAdd(unique + (sample - sample_first) * n_genes + gene, count);
-    // other[sample][0 / 1]: one atomic per distinct word of the wave
-    const int64_t word = (sample - sample_first) * 2 + (kind == GENE_KIND_UNNAMED ? 1 : 0);
-    todo = __ballot(kind == GENE_KIND_AMBIGUOUS || kind == GENE_KIND_UNNAMED);
-    while (todo) {
-        const int src = __ffsll(todo) - 1;
-        const int64_t src_word = __shfl(word, src);
-        const unsigned long long mine = __ballot(word == src_word) & todo;
-        unsigned long long sum = (mine >> lane) & 1 ? count : 0;
-        for (int step = 32; step > 0; step >>= 1) sum += __shfl_xor(sum, step);
-        if (lane == src) atomicAdd(other + src_word, sum);
-        todo &= ~mine;
-    }
+    const GeneClass g = gene_classify(t, c, lane, tx_gene, n_tx, sample_first, sample_end, error);
+    if (g.kind == GENE_KIND_UNIQUE)
+        atomicAdd(unique + (g.sample - sample_first) * n_genes + g.gene, g.count);
+    gene_add_other(g, sample_first, lane, other);
 }
 
 void launch_gene_unique(const GeneClasses &t, const int32_t *tx_gene, int64_t n_tx, int64_t n_genes, int64_t sample_first,

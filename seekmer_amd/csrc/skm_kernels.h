@@ -545,6 +545,20 @@ void launch_gene_unique(const GeneClasses &t, const int32_t *tx_gene, int64_t n_
                         int64_t sample_end, unsigned long long *unique, unsigned long long *other, int *error,
                         hipStream_t stream);
 
+// ---- count matrix (skm_gene_matrix.hip; DESIGN.md section 4, "Count matrix"): the same rule as a CSR over samples
+// keys[c] = sample << 32 | gene for a class inside one named gene with a count > 0, n_samples << 32 for every other
+// class (one of a sample outside [0, n_samples) among them); vals[c] = c; other[n_samples][2] (zeroed by the caller)
+// as launch_gene_unique leaves it; *error as there.  n_classes < 2^32, n_samples <= 2^31 - 2 (the caller has checked).
+void launch_gene_matrix_keys(const GeneClasses &t, const int32_t *tx_gene, int64_t n_tx, int64_t n_samples,
+                             unsigned long long *keys, int32_t *vals, unsigned long long *other, int *error, hipStream_t stream);
+// heads[i] = 1 where sorted key i is a (sample, gene) key that differs from key i - 1, else 0
+void launch_gene_matrix_heads(const unsigned long long *keys, int64_t n, int64_t n_samples, int64_t *heads, hipStream_t stream);
+// keys / vals sorted, runs[n + 1] the exclusive scan of heads with its total nnz -> indptr[n_samples + 1], indices[nnz],
+// data[nnz] (zeroed by the caller; counts taken from t by vals).  n > 0.
+void launch_gene_matrix_fill(const GeneClasses &t, const unsigned long long *keys, const int32_t *vals, const int64_t *runs,
+                             int64_t n, int64_t n_samples, int64_t *indptr, int32_t *indices, unsigned long long *data,
+                             hipStream_t stream);
+
 // ---- cell barcodes (skm_barcodes.hip; DESIGN.md section 4, "Cell barcodes")
 // The stable radix sort of skm_quant_setup.hip for (uint32 key, int32 value) pairs, in max(1, ceil(end_bit / 9))
 // whole 9-bit passes (the order is by the key bits those passes cover; keys below 2^end_bit: by the key):

@@ -5,12 +5,14 @@ and the bootstrap resampling run as HIP kernels behind the C ABI.
 """
 import ctypes
 import datetime
+import io
 import json
 import logging
 import os
 import pathlib
 import shlex
 import sys
+import zipfile
 
 import numpy
 
@@ -245,7 +247,100 @@ def gene_unique_counts(results, tx_gene, n_genes, device=0):
     return unique[:n_genes], other
 
 
-GENE_COLUMNS = ('gene_id', 'n_transcripts', 'length', 'eff_length', 'est_count', 'tpm', 'unique_count')
+def gene_count_matrix(results_list, tx_gene, n_genes, device=0):
+    """(indptr int64[K + 1], indices int32[nnz], data int64[nnz], other int64[K, 2]) for K SummarizedResults over the
+    same transcripts: row i of the CSR holds the nonzeros of gene_unique_counts(results_list[i]), genes ascending, and
+    other[i] its second value.  The tables are stacked with a sample per class and pass through the device once
+    (skm_gene_matrix_from_classes; DESIGN.md section 4, "Count matrix"): no dense row is made."""
+    results_list = list(results_list)
+    tables = [_table_csr(results) for results in results_list]
+    sizes = [counts.size for _, _, counts in tables]
+    class_sample = numpy.repeat(numpy.arange(len(tables), dtype=numpy.int32), sizes)
+    offsets = numpy.zeros(sum(sizes) + 1, dtype=numpy.int64)
+    at, ids = 0, 0
+    for (table_offsets, table_targets, counts) in tables:
+        offsets[at + 1:at + counts.size + 1] = table_offsets[1:] + ids
+        at, ids = at + counts.size, ids + table_targets.size
+    targets = numpy.ascontiguousarray(numpy.concatenate([t for _, t, _ in tables] or [numpy.zeros(0, dtype=numpy.int32)]),
+                                      dtype=numpy.int32)
+    class_count = numpy.ascontiguousarray(numpy.concatenate([c for _, _, c in tables] or [numpy.zeros(0)]), dtype=numpy.int64)
+    n_tx = numpy.size(results_list[0].effective_lengths) if results_list else numpy.size(tx_gene)
+    tx_gene = mapper.gene_numbers(tx_gene, n_tx)
+    handle = ctypes.c_void_p()
+    _native.check(_native.hip().skm_gene_matrix_from_classes(
+        device, class_count.size, _native.ptr(offsets, _native.c_i64p),
+        _native.ptr(targets, _native.c_i32p) if targets.size else None,
+        _native.ptr(class_count, _native.c_i64p) if class_count.size else None,
+        _native.ptr(class_sample, _native.c_i32p) if class_sample.size else None, len(tables), tx_gene.size, int(n_genes),
+        _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
+    return mapper.read_gene_matrix(handle)
+
+
+def stack_count_rows(rows):
+    """The CSR (indptr, indices, data) of rows given one by one as (indices, data) pairs."""
+    rows = list(rows)
+    indptr = numpy.zeros(len(rows) + 1, dtype=numpy.int64)
+    indptr[1:] = numpy.cumsum([len(indices) for indices, _ in rows])
+    indices = numpy.concatenate([numpy.asarray(i, dtype=numpy.int32) for i, _ in rows] or [numpy.zeros(0, dtype=numpy.int32)])
+    data = numpy.concatenate([numpy.asarray(d, dtype=numpy.int64) for _, d in rows] or [numpy.zeros(0, dtype=numpy.int64)])
+    return indptr, indices.astype(numpy.int32, copy=False), data.astype(numpy.int64, copy=False)
+
+
+COUNT_MATRIX_COMMENT = ('% infer-many --count-matrix: rows are genes (genes.tsv), columns are cells/samples (cells.tsv); '
+                        'a value is the units of the cell that lie inside that one gene')
+
+
+def output_count_matrix(output_path, gene_ids, names, units, indptr, indices, data, other):
+    """output/counts/ of `infer-many --count-matrix`: matrix.mtx (MatrixMarket coordinate integer general; genes as
+    rows, samples as columns, 1-based, samples ascending and genes ascending inside a sample), genes.tsv (one gene id
+    per line), cells.tsv (per sample: name, units, aligned units, units inside one gene, ambiguous between genes,
+    units of unnamed transcripts, genes with a count -- columns 4 to 6 add up to column 3) and matrix.npz (indptr,
+    indices, data, shape = (n_samples, n_genes), format = b'csr': the keys scipy.sparse.load_npz reads).
+    units int64[n_samples]: every sample's units; (indptr, indices, data) the CSR over samples; other[n_samples, 2]."""
+    indptr = numpy.asarray(indptr, dtype=numpy.int64)
+    indices = numpy.asarray(indices, dtype=numpy.int32)
+    data = numpy.asarray(data, dtype=numpy.int64)
+    other = numpy.asarray(other, dtype=numpy.int64).reshape(-1, 2)
+    n_samples, n_genes = len(names), len(gene_ids)
+    if indptr.shape != (n_samples + 1,) or indices.shape != data.shape or indptr[-1] != data.size or len(other) != n_samples:
+        raise ValueError('a count matrix of %d samples needs indptr[%d], as many indices as data, and other[%d, 2]'
+                         % (n_samples, n_samples + 1, n_samples))
+    counts_path = output_path / 'counts'
+    counts_path.mkdir(exist_ok=True)
+    sample_of = numpy.repeat(numpy.arange(n_samples, dtype=numpy.int64), numpy.diff(indptr))
+    with (counts_path / 'matrix.mtx').open('w') as f:
+        f.write('%%MatrixMarket matrix coordinate integer general\n')
+        f.write(COUNT_MATRIX_COMMENT + '\n')
+        f.write('%d %d %d\n' % (n_genes, n_samples, data.size))
+        for begin in range(0, data.size, 1 << 16):
+            chunk = slice(begin, begin + (1 << 16))
+            f.writelines('%d %d %d\n' % entry for entry in zip((indices[chunk].astype(numpy.int64) + 1).tolist(),
+                                                               (sample_of[chunk] + 1).tolist(), data[chunk].tolist()))
+    with (counts_path / 'genes.tsv').open('w') as f:
+        f.writelines(gene.decode() + '\n' for gene in numpy.asarray(gene_ids).tolist())
+    inside = numpy.zeros(n_samples, dtype=numpy.int64)
+    numpy.add.at(inside, sample_of, data)
+    with (counts_path / 'cells.tsv').open('w') as f:
+        for i, name in enumerate(names):
+            aligned = int(inside[i] + other[i, 0] + other[i, 1])
+            f.write('%s\t%d\t%d\t%d\t%d\t%d\t%d\n' % (name, units[i], aligned, inside[i], other[i, 0], other[i, 1],
+                                                      indptr[i + 1] - indptr[i]))
+    # (numpy.savez stamps every member with the time of day; this container holds the same members without one, so
+    # that two runs with the same counts write the same bytes)
+    arrays = {'indptr': indptr, 'indices': indices, 'data': data,
+              'shape': numpy.asarray([n_samples, n_genes], dtype=numpy.int64), 'format': numpy.asarray(b'csr')}
+    with zipfile.ZipFile(str(counts_path / 'matrix.npz'), 'w', zipfile.ZIP_STORED, allowZip64=True) as container:
+        for key, array in arrays.items():
+            member = io.BytesIO()
+            numpy.lib.format.write_array(member, numpy.ascontiguousarray(array), allow_pickle=False)
+            container.writestr(zipfile.ZipInfo(key + '.npy', date_time=(1980, 1, 1, 0, 0, 0)), member.getvalue())
+
+
+MATRIX_ONLY_NEEDS_EM = ('--matrix-only stops before the EM: %s needs the EM (take --count-matrix, which writes the '
+                        'count matrix beside the full run)')
+
+
+GENE_COLUMNS =('gene_id', 'n_transcripts', 'length', 'eff_length', 'est_count', 'tpm', 'unique_count')
 
 
 def gene_table(index, gene_ids, tx_gene, results, tpm, est_counts, unique, device=0):
@@ -428,7 +523,8 @@ def sample_set_members(sizes, max_bytes, per_sample=None):
 def run_many(index_path, output_path, fastq_paths, job_count, single_ended, bootstrap, debug, device=0, seed=None,
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
              barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
-             discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0, **__):
+             discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0,
+             count_matrix=False, matrix_only=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -488,7 +584,21 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     unless discover_keep_neighbours -- no candidate one substitution away from an earlier one).  The picked barcodes
     go to output/barcodes.discovered.txt, a valid whitelist, every candidate to output/barcodes.census.tsv (barcode,
     count, picked 0/1), and barcodes.json gains the key "discovery".  From there the run is `barcodes` on that list,
-    which reads the barcode file a second time."""
+    which reads the barcode file a second time.
+
+    count_matrix: --count-matrix.  output/counts/ then holds the sparse gene x cell count matrix (output_count_matrix:
+    matrix.mtx, genes.tsv, cells.tsv, matrix.npz) of the units that lie inside one gene -- the numbers of
+    genes.unique_counts.tsv without its zeros.  It needs genes as `genes` does, from the index or from `gene_map`
+    (NO_GENES before any read file is opened), but does not switch the gene-level tables on: with it, `gene_map`
+    alone no longer implies `genes`.  The samples of the set get their rows from ONE SampleSet.gene_count_matrix call
+    on the resident table ("Count matrix"), every other sample from the nonzeros of its mapper's
+    MapResult.gene_unique_counts; the files are the same either way, and every other file of the run is what it is
+    without the option.
+
+    matrix_only: --matrix-only, which implies count_matrix.  The run stops after mapping (and demultiplexing and UMI
+    collapse): no summarize(), no EM, no folder per sample; it writes counts/, samples.tsv and the barcodes.* files,
+    each byte for byte that of the full run.  bootstrap, bias and genes need the EM and are refused here, before the
+    index is loaded (MATRIX_ONLY_NEEDS_EM)."""
     from . import impute
     from . import parallel
     start_time = datetime.datetime.utcnow()
@@ -496,6 +606,11 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     mapper.strand_mode(strand)
     length_model, _ = mapper.length_model_weights(length_model)
     umi_mismatches = mapper.check_umi_mismatches(umi_mismatches, umi_length)
+    count_matrix = bool(count_matrix) or bool(matrix_only)
+    if matrix_only:
+        for given, flag in ((bootstrap and bootstrap > 0, '-b N'), (bias, '--bias'), (genes, '--genes')):
+            if given:
+                raise ValueError(MATRIX_ONLY_NEEDS_EM % flag)
     whitelist = None
     pooled = barcodes is not None or discover_cells is not None
     if not pooled:
@@ -540,9 +655,10 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     _log_length_model(length_model, single_ended)
     _native.check(_native.hip().skm_pinned_set_device(device))
     index = common.KMerIndex.load(index_path)
-    genes = genes or gene_map is not None
-    gene_names = _gene_map(index, gene_map) if genes else None     # (fails before any read file is opened)
+    genes = genes or (gene_map is not None and not count_matrix)
+    gene_names = _gene_map(index, gene_map) if genes or count_matrix else None     # (fails before any read file is opened)
     gene_counts = [None] * len(groups)
+    matrix_rows, matrix_other, sizes = [None] * len(groups), [None] * len(groups), [None] * len(groups)
     index.device_handle(device)
     paired = not single_ended
     in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
@@ -595,6 +711,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
         in_set = list(range(len(names)))
         gene_counts, observed = [None] * len(names), [None] * len(names)
         summaries, means = [None] * len(names), [None] * len(names)
+        matrix_rows, matrix_other, sizes = [None] * len(names), [None] * len(names), [None] * len(names)
         trace('demultiplexing')
     elif in_set:
         _LOG.info('Mapping %d samples in shared launches', len(in_set))
@@ -602,7 +719,17 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
                    else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
         sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
                                            strand=strand, per_sample_lengths=True, length_model=length_model, bias=bias)
-    if in_set:
+    if in_set and count_matrix:             # (one pass over the set's table where it lies: no dense row)
+        indptr, indices, data, other = sample_set.gene_count_matrix(gene_names[1], gene_names[0].size)
+        for k, i in enumerate(in_set):
+            matrix_rows[i] = (indices[indptr[k]:indptr[k + 1]], data[indptr[k]:indptr[k + 1]])
+            matrix_other[i] = other[k]
+    if in_set and matrix_only:
+        for i, row, mean in zip(in_set, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
+            sizes[i], means[i] = row, mean
+        trace('mapping (set)')
+        del sample_set
+    elif in_set:
         for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
             summaries[i], means[i] = summary, mean
         if bias:
@@ -625,20 +752,40 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
             trace('quantification (set)')
         del sample_set
     for i, group in enumerate(groups):
-        if summaries[i] is not None:
+        if summaries[i] is not None or sizes[i] is not None:
             continue
         _LOG.info('Mapping sample %s', names[i])
         map_result = mapper.map_reads(index, _feeder(list(group), paired, None, None, False), job_count=job_count,
                                       debug=debug, device=device, strand=strand, length_model=length_model,
                                       bias=bias)
-        summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
+        if matrix_only:
+            sizes[i], means[i] = map_result.sizes(), map_result.harmonic_mean_fragment_length
+        else:
+            summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
         if bias:
             observed[i] = map_result.bias_observed()
-        if genes:
-            gene_counts[i] = map_result.gene_unique_counts(gene_names[1], gene_names[0].size)
+        if genes or count_matrix:           # (one dense row of the mapper's own table)
+            unique, other = map_result.gene_unique_counts(gene_names[1], gene_names[0].size)
+            gene_counts[i] = (unique, other)
+            matrix_rows[i], matrix_other[i] = (numpy.flatnonzero(unique), unique[unique != 0]), other
         del map_result
     _LOG.info('Mapped all reads')
     trace('mapping (one by one)')
+    if matrix_only:
+        # units = unaligned + the units of the classes, which the matrix and `other` hold between them
+        aligned = [int(row[1].sum() + other.sum()) for row, other in zip(matrix_rows, matrix_other)]
+        units = [count + int(size[2]) for count, size in zip(aligned, sizes)]
+        for name, total in zip(names, units):
+            if total == 0:
+                raise ValueError('sample %s has no reads' % name)
+        output_count_matrix(output_path, gene_names[0], names, units, *stack_count_rows(matrix_rows), matrix_other)
+        with (output_path / 'samples.tsv').open('w') as f:
+            for name, total, count, mean in zip(names, units, aligned, means):
+                f.write('%s\t%d\t%d\t%.2f\n' % (name, total, count, mean))
+        trace('writing', pause=True)
+        trace(None)
+        _LOG.info('Wrote the count matrix to %s', output_path / 'counts')
+        return
     for name, summary in zip(names, summaries):
         if summary.total == 0:
             raise ValueError('sample %s has no reads' % name)
@@ -684,6 +831,9 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
                             gene_sums(tx_gene, gene_ids.size, numpy.stack(estimates), device=device), '%g')
         _output_gene_matrix(output_path / 'genes.unique_counts.tsv', gene_ids, names,
                             numpy.stack([unique for unique, _ in gene_counts]), '%d')
+    if count_matrix:
+        output_count_matrix(output_path, gene_names[0], names, [summary.total for summary in summaries],
+                            *stack_count_rows(matrix_rows), matrix_other)
     with (output_path / 'samples.tsv').open('w') as f:
         for name, summary, mean in zip(names, summaries, means):
             f.write('%s\t%d\t%d\t%.2f\n' % (name, summary.total, summary.aligned, mean))
@@ -1482,6 +1632,7 @@ def add_many_subcommand_parser(subparsers):
     add_length_model_arguments(parser)
     add_bias_argument(parser)
     add_gene_arguments(parser)
+    add_count_matrix_arguments(parser)
     add_barcode_arguments(parser)
 
 
@@ -1584,9 +1735,23 @@ def add_gene_arguments(parser):
 
 
 def gene_option(opts):
-    """The parsed options: --gene-map implies --genes."""
-    opts['genes'] = bool(opts.get('genes')) or opts.get('gene_map') is not None
+    """The parsed options: --gene-map implies --genes -- unless --count-matrix or --matrix-only is given, which the map
+    then serves: they need genes but do not switch the gene-level tables on.  --matrix-only implies --count-matrix."""
+    opts['count_matrix'] = bool(opts.get('count_matrix')) or bool(opts.get('matrix_only'))
+    opts['genes'] = bool(opts.get('genes')) or (opts.get('gene_map') is not None and not opts['count_matrix'])
     return opts
+
+
+def add_count_matrix_arguments(parser):
+    """--count-matrix and --matrix-only: dest 'count_matrix', 'matrix_only' (gene_option makes the second imply the first)."""
+    parser.add_argument('--count-matrix', action='store_true', dest='count_matrix',
+                        help='also write output/counts/: the sparse gene x cell matrix of the units that lie inside one '
+                             'gene (matrix.mtx, genes.tsv, cells.tsv, matrix.npz), made on the GPU; the genes are the '
+                             'index\'s or those of --gene-map')
+    parser.add_argument('--matrix-only', action='store_true', dest='matrix_only',
+                        help='write the count matrix, samples.tsv and the barcodes.* files only: stop after mapping (and '
+                             'UMI collapse), run no EM, write no folder per sample; implies --count-matrix, refuses -b, '
+                             '--bias and --genes')
 
 
 def add_bias_argument(parser):

@@ -82,6 +82,24 @@ def gene_numbers(tx_gene, n_tx):
     return tx_gene if tx_gene.size else numpy.zeros(1, dtype=numpy.int32)[:0]
 
 
+def read_gene_matrix(handle):
+    """The arrays of a skm_gene_matrix handle (indptr, indices, data, other), copied home; the handle is destroyed."""
+    try:
+        shape = [ctypes.c_int64(0) for _ in range(3)]
+        _native.check(_native.hip().skm_gene_matrix_shape(handle, *[ctypes.byref(word) for word in shape]))
+        n_samples, _, nnz = [int(word.value) for word in shape]
+        indptr = numpy.zeros(n_samples + 1, dtype=numpy.int64)
+        indices = numpy.zeros(max(nnz, 1), dtype=numpy.int32)
+        data = numpy.zeros(max(nnz, 1), dtype=numpy.int64)
+        other = numpy.zeros((max(n_samples, 1), 2), dtype=numpy.int64)
+        _native.check(_native.hip().skm_gene_matrix_read(
+            handle, _native.ptr(indptr, _native.c_i64p), _native.ptr(indices, _native.c_i32p),
+            _native.ptr(data, _native.c_i64p), _native.ptr(other, _native.c_i64p)))
+        return indptr, indices[:nnz], data[:nnz], other[:n_samples]
+    finally:
+        _native.hip().skm_gene_matrix_destroy(handle)
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
@@ -824,6 +842,17 @@ class SampleSet:
                 continue
             _native.check(code)
             return unique, other
+
+    def gene_count_matrix(self, tx_gene, n_genes):
+        """(indptr int64[n_samples + 1], indices int32[nnz], data int64[nnz], other int64[n_samples, 2]): what
+        gene_unique_counts gives, as a CSR over samples made on the device (skm_sample_set_gene_matrix; DESIGN.md
+        section 4, "Count matrix") -- row i holds the genes of sample i with a count, ascending, and no dense row
+        exists anywhere."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_sample_set_gene_matrix(
+            self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
+        return read_gene_matrix(handle)
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
