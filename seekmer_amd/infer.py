@@ -12,6 +12,8 @@ import os
 import pathlib
 import shlex
 import sys
+import time
+import types
 import zipfile
 
 import numpy
@@ -599,247 +601,324 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     collapse): no summarize(), no EM, no folder per sample; it writes counts/, samples.tsv and the barcodes.* files,
     each byte for byte that of the full run.  bootstrap, bias and genes need the EM and are refused here, before the
     index is loaded (MATRIX_ONLY_NEEDS_EM)."""
+    # what the phases below share: every option under its own name (locals(): this stays the first statement, so that a
+    # new option needs no second list), and with them the index, the genes and the trace's clock
+    job = types.SimpleNamespace(**locals(), paired=not single_ended, pooled=barcodes is not None or discover_cells is not None,
+                                index=None, gene_names=None, start_time=datetime.datetime.utcnow(), trace=_phase_trace())
     from . import impute
     from . import parallel
-    start_time = datetime.datetime.utcnow()
-    trace = _phase_trace()
-    mapper.strand_mode(strand)
-    length_model, _ = mapper.length_model_weights(length_model)
-    umi_mismatches = mapper.check_umi_mismatches(umi_mismatches, umi_length)
-    count_matrix = bool(count_matrix) or bool(matrix_only)
-    if matrix_only:
-        for given, flag in ((bootstrap and bootstrap > 0, '-b N'), (bias, '--bias'), (genes, '--genes')):
-            if given:
-                raise ValueError(MATRIX_ONLY_NEEDS_EM % flag)
-    whitelist = None
-    pooled = barcodes is not None or discover_cells is not None
-    if not pooled:
-        if barcode_file is not None:
-            raise ValueError('--barcode-file goes with --barcodes')
-        if umi_length or umi_start:
-            raise ValueError('--umi-length and --umi-start go with --barcodes')
-        if barcode_length is not None:
-            raise ValueError('--barcode-length goes with --discover-cells')
-        if discover_keep_neighbours:
-            raise ValueError('--discover-keep-neighbours goes with --discover-cells')
-        groups = sample_groups(fastq_paths, single_ended)
-        if not groups:
-            raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if single_ended else 'two files per sample'))
-        names = sample_names(groups, names)
-    else:
-        whitelist = barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start,
-                                    barcode_mismatches, min_units, umi_start, umi_length, discover_cells=discover_cells,
-                                    barcode_length=barcode_length, discover_keep_neighbours=discover_keep_neighbours)
-        groups = [tuple(fastq_paths)]
+    groups, names, whitelist = _check_many_options(job, names)
     ranks = parallel.Ranks.from_env()
     if ranks.world > 1:
         ranks.close()
         raise ValueError('infer-many runs in one process on one GPU: start it without a launcher')
-    for path in list(fastq_paths) + ([barcode_file] if pooled else []):
+    _open_run(job, len(groups), whitelist)
+    _native.check(_native.hip().skm_pinned_set_device(device))
+    job.index = common.KMerIndex.load(index_path)
+    job.genes = genes or (gene_map is not None and not job.count_matrix)
+    if job.genes or job.count_matrix:       # (fails before any read file is opened)
+        job.gene_names = _gene_map(job.index, gene_map)
+    job.index.device_handle(device)
+    if not job.pooled:                      # the records are made once: here, or by _map_pooled when the cells are known
+        sizes = [impute.cell_text_bytes(group) for group in groups]
+        in_set = set(sample_set_members(sizes, impute.SAMPLE_SET_MAX_CELL_BYTES))
+        samples = [_Sample(name, group, i in in_set) for i, (name, group) in enumerate(zip(names, groups))]
+    job.trace('index load')
+    if job.pooled:
+        sample_set, samples = _map_pooled(job, whitelist)
+    else:
+        sample_set = _map_set(job, [sample for sample in samples if sample.in_set])
+    if sample_set is not None:
+        _take_from_set(job, sample_set, [sample for sample in samples if sample.in_set])
+        del sample_set                      # (the set ends here, before any sample gets a mapper of its own)
+    for sample in samples:
+        if not sample.in_set:
+            _map_alone(job, sample)         # (the sample's MapResult ends in there, before the next is made)
+    _LOG.info('Mapped all reads')
+    job.trace('mapping (one by one)')
+    _finish(job, samples)
+
+
+class _Sample:
+    """What run_many keeps of one sample -- a file group, or a cell of a pooled run -- from the mapping to the files:
+    name (the folder's) and group (its FASTQ files; () for a cell); in_set, mapped through the sample set and not by a
+    mapper of its own; summary (SummarizedResult) or, with matrix_only, sizes (the sizes() row of its table); mean, the
+    observed harmonic mean fragment length; observed, its hexamer counts (bias); gene_counts, (unique, other) of
+    gene_unique_counts (genes); matrix_row, (gene indices, counts) of the count matrix, and the matrix_other pair that
+    goes with it; set_estimate, the first-pass TPM where the set or the shared bias pass made one; corrected, (summary,
+    TPM) of the set's shared bias pass; estimate, the TPM it was written with.  What was not made is None.  Host values
+    only: a record never holds the SampleSet or a MapResult, whose device memory ends where run_many says."""
+    __slots__ = ('name', 'group', 'in_set', 'summary', 'sizes', 'mean', 'observed', 'gene_counts', 'matrix_row',
+                 'matrix_other', 'set_estimate', 'corrected', 'estimate')
+
+    def __init__(self, name, group, in_set):
+        self.name, self.group, self.in_set = name, group, in_set
+        for field in self.__slots__[3:]:
+            setattr(self, field, None)
+
+    def units(self):
+        """(units, aligned units): the summary's, or without one (matrix_only) from the count-matrix row, `other`
+        and the sizes row -- units = unaligned + the units of the classes, which row and `other` hold between them."""
+        if self.summary is not None:
+            return self.summary.total, self.summary.aligned
+        aligned = int(self.matrix_row[1].sum() + self.matrix_other.sum())
+        return aligned + int(self.sizes[2]), aligned
+
+
+def _check_many_options(job, names):
+    """run_many's checks that need no file and no GPU, in the order in which they refuse.  Settles job.length_model,
+    job.umi_mismatches and job.count_matrix and returns the plan (groups, names, whitelist): the samples' file groups
+    and names with whitelist None -- or, for a pooled run, its one group, names None and the whitelist of
+    barcode_options (None: the cells are to be discovered)."""
+    mapper.strand_mode(job.strand)
+    job.length_model, _ = mapper.length_model_weights(job.length_model)
+    job.umi_mismatches = mapper.check_umi_mismatches(job.umi_mismatches, job.umi_length)
+    job.count_matrix = bool(job.count_matrix) or bool(job.matrix_only)
+    if job.matrix_only:
+        for given, flag in ((job.bootstrap and job.bootstrap > 0, '-b N'), (job.bias, '--bias'), (job.genes, '--genes')):
+            if given:
+                raise ValueError(MATRIX_ONLY_NEEDS_EM % flag)
+    if job.pooled:
+        whitelist = barcode_options(job.fastq_paths, job.single_ended, names, job.barcodes, job.barcode_file,
+                                    job.barcode_start, job.barcode_mismatches, job.min_units, job.umi_start,
+                                    job.umi_length, discover_cells=job.discover_cells, barcode_length=job.barcode_length,
+                                    discover_keep_neighbours=job.discover_keep_neighbours)
+        return [tuple(job.fastq_paths)], None, whitelist
+    if job.barcode_file is not None:
+        raise ValueError('--barcode-file goes with --barcodes')
+    if job.umi_length or job.umi_start:
+        raise ValueError('--umi-length and --umi-start go with --barcodes')
+    if job.barcode_length is not None:
+        raise ValueError('--barcode-length goes with --discover-cells')
+    if job.discover_keep_neighbours:
+        raise ValueError('--discover-keep-neighbours goes with --discover-cells')
+    groups = sample_groups(job.fastq_paths, job.single_ended)
+    if not groups:
+        raise ValueError('no samples: infer-many takes %s' % ('a file per sample' if job.single_ended else 'two files per sample'))
+    return groups, sample_names(groups, names), None
+
+
+def _open_run(job, n_samples, whitelist):
+    """The last checks before the GPU is touched -- every read file exists, and a pooled run's are plain FASTQ --,
+    then the output folder and the log lines that say what the run is."""
+    for path in list(job.fastq_paths) + ([job.barcode_file] if job.pooled else []):
         if not pathlib.Path(path).exists():
             raise ValueError(f'invalid FastQ file: {path}')
-        if pooled and not common.PackedReadFeeder.eligible([path]):
+        if job.pooled and not common.PackedReadFeeder.eligible([path]):
             raise ValueError('%s reads plain FASTQ files: decompress %s first'
-                             % ('--barcodes' if barcodes is not None else '--discover-cells', path))
+                             % ('--barcodes' if job.barcodes is not None else '--discover-cells', path))
     try:
-        output_path.mkdir(parents=True)
+        job.output_path.mkdir(parents=True)
     except FileExistsError:
         _LOG.warning('The output folder exists. Overriding...')
-    if not pooled:
-        _LOG.info('Inferring transcript abundance of %d samples', len(groups))
+    if not job.pooled:
+        _LOG.info('Inferring transcript abundance of %d samples', n_samples)
     elif whitelist is None:
         _LOG.info('Inferring transcript abundance of the cells of one pooled run (about %d cells, found in the barcode reads)',
-                  discover_cells)
+                  job.discover_cells)
     else:
         _LOG.info('Inferring transcript abundance of the cells of one pooled run (%d barcodes)', len(whitelist[0]))
-    _log_length_model(length_model, single_ended)
-    _native.check(_native.hip().skm_pinned_set_device(device))
-    index = common.KMerIndex.load(index_path)
-    genes = genes or (gene_map is not None and not count_matrix)
-    gene_names = _gene_map(index, gene_map) if genes or count_matrix else None     # (fails before any read file is opened)
-    gene_counts = [None] * len(groups)
-    matrix_rows, matrix_other, sizes = [None] * len(groups), [None] * len(groups), [None] * len(groups)
-    index.device_handle(device)
-    paired = not single_ended
-    in_set = sample_set_members([impute.cell_text_bytes(group) for group in groups], impute.SAMPLE_SET_MAX_CELL_BYTES)
-    observed = [None] * len(groups)
-    summaries, means = [None] * len(groups), [None] * len(groups)
-    set_estimates = {}
-    trace('index load')
-    sample_set = None
-    if pooled:
-        # the cells of the pooled run are the samples, all of them in one set
-        parse_threads = 0 if debug or job_count <= 1 else min(int(job_count), 8)     # (one large file: -j parses it)
-        discovery = None
-        if whitelist is None:
-            # no whitelist: the census of the barcode reads gives one (the barcode file is read again below)
-            n_units = min(mapper.fastq_records(path) for path in [barcode_file] + list(fastq_paths))
-            picked, _, found = mapper.discover_barcodes(
-                common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads), barcode_length, discover_cells,
-                start=barcode_start, drop_neighbours=not discover_keep_neighbours, device=device, n_units=n_units)
-            discovery = _output_discovery(output_path, picked, found, discover_cells, barcode_length, barcode_start,
-                                          discover_keep_neighbours)
-            _LOG.info('Barcodes of %d units: %d counted, %d short, %d unreadable, %d distinct; rank %d has %d, threshold %d: '
-                      '%d candidates, %d dropped as neighbours, %d picked', found['units'], found['counted'], found['short'],
-                      found['unreadable'], found['distinct'], found['rank'], found['rank_count'], found['threshold'],
-                      found['candidates'], found['dropped'], found['picked'])
-            whitelist = mapper.check_whitelist(picked)
-            trace('cell discovery')
-        table = mapper.BarcodeTable(*whitelist, device=device)
-        sample_set, kept, demux = mapper.map_barcoded(
-            index, table, common.PackedReadFeeder([barcode_file], paired=False, threads=parse_threads),
-            common.PackedReadFeeder(list(fastq_paths), paired=paired, threads=parse_threads), paired, start=barcode_start,
-            mismatches=barcode_mismatches, min_units=min_units, device=device, strand=strand, per_sample_lengths=True,
-            length_model=length_model, bias=bias, umi_start=umi_start, umi_length=umi_length,
-            umi_mismatches=umi_mismatches)
-        _LOG.info('Barcodes of %d units: %d exact, %d corrected, %d ambiguous, %d without a match, %d short or unreadable',
-                  demux['units'], *[demux[name] for name in mapper.BARCODE_STATS])
-        if umi_length and umi_mismatches:
-            _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed, %d of them only for a UMI '
-                      'one substitution away', umi_length, demux['umi_unreadable'], demux['umi_duplicates'],
-                      demux['umi_near_duplicates'])
-        elif umi_length:
-            _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed', umi_length,
-                      demux['umi_unreadable'], demux['umi_duplicates'])
-        _output_barcodes(output_path, table, kept, demux, barcode_start, barcode_mismatches, min_units, umi_start, umi_length,
-                         discovery=discovery, umi_mismatches=umi_mismatches)
-        if not kept.size:
-            raise ValueError('no cell has %d units or more (see %s)' % (min_units, output_path / 'barcodes.tsv'))
-        names = [table.names[c] for c in kept]
-        _LOG.info('%d cells have %d units or more', len(names), min_units)
-        groups = [()] * len(names)
-        in_set = list(range(len(names)))
-        gene_counts, observed = [None] * len(names), [None] * len(names)
-        summaries, means = [None] * len(names), [None] * len(names)
-        matrix_rows, matrix_other, sizes = [None] * len(names), [None] * len(names), [None] * len(names)
-        trace('demultiplexing')
-    elif in_set:
-        _LOG.info('Mapping %d samples in shared launches', len(in_set))
-        feeders = [common.PackedReadFeeder(list(groups[i]), paired=paired) if common.PackedReadFeeder.eligible(groups[i])
-                   else common.NativeReadFeeder(list(groups[i]), paired=paired) for i in in_set]
-        sample_set = mapper.map_sample_set(index, feeders, job_count=1 if debug else max(1, job_count), device=device,
-                                           strand=strand, per_sample_lengths=True, length_model=length_model, bias=bias)
-    if in_set and count_matrix:             # (one pass over the set's table where it lies: no dense row)
-        indptr, indices, data, other = sample_set.gene_count_matrix(gene_names[1], gene_names[0].size)
-        for k, i in enumerate(in_set):
-            matrix_rows[i] = (indices[indptr[k]:indptr[k + 1]], data[indptr[k]:indptr[k + 1]])
-            matrix_other[i] = other[k]
-    if in_set and matrix_only:
-        for i, row, mean in zip(in_set, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
-            sizes[i], means[i] = row, mean
-        trace('mapping (set)')
-        del sample_set
-    elif in_set:
-        for i, summary, mean in zip(in_set, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
-            summaries[i], means[i] = summary, mean
-        if bias:
-            for i, row in zip(in_set, sample_set.bias_observed()):
-                observed[i] = row
-        if genes:                           # (one pass over the set's table where it lies)
-            for i, unique, other in zip(in_set, *sample_set.gene_unique_counts(gene_names[1], gene_names[0].size)):
-                gene_counts[i] = (unique, other)
-        trace('mapping (set)')
-        # (the main estimates of the set's samples in shared EM launches, from the table where it lies)
-        if all(summaries[i].total for i in in_set) and impute.use_set_quant(
-                len(in_set), index.transcripts.size, sum(summaries[i].class_count.size for i in in_set)):
-            try:
-                set_estimates = dict(zip(in_set, sample_set.quantify()))
-            except _native.NativeError as error:
-                # (a sample that leaves no abundance above the floor: the loop below writes the samples before
-                # it and raises at that one, as it always has)
-                if error.code != _native.SKM_ERR_UNDEFINED:
-                    raise
-            trace('quantification (set)')
-        del sample_set
-    for i, group in enumerate(groups):
-        if summaries[i] is not None or sizes[i] is not None:
-            continue
-        _LOG.info('Mapping sample %s', names[i])
-        map_result = mapper.map_reads(index, _feeder(list(group), paired, None, None, False), job_count=job_count,
-                                      debug=debug, device=device, strand=strand, length_model=length_model,
-                                      bias=bias)
-        if matrix_only:
-            sizes[i], means[i] = map_result.sizes(), map_result.harmonic_mean_fragment_length
-        else:
-            summaries[i], means[i] = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
-        if bias:
-            observed[i] = map_result.bias_observed()
-        if genes or count_matrix:           # (one dense row of the mapper's own table)
-            unique, other = map_result.gene_unique_counts(gene_names[1], gene_names[0].size)
-            gene_counts[i] = (unique, other)
-            matrix_rows[i], matrix_other[i] = (numpy.flatnonzero(unique), unique[unique != 0]), other
-        del map_result
-    _LOG.info('Mapped all reads')
-    trace('mapping (one by one)')
-    if matrix_only:
-        # units = unaligned + the units of the classes, which the matrix and `other` hold between them
-        aligned = [int(row[1].sum() + other.sum()) for row, other in zip(matrix_rows, matrix_other)]
-        units = [count + int(size[2]) for count, size in zip(aligned, sizes)]
-        for name, total in zip(names, units):
-            if total == 0:
-                raise ValueError('sample %s has no reads' % name)
-        output_count_matrix(output_path, gene_names[0], names, units, *stack_count_rows(matrix_rows), matrix_other)
-        with (output_path / 'samples.tsv').open('w') as f:
-            for name, total, count, mean in zip(names, units, aligned, means):
-                f.write('%s\t%d\t%d\t%.2f\n' % (name, total, count, mean))
-        trace('writing', pause=True)
-        trace(None)
-        _LOG.info('Wrote the count matrix to %s', output_path / 'counts')
+    _log_length_model(job.length_model, job.single_ended)
+
+
+def _map_pooled(job, whitelist):
+    """The pooled route: the cells of the pooled run are the samples, all of them in one set.  Finds the cells where
+    there is no whitelist, demultiplexes and maps (mapper.map_barcoded) and writes the barcodes.* files -> (the
+    SampleSet, the records of the cells that are kept)."""
+    parse_threads = 0 if job.debug or job.job_count <= 1 else min(int(job.job_count), 8)     # (one large file: -j parses it)
+    discovery = None
+    if whitelist is None:
+        # no whitelist: the census of the barcode reads gives one (the barcode file is read again below)
+        n_units = min(mapper.fastq_records(path) for path in [job.barcode_file] + list(job.fastq_paths))
+        picked, _, found = mapper.discover_barcodes(
+            common.PackedReadFeeder([job.barcode_file], paired=False, threads=parse_threads), job.barcode_length,
+            job.discover_cells, start=job.barcode_start, drop_neighbours=not job.discover_keep_neighbours,
+            device=job.device, n_units=n_units)
+        discovery = _output_discovery(job.output_path, picked, found, job.discover_cells, job.barcode_length,
+                                      job.barcode_start, job.discover_keep_neighbours)
+        _LOG.info('Barcodes of %d units: %d counted, %d short, %d unreadable, %d distinct; rank %d has %d, threshold %d: '
+                  '%d candidates, %d dropped as neighbours, %d picked', found['units'], found['counted'], found['short'],
+                  found['unreadable'], found['distinct'], found['rank'], found['rank_count'], found['threshold'],
+                  found['candidates'], found['dropped'], found['picked'])
+        whitelist = mapper.check_whitelist(picked)
+        job.trace('cell discovery')
+    table = mapper.BarcodeTable(*whitelist, device=job.device)
+    sample_set, kept, demux = mapper.map_barcoded(
+        job.index, table, common.PackedReadFeeder([job.barcode_file], paired=False, threads=parse_threads),
+        common.PackedReadFeeder(list(job.fastq_paths), paired=job.paired, threads=parse_threads), job.paired,
+        start=job.barcode_start, mismatches=job.barcode_mismatches, min_units=job.min_units, device=job.device,
+        strand=job.strand, per_sample_lengths=True, length_model=job.length_model, bias=job.bias, umi_start=job.umi_start,
+        umi_length=job.umi_length, umi_mismatches=job.umi_mismatches)
+    _LOG.info('Barcodes of %d units: %d exact, %d corrected, %d ambiguous, %d without a match, %d short or unreadable',
+              demux['units'], *[demux[name] for name in mapper.BARCODE_STATS])
+    if job.umi_length and job.umi_mismatches:
+        _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed, %d of them only for a UMI '
+                  'one substitution away', job.umi_length, demux['umi_unreadable'], demux['umi_duplicates'],
+                  demux['umi_near_duplicates'])
+    elif job.umi_length:
+        _LOG.info('UMIs of %d bases: %d units without a readable one, %d duplicates removed', job.umi_length,
+                  demux['umi_unreadable'], demux['umi_duplicates'])
+    _output_barcodes(job.output_path, table, kept, demux, job.barcode_start, job.barcode_mismatches, job.min_units,
+                     job.umi_start, job.umi_length, discovery=discovery, umi_mismatches=job.umi_mismatches)
+    if not kept.size:
+        raise ValueError('no cell has %d units or more (see %s)' % (job.min_units, job.output_path / 'barcodes.tsv'))
+    samples = [_Sample(table.names[c], (), True) for c in kept]
+    _LOG.info('%d cells have %d units or more', len(samples), job.min_units)
+    job.trace('demultiplexing')
+    return sample_set, samples
+
+
+def _map_set(job, members):
+    """The set route: the samples that share launches, through one mapper.SampleSet -> the set, or None when no
+    sample goes that way."""
+    if not members:
+        return None
+    _LOG.info('Mapping %d samples in shared launches', len(members))
+    feeders = [common.PackedReadFeeder(list(sample.group), paired=job.paired) if common.PackedReadFeeder.eligible(sample.group)
+               else common.NativeReadFeeder(list(sample.group), paired=job.paired) for sample in members]
+    return mapper.map_sample_set(job.index, feeders, job_count=1 if job.debug else max(1, job.job_count), device=job.device,
+                                 strand=job.strand, per_sample_lengths=True, length_model=job.length_model, bias=job.bias)
+
+
+def _take_from_set(job, sample_set, members):
+    """Fills the records of the set's samples, `members` in the set's order, with what the run needs of the set:
+    count-matrix rows, then sizes (matrix_only) or summaries with hexamer rows, gene counts and -- inside the regime of
+    impute.use_set_quant -- the main estimates from shared EM launches on the table where it lies."""
+    from . import impute
+    n_genes = None if job.gene_names is None else job.gene_names[0].size
+    if job.count_matrix:                    # (one pass over the set's table where it lies: no dense row)
+        indptr, indices, data, other = sample_set.gene_count_matrix(job.gene_names[1], n_genes)
+        for k, sample in enumerate(members):
+            sample.matrix_row = (indices[indptr[k]:indptr[k + 1]], data[indptr[k]:indptr[k + 1]])
+            sample.matrix_other = other[k]
+    if job.matrix_only:
+        for sample, row, mean in zip(members, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
+            sample.sizes, sample.mean = row, mean
+        job.trace('mapping (set)')
         return
-    for name, summary in zip(names, summaries):
-        if summary.total == 0:
-            raise ValueError('sample %s has no reads' % name)
-        if bootstrap > 0 and summary.aligned > RESAMPLE_LIMIT:
-            raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
-                             % (RESAMPLE_LIMIT, name, summary.aligned))
-    estimates = [None] * len(groups)        # (the TPM each sample is written with)
-    corrected = {}
-    if bias and in_set:
-        # the second pass of the set's samples together; a sample that leaves no abundance above the floor, in
-        # either pass, sends them all through the loop below, which writes the samples before it and raises there
+    for sample, summary, mean in zip(members, sample_set.summarize(), sample_set.harmonic_mean_fragment_lengths()):
+        sample.summary, sample.mean = summary, mean
+    if job.bias:
+        for sample, row in zip(members, sample_set.bias_observed()):
+            sample.observed = row
+    if job.genes:                           # (one pass over the set's table where it lies)
+        for sample, unique, other in zip(members, *sample_set.gene_unique_counts(job.gene_names[1], n_genes)):
+            sample.gene_counts = (unique, other)
+    job.trace('mapping (set)')
+    if all(sample.summary.total for sample in members) and impute.use_set_quant(
+            len(members), job.index.transcripts.size, sum(sample.summary.class_count.size for sample in members)):
         try:
-            for i in in_set:
-                if i not in set_estimates:
-                    set_estimates[i] = quantify(summaries[i], device=device)
-            passed, second = bias_pass_many(index, [summaries[i] for i in in_set], [set_estimates[i] for i in in_set],
-                                            [observed[i] for i in in_set], strand, device=device)
-            corrected = {i: (passed[k], second[k]) for k, i in enumerate(in_set)}
+            for sample, estimate in zip(members, sample_set.quantify()):
+                sample.set_estimate = estimate
         except _native.NativeError as error:
+            # (a sample that leaves no abundance above the floor: _finish writes the samples before it and raises
+            # at that one, as it always has)
             if error.code != _native.SKM_ERR_UNDEFINED:
                 raise
-        trace('sequence bias (set)')
-    for i, (name, summary) in enumerate(zip(names, summaries)):
-        _LOG.info('Quantifying sample %s', name)
-        if i in corrected:
-            summary, main_result = corrected[i]
-        else:
-            main_result = set_estimates[i] if i in set_estimates else quantify(summary, device=device)
-            if bias:
-                summary, main_result = bias_pass(index, summary, main_result, observed[i], strand, device=device)
-        trace('quantification', pause=True)
-        bootstrapped_results = bootstrap_quantify(summary, main_result, bootstrap, seed=seed, device=device)
-        trace('bootstraps', pause=True)
-        sample_path = output_path / name
-        sample_path.mkdir(exist_ok=True)
-        output_results(sample_path, index, start_time, summary, main_result, bootstrapped_results,
-                       genes=gene_names + gene_counts[i] if genes else None, device=device)
-        estimates[i] = main_result
-        trace('writing', pause=True)
-    if genes:
-        gene_ids, tx_gene = gene_names
-        _output_gene_matrix(output_path / 'genes.tpm.tsv', gene_ids, names,
-                            gene_sums(tx_gene, gene_ids.size, numpy.stack(estimates), device=device), '%g')
-        _output_gene_matrix(output_path / 'genes.unique_counts.tsv', gene_ids, names,
-                            numpy.stack([unique for unique, _ in gene_counts]), '%d')
-    if count_matrix:
-        output_count_matrix(output_path, gene_names[0], names, [summary.total for summary in summaries],
-                            *stack_count_rows(matrix_rows), matrix_other)
-    with (output_path / 'samples.tsv').open('w') as f:
-        for name, summary, mean in zip(names, summaries, means):
-            f.write('%s\t%d\t%d\t%.2f\n' % (name, summary.total, summary.aligned, mean))
-    trace('writing', pause=True)
-    trace(None)
-    _LOG.info('Wrote results to %s', output_path)
+        job.trace('quantification (set)')
+
+
+def _map_alone(job, sample):
+    """The one-by-one route: fills one record from a mapper of its own on the resident index.  The MapResult, and
+    with it the sample's table in device memory, ends when this returns."""
+    _LOG.info('Mapping sample %s', sample.name)
+    map_result = mapper.map_reads(job.index, _feeder(list(sample.group), job.paired, None, None, False),
+                                  job_count=job.job_count, debug=job.debug, device=job.device, strand=job.strand,
+                                  length_model=job.length_model, bias=job.bias)
+    if job.matrix_only:
+        sample.sizes, sample.mean = map_result.sizes(), map_result.harmonic_mean_fragment_length
+    else:
+        sample.summary, sample.mean = map_result.summarize().detach(), map_result.harmonic_mean_fragment_length
+    if job.bias:
+        sample.observed = map_result.bias_observed()
+    if job.genes or job.count_matrix:       # (one dense row of the mapper's own table)
+        unique, other = map_result.gene_unique_counts(job.gene_names[1], job.gene_names[0].size)
+        sample.gene_counts = (unique, other)
+        sample.matrix_row, sample.matrix_other = (numpy.flatnonzero(unique), unique[unique != 0]), other
+
+
+def _finish(job, samples):
+    """Both endings: the refusals that need the units, before anything of a sample is written; unless matrix_only the
+    estimates, folders and gene tables (_quantify_samples); then output/counts/ and output/samples.tsv."""
+    units = [sample.units() for sample in samples]
+    for sample, (total, aligned) in zip(samples, units):
+        if total == 0:
+            raise ValueError('sample %s has no reads' % sample.name)
+        if not job.matrix_only and job.bootstrap > 0 and aligned > RESAMPLE_LIMIT:
+            raise ValueError('-b/--bootstrap resamples at most %d aligned units per replicate; sample %s has %d'
+                             % (RESAMPLE_LIMIT, sample.name, aligned))
+    if not job.matrix_only:
+        _quantify_samples(job, samples)
+    if job.count_matrix:
+        output_count_matrix(job.output_path, job.gene_names[0], [sample.name for sample in samples],
+                            [total for total, _ in units], *stack_count_rows(sample.matrix_row for sample in samples),
+                            [sample.matrix_other for sample in samples])
+    with (job.output_path / 'samples.tsv').open('w') as f:
+        for sample, (total, aligned) in zip(samples, units):
+            f.write('%s\t%d\t%d\t%.2f\n' % (sample.name, total, aligned, sample.mean))
+    job.trace('writing', pause=True)
+    job.trace(None)
+    if job.matrix_only:
+        _LOG.info('Wrote the count matrix to %s', job.output_path / 'counts')
+    else:
+        _LOG.info('Wrote results to %s', job.output_path)
+
+
+def _quantify_samples(job, samples):
+    """What the full ending has over matrix_only: the shared bias pass of the set's samples, every sample's estimate,
+    bootstraps and folder in the order of the samples, and the gene tables of the run."""
+    members = [sample for sample in samples if sample.in_set]
+    if job.bias and members:
+        _bias_pass_set(job, members)
+    for sample in samples:
+        _quantify_and_write(job, sample)
+    if job.genes:
+        gene_ids, tx_gene = job.gene_names
+        names, estimates = [sample.name for sample in samples], numpy.stack([sample.estimate for sample in samples])
+        _output_gene_matrix(job.output_path / 'genes.tpm.tsv', gene_ids, names,
+                            gene_sums(tx_gene, gene_ids.size, estimates, device=job.device), '%g')
+        _output_gene_matrix(job.output_path / 'genes.unique_counts.tsv', gene_ids, names,
+                            numpy.stack([sample.gene_counts[0] for sample in samples]), '%d')
+
+
+def _bias_pass_set(job, members):
+    """The second pass of the set's samples together (bias_pass_many) -> their `corrected`.  A sample that leaves no
+    abundance above the floor, in either pass, leaves them all without: _quantify_and_write then takes them one by
+    one, writes the samples before that one and raises there."""
+    try:
+        for sample in members:
+            if sample.set_estimate is None:
+                sample.set_estimate = quantify(sample.summary, device=job.device)
+        passed, second = bias_pass_many(job.index, [sample.summary for sample in members],
+                                        [sample.set_estimate for sample in members],
+                                        [sample.observed for sample in members], job.strand, device=job.device)
+        for k, sample in enumerate(members):
+            sample.corrected = (passed[k], second[k])
+    except _native.NativeError as error:
+        if error.code != _native.SKM_ERR_UNDEFINED:
+            raise
+    job.trace('sequence bias (set)')
+
+
+def _quantify_and_write(job, sample):
+    """One sample's estimate (the set's, or quantify() and bias_pass here), its bootstraps and its folder."""
+    _LOG.info('Quantifying sample %s', sample.name)
+    if sample.corrected is not None:
+        summary, main_result = sample.corrected
+    else:
+        summary = sample.summary
+        main_result = sample.set_estimate if sample.set_estimate is not None else quantify(summary, device=job.device)
+        if job.bias:
+            summary, main_result = bias_pass(job.index, summary, main_result, sample.observed, job.strand, device=job.device)
+    job.trace('quantification', pause=True)
+    bootstrapped_results = bootstrap_quantify(summary, main_result, job.bootstrap, seed=job.seed, device=job.device)
+    job.trace('bootstraps', pause=True)
+    sample_path = job.output_path / sample.name
+    sample_path.mkdir(exist_ok=True)
+    output_results(sample_path, job.index, job.start_time, summary, main_result, bootstrapped_results,
+                   genes=job.gene_names + sample.gene_counts if job.genes else None, device=job.device)
+    sample.estimate = main_result
+    job.trace('writing', pause=True)
 
 
 def barcode_options(fastq_paths, single_ended, names, barcodes, barcode_file, barcode_start, barcode_mismatches,
@@ -943,8 +1022,6 @@ def _phase_trace():
     """SKM_TRACE_INFER (set to anything): run_many's host wall time per phase on stderr.  trace(phase) closes the
     lap since the last call and prints it; with pause=True the lap is added to the phase's sum instead, and
     trace(None) prints the sums.  Without the switch the calls do nothing."""
-    import sys
-    import time
     if os.environ.get('SKM_TRACE_INFER') is None:
         return lambda phase, pause=False: None
     state = {'last': time.perf_counter(), 'sums': {}}
@@ -990,7 +1067,6 @@ def _feeder(fastq_paths, paired, parse_threads, shard, keep_reference_batches, s
     of 65 536, seekmer/common.py:17) go through common.NativeReadFeeder: plain files parsed by up to 8 threads, into page-locked slabs when
     there is enough text (> 4 GiB) to pay for pinning them, in batches of 2^18 units (2^20 above
     16 GiB of text); parse_threads 0 = its sequential engine."""
-    import os
     cores = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
     total = 0
     for path in fastq_paths:
@@ -1030,7 +1106,6 @@ def finish(map_result, ranks, quantify_ranks, comm=None):
         return summarized, quantify(summarized)
     _LOG.info('Quantifying transcripts')
     tpm = quantify_ranks(map_result)
-    import os
     if comm and os.environ.get('SKM_HANDOVER') == 'rccl':
         parallel.hand_over_device(map_result, comm, ranks)
         return (map_result.summarize() if ranks.rank == 0 else None), tpm
