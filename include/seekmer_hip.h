@@ -275,6 +275,16 @@ int skm_mapper_keep_spans(skm_mapper *mapper, int enable);
 int skm_mapper_copy_records(skm_mapper *mapper, int64_t first_read, int64_t n_reads, uint32_t *out,
                             int32_t *record_words, int32_t *words_per_read);
 int skm_pack_stage_reads(int32_t words_per_read, int32_t *reads_per_block);
+/* The map kernel exists twice, over two layouts of its unit contexts: packed (more contexts in a
+ * workgroup's LDS; reads and target lists up to fixed bounds) and wide (everything the library accepts).
+ * skm_map_geometry: which one a launch takes -- *packed 1 or 0 --, its contexts per workgroup and its
+ * grid, from the launch's bounds alone: units, longest read, the index's longest target list
+ * (skm_index_info: max_target_count), compute units of the device, block_cap = a cap on the grid (0: none).
+ * No GPU is needed.  skm_mapper_map_layout: the same three of the mapper's last launch (SKM_ERR_STATE
+ * before the first batch). */
+int skm_map_geometry(int64_t n_units, int32_t max_read_len, int32_t max_target_count, int32_t cu_count,
+                     int32_t block_cap, int32_t *packed, int32_t *contexts, int64_t *blocks);
+int skm_mapper_map_layout(skm_mapper *mapper, int32_t *packed, int32_t *contexts, int32_t *blocks);
 /* Strand-specific libraries (kallisto's --fr-stranded / --rf-stranded).  Every target entry of a
  * unit is signed: e >= 0 means mate 1 (or the single read) lies in transcript e's own orientation,
  * e < 0 that it lies antisense to transcript ~e.  SKM_STRAND_FR keeps a unit's entries with

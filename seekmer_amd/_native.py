@@ -99,6 +99,9 @@ HIP_SYMBOLS = {
     'skm_mapper_keep_spans': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_copy_records': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_u32p, c_i32p, c_i32p]),
     'skm_pack_stage_reads': (ctypes.c_int, [ctypes.c_int32, c_i32p]),
+    'skm_map_geometry': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       c_i32p, c_i32p, c_i64p]),
+    'skm_mapper_map_layout': (ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p]),
     'skm_mapper_set_strand': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'skm_mapper_set_length_weights': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_mapper_set_bias': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),

@@ -175,12 +175,18 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
 
     SKM_TRY(m->batch_ctl.ensure(BC_WORDS));
 
-    // launch geometry: persistent blocks of 256 lanes, each with MAP_CONTEXTS unit contexts in LDS
-    // (just under 40 KB -> 4 blocks per CU); fewer blocks when the per-context list workspace
-    // (2 lists of max_target_count entries) would not fit the budget
-    constexpr int64_t CONTEXTS = MAP_CONTEXTS;
-    int64_t blocks = std::min<int64_t>((n_units + CONTEXTS - 1) / CONTEXTS, (int64_t)ix->cu_count * MAP_BLOCKS_PER_CU);
-    if (m->test_map_blocks) blocks = std::min<int64_t>(blocks, m->test_map_blocks);
+    // launch geometry: persistent blocks of 256 lanes, each with its kernel's unit contexts in LDS (just
+    // under 40 KB -> 4 blocks per CU).  The packed contexts where the launch's bounds allow them, the
+    // wide ones otherwise (map_geometry); the relaunch after an arena overflow is the same launch again.
+    const MapGeometry geometry = map_geometry(n_units, max_len, ix->d.max_target_count, ix->cu_count,
+                                              m->test_map_blocks, m->test_map_layout);
+    if (geometry.packed < 0)
+        return fail(SKM_ERR_ARG, "SKM_TEST_MAP_LAYOUT=packed: reads of %d bases or lists of %d targets do not fit",
+                    max_len, (int)ix->d.max_target_count);
+    const int64_t CONTEXTS = geometry.contexts;
+    const int64_t blocks = geometry.blocks;
+    m->last_map_packed = geometry.packed;
+    m->last_map_contexts = geometry.contexts;
     // per context: mask extension words (live + staging, two mates) for slices > 64 targets
     const int64_t ext_words = std::max<int64_t>(0, (ix->d.max_target_count + 63) / 64 - 1);
     SKM_TRY(m->workspace.ensure((size_t)(blocks * CONTEXTS * 4 * ext_words * 2 + 16)));
@@ -233,7 +239,7 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
         b.ids_capacity = (int64_t)m->unit_entries.cap;
         b.ids_chunk = attempt == 0 ? MAP_ARENA_CHUNK : 0;
         HIP_TRY(hipMemsetAsync(m->batch_ctl.p, 0, BC_WORDS * sizeof(unsigned long long), m->stream));
-        launch_map_units(ix->d, b, m->grid_blocks, m->want_stats, m->stream);
+        launch_map_units(ix->d, b, m->grid_blocks, m->want_stats, geometry.packed == 1, m->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(m->ev[2], m->stream));
         unsigned long long *cursor_and_flag = m->pinned + 32;
@@ -385,6 +391,11 @@ extern "C" int skm_mapper_create(skm_index *ix, skm_mapper **out)
         if (n < 1 || n > (1LL << 30))
             return fail(SKM_ERR_ARG, "SKM_TEST_MAP_BLOCKS must be a number from 1 to 2^30, not '%s'", v);
         m->test_map_blocks = (int)n;
+    }
+    if (const char *v = getenv("SKM_TEST_MAP_LAYOUT")) {         // test hook: the map kernel of every launch
+        if (!strcmp(v, "wide")) m->test_map_layout = MAP_LAYOUT_WIDE;
+        else if (!strcmp(v, "packed")) m->test_map_layout = MAP_LAYOUT_PACKED;   // (a launch that does not fit fails)
+        else return fail(SKM_ERR_ARG, "SKM_TEST_MAP_LAYOUT must be 'wide' or 'packed', not '%s'", v);
     }
     SKM_TRY(table_reset(m.get(), first_slots));
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1152,6 +1163,30 @@ extern "C" int skm_pack_stage_reads(int32_t words_per_read, int32_t *reads_per_b
 {
     if (words_per_read < 1 || !reads_per_block) return fail(SKM_ERR_ARG, "bad argument");
     *reads_per_block = pack_stage_reads(words_per_read);
+    return SKM_OK;
+}
+
+extern "C" int skm_map_geometry(int64_t n_units, int32_t max_read_len, int32_t max_target_count, int32_t cu_count,
+                                int32_t block_cap, int32_t *packed, int32_t *contexts, int64_t *blocks)
+{
+    if (n_units < 0 || max_read_len < 0 || max_target_count < 0 || cu_count < 1 || block_cap < 0 || !packed || !contexts || !blocks)
+        return fail(SKM_ERR_ARG, "bad argument");
+    const MapGeometry g = map_geometry(n_units, max_read_len, max_target_count, cu_count, block_cap, MAP_LAYOUT_AUTO);
+    *packed = g.packed;
+    *contexts = g.contexts;
+    *blocks = g.blocks;
+    return SKM_OK;
+}
+
+extern "C" int skm_mapper_map_layout(skm_mapper *m, int32_t *packed, int32_t *contexts, int32_t *blocks)
+{
+    if (!m || !packed || !contexts || !blocks) return fail(SKM_ERR_ARG, "NULL argument");
+    (void)wait_jobs(m, 0, false);
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (m->last_map_packed < 0) return fail(SKM_ERR_STATE, "no batch has been mapped yet");
+    *packed = m->last_map_packed;
+    *contexts = m->last_map_contexts;
+    *blocks = m->grid_blocks;
     return SKM_OK;
 }
 

@@ -101,6 +101,8 @@ struct skm_mapper {
     bool test_class_slots = false;             // SKM_TEST_CLASS_SLOTS: table_reserve[_for_sample] leave the slot count alone
     int64_t deferred_grows = 0;                // table_grow calls with units in flight (after a pass that deferred units)
     int test_map_blocks = 0;                   // SKM_TEST_MAP_BLOCKS: a cap on the map kernel's grid (0: none)
+    int test_map_layout = 0;                   // SKM_TEST_MAP_LAYOUT: MAP_LAYOUT_WIDE / _PACKED instead of map_geometry's choice
+    int last_map_packed = -1, last_map_contexts = 0;   // skm_mapper_map_layout: the kernel of the last launch (-1: none yet)
     int64_t map_relaunches = 0;                // map kernel launches repeated because the entry arena overflowed
     unsigned long long stats_total[48] = {0};
     // ---- host batches: staging lanes + one worker (skm_mapper_map_batch[_async])

@@ -48,11 +48,59 @@ struct MapBatch {
 #endif
 constexpr int MAP_THREADS = SKM_MAP_THREADS;
 constexpr int MAP_BLOCKS_PER_CU = 4;
-#ifndef SKM_MAP_CONTEXTS
-#define SKM_MAP_CONTEXTS 480
-#endif
-constexpr int MAP_CONTEXTS = SKM_MAP_CONTEXTS;   // unit contexts per block: 16 words + 7 ring entries each, 4 blocks in 160 KB of LDS
+constexpr int MAP_LDS_PER_BLOCK = 160 * 1024 / MAP_BLOCKS_PER_CU;   // bytes of LDS a block may take
 constexpr int MAP_ARENA_CHUNK = 2048;            // ids a wave takes from the entry arena per atomic
+
+// ---- unit contexts of the map kernel: two layouts of one body (skm_map.hip: WideContexts, PackedContexts)
+// The WIDE layout holds every launch the library accepts: 16 words + 7 ring entries + half a pair counter a
+// context, 80 bytes, 480 contexts a block.  The PACKED layout keeps the same fields in 13 words:
+//   state word   state | first hit kept | attempt | list size n | list length + 1 | list orientation
+//   left word    span.begin | span.end | "is ACGT" bits of the read's last 8 bases
+//   scan word    scan position | read length | "is ACGT" bits of the read's first 8 bases
+// and two bits a pair slot for the pair counter: 66 1/8 bytes, MAP_CONTEXTS contexts in the same LDS.  What the
+// widths below cannot hold takes the wide kernel (map_geometry).
+constexpr int MAP_CONTEXTS_WIDE = 480;
+#ifndef SKM_MAP_CONTEXTS
+#define SKM_MAP_CONTEXTS 576
+#endif
+constexpr int MAP_CONTEXTS = SKM_MAP_CONTEXTS;   // contexts per block of the packed layout (tuning builds: at most what the LDS holds)
+constexpr int MAP_PACKED_POS_BITS = 12;          // begin, end, scan position, read length: 0 .. read length
+constexpr int MAP_PACKED_EDGE_BITS = 8;          // "is ACGT" of 8 bases
+constexpr int MAP_PACKED_STATE_BITS = 5;         // (skm_map.hip asserts its last state fits)
+constexpr int MAP_PACKED_COUNT_BITS = 12;        // entries left of the running list: 0 .. its length
+constexpr int MAP_PACKED_TLEN_BITS = 12;         // length of the list's slice + 1 (0: the list is still to come)
+static_assert(2 * MAP_PACKED_POS_BITS + MAP_PACKED_EDGE_BITS == 32, "three fields a word");
+static_assert(MAP_PACKED_STATE_BITS + 2 + MAP_PACKED_COUNT_BITS + MAP_PACKED_TLEN_BITS + 1 == 32, "the state word");
+constexpr int MAP_PACKED_MAX_LEN = (1 << MAP_PACKED_POS_BITS) - 1;           // longest read of a packed launch
+constexpr int MAP_PACKED_MAX_TARGETS =                                       // largest max_target_count of one
+    (1 << MAP_PACKED_COUNT_BITS) - 1 < (1 << MAP_PACKED_TLEN_BITS) - 2 ? (1 << MAP_PACKED_COUNT_BITS) - 1
+                                                                       : (1 << MAP_PACKED_TLEN_BITS) - 2;
+static_assert(MAP_CONTEXTS % 2 == 0 && MAP_CONTEXTS_WIDE % 2 == 0, "pair slots");
+static_assert(MAP_CONTEXTS < 0x8000 && MAP_CONTEXTS_WIDE < 0x8000, "a ring entry is context | 0x8000");
+
+// Which kernel a launch takes and its grid: a pure function of the launch's bounds.
+//   max_len, max_target_count   the packed layout's bounds above (a context's unit index has 32 bits in both
+//                               layouts -- narrowing it frees no word -- so units per block bound nothing)
+//   block_cap                   SKM_TEST_MAP_BLOCKS, 0 = none
+//   force                       MAP_LAYOUT_AUTO, or a test's choice; packed < 0: forced packed does not fit
+enum : int { MAP_LAYOUT_AUTO = 0, MAP_LAYOUT_WIDE = 1, MAP_LAYOUT_PACKED = 2 };
+struct MapGeometry {
+    int packed;          // 1: map_units_kernel (packed contexts), 0: map_units_wide_kernel, -1: refused
+    int contexts;        // contexts per block of that kernel
+    int64_t blocks;
+};
+inline MapGeometry map_geometry(int64_t n_units, int max_len, int max_target_count, int cu_count, int block_cap,
+                                int force)
+{
+    const bool fits = max_len <= MAP_PACKED_MAX_LEN && max_target_count <= MAP_PACKED_MAX_TARGETS;
+    MapGeometry g{};
+    g.packed = force == MAP_LAYOUT_WIDE ? 0 : (fits ? 1 : (force == MAP_LAYOUT_PACKED ? -1 : 0));
+    g.contexts = g.packed == 1 ? MAP_CONTEXTS : MAP_CONTEXTS_WIDE;
+    g.blocks = (n_units + g.contexts - 1) / g.contexts;
+    if (g.blocks > (int64_t)cu_count * MAP_BLOCKS_PER_CU) g.blocks = (int64_t)cu_count * MAP_BLOCKS_PER_CU;
+    if (block_cap > 0 && g.blocks > block_cap) g.blocks = block_cap;
+    return g;
+}
 
 // ASCII reads -> records.  Blocks of pack_stage_reads(words_per_read) consecutive reads go through LDS
 // (pack_reads_staged_kernel); 0 = reads too long for the stage, the launch takes pack_reads_kernel.
@@ -87,8 +135,9 @@ void launch_successor_build(const DevIndex &ix, DevContig *records, int64_t n_co
 // that the structure `mode` asks exists
 void launch_index_probe(const DevIndex &ix, int mode, const uint64_t *kmers, int64_t n, int32_t *entry, int32_t *offset,
                         hipStream_t stream);
-// stats: 0 production, 1 counting build, 2 census build (skm_map.hip)
-void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, int stats,
+// stats: 0 production, 1 counting build, 2 census build (skm_map.hip); packed: MapGeometry::packed of the
+// launch, whose grid and workspace the caller has sized for that kernel's contexts
+void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, int stats, bool packed,
                       hipStream_t stream);
 void launch_pack_sequences(const char *bases, int64_t n_bases, uint64_t *seq2, int64_t n_words,
                            hipStream_t stream);

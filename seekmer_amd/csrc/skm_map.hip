@@ -1038,9 +1038,194 @@ constexpr int SCAN_ROUNDS = SKM_SCAN_ROUNDS;    // k-mers one round of the first
 constexpr int SIGNED_CANDIDATES = SKM_SIGNED_CANDIDATES;            // ... with the signatures in front: a window of k + 6 bases of the read
 
 
-constexpr int NCTX = MAP_CONTEXTS;    // unit contexts per block (LDS)
-
 constexpr int FLD_WINDOW = 512;       // fragment lengths below this are counted in LDS
+constexpr int MAP_QUEUE_WORDS = 2 * N_ACTIONS + 4;     // queue heads and tails, next_unit, done_units, busy, stalled
+
+// ---- a block's unit contexts in LDS
+// The actions work on a context in registers (Context) and on a few single fields of the other mate's
+// context; how the fields lie in LDS is the layout's business.  Both layouts answer the same calls:
+//   load / store         the whole context
+//   unit, count, list_*, mask, begin, end, anchor, read_len      single fields (the emission of a pair)
+//   restart / retire     a finished context takes its next unit, or none (ST_IDLE)
+//   pair_arrive / pair_reset     the finished mates of a pair slot
+//   ring                 one MPMC ring per action: entry = context | 0x8000 once written, 0 while empty
+struct Context {
+    int state, first_hit_kept, attempt;
+    int32_t n;                          // Span::n
+    int32_t begin, end;
+    Coord anchor;
+    uint32_t look, edge;
+    int scan;                           // scan_i
+    int len;                            // the read's length
+    uint32_t head_acgt, tail_acgt;
+    uint64_t kmer;
+    int32_t tstart, tlength;            // TSet::start, length (< 0: the list is still to come)
+    bool forward;
+    uint64_t mask;                      // TSet::word0
+};
+
+template <int N>
+struct WideContexts {
+    static constexpr int CONTEXTS = N;
+    int32_t c_state[N], c_unit[N], c_begin[N], c_end[N], c_aentry[N],
+            c_aoffset[N], c_scan[N], c_len[N], c_tstart[N], c_tlen[N];
+    // c_look: the 16 read bases (2-bit codes) of the aligned half word that holds base c_scan,
+    // so that rolling the first k-mer forward touches the read record once per 16 bases
+    uint32_t c_kmer_lo[N], c_kmer_hi[N], c_mask_lo[N], c_mask_hi[N], c_look[N];
+    // c_edge: the first 8 (low half) and the last 8 (high half) bases of the current read as
+    // 2-bit codes -- what the two closing checks compare (_mapper.pyx:270-275, :335-343); their
+    // "is ACGT" bits ride in bits 24-31 of c_scan (head) and c_len (tail).  The read record
+    // is in L2 for ~10 us after a touch and a unit lives 15 rounds: without the copy every
+    // closing check fetches the record's sector again.
+    uint32_t c_edge[N];
+    uint16_t ring[N_ACTIONS][N];
+    uint32_t pair_done[N / 2];
+
+    __device__ __forceinline__ Context load(int c, bool valid) const
+    {
+        Context x;
+        const int word = valid ? c_state[c] : ST_IDLE;
+        x.state = word & 0xff;
+        x.attempt = (word >> 9) & 1;
+        x.first_hit_kept = (word >> 8) & 1;
+        x.n = (int32_t)((uint32_t)word >> 10);
+        x.begin = c_begin[c];
+        x.end = c_end[c];
+        x.anchor = Coord{c_aentry[c], c_aoffset[c]};
+        x.look = c_look[c];
+        x.edge = c_edge[c];
+        const uint32_t scan_word = (uint32_t)c_scan[c], len_word = (uint32_t)c_len[c];
+        x.scan = (int)(scan_word & 0xffffffu);
+        x.len = (int)(len_word & 0xffffffu);
+        x.head_acgt = scan_word >> 24;
+        x.tail_acgt = len_word >> 24;
+        x.kmer = ((uint64_t)c_kmer_hi[c] << 32) | c_kmer_lo[c];
+        x.tstart = c_tstart[c];
+        x.tlength = c_tlen[c] >> 1;
+        x.forward = (c_tlen[c] & 1) != 0;
+        x.mask = ((uint64_t)c_mask_hi[c] << 32) | c_mask_lo[c];
+        return x;
+    }
+    __device__ __forceinline__ void store(int c, const Context &x)
+    {
+        c_state[c] = (int32_t)((uint32_t)x.state | ((uint32_t)x.first_hit_kept << 8) | ((uint32_t)x.attempt << 9)
+                               | ((uint32_t)x.n << 10));
+        c_begin[c] = x.begin;
+        c_end[c] = x.end;
+        c_aentry[c] = x.anchor.entry;
+        c_aoffset[c] = x.anchor.offset;
+        c_look[c] = x.look;
+        c_edge[c] = x.edge;
+        c_scan[c] = (int32_t)((uint32_t)x.scan | (x.head_acgt << 24));
+        c_len[c] = (int32_t)((uint32_t)x.len | (x.tail_acgt << 24));
+        c_kmer_lo[c] = (uint32_t)x.kmer;
+        c_kmer_hi[c] = (uint32_t)(x.kmer >> 32);
+        c_tstart[c] = x.tstart;
+        c_tlen[c] = (x.tlength << 1) | (x.forward ? 1 : 0);
+        c_mask_lo[c] = (uint32_t)x.mask;
+        c_mask_hi[c] = (uint32_t)(x.mask >> 32);
+    }
+    __device__ __forceinline__ int32_t unit(int c) const { return c_unit[c]; }
+    __device__ __forceinline__ int32_t count(int c) const { return (int32_t)((uint32_t)c_state[c] >> 10); }
+    __device__ __forceinline__ int32_t list_start(int c) const { return c_tstart[c]; }
+    __device__ __forceinline__ int32_t list_length(int c) const { return c_tlen[c] >> 1; }
+    __device__ __forceinline__ bool list_forward(int c) const { return (c_tlen[c] & 1) != 0; }
+    __device__ __forceinline__ uint64_t mask(int c) const { return ((uint64_t)c_mask_hi[c] << 32) | c_mask_lo[c]; }
+    __device__ __forceinline__ int32_t begin(int c) const { return c_begin[c]; }
+    __device__ __forceinline__ int32_t end(int c) const { return c_end[c]; }
+    __device__ __forceinline__ Coord anchor(int c) const { return Coord{c_aentry[c], c_aoffset[c]}; }
+    __device__ __forceinline__ int read_len(int c) const { return (int)((uint32_t)c_len[c] & 0xffffffu); }
+    __device__ __forceinline__ void restart(int c, int32_t unit, int state) { c_unit[c] = unit; c_state[c] = state; }
+    __device__ __forceinline__ void retire(int c) { c_state[c] = ST_IDLE; }
+    __device__ __forceinline__ void pairs_clear(int i) { pair_done[i] = 0; }
+    static constexpr int PAIR_WORDS = N / 2;
+    __device__ __forceinline__ uint32_t pair_arrive(int slot) { return atomicAdd(&pair_done[slot], 1u); }
+    __device__ __forceinline__ void pair_reset(int slot) { pair_done[slot] = 0; }
+};
+
+template <int N>
+struct PackedContexts {
+    static constexpr int CONTEXTS = N;
+    static constexpr int POS = MAP_PACKED_POS_BITS, EDGE = MAP_PACKED_EDGE_BITS, STATE = MAP_PACKED_STATE_BITS,
+                         COUNT = MAP_PACKED_COUNT_BITS, TLEN = MAP_PACKED_TLEN_BITS;
+    static constexpr int KEPT_AT = STATE, ATTEMPT_AT = STATE + 1, COUNT_AT = STATE + 2, TLEN_AT = COUNT_AT + COUNT;
+    static_assert(ST_HALF < (1 << STATE), "the last state");
+    static_assert(TLEN_AT + TLEN == 31, "bit 31: the list's orientation");
+    uint32_t c_state[N];               // state | first_hit_kept | attempt | n | list length + 1 | forward
+    uint32_t c_left[N];                // begin | end << POS | tail_acgt << 2 POS
+    uint32_t c_scan[N];                // scan | len << POS | head_acgt << 2 POS
+    int32_t c_unit[N], c_aentry[N], c_aoffset[N], c_tstart[N];
+    uint32_t c_kmer_lo[N], c_kmer_hi[N], c_mask_lo[N], c_mask_hi[N], c_look[N], c_edge[N];
+    uint16_t ring[N_ACTIONS][N];
+    static constexpr int PAIR_WORDS = (N / 2 + 15) / 16;
+    uint32_t pair_done[PAIR_WORDS];    // two bits a pair slot
+
+    __device__ __forceinline__ Context load(int c, bool valid) const
+    {
+        Context x;
+        const uint32_t word = valid ? c_state[c] : (uint32_t)ST_IDLE;
+        x.state = (int)(word & ((1u << STATE) - 1u));
+        x.first_hit_kept = (int)((word >> KEPT_AT) & 1u);
+        x.attempt = (int)((word >> ATTEMPT_AT) & 1u);
+        x.n = (int32_t)((word >> COUNT_AT) & ((1u << COUNT) - 1u));
+        x.tlength = (int32_t)((word >> TLEN_AT) & ((1u << TLEN) - 1u)) - 1;
+        x.forward = (word >> 31) != 0;
+        const uint32_t left = c_left[c], scan = c_scan[c];
+        x.begin = (int32_t)(left & ((1u << POS) - 1u));
+        x.end = (int32_t)((left >> POS) & ((1u << POS) - 1u));
+        x.tail_acgt = left >> (2 * POS);
+        x.scan = (int)(scan & ((1u << POS) - 1u));
+        x.len = (int)((scan >> POS) & ((1u << POS) - 1u));
+        x.head_acgt = scan >> (2 * POS);
+        x.anchor = Coord{c_aentry[c], c_aoffset[c]};
+        x.look = c_look[c];
+        x.edge = c_edge[c];
+        x.kmer = ((uint64_t)c_kmer_hi[c] << 32) | c_kmer_lo[c];
+        x.tstart = c_tstart[c];
+        x.mask = ((uint64_t)c_mask_hi[c] << 32) | c_mask_lo[c];
+        return x;
+    }
+    __device__ __forceinline__ void store(int c, const Context &x)
+    {
+        c_state[c] = (uint32_t)x.state | ((uint32_t)x.first_hit_kept << KEPT_AT) | ((uint32_t)x.attempt << ATTEMPT_AT)
+                     | ((uint32_t)x.n << COUNT_AT) | ((uint32_t)(x.tlength + 1) << TLEN_AT) | ((uint32_t)x.forward << 31);
+        c_left[c] = (uint32_t)x.begin | ((uint32_t)x.end << POS) | (x.tail_acgt << (2 * POS));
+        c_scan[c] = (uint32_t)x.scan | ((uint32_t)x.len << POS) | (x.head_acgt << (2 * POS));
+        c_aentry[c] = x.anchor.entry;
+        c_aoffset[c] = x.anchor.offset;
+        c_look[c] = x.look;
+        c_edge[c] = x.edge;
+        c_kmer_lo[c] = (uint32_t)x.kmer;
+        c_kmer_hi[c] = (uint32_t)(x.kmer >> 32);
+        c_tstart[c] = x.tstart;
+        c_mask_lo[c] = (uint32_t)x.mask;
+        c_mask_hi[c] = (uint32_t)(x.mask >> 32);
+    }
+    __device__ __forceinline__ int32_t unit(int c) const { return c_unit[c]; }
+    __device__ __forceinline__ int32_t count(int c) const { return (int32_t)((c_state[c] >> COUNT_AT) & ((1u << COUNT) - 1u)); }
+    __device__ __forceinline__ int32_t list_start(int c) const { return c_tstart[c]; }
+    __device__ __forceinline__ int32_t list_length(int c) const { return (int32_t)((c_state[c] >> TLEN_AT) & ((1u << TLEN) - 1u)) - 1; }
+    __device__ __forceinline__ bool list_forward(int c) const { return (c_state[c] >> 31) != 0; }
+    __device__ __forceinline__ uint64_t mask(int c) const { return ((uint64_t)c_mask_hi[c] << 32) | c_mask_lo[c]; }
+    __device__ __forceinline__ int32_t begin(int c) const { return (int32_t)(c_left[c] & ((1u << POS) - 1u)); }
+    __device__ __forceinline__ int32_t end(int c) const { return (int32_t)((c_left[c] >> POS) & ((1u << POS) - 1u)); }
+    __device__ __forceinline__ Coord anchor(int c) const { return Coord{c_aentry[c], c_aoffset[c]}; }
+    __device__ __forceinline__ int read_len(int c) const { return (int)((c_scan[c] >> POS) & ((1u << POS) - 1u)); }
+    __device__ __forceinline__ void restart(int c, int32_t unit, int state) { c_unit[c] = unit; c_state[c] = (uint32_t)state; }
+    __device__ __forceinline__ void retire(int c) { c_state[c] = (uint32_t)ST_IDLE; }
+    __device__ __forceinline__ void pairs_clear(int i) { pair_done[i] = 0; }
+    // (the other slots of the word belong to other lanes, other waves: both calls are atomics)
+    __device__ __forceinline__ uint32_t pair_arrive(int slot)
+    {
+        const int at = 2 * (slot & 15);
+        return (atomicAdd(&pair_done[slot >> 4], 1u << at) >> at) & 3u;
+    }
+    __device__ __forceinline__ void pair_reset(int slot) { atomicAnd(&pair_done[slot >> 4], ~(3u << (2 * (slot & 15)))); }
+};
+typedef WideContexts<MAP_CONTEXTS_WIDE> WideLayout;
+typedef PackedContexts<MAP_CONTEXTS> PackedLayout;
+static_assert(sizeof(WideLayout) + 4 * (FLD_WINDOW + MAP_QUEUE_WORDS) <= MAP_LDS_PER_BLOCK, "4 blocks per CU");
+static_assert(sizeof(PackedLayout) + 4 * (FLD_WINDOW + MAP_QUEUE_WORDS) <= MAP_LDS_PER_BLOCK, "4 blocks per CU");
 
 __device__ __forceinline__ int action_of(int state)
 {
@@ -1066,44 +1251,34 @@ __device__ __forceinline__ Coord lookup_kmer(const DevIndex &ix, uint64_t kmer, 
 // performed in the reference's table layout and counted (these counts are the algorithmic bytes),
 // plus the scheduler census.  <true, true>: the census build, a profiling aid -- the production
 // code paths with the scheduler census and cycle stamps (its access counters undercount).
-template <bool STATS, bool BUCKETS>
-__global__ void __launch_bounds__(MAP_THREADS, SKM_MAP_WAVES_PER_EU)
-map_units_kernel(DevIndex ix, MapBatch b)
+// The kernels' one body, over the layout of the contexts (LAYOUT: WideLayout or PackedLayout).
+template <bool STATS, bool BUCKETS, class LAYOUT>
+__device__ __forceinline__ void map_units_body(const DevIndex &ix, const MapBatch &b)
 {
     constexpr bool COUNT = STATS && !BUCKETS;
+    constexpr int NCTX = LAYOUT::CONTEXTS;            // unit contexts per block
     // junction lookups answered by the contig records (DevContig::succ; the counting build performs
     // and counts the reference's lookups).  Uniform over the launch.
     const bool SUCCESSORS = BUCKETS && ix.successors != 0;
     __shared__ uint32_t fld_lds[FLD_WINDOW];
-    // contexts, structure of arrays
-    __shared__ int32_t c_state[NCTX], c_unit[NCTX], c_begin[NCTX], c_end[NCTX], c_aentry[NCTX],
-                       c_aoffset[NCTX], c_scan[NCTX], c_len[NCTX], c_tstart[NCTX], c_tlen[NCTX];
-    // c_look: the 16 read bases (2-bit codes) of the aligned half word that holds base c_scan,
-    // so that rolling the first k-mer forward touches the read record once per 16 bases
-    __shared__ uint32_t c_kmer_lo[NCTX], c_kmer_hi[NCTX], c_mask_lo[NCTX], c_mask_hi[NCTX], c_look[NCTX];
-    // c_edge: the first 8 (low half) and the last 8 (high half) bases of the current read as
-    // 2-bit codes -- what the two closing checks compare (_mapper.pyx:270-275, :335-343); their
-    // "is ACGT" bits ride in bits 20-27 of c_scan (head) and c_len (tail).  The read record
-    // is in L2 for ~10 us after a touch and a unit lives 15 rounds: without the copy every
-    // closing check fetches the record's sector again.
-    __shared__ uint32_t c_edge[NCTX];
-    // one MPMC ring per action: entry = context | 0x8000 once written, 0 while empty
-    __shared__ uint16_t ring[N_ACTIONS][NCTX];
-    __shared__ uint32_t q_head[N_ACTIONS], q_tail[N_ACTIONS], next_unit, done_units, busy, stalled;
+    // Contexts, structure of arrays, and one ring per action.
     // Paired batches: the two mates of a unit are mapped SIDE BY SIDE by the contexts 2p (mate 1)
     // and 2p + 1 (mate 2) of pair slot p -- map_read_pair maps them independently and only then
     // intersects (_mapper.pyx:119-128).  The mate that finishes first stays in its context
     // (ST_HALF); the one that finishes second takes the unit to the emission, which reads both
-    // contexts.  pair_done[p] counts the finished mates of the slot.  (Mapping the mates one after
+    // contexts.  The layout counts the finished mates of a slot (pair_arrive).  (Mapping the mates one after
     // the other in one context meant parking mate 1's span and set in HBM: a sector written and
     // a sector read back per pair.)
-    __shared__ uint32_t pair_done[NCTX / 2];
+    __shared__ LAYOUT ctx;
+    auto &ring = ctx.ring;
+    __shared__ uint32_t q_head[N_ACTIONS], q_tail[N_ACTIONS], next_unit, done_units, busy, stalled;
+    static_assert(MAP_QUEUE_WORDS == 2 * N_ACTIONS + 4, "the queue words of the LDS budget");
 
     for (int i = threadIdx.x; i < FLD_WINDOW; i += blockDim.x) fld_lds[i] = 0;
     for (int i = threadIdx.x; i < N_ACTIONS * NCTX; i += blockDim.x) (&ring[0][0])[i] = 0;
     if (threadIdx.x < N_ACTIONS) { q_head[threadIdx.x] = 0; q_tail[threadIdx.x] = 0; }
     if (threadIdx.x == 0) { next_unit = 0; done_units = 0; busy = 0; stalled = 0; }
-    for (int i = threadIdx.x; i < NCTX / 2; i += blockDim.x) pair_done[i] = 0;
+    for (int i = threadIdx.x; i < LAYOUT::PAIR_WORDS; i += blockDim.x) ctx.pairs_clear(i);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -1135,8 +1310,7 @@ map_units_kernel(DevIndex ix, MapBatch b)
         const uint32_t k = atomicAdd(&next_unit, 1u);
         if ((int64_t)k < block_units) {
             for (int m = 0; m < slot_width; ++m) {
-                c_unit[c + m] = (int32_t)k;
-                c_state[c + m] = ST_NEW;
+                ctx.restart(c + m, (int32_t)k, ST_NEW);
                 ring[A_START][atomicAdd(&q_tail[A_START], 1u) % NCTX] = (uint16_t)((c + m) | 0x8000);
             }
         }
@@ -1200,26 +1374,25 @@ map_units_kernel(DevIndex ix, MapBatch b)
         {
             const unsigned long long t_action = STATS ? clock64() : 0;
             // load the context
-            int word = valid ? c_state[c] : ST_IDLE;
-            int state = word & 0xff, attempt = (word >> 9) & 1;
+            const Context held = ctx.load(c, valid);
+            int state = held.state, attempt = held.attempt;
             // the k-mer words hold the first hit's position while the left filter runs (see N_RIGHT_ENTER)
-            int first_hit_kept = (word >> 8) & 1;
+            int first_hit_kept = held.first_hit_kept;
             const int mate = b.paired ? (c & 1) : 0;
-            const int64_t u = block_first + c_unit[c];
-            Span span{c_begin[c], c_end[c], Coord{c_aentry[c], c_aoffset[c]}, (int32_t)((uint32_t)word >> 10)};
-            uint32_t look = c_look[c];
-            uint32_t edge = c_edge[c];
-            const uint32_t scan_word = (uint32_t)c_scan[c], len_word = (uint32_t)c_len[c];
-            int scan_i = (int)(scan_word & 0xffffffu);
-            uint32_t head_acgt = scan_word >> 24, tail_acgt = len_word >> 24;
-            uint64_t kmer = ((uint64_t)c_kmer_hi[c] << 32) | c_kmer_lo[c];
+            const int32_t my_unit = ctx.unit(c);
+            const int64_t u = block_first + my_unit;
+            Span span{held.begin, held.end, held.anchor, held.n};
+            uint32_t look = held.look;
+            uint32_t edge = held.edge;
+            int scan_i = held.scan;
+            uint32_t head_acgt = held.head_acgt, tail_acgt = held.tail_acgt;
+            uint64_t kmer = held.kmer;
             uint64_t *const ext1 = ws_block + (size_t)(b.paired ? (c & ~1) : c) * 4 * (size_t)ext_words;
             uint64_t *const ext2 = ext1 + 2 * (size_t)ext_words;       // (mate 2 of the pair slot)
-            TSet set{c_tstart[c], c_tlen[c] >> 1, (c_tlen[c] & 1) != 0,
-                     ((uint64_t)c_mask_hi[c] << 32) | c_mask_lo[c], mate ? ext2 : ext1, ext_words};
-            const uint32_t first_read = b.paired ? 2u * (uint32_t)c_unit[c] : (uint32_t)c_unit[c];
+            TSet set{held.tstart, held.tlength, held.forward, held.mask, mate ? ext2 : ext1, ext_words};
+            const uint32_t first_read = b.paired ? 2u * (uint32_t)my_unit : (uint32_t)my_unit;
             ReadView rv{block_records, (first_read + (uint32_t)mate) * record_bytes, b.words_per_read,
-                        (int)(len_word & 0xffffffu)};   // (the length is kept with the context: saves touching the record)
+                        held.len};                      // (the length is kept with the context: saves touching the record)
             // first and last 8 bases of a read that is about to be mapped -> edge, head_acgt, tail_acgt
             auto keep_edges = [&]() {
                 uint32_t codes, acgt;
@@ -1646,18 +1819,16 @@ map_units_kernel(DevIndex ix, MapBatch b)
                         const int c1 = c & ~1, c2 = c | 1;
                         // (only the lists and their sizes before the intersection: what the fragment
                         // length needs is read from the contexts behind it -- registers are short here)
-                        Span s1{0, 0, Coord{0, 0}, (int32_t)((uint32_t)c_state[c1] >> 10)};
-                        TSet set1{c_tstart[c1], c_tlen[c1] >> 1, (c_tlen[c1] & 1) != 0,
-                                  ((uint64_t)c_mask_hi[c1] << 32) | c_mask_lo[c1], ext1, ext_words};
-                        span = Span{0, 0, Coord{0, 0}, (int32_t)((uint32_t)c_state[c2] >> 10)};
-                        set = TSet{c_tstart[c2], c_tlen[c2] >> 1, (c_tlen[c2] & 1) != 0,
-                                   ((uint64_t)c_mask_hi[c2] << 32) | c_mask_lo[c2], ext2, ext_words};
+                        Span s1{0, 0, Coord{0, 0}, ctx.count(c1)};
+                        TSet set1{ctx.list_start(c1), ctx.list_length(c1), ctx.list_forward(c1), ctx.mask(c1), ext1, ext_words};
+                        span = Span{0, 0, Coord{0, 0}, ctx.count(c2)};
+                        set = TSet{ctx.list_start(c2), ctx.list_length(c2), ctx.list_forward(c2), ctx.mask(c2), ext2, ext_words};
                         phase(0);
                         const bool common = intersect<COUNT>(ix, set1, s1, set, span);
-                        s1.begin = c_begin[c1];
-                        s1.end = c_end[c1];
-                        s1.anchor = Coord{c_aentry[c1], c_aoffset[c1]};
-                        const Coord anchor2{c_aentry[c2], c_aoffset[c2]};
+                        s1.begin = ctx.begin(c1);
+                        s1.end = ctx.end(c1);
+                        s1.anchor = ctx.anchor(c1);
+                        const Coord anchor2 = ctx.anchor(c2);
                         if (!common) {
                             s1.n = 0;
                             s1.begin = 0;
@@ -1666,10 +1837,10 @@ map_units_kernel(DevIndex ix, MapBatch b)
                             s1.begin = 0;
                             s1.end = -K;
                         } else {
-                            const int len1 = (int)((uint32_t)c_len[c1] & 0xffffffu), len2 = (int)((uint32_t)c_len[c2] & 0xffffffu);
+                            const int len1 = ctx.read_len(c1), len2 = ctx.read_len(c2);
                             int interval = anchor2.offset - s1.anchor.offset;
                             if (s1.anchor.entry < 0) interval = -interval;
-                            s1.end = (len1 - K) + interval + (len2 - K) - c_begin[c2];
+                            s1.end = (len1 - K) + interval + (len2 - K) - ctx.begin(c2);
                         }
                         span = s1;
                         set = set1;
@@ -1755,17 +1926,15 @@ map_units_kernel(DevIndex ix, MapBatch b)
                     const bool more = (int64_t)k < block_units;
                     if (b.paired) {                       // both contexts of the pair slot start over
                         const int c1 = c & ~1, c2 = c | 1;
-                        c_unit[c1] = (int32_t)k; c_unit[c2] = (int32_t)k;
-                        c_state[c1] = more ? ST_NEW : ST_IDLE;
-                        c_state[c2] = more ? ST_NEW : ST_IDLE;
-                        pair_done[c >> 1] = 0;
+                        ctx.restart(c1, (int32_t)k, more ? ST_NEW : ST_IDLE);
+                        ctx.restart(c2, (int32_t)k, more ? ST_NEW : ST_IDLE);
+                        ctx.pair_reset(c >> 1);
                         if (more) { next_action = A_START; partner = c ^ 1; }
                     } else if (more) {
-                        c_unit[c] = (int32_t)k;
-                        c_state[c] = ST_NEW;
+                        ctx.restart(c, (int32_t)k, ST_NEW);
                         next_action = A_START;
                     } else {
-                        c_state[c] = ST_IDLE;
+                        ctx.retire(c);
                     }
                 }
             }
@@ -1816,27 +1985,19 @@ map_units_kernel(DevIndex ix, MapBatch b)
 
             // store the context
             if (valid && action != A_EMIT) {
-                c_state[c] = (int32_t)((uint32_t)state | ((uint32_t)first_hit_kept << 8) | ((uint32_t)attempt << 9)
-                                       | ((uint32_t)span.n << 10));
-                c_begin[c] = span.begin;
-                c_end[c] = span.end;
-                c_aentry[c] = span.anchor.entry;
-                c_aoffset[c] = span.anchor.offset;
-                c_look[c] = look;
-                c_edge[c] = edge;
-                c_scan[c] = (int32_t)((uint32_t)scan_i | (head_acgt << 24));
-                c_len[c] = (int32_t)((uint32_t)rv.len | (tail_acgt << 24));
-                c_kmer_lo[c] = (uint32_t)kmer;
-                c_kmer_hi[c] = (uint32_t)(kmer >> 32);
-                c_tstart[c] = set.start;
-                c_tlen[c] = (set.length << 1) | (set.forward ? 1 : 0);
-                c_mask_lo[c] = (uint32_t)set.word0;
-                c_mask_hi[c] = (uint32_t)(set.word0 >> 32);
+                Context keep;
+                keep.state = state; keep.first_hit_kept = first_hit_kept; keep.attempt = attempt;
+                keep.n = span.n; keep.begin = span.begin; keep.end = span.end; keep.anchor = span.anchor;
+                keep.look = look; keep.edge = edge;
+                keep.scan = scan_i; keep.len = rv.len; keep.head_acgt = head_acgt; keep.tail_acgt = tail_acgt;
+                keep.kmer = kmer;
+                keep.tstart = set.start; keep.tlength = set.length; keep.forward = set.forward; keep.mask = set.word0;
+                ctx.store(c, keep);
                 if (state == ST_HALF) {
                     // this mate is done and its context complete: whoever finds the other mate done
                     // already takes the unit to the emission, the first one just stays put
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    const uint32_t before = atomicAdd(&pair_done[c >> 1], 1u);
+                    const uint32_t before = ctx.pair_arrive(c >> 1);
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     next_action = before == 1u ? A_EMIT : -1;
                 } else {
@@ -1902,6 +2063,21 @@ map_units_kernel(DevIndex ix, MapBatch b)
             for (int i = 0; i < 2 + N_ACTIONS + 6; ++i) atomicAdd(&o[32 + i], cyc[i]);
         }
     }
+}
+
+// The packed contexts: every launch whose bounds they hold (map_geometry).
+template <bool STATS, bool BUCKETS>
+__global__ void __launch_bounds__(MAP_THREADS, SKM_MAP_WAVES_PER_EU)
+map_units_kernel(DevIndex ix, MapBatch b)
+{
+    map_units_body<STATS, BUCKETS, PackedLayout>(ix, b);
+}
+// The wide contexts: reads of up to 2^20 bases, target lists of any length.
+template <bool STATS, bool BUCKETS>
+__global__ void __launch_bounds__(MAP_THREADS, SKM_MAP_WAVES_PER_EU)
+map_units_wide_kernel(DevIndex ix, MapBatch b)
+{
+    map_units_body<STATS, BUCKETS, WideLayout>(ix, b);
 }
 
 void launch_bucket_build(const DevIndex &ix, uint64_t n_slots, DevBucket *buckets, uint32_t bucket_mask,
@@ -1999,24 +2175,30 @@ void launch_unpack_exceptions(const uint32_t *exc_reads, const uint32_t *exc_mas
                        n_exceptions, code_words, first_read, words_per_read, dst, dst_stride);
 }
 
-void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, int stats,
+template <bool STATS, bool BUCKETS>
+static void launch_map_layout(const DevIndex &ix, const MapBatch &b, int grid_blocks, bool packed, hipStream_t stream)
+{
+    if (packed)
+        hipLaunchKernelGGL((map_units_kernel<STATS, BUCKETS>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
+    else
+        hipLaunchKernelGGL((map_units_wide_kernel<STATS, BUCKETS>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
+}
+
+void launch_map_units(const DevIndex &ix, const MapBatch &b, int grid_blocks, int stats, bool packed,
                       hipStream_t stream)
 {
     if (b.n_units == 0) return;
-    if (stats == 2 && ix.buckets)
-        hipLaunchKernelGGL((map_units_kernel<true, true>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
-    else if (stats)
-        hipLaunchKernelGGL((map_units_kernel<true, false>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
-    else if (ix.buckets)
-        hipLaunchKernelGGL((map_units_kernel<false, true>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
-    else
-        hipLaunchKernelGGL((map_units_kernel<false, false>), dim3(grid_blocks), dim3(MAP_THREADS), 0, stream, ix, b);
+    if (stats == 2 && ix.buckets) launch_map_layout<true, true>(ix, b, grid_blocks, packed, stream);
+    else if (stats) launch_map_layout<true, false>(ix, b, grid_blocks, packed, stream);
+    else if (ix.buckets) launch_map_layout<false, true>(ix, b, grid_blocks, packed, stream);
+    else launch_map_layout<false, false>(ix, b, grid_blocks, packed, stream);
 }
 
 void warm_code_map()
 {
     hipFuncAttributes attributes;
     (void)hipFuncGetAttributes(&attributes, reinterpret_cast<const void *>(&map_units_kernel<false, true>));
+    (void)hipFuncGetAttributes(&attributes, reinterpret_cast<const void *>(&map_units_wide_kernel<false, true>));
     (void)hipFuncGetAttributes(&attributes, reinterpret_cast<const void *>(&unpack_reads_kernel));
 }
 

@@ -420,6 +420,14 @@ class MapResult:
                 'batches': int(out[3]), 'units': int(out[4]), 'em_ns': out[5], 'em_iterations': int(out[6]),
                 'deferred_grows': int(out[7]), 'map_relaunches': relaunches.value}
 
+    def map_layout(self):
+        """skm_mapper_map_layout: which map kernel the last launch took ('packed' or 'wide' unit contexts), its
+        contexts per workgroup and its grid."""
+        packed, contexts, blocks = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _native.check(_native.hip().skm_mapper_map_layout(self._handle, ctypes.byref(packed), ctypes.byref(contexts),
+                                                           ctypes.byref(blocks)))
+        return {'layout': 'packed' if packed.value else 'wide', 'contexts': contexts.value, 'blocks': blocks.value}
+
 
 class ReadMapper:
     """A read mapper (seekmer/_mapper.pyx:31-105)."""
