@@ -1,11 +1,13 @@
-// The index and mapper handles of the C ABI glue, for the units that look into them (skm_abi_index.hip and
-// skm_abi.hip, which own them, skm_abi_samples.hip, skm_abi_genes.hip and skm_abi_quant.hip), with the words of the
-// mapper's counter blocks and the calls of the mapper that other families make.  The handles are the C ABI's global
-// types and their members are types of `skm` and `skm::abi`, so this header names both namespaces as the units that
-// include it do.
+// The index and mapper handles of the C ABI glue, for the units that look into them (skm_abi_index.hip, which owns
+// the index; skm_abi.hip, which owns the mapper's map/class stage -- everything under `mu`; skm_abi_feed.hip, which
+// owns `skm_mapper::feed`, how reads reach that stage -- everything under `feed.q_mu`; skm_abi_samples.hip,
+// skm_abi_genes.hip and skm_abi_quant.hip), with the words of the mapper's counter blocks and the calls of the
+// mapper that other units make.  The handles are the C ABI's global types and their members are types of `skm` and
+// `skm::abi`, so this header names both namespaces as the units that include it do.
 #pragma once
 #include "skm_abi.h"
 #include "skm_bias.h"
+#include "skm_packed_book.h"
 
 #include <atomic>
 #include <condition_variable>
@@ -117,46 +119,38 @@ struct skm_mapper {
         bool busy = false;
     };
     static constexpr int N_LANES = 3;
-    Lane lanes[N_LANES];
     struct Job { int lane; int64_t n_units; int paired; int64_t offset_base; int64_t first_unit; uint64_t ticket; };
-    std::mutex q_mu;
-    std::condition_variable q_cv;             // job queued / stop
-    std::condition_variable done_cv;          // job finished, lane released
-    std::deque<Job> jobs;
-    std::thread worker;
-    bool worker_started = false, stop = false;
-    uint64_t next_ticket = 1, done_ticket = 0;
-    int job_error = SKM_OK;                   // first failure of a queued batch (sticky until reported)
-    uint64_t job_error_ticket = 0;
-    std::string job_error_msg;
-    DBuf<unsigned long long> scan_out;        // device-side max read length / monotonicity of a batch
-    // ---- packed pieces (skm_mapper_push_packed): reads that arrive as 2-bit code words wait in HBM,
-    // one ascending list of pieces per stream, until the worker maps a run of units that every
-    // stream covers.  All of it under q_mu.
-    struct Piece {
-        int64_t first = 0, n = 0;             // units [first, first + n) of the stream (what is left of the piece)
-        int64_t origin = 0;                   // first_read of the piece as pushed: the arrays start there
-        int cw = 1;
-        int64_t uniform_len = -1;
-        std::shared_ptr<char> block;          // one HBM allocation: codes | lengths | exception reads | masks
-        uint64_t *codes = nullptr;            // [n as pushed][cw]
-        uint32_t *lengths = nullptr;          // or NULL (uniform_len)
-        uint32_t *exc_reads_dev = nullptr, *exc_masks = nullptr;
-        std::vector<uint32_t> exc_reads;      // host copy (indices relative to origin), for cutting runs
-        bool in_job = false;
-    };
-    std::deque<Piece> pending[2];
-    Stream packed_stream;
-    int packed_paired = -1;                   // -1 until the first piece
-    int packed_flush = 0;                     // callers waiting for everything mappable to be mapped
-    int packed_waiters = 0;                   // pushers held back by the byte limit: whatever run there is gets mapped
-    int64_t packed_max_pending = 8LL << 30;   // bytes of HBM that pieces may hold before a pusher waits
-    bool packed_busy = false;
-    int64_t packed_dropped = 0;               // reads that never got a mate
-    // HBM held by pieces that wait to be mapped; a pusher that is ahead of the GPU by more than
-    // PACKED_MAX_PENDING bytes waits (only while the worker has something to map: a caller that
-    // pushes one stream long before the other is never blocked on itself)
-    std::shared_ptr<std::atomic<int64_t>> packed_bytes = std::make_shared<std::atomic<int64_t>>(0);
+    // The feed (skm_abi_feed.hip): everything in it but `scan_out` (the worker's, used under `mu`) is under q_mu.
+    struct __attribute__((visibility("hidden"))) Feed {
+        Lane lanes[N_LANES];
+        std::mutex q_mu;
+        std::condition_variable q_cv;             // job queued / stop
+        std::condition_variable done_cv;          // job finished, lane released
+        std::deque<Job> jobs;
+        std::thread worker;
+        bool worker_started = false, stop = false;
+        uint64_t next_ticket = 1, done_ticket = 0;
+        int job_error = SKM_OK;                   // first failure of a queued batch (sticky until reported)
+        uint64_t job_error_ticket = 0;
+        std::string job_error_msg;
+        DBuf<unsigned long long> scan_out;        // device-side max read length / monotonicity of a batch
+        // ---- packed pieces (skm_mapper_push_packed): reads that arrive as 2-bit code words wait in HBM,
+        // one ascending list of pieces per stream, until the worker maps a run of units that every
+        // stream covers (skm_packed_book.h).
+        PackedBook book;
+        Stream packed_stream;
+        int packed_flush = 0;                     // callers waiting for everything mappable to be mapped
+        int packed_waiters = 0;                   // pushers held back by the byte limit: whatever run there is gets mapped
+        int64_t packed_max_pending = 8LL << 30;   // bytes of HBM that pieces may hold before a pusher waits
+        bool packed_busy = false;
+        // HBM held by pieces that wait to be mapped; a pusher that is ahead of the GPU by more than
+        // PACKED_MAX_PENDING bytes waits (only while the worker has something to map: a caller that
+        // pushes one stream long before the other is never blocked on itself)
+        std::shared_ptr<std::atomic<int64_t>> packed_bytes = std::make_shared<std::atomic<int64_t>>(0);
+        // (q_mu held) the first failure of a queued batch or run sticks; ticket 0: every wait reports it
+        void record_failure(int rc, uint64_t ticket, const std::string &message);
+        void shutdown();                          // stop the worker once it has finished what is queued, and join it
+    } feed;
     int vote[8] = {1, 1, 1, 1, 1, 1, 1, 0};   // quorum per action (start, lookup, merge, left, right, emit, scan)
     // skm_mapper_device_table: the classes in registry order, as class_compact leaves them
     DBuf<int64_t> view_start, view_len;
@@ -172,18 +166,17 @@ constexpr int CTR_ARENA = 0, CTR_CLASSES = 1, CTR_UNALIGNED = 2, CTR_UNITS = 3, 
               CTR_DEFERRED = 5, CTR_COMMITTED = 6, CTR_FLD = 8;
 constexpr int CTR_WORDS = 8 + MAX_FRAGMENT_LENGTH;
 constexpr int BC_IDS = 0, BC_FLD = 8, BC_STATS = 2048, BC_WORDS = 2096;
-constexpr int64_t PACKED_MIN_UNITS = 1 << 15;      // smaller runs wait for more (or for a flush)
-constexpr int64_t PACKED_MAX_UNITS = 1 << 21;      // one launch
 
-// (all defined in skm_abi.hip)
-// wait until every queued batch up to `ticket` (0: all of them) has been mapped; reports (and, with `consume`,
-// forgets) the first failure among them
+// (skm_abi_feed.hip) wait until every queued batch up to `ticket` (0: all of them) has been mapped; reports (and,
+// with `consume`, forgets) the first failure among them
 int wait_jobs(skm_mapper *m, uint64_t ticket, bool consume);
-// the weights of a fragment-length model: every one finite and >= 0
+// (skm_abi.hip) the weights of a fragment-length model: every one finite and >= 0
 bool length_weights_valid(const double *p, int64_t count);
+// (skm_abi.hip, m->mu held) what skm_mapper_expect_units announced: table and arena sized for the sample at once
+int table_reserve_for_sample(skm_mapper *m, int64_t sample_units);
 
-// ---- what a sample set, which drives its mapper's launches itself, uses of the mapper
-// map_batch_resident (m->mu held) -- first_unit: global index of the batch's first unit (first-seen values count from it), or -1
+// ---- what the feed and a sample set, which drives its mapper's launches itself, use of the mapper
+// map_batch_resident (skm_abi.hip, m->mu held) -- first_unit: global index of the batch's first unit (first-seen values count from it), or -1
 // to continue after the units mapped so far
 // fill_records: what makes the read records of the batch (records, words per read, u32 words per
 // record); nullptr = pack_reads_kernel over ASCII bases + offsets
@@ -198,20 +191,7 @@ int map_batch_resident(skm_mapper *m, const uint8_t *d_bases, const int64_t *d_o
                        const RecordStage *fill_records = nullptr, const SampleSalt *salt = nullptr,
                        unsigned long long *sample_bias_rows = nullptr, const BatchStage *collapse = nullptr);
 
-struct PackedSegment {               // part of one piece inside a run
-    int mate;
-    int64_t first, n;                // units
-    const uint64_t *codes;
-    const uint32_t *lengths;
-    int cw;
-    uint32_t uniform_len;
-    const uint32_t *exc_reads, *exc_masks;   // device, already offset to the segment's first exception
-    int64_t n_exc;
-    int64_t exc_base;                // index (relative to the piece as pushed) of the segment's first read
-};
-// the parts of a stream's pieces that lie in units [lo, hi), as segments of a launch
-void packed_segments(std::deque<skm_mapper::Piece> &pieces, int mate, int64_t lo, int64_t hi, bool mark_in_job,
-                     std::vector<PackedSegment> *segments, int *max_cw);
+// ---- what a sample set uses of the feed (all defined in skm_abi_feed.hip)
 // the read records of a launch's packed segments (`first_unit`: the unit that stands at record 0)
 void packed_unpack(const std::vector<PackedSegment> &segments, int64_t first_unit, int mates, uint32_t *records, int words,
                    int record_words, int *error, hipStream_t stream);
@@ -222,7 +202,7 @@ inline size_t packed_round(size_t b) { return (b + 255) & ~(size_t)255; }
 int packed_block(int64_t bytes, const std::shared_ptr<std::atomic<int64_t>> &counter, std::shared_ptr<char> *block);
 // take the block (counted in *counter while it lives) and QUEUE the copies of the piece's arrays on `stream`
 int packed_upload(const skm_packed_reads *piece, const std::shared_ptr<std::atomic<int64_t>> &counter, hipStream_t stream,
-                  skm_mapper::Piece *out);
+                  PackedPiece *out);
 
 }  // namespace abi
 }  // namespace skm

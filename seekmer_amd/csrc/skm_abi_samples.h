@@ -3,6 +3,7 @@
 // by sample.
 #pragma once
 #include "skm_abi_mapper.h"
+#include "skm_packed_book.h"
 
 #include <atomic>
 #include <condition_variable>
@@ -18,7 +19,7 @@ namespace skm {
 namespace abi __attribute__((visibility("hidden"))) {
 
 struct SetChunk {                        // the reads of one added segment where they lie in HBM
-    std::deque<skm_mapper::Piece> pieces[2];   // packed form: one piece per mate, numbered by the sample's units
+    std::deque<PackedPiece> pieces[2];         // packed form: one piece per mate, numbered by the sample's units
     std::shared_ptr<char> ascii;         // ASCII form: one block, offsets | bases
     const uint8_t *bases = nullptr;      // biased: read r of the segment = bases[offsets[r] .. offsets[r + 1])
     const int64_t *offsets = nullptr;    // [reads + 1], as the caller gave them

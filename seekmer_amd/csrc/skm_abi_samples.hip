@@ -114,7 +114,7 @@ int set_launch(skm_sample_set *s, const std::vector<SetPart> &parts, int64_t n_u
         if (part.data->ascii) { max_len = std::max(max_len, part.data->max_len); continue; }
         for (int mate = 0; mate < mates; ++mate) {
             const size_t from = segments.size();
-            packed_segments(part.data->pieces[mate], mate, part.first, part.first + part.n, false, &segments, &max_cw);
+            PackedBook::segments(part.data->pieces[mate], mate, part.first, part.first + part.n, false, &segments, &max_cw);
             for (size_t k = from; k < segments.size(); ++k) segments[k].first += part.at - part.first;
         }
     }
@@ -530,7 +530,7 @@ int set_add_packed(skm_sample_set *s, int64_t sample, int64_t first_unit, const 
         for (int k = 0; k < (s->paired ? 2 : 1); ++k) {
             skm_packed_reads piece = *mates[k];
             piece.first_read = first_unit;             // (numbered by the sample's units)
-            skm_mapper::Piece held;
+            PackedPiece held;
             SKM_TRY(packed_upload(&piece, s->bytes, s->copy_stream, &held));
             data->pieces[k].push_back(std::move(held));
         }
