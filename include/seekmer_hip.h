@@ -859,6 +859,21 @@ int skm_sample_set_quantify(skm_sample_set *set, const double *lengths, int64_t 
  * [n_classes] = tile of every class in the caller's class order. */
 int skm_quant_components(skm_quant *quant, int64_t info[8], int32_t *tx_label, int32_t *tx_tile,
                          int32_t *class_tile);
+/* The tiles' arrays as the set-up left them on the device (EmTiles; diagnostics, tests), every array optional.
+ * With S = tiles, T = n_tx, C = classes, M = pairs of the handle: tile_tx[S + 1] and tile_cls[S + 1] first place of
+ * tile i in tx_list / cls_list; tx_list[T] transcript ids and cls_list[C] INTERNAL class indices, tile by tile;
+ * tx_pair[T + 1] and cls_pair[C + 1] by place in the lists: first pair of the member in tx_cls / cls_tx;
+ * cls_tx[M] tile-local transcript of every pair, class-major; tx_cls[M] tile-local class of every pair,
+ * transcript-major; order[S] the tiles in launch order; perm[C] the caller's index of internal class k.
+ * Only what belongs to the tiles is defined: list places below tile_tx[S] / tile_cls[S], the pair entries up to and
+ * including those places, pairs below cls_pair[tile_cls[S]]; whatever lies behind belongs to components above
+ * the capacity and is never read.  SKM_ERR_ARG when no tiles were built for the handle. */
+int skm_quant_tile_arrays(skm_quant *quant, int64_t *tile_tx, int64_t *tile_cls, int32_t *tx_list, int32_t *cls_list,
+                          int64_t *tx_pair, int64_t *cls_pair, uint16_t *cls_tx, uint16_t *tx_cls, int32_t *order,
+                          int32_t *perm);
+/* numpy.sum(values[0 .. n)) as the device adds it up for the start vector and the TPM scaling (diagnostics, tests):
+ * upload, the production launches, download.  *sum = the sum (n = 0: 0.0).  SKM_ERR_ARG for n < 0, n >= 2^31, NULL. */
+int skm_device_np_sum_probe(int device, const double *values, int64_t n, double *sum);
 /* timing[0]=EM kernel ns total [1]=iterations [2]=launches */
 int skm_quant_timing(skm_quant *quant, double timing[4]);
 

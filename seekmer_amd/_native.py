@@ -200,6 +200,9 @@ HIP_SYMBOLS = {
                                                c_i64, c_i64p, c_f64p, c_f64p, c_i64p]),
     'skm_quant_timing': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
     'skm_quant_components': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i32p, c_i32p]),
+    'skm_quant_tile_arrays': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i32p, c_i32p, c_i64p, c_i64p,
+                                             ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_i32p]),
+    'skm_device_np_sum_probe': (ctypes.c_int, [ctypes.c_int, c_f64p, c_i64, c_f64p]),
     'skm_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_comm_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                        c_void_pp]),

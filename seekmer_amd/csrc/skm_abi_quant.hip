@@ -810,6 +810,44 @@ extern "C" int skm_quant_components(skm_quant *q, int64_t info[8], int32_t *tx_l
     return SKM_OK;
 }
 
+extern "C" int skm_quant_tile_arrays(skm_quant *q, int64_t *tile_tx, int64_t *tile_cls, int32_t *tx_list, int32_t *cls_list,
+                                     int64_t *tx_pair, int64_t *cls_pair, uint16_t *cls_tx, uint16_t *tx_cls, int32_t *order,
+                                     int32_t *perm)
+{
+    if (!q) return fail(SKM_ERR_ARG, "NULL argument");
+    std::lock_guard<std::mutex> lock(q->mu);
+    SKM_TRY(set_device(q->device));
+    const auto &t = q->tiles;
+    if (!t.built) return fail(SKM_ERR_ARG, "no component tiles were built for this handle");
+    HIP_TRY(hipStreamSynchronize(q->stream));
+    const int64_t S = t.n_tiles, T = q->n_tx, C = q->n_classes, M = q->n_ids;
+    auto home = [](void *to, const void *from, int64_t bytes) {
+        return to && bytes > 0 ? hipMemcpy(to, from, (size_t)bytes, hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    HIP_TRY(home(tile_tx, t.tile_tx.p, (S + 1) * 8)); HIP_TRY(home(tile_cls, t.tile_cls.p, (S + 1) * 8));
+    HIP_TRY(home(tx_list, t.tx_list.p, T * 4)); HIP_TRY(home(cls_list, t.cls_list.p, C * 4));
+    HIP_TRY(home(tx_pair, t.tx_pair.p, (T + 1) * 8)); HIP_TRY(home(cls_pair, t.cls_pair.p, (C + 1) * 8));
+    HIP_TRY(home(cls_tx, t.cls_tx.p, M * 2)); HIP_TRY(home(tx_cls, t.tx_cls.p, M * 2));
+    HIP_TRY(home(order, t.order.p, S * 4)); HIP_TRY(home(perm, q->perm.p, C * 4));
+    return SKM_OK;
+}
+
+extern "C" int skm_device_np_sum_probe(int device, const double *values, int64_t n, double *sum)
+{
+    SKM_TRY(check_device(device));
+    if (n < 0 || n >= (1LL << 31) || !sum || (n && !values)) return fail(SKM_ERR_ARG, "bad argument");
+    SKM_TRY(set_device(device));
+    DBuf<double> d_values, d_sums, d_out;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(d_values.ensure(std::max<int64_t>(n, 1))); SKM_TRY(d_sums.ensure((n + 8191) / 8192 + 1)); SKM_TRY(d_out.ensure(2));
+    if (n) HIP_TRY(hipMemcpy(d_values.p, values, n * 8, hipMemcpyHostToDevice));
+    launch_np_sum(d_values.p, n, 1.0, d_sums.p, d_out.p, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(sum, d_out.p, 8, hipMemcpyDeviceToHost));
+    drain.dismiss();                          // (the copy home has waited for the kernels)
+    return SKM_OK;
+}
+
 extern "C" int skm_quant_set_counts(skm_quant *q, const double *class_counts)
 {
     if (!q || (!class_counts && q->n_classes)) return fail(SKM_ERR_ARG, "NULL argument");

@@ -838,69 +838,12 @@ void launch_em_finalize(const EmProblem &p, int parity, bool from_acc, hipStream
 // loops_utils.h.src).  The start vector x /= x.sum() (seekmer/infer.py:118-119)
 // and the TPM scaling (:127-129) go through it, so doing them on the device
 // without it would move the EM input by an ulp.
-// The tree is evaluated in three steps per block of 8192: lane 0 walks the
-// recursion and lists its leaves (at most 128 elements each), one lane per leaf
-// adds its leaf up exactly as numpy does, lane 0 walks the recursion again
-// combining the leaf sums.  (The recursion is spelled as a chain of distinct
-// functions, one per level, so that the call graph is static: 8192 elements
-// split at most 7 times.)
-constexpr int NP_MAX_LEAVES = 160;
-
-__device__ __forceinline__ double np_leaf_sum(const double *a, int n)
-{
-    if (n < 8) {
-        double r = 0.0;                      // numpy starts from -0.0 + a[0]; same value for our data
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
-template <int LEVELS>
-__device__ __attribute__((noinline)) void np_list_leaves(int lo, int n, int *leaf_lo, int *leaf_n, int *count)
-{
-    if (n <= 128) {
-        if (*count < NP_MAX_LEAVES) { leaf_lo[*count] = lo; leaf_n[*count] = n; }
-        ++*count;
-        return;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    np_list_leaves<LEVELS - 1>(lo, n2, leaf_lo, leaf_n, count);
-    np_list_leaves<LEVELS - 1>(lo + n2, n - n2, leaf_lo, leaf_n, count);
-}
-template <>
-__device__ __attribute__((noinline)) void np_list_leaves<0>(int, int, int *, int *, int *count)
-{
-    *count = NP_MAX_LEAVES + 1;              // not reached for blocks of at most 8192 elements
-}
-
-template <int LEVELS>
-__device__ __attribute__((noinline)) double np_combine(int n, const double *leaf_sum, int *next)
-{
-    if (n <= 128) return leaf_sum[(*next)++];
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    const double left = np_combine<LEVELS - 1>(n2, leaf_sum, next);
-    const double right = np_combine<LEVELS - 1>(n - n2, leaf_sum, next);
-    return left + right;
-}
-template <>
-__device__ __attribute__((noinline)) double np_combine<0>(int, const double *, int *) { return 0.0; }
-
 // A full block of 8192 elements splits evenly all the way down: 64 leaves of 128 elements,
 // combined as a balanced binary tree.  Eight lanes per leaf run numpy's eight strided
 // accumulators (lane j adds elements j, j + 8, ... of the leaf in order), the combination
 // ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) is a three-step butterfly over those lanes and the 64 leaf
 // sums meet in a six-step butterfly -- the same additions in the same association (a + b = b + a
-// exactly, so only the shape of the tree matters), with none of the recursion of the general path.
+// exactly, so only the shape of the tree matters).
 __device__ __forceinline__ void np_sum_full_block(const double *__restrict__ a, double *__restrict__ out)
 {
     __shared__ double leaf[64];
@@ -921,6 +864,67 @@ __device__ __forceinline__ void np_sum_full_block(const double *__restrict__ a, 
     }
 }
 
+// The last block of an array, 0 < len < 8192 elements, in the same shape.  Its tree depends on len alone and is at
+// most seven splits deep (8191 -> 4103 -> 2055 -> 1031 -> 519 -> 263 -> 135 -> 71), so a node is named by the turns
+// that lead to it, left = 0, right = 1, first turn in the highest of seven bits, the rest zero: 128 names, a node and
+// its left child share one.  Eight lanes take a name, walk down from the root (no recursion, no list of leaves) and,
+// if the walk ends at a leaf just as the turns run out, add the leaf up as numpy does: eight strided accumulators,
+// the butterfly, then lane 0 the up to seven elements left over in order (a leaf below eight elements, which only
+// a block below eight has: lane 0 alone, in order).  The leaf sums then meet level by level from the deepest: a
+// lane per node walks to it and, if it was split, adds its right child's sum to the left child's, which stands
+// under the node's own name.  The same additions in the same association as pairwise_sum's recursion.
+constexpr int NP_SPLITS = 7, NP_NAMES = 1 << NP_SPLITS;
+
+// the node reached from the root of a block of len elements by the highest `turns` bits of `name`: first element,
+// size, and the number of turns made before a leaf ended the walk
+__device__ __forceinline__ int np_walk(int len, int name, int turns, int *lo_out, int *n_out)
+{
+    int lo = 0, n = len, d = 0;
+    for (; d < turns && n > 128; ++d) {
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        if ((name >> (NP_SPLITS - 1 - d)) & 1) { lo += n2; n -= n2; } else n = n2;
+    }
+    *lo_out = lo; *n_out = n;
+    return d;
+}
+
+__device__ __forceinline__ void np_sum_partial_block(const double *__restrict__ a, int len, double *__restrict__ out)
+{
+    __shared__ double node[NP_NAMES];
+    const int j = threadIdx.x & 7;
+    for (int name = threadIdx.x >> 3; name < NP_NAMES; name += 64) {          // (two turns of 64 names, block-uniform)
+        int lo, n;
+        const int d = np_walk(len, name, NP_SPLITS, &lo, &n);
+        // (a leaf d turns down stands under the name whose other bits are zero; the rest of the names are idle)
+        const bool mine = (name & ((1 << (NP_SPLITS - d)) - 1)) == 0;
+        const int whole = n - n % 8;
+        double r = 0.0;
+        if (mine && n >= 8) {
+            r = a[lo + j];
+            for (int i = 8 + j; i < whole; i += 8) r += a[lo + i];
+        }
+        r += __shfl_xor(r, 1, 8);
+        r += __shfl_xor(r, 2, 8);
+        r += __shfl_xor(r, 4, 8);
+        if (mine && j == 0) {
+            for (int i = n >= 8 ? whole : 0; i < n; ++i) r += a[lo + i];     // numpy starts from -0.0 + a[0]; same value for our data
+            node[name] = r;
+        }
+    }
+    __syncthreads();
+    for (int level = NP_SPLITS - 1; level >= 0; --level) {
+        if ((int)threadIdx.x < (1 << level)) {
+            const int name = threadIdx.x << (NP_SPLITS - level);
+            int lo, n;
+            const int d = np_walk(len, name, level, &lo, &n);
+            if (d == level && n > 128) node[name] += node[name + (1 << (NP_SPLITS - 1 - level))];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = node[0];
+}
+
 __global__ void __launch_bounds__(512)
 np_sum_blocks_kernel(const double *__restrict__ a, int64_t n, double *__restrict__ block_sums, int64_t stride)
 {
@@ -933,31 +937,7 @@ np_sum_blocks_kernel(const double *__restrict__ a, int64_t n, double *__restrict
         np_sum_full_block(a + first, block_sums + blockIdx.x);
         return;
     }
-    __shared__ double staged[8192];          // the block, fetched coalesced; leaves then read LDS
-    __shared__ int leaf_lo[NP_MAX_LEAVES], leaf_n[NP_MAX_LEAVES], n_leaves;
-    __shared__ double leaf_sum[NP_MAX_LEAVES];
-    for (int i = threadIdx.x; i < len; i += blockDim.x) staged[i] = a[first + i];
-    if (threadIdx.x == 0) {
-        int count = 0;
-        np_list_leaves<8>(0, len, leaf_lo, leaf_n, &count);
-        n_leaves = count;
-    }
-    __syncthreads();
-    if (n_leaves > NP_MAX_LEAVES) {          // cannot happen; keep the result defined
-        if (threadIdx.x == 0) {
-            double r = 0.0;
-            for (int i = 0; i < len; ++i) r += staged[i];
-            block_sums[blockIdx.x] = r;
-        }
-        return;
-    }
-    if ((int)threadIdx.x < n_leaves)
-        leaf_sum[threadIdx.x] = np_leaf_sum(staged + leaf_lo[threadIdx.x], leaf_n[threadIdx.x]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int next = 0;
-        block_sums[blockIdx.x] = np_combine<8>(len, leaf_sum, &next);
-    }
+    np_sum_partial_block(a + first, len, block_sums + blockIdx.x);
 }
 
 // out[0] = the sum, out[1] = sum / divisor (vector blockIdx.x of several: its own block sums and pair)

@@ -348,6 +348,8 @@ struct EmTiles {
                                   //     of EM_TILE_CLASS_BATCH entries first, ascending among equals)
     const int64_t *cls_pair;      // [C + 1] by place in cls_list: first pair of the class in cls_tx
     const int64_t *tx_pair;       // [T + 1] by place in tx_list: first pair of the transcript in tx_cls
+                                  // (the four arrays above are written for the tiles' members and the one entry
+                                  //  behind the last: what lies in no tile is listed nowhere and nothing reads it)
     const uint16_t *cls_tx;       // [M] tile-local transcript of every pair, class-major, tuple order
     const uint16_t *tx_cls;       // [M] tile-local class of every pair, transcript-major, internal class order
     double *step_max;             // [EM_CHUNK_MAX][n_tiles] the tiles' partials of the stopping rule, per step
@@ -508,8 +510,8 @@ struct QuantBuild {
     // the component tiles (EmTiles), built when tile_tx is given; tile_info[0] = tiles, [1] = components
     // above the tile capacity (then the tiles are not used), both read by the host with the row count
     int64_t *tile_tx, *tile_cls;  // [T + 2], [T + 2] out
-    int32_t *tx_list, *cls_list;  // [T], [C] out
-    int64_t *cls_pair, *tx_pair;  // [C + 1], [T + 1] out
+    int32_t *tx_list, *cls_list;  // [T], [C] out: the tiles' members (tile_tx[tiles], tile_cls[tiles] places)
+    int64_t *cls_pair, *tx_pair;  // [C + 1], [T + 1] out: for those places and the one behind them
     uint16_t *tile_cls_tx, *tile_tx_cls;   // [M], [M] out
     int32_t *tx_label, *tx_tile, *cls_tile;   // [T], [T], [C] out: component (smallest id), tile of each
     int32_t *tile_order;          // [T + 1] out: the tiles by descending pair count (EmTiles::order)

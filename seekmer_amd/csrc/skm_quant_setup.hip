@@ -8,9 +8,12 @@
 // From a mapper's table the first-seen RANK of every class comes from a bitmap
 // over the unit indices (first-seen values are distinct: a unit belongs to one
 // class) and a prefix popcount -- no sort; one stable 18-bit radix sort of the
-// classes by smallest id and one of the pairs by transcript remain (rocPRIM's
-// onesweep), everything else is small index-moving kernels.  One-time setup per
-// quantification, not part of the per-step hot loop.
+// classes by smallest id and one of the pairs by transcript remain (the
+// hand-written sort_pairs below: no library code on the path), everything else
+// is small index-moving kernels.  The tiles of the component EM need no sort:
+// their sizes follow from the components, their members are dropped into place
+// in any order and a workgroup per tile orders them in LDS (build_tiles).
+// One-time setup per quantification, not part of the per-step hot loop.
 #include "skm_kernels.h"
 #include "skm_pool.h"
 
@@ -883,14 +886,28 @@ cc_classes_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_class
 // no tile counts as 0) and finds the open tile's end with a ballot -- the first lane whose prefix sum,
 // less the sum at the tile's start, is above a capacity opens the next tile.  One turn of that loop per
 // tile; the fill of the tile left open is carried to the next 64 ids.
+// The walk runs twice.  STARTS = false leaves root_tile, the components above the capacity and per run
+// seg_sizes[0 .. 3][run] = its tiles and the transcripts, classes and pairs that went into them.  After
+// one scan over those (seg_scan_kernel: seg_base[k][run]) STARTS = true walks the same runs and writes,
+// where a tile opens, what lies before it: tile_tx / tile_cls / tile_pair[seg_base[0][run] + tile of the
+// run] = the run's base + the packed sizes before the component that opens it.  Nothing else differs.
+template <bool STARTS>
 __global__ void __launch_bounds__(256)
 tile_pack_kernel(const int32_t *__restrict__ comp, int64_t n_tx, int64_t n_segments, int32_t *__restrict__ root_tile,
-                 int64_t *__restrict__ seg_tiles, unsigned long long *__restrict__ oversize)
+                 int64_t *__restrict__ seg_sizes, unsigned long long *__restrict__ oversize,
+                 const int64_t *__restrict__ seg_base, int64_t *__restrict__ tile_tx, int64_t *__restrict__ tile_cls,
+                 int64_t *__restrict__ tile_pair)
 {
     const int lane = threadIdx.x & 63;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t g = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6; g < n_segments; g += n_waves) {
         int tx = 0, pairs = 0, classes = 0, n = 0;          // (wave-uniform: the open tile's fill, the run's tiles)
+        int run_tx = 0, run_pairs = 0, run_classes = 0;     // (wave-uniform: packed before these 64 ids)
+        int64_t first_tile = 0, first_tx = 0, first_cls = 0, first_pair = 0;
+        if (STARTS) {
+            first_tile = seg_base[g]; first_tx = seg_base[(n_segments + 1) + g];
+            first_cls = seg_base[2 * (n_segments + 1) + g]; first_pair = seg_base[3 * (n_segments + 1) + g];
+        }
         const int64_t last = min(n_tx, (g + 1) * EM_TILE_SEGMENT);
         for (int64_t t0 = g * EM_TILE_SEGMENT; t0 < last; t0 += 64) {
             const int64_t t = t0 + lane;
@@ -918,38 +935,141 @@ tile_pack_kernel(const int32_t *__restrict__ comp, int64_t n_tx, int64_t n_segme
                 base_tx = __shfl(s_tx - c_tx, at, 64);
                 base_pairs = __shfl(s_pairs - c_pairs, at, 64);
                 base_classes = __shfl(s_classes - c_classes, at, 64);
+                if (STARTS && lane == 0) {
+                    tile_tx[first_tile + n] = first_tx + run_tx + base_tx;
+                    tile_cls[first_tile + n] = first_cls + run_classes + base_classes;
+                    tile_pair[first_tile + n] = first_pair + run_pairs + base_pairs;
+                }
                 ++n;
                 if (lane >= at) ++opened;
                 behind = at == 63 ? 0ULL : ~0ULL << (at + 1);   // (the component at the start fits by itself)
             }
-            if (t < last) root_tile[t] = !root ? -1 : big ? -2 : before + opened - 1;
-            const unsigned long long bigs = __ballot(root && big);
-            if (bigs && lane == 0) atomicAdd(oversize, (unsigned long long)__popcll(bigs));
-            tx = __shfl(s_tx, 63, 64) - base_tx;
-            pairs = __shfl(s_pairs, 63, 64) - base_pairs;
-            classes = __shfl(s_classes, 63, 64) - base_classes;
+            if (!STARTS) {
+                if (t < last) root_tile[t] = !root ? -1 : big ? -2 : before + opened - 1;
+                const unsigned long long bigs = __ballot(root && big);
+                if (bigs && lane == 0) atomicAdd(oversize, (unsigned long long)__popcll(bigs));
+            }
+            const int all_tx = __shfl(s_tx, 63, 64), all_pairs = __shfl(s_pairs, 63, 64), all_classes = __shfl(s_classes, 63, 64);
+            tx = all_tx - base_tx;
+            pairs = all_pairs - base_pairs;
+            classes = all_classes - base_classes;
+            run_tx += all_tx; run_pairs += all_pairs; run_classes += all_classes;
         }
-        if (lane == 0) seg_tiles[g] = n;
+        if (!STARTS && lane == 0) {
+            seg_sizes[g] = n;
+            seg_sizes[n_segments + g] = run_tx;
+            seg_sizes[2 * n_segments + g] = run_classes;
+            seg_sizes[3 * n_segments + g] = run_pairs;
+        }
     }
 }
 
-// tile of every transcript (n_tx: a component above the capacity -- sorts behind every tile), and the key
-// its place in the tile's list is sorted by: the tile, then (degree_bits > 0) transcripts of many pairs
-// first -- the row phase of em_local_chunk_kernel gives a wave eight neighbours of the list at a time and
-// loops as long as the longest of them, so neighbours should be of a length; the EM's arithmetic does
-// not depend on the order of a tile's transcripts
-__global__ void __launch_bounds__(256)
-tx_tile_kernel(const int32_t *label, const int32_t *root_tile, const int64_t *seg_base, int64_t n_tx,
-               const int64_t *tx_row, const int64_t *row_start, int degree_bits, int32_t *tx_tile, int32_t *key)
+// seg_base[k][0 .. n_segments] = the exclusive prefix sums of seg_sizes[k][0 .. n_segments) and their total, k = 0:
+// tiles, 1: transcripts, 2: classes, 3: pairs of the tiles, by ONE workgroup (a few hundred runs; each lane walks a
+// stretch of them, so any number is handled).  It also writes the end entries that em_local_chunk_kernel and
+// tile_order_kernel read behind the last tile: tile_tx / tile_cls / tile_pair[tiles] and the pair total at the place
+// behind the last listed transcript and class.
+__global__ void __launch_bounds__(1024)
+seg_scan_kernel(const int64_t *__restrict__ seg_sizes, int64_t n_segments, int64_t *__restrict__ seg_base,
+                int64_t *__restrict__ tile_tx, int64_t *__restrict__ tile_cls, int64_t *__restrict__ tile_pair,
+                int64_t *__restrict__ tx_pair, int64_t *__restrict__ cls_pair)
 {
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tx;
-         t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t r = label[t], at = root_tile[r];
-        const int32_t tile = at < 0 ? (int32_t)n_tx : (int32_t)(seg_base[r / EM_TILE_SEGMENT] + at);
-        tx_tile[t] = tile;
-        const int64_t turns = (row_start[tx_row[t + 1]] - row_start[tx_row[t]] + 7) >> 3;     // (of an 8-lane group)
-        const int32_t longest = (1 << degree_bits) - 1;
-        key[t] = (tile << degree_bits) | (longest - (int32_t)min(turns, (int64_t)longest));
+    __shared__ int64_t s_part[4][1024];
+    const int64_t per = (n_segments + 1023) / 1024;
+    const int64_t first = min(n_segments, threadIdx.x * per), last = min(n_segments, first + per);
+    int64_t sum[4];
+    for (int k = 0; k < 4; ++k) {
+        sum[k] = 0;
+        for (int64_t i = first; i < last; ++i) sum[k] += seg_sizes[k * n_segments + i];
+        s_part[k][threadIdx.x] = sum[k];
+    }
+    __syncthreads();
+    for (int step = 1; step < 1024; step <<= 1) {
+        int64_t add[4];
+        for (int k = 0; k < 4; ++k) add[k] = (int)threadIdx.x >= step ? s_part[k][threadIdx.x - step] : 0;
+        __syncthreads();
+        for (int k = 0; k < 4; ++k) s_part[k][threadIdx.x] += add[k];
+        __syncthreads();
+    }
+    for (int k = 0; k < 4; ++k) {
+        int64_t at = s_part[k][threadIdx.x] - sum[k];
+        for (int64_t i = first; i < last; ++i) { seg_base[k * (n_segments + 1) + i] = at; at += seg_sizes[k * n_segments + i]; }
+    }
+    if (threadIdx.x == 1023) {
+        const int64_t tiles = s_part[0][1023], txs = s_part[1][1023], classes = s_part[2][1023], pairs = s_part[3][1023];
+        seg_base[n_segments] = tiles; seg_base[2 * n_segments + 1] = txs;
+        seg_base[3 * n_segments + 2] = classes; seg_base[4 * n_segments + 3] = pairs;
+        tile_tx[tiles] = txs; tile_cls[tiles] = classes; tile_pair[tiles] = pairs;
+        tx_pair[txs] = pairs; cls_pair[classes] = pairs;
+    }
+}
+
+// ---- a tile's members: dropped into the tile's places in any order, then put in order by the tile's workgroup
+// The lanes of a wave hold consecutive items; a run of neighbouring lanes that name the same tile draws its places
+// with ONE returning add on the tile's cursor (tile < 0: the lane places nothing).  Returns the lane's place in its
+// tile.  Called by whole waves.
+__device__ __forceinline__ int32_t tile_draw_place(int32_t tile, int32_t *cursor, int lane)
+{
+    const int32_t before = __shfl_up(tile, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || before != tile);
+    const int head = 63 - __clzll((long long)(heads & ((2ULL << lane) - 1ULL)));     // (the start of my run)
+    int32_t base = 0;
+    if (tile >= 0 && head == lane) {
+        const unsigned long long later = lane == 63 ? 0ULL : heads >> (lane + 1);
+        const int run = later ? __ffsll((long long)later) : 64 - lane;
+        base = atomicAdd(&cursor[tile], run);
+    }
+    return __shfl(base, head, 64) + (lane - head);
+}
+
+// tile of every transcript (n_tx: a component above the capacity -- in no tile), and its place, not yet in
+// order, among the tile's transcripts in tx_list
+__global__ void __launch_bounds__(256)
+tx_place_kernel(const int32_t *__restrict__ label, const int32_t *__restrict__ root_tile, const int64_t *__restrict__ seg_base,
+                int64_t n_tx, const int64_t *__restrict__ tile_tx, int32_t *__restrict__ cursor, int32_t *__restrict__ tx_tile,
+                int32_t *__restrict__ tx_list)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; t0 < n_tx; t0 += stride) {
+        const int64_t t = t0 + lane;
+        int32_t tile = -1;
+        if (t < n_tx) {
+            const int32_t r = label[t], at = root_tile[r];
+            tile = at < 0 ? -1 : (int32_t)(seg_base[r / EM_TILE_SEGMENT] + at);
+            tx_tile[t] = tile < 0 ? (int32_t)n_tx : tile;
+        }
+        const int32_t place = tile_draw_place(tile, cursor, lane);
+        if (tile >= 0) {
+            const int64_t to = tile_tx[tile] + place;
+            if (to >= 0 && to < n_tx) tx_list[to] = (int32_t)t;           // (always: a tile's transcripts are those counted into it)
+        }
+    }
+}
+
+// the same for the classes: a class lies in the tile of its first transcript (one without transcripts: of
+// transcript 0, as cc_classes_kernel counted it)
+__global__ void __launch_bounds__(256)
+cls_place_kernel(const int64_t *__restrict__ cls_offset, const int32_t *__restrict__ ids, int64_t n_classes, int64_t n_tx,
+                 const int32_t *__restrict__ tx_tile, const int64_t *__restrict__ tile_cls, int32_t *__restrict__ cursor,
+                 int32_t *__restrict__ cls_tile, int32_t *__restrict__ cls_list)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t c0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; c0 < n_classes; c0 += stride) {
+        const int64_t c = c0 + lane;
+        int32_t tile = -1;
+        if (c < n_classes) {
+            const int64_t begin = cls_offset[c];
+            tile = tx_tile[begin < cls_offset[c + 1] ? ids[begin] : 0];
+            cls_tile[c] = tile;
+            if (tile == (int32_t)n_tx) tile = -1;
+        }
+        const int32_t place = tile_draw_place(tile, cursor, lane);
+        if (tile >= 0) {
+            const int64_t to = tile_cls[tile] + place;
+            if (to >= 0 && to < n_classes) cls_list[to] = (int32_t)c;
+        }
     }
 }
 
@@ -958,96 +1078,148 @@ tx_tile_kernel(const int32_t *label, const int32_t *root_tile, const int64_t *se
 #ifndef SKM_EM_CLASS_ORDER
 #define SKM_EM_CLASS_ORDER 1
 #endif
-// tile of every class, and the key its place in the tile's list is sorted by: the tile, then
-// (length_bits > 0) classes of many batches first -- a lane of em_local_chunk_kernel's class phase takes
-// its tuple EM_TILE_CLASS_BATCH entries at a time and a wave loops as long as the longest of its 64
-// classes, so neighbours in the list should take like numbers of turns.  A class's place in the list is a
-// label only: the tuple keeps its order and every row of the transcript view keeps its entries' order
-// (tile_fill_tx_kernel), so no sum changes.
-__global__ void __launch_bounds__(256)
-cls_tile_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, const int32_t *tx_tile,
-                int length_bits, int32_t *cls_tile, int32_t *key)
+
+// The order of a tile's members and the prefix sums of their pairs, by the tile's workgroup of 256 lanes in LDS.
+// In: n <= CAP members in any order, s_item[i] with the DISTINCT key s_key[i] and s_off[i] pairs.  Out: s_item in
+// ascending order of the keys, s_off[0 .. n] the exclusive prefix sums of the pairs in that order and their total.
+// A member's place is the number of keys below its own: n reads of LDS, all lanes the same word, per member.
+template <int CAP>
+__device__ __forceinline__ void tile_rank_and_scan(int n, const unsigned long long *s_key, int32_t *s_item, int32_t *s_off,
+                                                   int32_t *s_wave)
 {
-    for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < n_classes;
-         c += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t begin = cls_offset[c], end = cls_offset[c + 1];
-        const int32_t tile = tx_tile[begin < end ? ids[begin] : 0];
-        cls_tile[c] = tile;
-        const int64_t turns = (end - begin + EM_TILE_CLASS_BATCH - 1) / EM_TILE_CLASS_BATCH;
-        const int32_t longest = (1 << length_bits) - 1;
-        key[c] = (tile << length_bits) | (longest - (int32_t)min(turns, (int64_t)longest));
+    constexpr int PER = CAP / 256 + 1;                // (256 PER > CAP: the scan below reaches entry n)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long key[PER];
+    int32_t item[PER], len[PER], rank[PER];
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+        const int i = tid + p * 256;
+        const bool mine = i < n;
+        key[p] = mine ? s_key[i] : 0ULL;
+        item[p] = mine ? s_item[i] : 0;
+        len[p] = mine ? s_off[i] : 0;
+        rank[p] = 0;
     }
+    for (int j = 0; j < n; ++j) {
+        const unsigned long long other = s_key[j];
+#pragma unroll
+        for (int p = 0; p < PER; ++p) rank[p] += other < key[p] ? 1 : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < PER; ++p)
+        if (tid + p * 256 < n && rank[p] < n) { s_item[rank[p]] = item[p]; s_off[rank[p]] = len[p]; }
+    __syncthreads();
+    int32_t v[PER], sum = 0;
+#pragma unroll
+    for (int p = 0; p < PER; ++p) { const int e = tid * PER + p; v[p] = e < n ? s_off[e] : 0; sum += v[p]; }
+    int32_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int32_t up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int32_t at = incl - sum;
+    for (int w = 0; w < wave; ++w) at += s_wave[w];
+#pragma unroll
+    for (int p = 0; p < PER; ++p) {
+        const int e = tid * PER + p;
+        if (e <= n) s_off[e] = at;
+        at += v[p];
+    }
+    __syncthreads();
 }
 
-// first[i] = first place of tile i in a list sorted by tile, for i = 0 .. *n_tiles (whatever lies in no
-// tile -- key n_tx -- sorts last and starts at first[*n_tiles]); a tile may be empty (one of transcripts
-// that are in no class has no classes)
+// One workgroup per tile, a fixed grid striding over the *n_tiles tiles.  It reads the tile's transcripts and
+// classes as the two placement kernels left them, puts them into the order the chunk kernel wants -- the order the
+// two sorts by (tile, turns, index) gave before:
+//   transcripts by min(ceil(degree / 8), 31) descending (degree_bits > 0), then id ascending: the row phase of
+//   em_local_chunk_kernel gives a wave eight neighbours of the list at a time and loops as long as the longest;
+//   classes by min(ceil(length / EM_TILE_CLASS_BATCH), 31) descending (length_bits > 0), then internal index
+//   ascending: a lane of the class phase takes its tuple EM_TILE_CLASS_BATCH entries at a time and a wave loops as
+//   long as the longest of its 64 classes
+// -- and writes tx_list / cls_list back in place, tx_pair / cls_pair (the tile's first pair plus the prefix sums
+// of degrees / lengths), the tile-local names tx_local / cls_local, and with them the tile's two views: tuples in
+// tuple order, rows in the order of the global transposed view.  A class's place in the list is a label only, so
+// no sum of the EM changes with it.  The names pass through global memory inside the workgroup (written before a
+// barrier, read after it); no workgroup reads what another wrote in this launch.
+// A tile whose sizes are not what the packing promised is left alone (em_local_chunk_kernel then raises its
+// fault word from the same sizes).
 __global__ void __launch_bounds__(256)
-tile_starts_kernel(const int32_t *sorted_tile, int shift, int64_t n, const int64_t *n_tiles, int64_t *first)
+tile_build_kernel(const int64_t *__restrict__ n_tiles, const int64_t *__restrict__ tile_tx, const int64_t *__restrict__ tile_cls,
+                  const int64_t *__restrict__ tile_pair, int64_t n_tx, int64_t n_classes, int64_t n_ids,
+                  const int64_t *__restrict__ tx_row, const int64_t *__restrict__ row_start, const int32_t *__restrict__ tx_cls,
+                  const int64_t *__restrict__ cls_offset, const int32_t *__restrict__ ids, int degree_bits, int length_bits,
+                  int32_t *tx_list, int32_t *cls_list, int64_t *__restrict__ tx_pair, int64_t *__restrict__ cls_pair,
+                  int32_t *tx_local, int32_t *cls_local, uint16_t *__restrict__ out_cls_tx, uint16_t *__restrict__ out_tx_cls)
 {
+    __shared__ unsigned long long s_key[EM_TILE_CLASSES > EM_TILE_TX ? EM_TILE_CLASSES : EM_TILE_TX];
+    __shared__ int32_t s_tx[EM_TILE_TX], s_tx_off[EM_TILE_TX + 1];
+    __shared__ int32_t s_cls[EM_TILE_CLASSES], s_cls_off[EM_TILE_CLASSES + 1];
+    __shared__ int32_t s_wave[4];
+    const int tid = threadIdx.x;
     const int64_t tiles = *n_tiles;
-    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j <= n;
-         j += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t lo = j == 0 ? -1 : min((int64_t)(sorted_tile[j - 1] >> shift), tiles);
-        const int64_t hi = j == n ? tiles : min((int64_t)(sorted_tile[j] >> shift), tiles);
-        for (int64_t t = lo + 1; t <= hi; ++t) first[t] = j;
-    }
-}
-
-// item list[i] sits at place i - first[tile] of its tile; len[i] = its number of pairs
-__global__ void __launch_bounds__(256)
-tile_local_tx_kernel(const int32_t *list, const int32_t *tile_sorted, int shift, const int64_t *first, const int64_t *n_tiles, int64_t n,
-                     const int64_t *tx_row, const int64_t *row_start, int32_t *local, int64_t *len)
-{
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t t = list[i];
-        local[t] = (int32_t)(i - first[min((int64_t)(tile_sorted[i] >> shift), *n_tiles)]);
-        len[i] = row_start[tx_row[t + 1]] - row_start[tx_row[t]];
-    }
-}
-
-__global__ void __launch_bounds__(256)
-tile_local_cls_kernel(const int32_t *list, const int32_t *tile_sorted, int shift, const int64_t *first, const int64_t *n_tiles, int64_t n,
-                      const int64_t *cls_offset, int32_t *local, int64_t *len)
-{
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n;
-         k += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t c = list[k];
-        local[c] = (int32_t)(k - first[min((int64_t)(tile_sorted[k] >> shift), *n_tiles)]);
-        len[k] = cls_offset[c + 1] - cls_offset[c];
-    }
-}
-
-// the pairs of listed item i, from src[src_first(i) ...], renamed by `local`, to dst[dst_pair[i] ...];
-// nothing for what lies in no tile (tile == residual_tile: a local index need not fit 16 bits there)
-__global__ void __launch_bounds__(256)
-tile_fill_cls_kernel(const int32_t *cls_list, int64_t n_classes, const int64_t *cls_offset, const int32_t *ids,
-                     const int32_t *tx_local, const int64_t *cls_pair, const int32_t *cls_tile, int32_t residual_tile,
-                     uint16_t *out)
-{
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_classes;
-         k += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t c = cls_list[k];
-        if (cls_tile[c] == residual_tile) continue;
-        const int64_t src = cls_offset[c], n = cls_offset[c + 1] - src, dst = cls_pair[k];
-        for (int64_t j = 0; j < n; ++j) out[dst + j] = (uint16_t)tx_local[ids[src + j]];
-    }
-}
-
-// (eight lanes per transcript: a transcript has 22 pairs on average)
-__global__ void __launch_bounds__(256)
-tile_fill_tx_kernel(const int32_t *tx_list, int64_t n_tx, const int64_t *tx_row, const int64_t *row_start,
-                    const int32_t *tx_cls, const int32_t *cls_local, const int64_t *tx_pair, const int32_t *tx_tile,
-                    uint16_t *out)
-{
-    const int sub = threadIdx.x & 7;
-    for (int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3; i < n_tx;
-         i += ((int64_t)gridDim.x * blockDim.x) >> 3) {
-        const int32_t t = tx_list[i];
-        if (tx_tile[t] == (int32_t)n_tx) continue;
-        const int64_t src = row_start[tx_row[t]], n = row_start[tx_row[t + 1]] - src, dst = tx_pair[i];
-        for (int64_t j = sub; j < n; j += 8) out[dst + j] = (uint16_t)cls_local[tx_cls[src + j]];
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t tx0 = tile_tx[tile], cls0 = tile_cls[tile], pair0 = tile_pair[tile];
+        const int64_t tx_n = tile_tx[tile + 1] - tx0, cls_n = tile_cls[tile + 1] - cls0, pair_n = tile_pair[tile + 1] - pair0;
+        if (tx0 < 0 || cls0 < 0 || pair0 < 0 || tx_n < 0 || cls_n < 0 || pair_n < 0 || tx_n > EM_TILE_TX ||
+            cls_n > EM_TILE_CLASSES || pair_n > EM_TILE_PAIRS || tx0 + tx_n > n_tx || cls0 + cls_n > n_classes ||
+            pair0 + pair_n > n_ids) continue;                       // (block-uniform)
+        const int n_t = (int)tx_n, n_c = (int)cls_n;
+        for (int i = tid; i < n_t; i += 256) {
+            const int32_t t = tx_list[tx0 + i];
+            const int64_t degree = row_start[tx_row[t + 1]] - row_start[tx_row[t]];
+            const int64_t longest = (1 << degree_bits) - 1;
+            s_tx[i] = t;
+            s_tx_off[i] = (int32_t)degree;
+            s_key[i] = (unsigned long long)(longest - min((degree + 7) >> 3, longest)) << 32 | (uint32_t)t;
+        }
+        __syncthreads();
+        tile_rank_and_scan<EM_TILE_TX>(n_t, s_key, s_tx, s_tx_off, s_wave);
+        for (int i = tid; i < n_t; i += 256) {
+            const int32_t t = s_tx[i];
+            tx_list[tx0 + i] = t;
+            tx_pair[tx0 + i] = pair0 + s_tx_off[i];
+            tx_local[t] = i;
+        }
+        __syncthreads();                                            // (s_key is taken again)
+        for (int k = tid; k < n_c; k += 256) {
+            const int32_t c = cls_list[cls0 + k];
+            const int64_t length = cls_offset[c + 1] - cls_offset[c];
+            const int64_t longest = (1 << length_bits) - 1;
+            s_cls[k] = c;
+            s_cls_off[k] = (int32_t)length;
+            s_key[k] = (unsigned long long)(longest - min((length + EM_TILE_CLASS_BATCH - 1) / EM_TILE_CLASS_BATCH, longest)) << 32 |
+                       (uint32_t)c;
+        }
+        __syncthreads();
+        tile_rank_and_scan<EM_TILE_CLASSES>(n_c, s_key, s_cls, s_cls_off, s_wave);
+        for (int k = tid; k < n_c; k += 256) {
+            const int32_t c = s_cls[k];
+            cls_list[cls0 + k] = c;
+            cls_pair[cls0 + k] = pair0 + s_cls_off[k];
+            cls_local[c] = k;
+        }
+        __syncthreads();                                            // (the names are in memory for this workgroup)
+        // (only what adds up to the tile's pairs is written: a place past them would be another tile's)
+        if (s_tx_off[n_t] == (int32_t)pair_n && s_cls_off[n_c] == (int32_t)pair_n) {
+            for (int k = tid; k < n_c; k += 256) {
+                const int64_t src = cls_offset[s_cls[k]], dst = pair0 + s_cls_off[k];
+                const int n = s_cls_off[k + 1] - s_cls_off[k];
+                for (int j = 0; j < n; ++j) out_cls_tx[dst + j] = (uint16_t)tx_local[ids[src + j]];
+            }
+            // (eight lanes per transcript: a transcript has 22 pairs on average)
+            const int sub = tid & 7;
+            for (int i = tid >> 3; i < n_t; i += 32) {
+                const int32_t t = s_tx[i];
+                const int64_t src = row_start[tx_row[t]], dst = pair0 + s_tx_off[i];
+                const int n = s_tx_off[i + 1] - s_tx_off[i];
+                for (int j = sub; j < n; j += 8) out_tx_cls[dst + j] = (uint16_t)cls_local[tx_cls[src + j]];
+            }
+        }
+        __syncthreads();                                            // (the next tile takes the arrays again)
     }
 }
 
@@ -1088,19 +1260,23 @@ tile_order_kernel(const int64_t *__restrict__ tile_cls, const int64_t *__restric
 }
 static_assert(TILE_ORDER_BINS % 64 == 0, "the scan gives every lane of a wave the same number of bins");
 
+constexpr int TILE_BUILD_BLOCKS = 2048;       // tile_build_kernel's grid: eight workgroups a CU, striding over the tiles
+
 int build_tiles(Scratch &scratch, QuantBuild &q)
 {
     hipStream_t stream = scratch.stream;
     const int64_t C = q.n_classes, M = q.n_ids, T = q.n_tx;
     if (M >= (1LL << 31) || C >= (1LL << 31) || T >= (1LL << 31) - 2) return -2;
     const int64_t n_segments = (T + EM_TILE_SEGMENT - 1) / EM_TILE_SEGMENT;
-    QB_ALLOC(parent, int32_t, T); QB_ALLOC(comp, int32_t, 3 * T); QB_ALLOC(root_tile, int32_t, T);
-    QB_ALLOC(seg_tiles, int64_t, n_segments); QB_ALLOC(seg_base, int64_t, n_segments + 1);
+    // comp[3 T], then the tiles' cursors of the two placement kernels, [T + 1] each: cleared together
+    QB_ALLOC(parent, int32_t, T); QB_ALLOC(comp, int32_t, 3 * T + 2 * (T + 1)); QB_ALLOC(root_tile, int32_t, T);
+    QB_ALLOC(seg_sizes, int64_t, 4 * n_segments); QB_ALLOC(seg_base, int64_t, 4 * (n_segments + 1));
     QB_ALLOC(oversize, unsigned long long, 1);
-    QB_ALLOC(iota, int32_t, std::max(T, C)); QB_ALLOC(sorted_tile, int32_t, std::max(T, C));
+    QB_ALLOC(tile_pair, int64_t, T + 2);
     QB_ALLOC(tx_local, int32_t, T); QB_ALLOC(cls_local, int32_t, C);
-    QB_ALLOC(len, int64_t, std::max(T, C));
-    QB_TRY(hipMemsetAsync(comp, 0, 3 * T * sizeof(int32_t), stream));
+    int32_t *cursor_tx = comp + 3 * T, *cursor_cls = cursor_tx + (T + 1);
+    const int64_t *n_tiles = seg_base + n_segments;
+    QB_TRY(hipMemsetAsync(comp, 0, (3 * T + 2 * (T + 1)) * sizeof(int32_t), stream));
     QB_TRY(hipMemsetAsync(oversize, 0, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, T);
     hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, parent);
@@ -1108,41 +1284,30 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
                        q.tx_label, comp);
     hipLaunchKernelGGL(cc_classes_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C,
                        q.tx_label, comp);
-    hipLaunchKernelGGL(tile_pack_kernel, dim3(blocks_for(64 * n_segments)), dim3(256), 0, stream, comp, T, n_segments,
-                       root_tile, seg_tiles, oversize);
-    if (exclusive_scan_with_total(scratch, seg_tiles, seg_base, n_segments)) return -1;
+    // the tiles' sizes are known from the components alone: their starts in the lists before anything is listed
+    hipLaunchKernelGGL(tile_pack_kernel<false>, dim3(blocks_for(64 * n_segments)), dim3(256), 0, stream, comp, T, n_segments,
+                       root_tile, seg_sizes, oversize, (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t *)nullptr,
+                       (int64_t *)nullptr);
+    hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, stream, seg_sizes, n_segments, seg_base, q.tile_tx,
+                       q.tile_cls, tile_pair, q.tx_pair, q.cls_pair);
+    hipLaunchKernelGGL(tile_pack_kernel<true>, dim3(blocks_for(64 * n_segments)), dim3(256), 0, stream, comp, T, n_segments,
+                       (int32_t *)nullptr, (int64_t *)nullptr, (unsigned long long *)nullptr, seg_base, q.tile_tx, q.tile_cls,
+                       tile_pair);
+    // members into their tiles in the order the lanes come by, then every tile in order by its own workgroup
     int end_bit = 1;
     while ((1LL << end_bit) < T + 1 && end_bit < 31) ++end_bit;
-    const int degree_bits = end_bit + 5 <= 31 ? 5 : 0;
-    QB_ALLOC(tx_key, int32_t, T);
-    hipLaunchKernelGGL(tx_tile_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_label, root_tile, seg_base, T,
-                       q.tx_row, q.row_start, degree_bits, q.tx_tile, tx_key);
-    // transcripts by tile and turns of the row phase (stable: ascending ids among equals), then the classes the
-    // same way by tile and turns of the class phase
-    hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(std::max(T, C))), dim3(256), 0, stream, iota, std::max(T, C));
-    if (sort_pairs(scratch, tx_key, sorted_tile, iota, q.tx_list, T, end_bit + degree_bits)) return -1;
-    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(T + 1)), dim3(256), 0, stream, sorted_tile, degree_bits, T,
-                       seg_base + n_segments, q.tile_tx);
-    hipLaunchKernelGGL(tile_local_tx_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_list, sorted_tile, degree_bits,
-                       q.tile_tx, seg_base + n_segments, T, q.tx_row, q.row_start, tx_local, len);
-    if (exclusive_scan_with_total(scratch, len, q.tx_pair, T)) return -1;
+    const int degree_bits = end_bit + 5 <= 31 ? 5 : 0;          // (the width the sorts by (tile, turns) had room for)
     const int length_bits = SKM_EM_CLASS_ORDER ? degree_bits : 0;
-    QB_ALLOC(cls_key, int32_t, C);
-    hipLaunchKernelGGL(cls_tile_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, q.tx_tile,
-                       length_bits, q.cls_tile, cls_key);
-    if (sort_pairs(scratch, cls_key, sorted_tile, iota, q.cls_list, C, end_bit + length_bits)) return -1;
-    hipLaunchKernelGGL(tile_starts_kernel, dim3(blocks_for(C + 1)), dim3(256), 0, stream, sorted_tile, length_bits, C,
-                       seg_base + n_segments, q.tile_cls);
-    hipLaunchKernelGGL(tile_local_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, sorted_tile, length_bits,
-                       q.tile_cls, seg_base + n_segments, C, q.cls_offset, cls_local, len);
-    if (exclusive_scan_with_total(scratch, len, q.cls_pair, C)) return -1;
-    hipLaunchKernelGGL(tile_fill_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_list, C, q.cls_offset,
-                       q.ids, tx_local, q.cls_pair, q.cls_tile, (int32_t)T, q.tile_cls_tx);
-    hipLaunchKernelGGL(tile_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_list, T, q.tx_row,
-                       q.row_start, q.tx_cls, cls_local, q.tx_pair, q.tx_tile, q.tile_tx_cls);
-    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, q.tile_cls, q.cls_pair, seg_base + n_segments,
-                       q.tile_order);
-    QB_TRY(hipMemcpyAsync(&q.tile_info[0], seg_base + n_segments, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    hipLaunchKernelGGL(tx_place_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_label, root_tile, seg_base, T,
+                       q.tile_tx, cursor_tx, q.tx_tile, q.tx_list);
+    hipLaunchKernelGGL(cls_place_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, T, q.tx_tile,
+                       q.tile_cls, cursor_cls, q.cls_tile, q.cls_list);
+    hipLaunchKernelGGL(tile_build_kernel, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(T, 1), TILE_BUILD_BLOCKS)), dim3(256),
+                       0, stream, n_tiles, q.tile_tx, q.tile_cls, tile_pair, T, C, M, q.tx_row, q.row_start, q.tx_cls,
+                       q.cls_offset, q.ids, degree_bits, length_bits, q.tx_list, q.cls_list, q.tx_pair, q.cls_pair, tx_local,
+                       cls_local, q.tile_cls_tx, q.tile_tx_cls);
+    hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, q.tile_cls, q.cls_pair, n_tiles, q.tile_order);
+    QB_TRY(hipMemcpyAsync(&q.tile_info[0], n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     QB_TRY(hipMemcpyAsync(&q.tile_info[1], oversize, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     return 0;
 }
