@@ -603,6 +603,25 @@ int skm_gene_matrix_shape(const skm_gene_matrix *matrix, int64_t *n_samples, int
 int skm_gene_matrix_read(const skm_gene_matrix *matrix, int64_t *indptr /*[n_samples + 1]*/, int32_t *indices /*[nnz]*/,
                          int64_t *data /*[nnz]*/, int64_t *other /*[n_samples][2]*/);
 int skm_gene_matrix_destroy(skm_gene_matrix *matrix);
+/* The molecule matrix ("Molecule matrix"): entry (sample, gene) = the number of DISTINCT UMIs
+ * among the sample's surviving units whose class lies inside that gene (the rule above), UMIs compared letter for
+ * letter -- where the count matrix adds up class counts and so counts a molecule once per class its reads fell into.
+ * The same handle: indptr, indices and other are those of skm_sample_set_gene_matrix of the same set, every data
+ * entry is >= 1 and <= the count matrix's.  A UMI seen in a class inside the gene and in an ambiguous class counts
+ * once, for the first; ambiguous classes that share a UMI are not intersected.  Parity with other tools' UMI rules
+ * is not claimed.
+ * skm_sample_set_molecule_matrix is a pass over what the set holds in HBM after its launches -- the molecule set of
+ * UMI collapse and the class table -- and waits and locks as skm_sample_set_gene_matrix does.  SKM_ERR_STATE for a
+ * set that keeps no UMIs (skm_sample_set_keep_umis); SKM_ERR_ARG for 2^32 molecules or more and for the limits of the
+ * count matrix: refused before anything is allocated.  Device memory while it runs: 8 bytes per slot of the class
+ * table, 8 per slot of the molecule set, 48 per surviving molecule.
+ * skm_gene_matrix_from_molecules makes the matrix of n host triples (sample, gene, UMI), other all zero: the
+ * sort, head and fill steps alone.  SKM_ERR_ARG for a sample outside [0, n_samples) or a gene outside [0, n_genes).
+ * On any failure *out is NULL. */
+int skm_sample_set_molecule_matrix(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                   skm_gene_matrix **out);
+int skm_gene_matrix_from_molecules(int device, int64_t n, const int32_t *sample, const int32_t *gene, const uint32_t *umi,
+                                   int64_t n_samples, int64_t n_genes, skm_gene_matrix **out);
 
 /* ---------------------------------------------------------------- cell barcodes
  * ("Cell barcodes".)  A pooled run -- one barcode read per unit beside the cDNA reads --

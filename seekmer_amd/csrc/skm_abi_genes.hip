@@ -1,6 +1,6 @@
 // C ABI of libseekmer_hip.so: gene-level tables -- sums of transcript values by gene, and the unique counts of a
 // class table given on the host, held by a mapper or held by a sample set -- as dense rows, or as the sparse count
-// matrix (skm_gene_matrix: a CSR over samples that stays in HBM until it is read).
+// matrix (skm_gene_matrix: a CSR over samples that stays in HBM until it is read), of units or of molecules.
 #include "skm_abi_samples.h"
 
 #include <algorithm>
@@ -293,6 +293,126 @@ int gene_matrix_device(const GeneClasses &t, int device, int64_t n_samples, int6
     return SKM_OK;
 }
 
+// ---- molecule matrix (skm_molecules.hip)
+// what the sort's 32-bit values can number: never wrapped silently
+int molecule_limits(int64_t n_molecules, int64_t n_samples)
+{
+    if (n_molecules >= (1LL << 32))
+        return fail(SKM_ERR_ARG, "a molecule matrix of %lld molecules: fewer than 2^32 are possible", (long long)n_molecules);
+    if (n_samples > (int64_t)INT32_MAX - 1)
+        return fail(SKM_ERR_ARG, "a molecule matrix of %lld samples: 2^31 - 2 at most are possible", (long long)n_samples);
+    return SKM_OK;
+}
+
+struct MoleculeKeys {             // n molecules in HBM: label (sample << 32 | gene, or n_samples << 32), UMI, number 0 .. n - 1
+    DBuf<unsigned long long> label, umi; DBuf<int32_t> number;
+    int ensure(int64_t n) { SKM_TRY(label.ensure(n)); SKM_TRY(umi.ensure(n)); SKM_TRY(number.ensure(n)); return SKM_OK; }
+};
+
+// Steps 3 and 4 (stream drained on return): the two stable sorts, heads and their scan, fill.  m->indptr is zeroed,
+// m->other is what the caller made of it.  `keys` is used up: its arrays are the sorts' second buffers.
+int molecule_matrix_sorted(skm_gene_matrix *m, MoleculeKeys &keys, int64_t n, int umi_bits, hipStream_t stream)
+{
+    const int64_t n_samples = m->n_samples;
+    DBuf<unsigned long long> d_umi_sorted; DBuf<int32_t> d_order, d_at; DBuf<uint32_t> d_first; DBuf<int64_t> d_runs;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    if (n && n_samples) {
+        SKM_TRY(d_umi_sorted.ensure(n)); SKM_TRY(d_order.ensure(n)); SKM_TRY(d_at.ensure(n)); SKM_TRY(d_first.ensure(n));
+        SKM_TRY(d_runs.ensure((size_t)n + 1));
+        // least significant key first: by UMI, then (stable) by the label gathered into that order
+        if (sort_pairs_u64(keys.umi.p, d_umi_sorted.p, keys.number.p, d_order.p, n, std::max(umi_bits, 1), stream) != 0)
+            return fail(SKM_ERR_HIP, "sorting %lld molecules by UMI: %s", (long long)n, quant_setup_failure());
+        unsigned long long *by_umi = keys.umi.p, *sorted = keys.label.p;      // (both free once the gather has run)
+        launch_molecule_gather(keys.label.p, d_order.p, n, by_umi, keys.number.p, stream);
+        HIP_TRY(hipGetLastError());
+        int end_bit = 33;
+        while ((1LL << (end_bit - 32)) <= n_samples) ++end_bit;   // (the labels go up to n_samples << 32 itself)
+        if (sort_pairs_u64(by_umi, sorted, keys.number.p, d_at.p, n, end_bit, stream) != 0)
+            return fail(SKM_ERR_HIP, "sorting %lld molecules by sample and gene: %s", (long long)n, quant_setup_failure());
+        launch_molecule_heads(sorted, d_at.p, d_umi_sorted.p, n, n_samples, d_runs.p, d_first.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (exclusive_scan_total_i64(d_runs.p, d_runs.p, n, stream) != 0)
+            return fail(SKM_ERR_HIP, "numbering the entries of %lld molecules: %s", (long long)n, quant_setup_failure());
+        HIP_TRY(hipMemcpyAsync(&m->nnz, d_runs.p + n, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (m->nnz < 0 || m->nnz > n) return fail(SKM_ERR_HIP, "%lld entries from %lld molecules", (long long)m->nnz, (long long)n);
+    }
+    SKM_TRY(m->indices.ensure((size_t)std::max<int64_t>(m->nnz, 1))); SKM_TRY(m->data.ensure((size_t)std::max<int64_t>(m->nnz, 1)));
+    if (n && n_samples) {
+        HIP_TRY(hipMemsetAsync(m->data.p, 0, (size_t)std::max<int64_t>(m->nnz, 1) * 8, stream));
+        launch_molecule_fill(keys.label.p, d_first.p, d_runs.p, n, n_samples, m->indptr.p, m->indices.p, m->data.p, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.dismiss();
+    return SKM_OK;
+}
+
+// an empty matrix of n_samples rows: indptr and other zero
+int molecule_matrix_new(int device, int64_t n_samples, int64_t n_genes, hipStream_t stream, std::unique_ptr<skm_gene_matrix> &m)
+{
+    m.reset(new skm_gene_matrix);
+    m->device = device; m->n_samples = n_samples; m->n_genes = n_genes;
+    SKM_TRY(m->indptr.ensure((size_t)n_samples + 1)); SKM_TRY(m->other.ensure((size_t)std::max<int64_t>(2 * n_samples, 1)));
+    HIP_TRY(hipMemsetAsync(m->indptr.p, 0, (size_t)(n_samples + 1) * 8, stream));
+    HIP_TRY(hipMemsetAsync(m->other.p, 0, (size_t)std::max<int64_t>(2 * n_samples, 1) * 8, stream));
+    return SKM_OK;
+}
+
+// Steps 1 and 2 on a set's resident state (s->mu and m->mu are held): labels by table slot, the live molecules
+// numbered by the scan, their (label, UMI); then the steps above.
+int molecule_matrix_set(skm_sample_set *s, const GeneClasses &t, int64_t n_samples, int64_t n_tx, int64_t n_genes,
+                        const int32_t *tx_gene, skm_gene_matrix **out)
+{
+    skm_mapper *mp = s->m;
+    hipStream_t stream = mp->stream;
+    SKM_TRY(gene_matrix_limits(t.n_classes, n_samples));
+    SKM_TRY(molecule_limits(s->umi_entries, n_samples));
+    if (t.n_classes && n_samples && n_tx == 0) return fail(SKM_ERR_ARG, "classes over no transcripts");
+    const uint64_t class_slots = mp->t.slots ? mp->t.slot_mask + 1 : 0;
+    if (t.n_classes && (!class_slots || !mp->t.class_list)) return fail(SKM_ERR_STATE, "classes without a table");
+    std::unique_ptr<skm_gene_matrix> m;
+    DBuf<int32_t> d_gene; DBuf<unsigned long long> d_labels; DBuf<int64_t> d_place; DBuf<int> d_error; MoleculeKeys keys;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    SKM_TRY(molecule_matrix_new(mp->ix->device, n_samples, n_genes, stream, m));
+    int64_t n = 0;
+    int error[2] = {0, 0};
+    if (t.n_classes && n_samples) {
+        SKM_TRY(d_gene.ensure(n_tx)); SKM_TRY(d_error.ensure(2)); SKM_TRY(d_labels.ensure((size_t)class_slots));
+        HIP_TRY(hipMemcpyAsync(d_gene.p, tx_gene, n_tx * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_error.p, 0, 2 * sizeof(int), stream));
+        launch_molecule_label_init(d_labels.p, class_slots, n_samples, stream);
+        launch_molecule_labels(t, mp->t.class_list, class_slots, d_gene.p, n_tx, n_samples, d_labels.p, m->other.p, d_error.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (s->umi_n_slots) {
+            const UmiSet set{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, mp->error.p};
+            SKM_TRY(d_place.ensure((size_t)s->umi_n_slots + 1));
+            launch_molecule_live(set, d_place.p, stream);
+            HIP_TRY(hipGetLastError());
+            if (exclusive_scan_total_i64(d_place.p, d_place.p, (int64_t)s->umi_n_slots, stream) != 0)
+                return fail(SKM_ERR_HIP, "numbering the molecules of %llu slots: %s", (unsigned long long)s->umi_n_slots, quant_setup_failure());
+            HIP_TRY(hipMemcpyAsync(&n, d_place.p + s->umi_n_slots, 8, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (n < 0 || n > s->umi_entries)
+                return fail(SKM_ERR_STATE, "%lld live molecules in a set of %lld", (long long)n, (long long)s->umi_entries);
+            if (n) {
+                SKM_TRY(keys.ensure(n));
+                launch_molecule_keys(set, mp->t, d_labels.p, d_place.p, n, n_samples, keys.label.p, keys.umi.p, keys.number.p,
+                                     d_error.p + 1, stream);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(error, d_error.p, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (error[0]) return fail(SKM_ERR_ARG, "a class names a transcript not below n_tx = %lld", (long long)n_tx);
+        if (error[1]) return fail(SKM_ERR_STATE, "a surviving molecule's class is not in the class table");
+    }
+    SKM_TRY(molecule_matrix_sorted(m.get(), keys, n, 2 * s->umi_bases, stream));
+    drain.dismiss();
+    *out = m.release();
+    return SKM_OK;
+}
+
 }  // namespace
 
 extern "C" int skm_sample_set_gene_matrix(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
@@ -332,6 +452,61 @@ extern "C" int skm_gene_matrix_from_classes(int device, int64_t n_classes, const
     SKM_TRY(up.upload(n_classes, class_offsets, class_targets, class_counts, class_sample));
     SKM_TRY(gene_matrix_device(up.t, device, n_samples, n_tx, n_genes, tx_gene, nullptr, out));
     drain.dismiss();
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_molecule_matrix(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                              skm_gene_matrix **out)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!s || !out) return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    if (!s->umi_bases) return fail(SKM_ERR_STATE, "the set keeps no UMIs: a molecule matrix needs skm_sample_set_keep_umis");
+    skm_sample_set::View &v = s->view;
+    const int64_t n_samples = (int64_t)v.units.size();
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    GeneClasses t{};
+    t.n_classes = (int64_t)v.start.size();
+    if (t.n_classes) { t.start = v.d_start.p; t.len = v.d_len.p; t.count_f64 = v.d_count.p; t.sample = v.d_sample.p; t.ids = m->arena.p; }
+    return molecule_matrix_set(s, t, n_samples, n_tx, n_genes, tx_gene, out);
+}
+
+extern "C" int skm_gene_matrix_from_molecules(int device, int64_t n, const int32_t *sample, const int32_t *gene, const uint32_t *umi,
+                                              int64_t n_samples, int64_t n_genes, skm_gene_matrix **out)
+{
+    SKM_TRY(check_device(device));
+    if (n < 0 || n_samples < 0 || n_genes < 0 || n_genes > INT32_MAX || !out || (n && (!sample || !gene || !umi)))
+        return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(molecule_limits(n, n_samples));
+    for (int64_t i = 0; i < n; ++i) {
+        if (sample[i] < 0 || sample[i] >= n_samples)
+            return fail(SKM_ERR_ARG, "molecule %lld belongs to sample %d of %lld", (long long)i, sample[i], (long long)n_samples);
+        if (gene[i] < 0 || gene[i] >= n_genes)
+            return fail(SKM_ERR_ARG, "molecule %lld lies in gene %d of %lld", (long long)i, gene[i], (long long)n_genes);
+    }
+    SKM_TRY(set_device(device));
+    std::unique_ptr<skm_gene_matrix> m;
+    DBuf<int32_t> d_sample, d_gene; DBuf<uint32_t> d_umi; MoleculeKeys keys;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(molecule_matrix_new(device, n_samples, n_genes, nullptr, m));
+    if (n) {
+        SKM_TRY(d_sample.ensure(n)); SKM_TRY(d_gene.ensure(n)); SKM_TRY(d_umi.ensure(n)); SKM_TRY(keys.ensure(n));
+        HIP_TRY(hipMemcpy(d_sample.p, sample, n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_gene.p, gene, n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_umi.p, umi, n * 4, hipMemcpyHostToDevice));
+        launch_molecule_triples(d_sample.p, d_gene.p, d_umi.p, n, keys.label.p, keys.umi.p, keys.number.p, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    SKM_TRY(molecule_matrix_sorted(m.get(), keys, n, 32, nullptr));
+    drain.dismiss();
+    *out = m.release();
     return SKM_OK;
 }
 

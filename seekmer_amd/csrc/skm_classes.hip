@@ -49,6 +49,8 @@ class_init_kernel(ClassSlot *slots, uint64_t n_slots)
 // changes once set, and a stale "empty" only costs the CAS that then reports the
 // real key -- device-scope atomics are served at the memory side of the fabric
 // (the XCDs' L2s are not coherent), so every one avoided is a fabric request less.
+// (Its read-only sibling for a table that is final, class_probe_find, lies in skm_kernels.h,
+// where skm_molecules.hip can reach it: the units are compiled without relocatable device code.)
 __device__ __forceinline__ uint64_t probe_claim(const ClassTable &t, unsigned long long key,
                                                 bool &claimed, uint64_t limit,
                                                 unsigned long long *seen = nullptr)

@@ -232,6 +232,20 @@ struct ClassTable {
     int *error;                   // SKM_ERR_* raised by a kernel
 };
 constexpr int CLASS_PROBE_LIMIT = 128;
+// The read-only probe beside probe_claim (skm_classes.hip), for a table that is final (no launch of the class kernels
+// is under way): linear from key & slot_mask, ends at the key or at an empty slot, n_slots steps at most, plain
+// loads only.  The slot of `key`, or ~0 when the table does not hold it.  `home_key` is the key word of the home
+// slot, which the caller has fetched ahead (several probes in flight per lane).
+__device__ __forceinline__ uint64_t class_probe_find(const ClassTable &t, unsigned long long key, unsigned long long home_key)
+{
+    uint64_t slot = key & t.slot_mask;
+    unsigned long long cur = home_key;
+    for (uint64_t n = 1; cur != key && cur != 0 && n <= t.slot_mask; ++n) {
+        slot = (slot + 1) & t.slot_mask;
+        cur = t.slots[slot].key;
+    }
+    return cur == key ? slot : ~0ULL;
+}
 // (the class kernels walk the batch record by record; unit_slot is indexed by record.)  insert:
 // find-or-create + count + commit of the new classes + on-the-spot compare with classes of earlier
 // launches, then the totals step (publishes the arena cursor; merge_fld: the batch histogram once)
@@ -681,7 +695,8 @@ struct alignas(32) UmiSlot {      // 32 B: one molecule (sample, class, UMI) of 
     unsigned long long tag;       // umi_tag(class_key, umi); 0 = empty
     unsigned long long class_key; // sample_key(the tuple's key, sample)
     uint32_t umi;
-    uint32_t unused;
+    uint32_t dropped;             // 1: the molecule's first unit was removed for a neighbour (mismatches = 1), so none of its
+                                  // units stays; stored by that unit's lane alone, read by the molecule matrix alone
     unsigned long long min_unit;  // the smallest sample-local unit number seen of the molecule (~0: none yet)
 };
 // the tag of a molecule: a mix of its salted class key and its UMI.  Only where the probe starts and what it compares
@@ -719,6 +734,40 @@ void launch_umi_resolve(const UmiSet &t, const MapBatch &b, const SampleSalt &sa
                         unsigned long long *removed, int umi_bases, int mismatches, hipStream_t stream);
 // `to` (any slots' contents) becomes a set that holds the molecules of `from`
 void launch_umi_rehash(const UmiSet &from, const UmiSet &to, hipStream_t stream);
+
+// ---- molecule matrix (skm_molecules.hip; DESIGN.md section 4, "Molecule matrix"): distinct UMIs per (sample, gene)
+// labels[slot] = n_samples << 32 for every slot of the class table (n_slots of them)
+void launch_molecule_label_init(unsigned long long *labels, uint64_t n_slots, int64_t n_samples, hipStream_t stream);
+// labels[class_list[c]] = sample << 32 | gene for class c of the view `t` (registry order: class c lies in table slot
+// class_list[c]) when it lies inside one named gene with a count > 0; other[n_samples][2] (zeroed by the caller) and
+// error[0] as launch_gene_matrix_keys leaves *error; a class_list entry not below n_slots sets error[1] = SKM_ERR_STATE
+void launch_molecule_labels(const GeneClasses &t, const int64_t *class_list, uint64_t n_slots, const int32_t *tx_gene,
+                            int64_t n_tx, int64_t n_samples, unsigned long long *labels, unsigned long long *other,
+                            int *error, hipStream_t stream);
+// live[i] = 1 where slot i of the molecule set holds a molecule that has a surviving unit (occupied, not dropped)
+void launch_molecule_live(const UmiSet &set, int64_t *live, hipStream_t stream);
+// place[] the exclusive scan of live[], n its total: the live molecule of slot i becomes molecule place[i] < n -- mol_label[] the label
+// of its class's slot in `classes`, mol_umi[] its UMI, mol_number[] = place[i].  A class key that the table does not
+// hold sets *error = SKM_ERR_STATE (and the molecule gets the label n_samples << 32).
+void launch_molecule_keys(const UmiSet &set, const ClassTable &classes, const unsigned long long *labels,
+                          const int64_t *place, int64_t n, int64_t n_samples, unsigned long long *mol_label,
+                          unsigned long long *mol_umi, int32_t *mol_number, int *error, hipStream_t stream);
+// the same three arrays from triples on the device (sample and gene checked by the caller)
+void launch_molecule_triples(const int32_t *sample, const int32_t *gene, const uint32_t *umi, int64_t n,
+                             unsigned long long *mol_label, unsigned long long *mol_umi, int32_t *mol_number,
+                             hipStream_t stream);
+// between the two sorts: label_out[i] = mol_label[order[i]], number_out[i] = i (order: the molecules by UMI)
+void launch_molecule_gather(const unsigned long long *mol_label, const int32_t *order, int64_t n,
+                            unsigned long long *label_out, int32_t *number_out, hipStream_t stream);
+// labels[] sorted, umi_of[at[i]] the UMI of sorted place i (ascending inside a label: the sorts are stable):
+// heads[i] = 1 where label i is an entry's label and differs from label i - 1; first[i] = 1 where it is an entry's
+// label and (label, UMI) differs from place i - 1's
+void launch_molecule_heads(const unsigned long long *labels, const int32_t *at, const unsigned long long *umi_of,
+                           int64_t n, int64_t n_samples, int64_t *heads, uint32_t *first, hipStream_t stream);
+// launch_gene_matrix_fill with first[] as what a lane adds
+void launch_molecule_fill(const unsigned long long *labels, const uint32_t *first, const int64_t *runs, int64_t n,
+                          int64_t n_samples, int64_t *indptr, int32_t *indices, unsigned long long *data,
+                          hipStream_t stream);
 
 // ---- cell discovery (skm_census.hip; DESIGN.md section 4, "Cell discovery")
 constexpr unsigned long long CENSUS_EMPTY = ~0ULL;    // the key of an empty slot; its one preimage (32 T) is counted in ctl[]

@@ -9,7 +9,8 @@
 //
 // (b) the molecule set of a sample set: an open-addressing table in HBM, linear probing, at most half full, that
 // lives as long as the set.  A slot is one 32-byte sector: tag (a 64-bit mix of the salted class key and the UMI,
-// 0 = empty), class key, UMI, and the smallest sample-local unit number seen of the molecule.  Between the strand
+// 0 = empty), class key, UMI, the smallest sample-local unit number seen of the molecule, and one word that says the
+// molecule's first unit was removed for a neighbour (`dropped`, below; read by skm_molecules.hip alone).  Between the strand
 // filter and everything that counts (hexamers, classes, fragment lengths) every launch runs
 //   claim   -- every record with a tuple finds or claims its molecule's slot (atomicCAS on the tag; the claimant
 //              stores key and UMI with plain stores) and lowers min_unit to its own unit (atomicMin);
@@ -19,7 +20,8 @@
 //              key 0, tuple length 0, a span that gives no fragment length -- from here on an unaligned unit,
 //              which the set subtracts again (removed[sample]).  With one mismatch allowed (umi_resolve_kernel<true>)
 //              the first unit of a molecule also looks up its 3 L one-substitution neighbours and removes itself
-//              when one of them has a smaller min_unit; it reads the set only, with plain loads, for the same
+//              when one of them has a smaller min_unit -- and then marks its molecule's slot `dropped`: no unit of
+//              the molecule is left; it reads the set only, with plain loads, for the same
 //              reason: claim has finished.  The units removed by a neighbour alone are counted in ctl[UMI_CTL_NEAR].
 // Units of earlier launches have smaller local numbers (a sample's segments are added in order), so an entry of an
 // earlier launch always wins; inside a launch the minimum does not depend on the order of arrival.  No lane waits
@@ -74,7 +76,7 @@ umi_init_kernel(UmiSlot *slots, uint64_t n_slots)
         slots[i].tag = 0;
         slots[i].class_key = 0;
         slots[i].umi = 0;
-        slots[i].unused = 0;
+        slots[i].dropped = 0;
         slots[i].min_unit = ~0ULL;
     }
 }
@@ -318,6 +320,9 @@ umi_resolve_kernel(UmiSet t, MapBatch b, const int32_t *__restrict__ seg_first, 
             if (!NEAR) continue;
             if (!umi_near_earlier(t, rec, L, n_slots)) continue;      // ... unless an earlier unit was one substitution away
             ++near;
+            // none of the molecule's units stays now (the others left for this one).  This lane alone stores the word,
+            // nobody reads it in this launch, and later launches bring larger units only: final.
+            if constexpr (NEAR) t.slots[slot].dropped = 1;
         }
         b.rec_key[r] = 0;
         b.rec_tuple[r] &= (1ULL << 40) - 1;       // tuple length 0: unaligned to everything that follows
@@ -352,6 +357,7 @@ umi_rehash_kernel(UmiSet from, UmiSet to)
         if (!placed) { lost = true; continue; }
         to.slots[slot].class_key = entry.class_key;
         to.slots[slot].umi = entry.umi;
+        to.slots[slot].dropped = entry.dropped;
         to.slots[slot].min_unit = entry.min_unit;
     }
     if (lost) atomicExch(to.error, SKM_ERR_STATE);

@@ -310,14 +310,7 @@ def output_count_matrix(output_path, gene_ids, names, units, indptr, indices, da
     counts_path = output_path / 'counts'
     counts_path.mkdir(exist_ok=True)
     sample_of = numpy.repeat(numpy.arange(n_samples, dtype=numpy.int64), numpy.diff(indptr))
-    with (counts_path / 'matrix.mtx').open('w') as f:
-        f.write('%%MatrixMarket matrix coordinate integer general\n')
-        f.write(COUNT_MATRIX_COMMENT + '\n')
-        f.write('%d %d %d\n' % (n_genes, n_samples, data.size))
-        for begin in range(0, data.size, 1 << 16):
-            chunk = slice(begin, begin + (1 << 16))
-            f.writelines('%d %d %d\n' % entry for entry in zip((indices[chunk].astype(numpy.int64) + 1).tolist(),
-                                                               (sample_of[chunk] + 1).tolist(), data[chunk].tolist()))
+    _write_mtx(counts_path / 'matrix.mtx', COUNT_MATRIX_COMMENT, n_genes, n_samples, sample_of, indices, data)
     with (counts_path / 'genes.tsv').open('w') as f:
         f.writelines(gene.decode() + '\n' for gene in numpy.asarray(gene_ids).tolist())
     inside = numpy.zeros(n_samples, dtype=numpy.int64)
@@ -327,15 +320,53 @@ def output_count_matrix(output_path, gene_ids, names, units, indptr, indices, da
             aligned = int(inside[i] + other[i, 0] + other[i, 1])
             f.write('%s\t%d\t%d\t%d\t%d\t%d\t%d\n' % (name, units[i], aligned, inside[i], other[i, 0], other[i, 1],
                                                       indptr[i + 1] - indptr[i]))
-    # (numpy.savez stamps every member with the time of day; this container holds the same members without one, so
-    # that two runs with the same counts write the same bytes)
+    _write_csr_npz(counts_path / 'matrix.npz', n_samples, n_genes, indptr, indices, data)
+
+
+def _write_mtx(path, comment, n_genes, n_samples, sample_of, indices, data):
+    """A MatrixMarket coordinate file of a CSR over samples: genes as rows, samples as columns, 1-based, in CSR order."""
+    with path.open('w') as f:
+        f.write('%%MatrixMarket matrix coordinate integer general\n')
+        f.write(comment + '\n')
+        f.write('%d %d %d\n' % (n_genes, n_samples, data.size))
+        for begin in range(0, data.size, 1 << 16):
+            chunk = slice(begin, begin + (1 << 16))
+            f.writelines('%d %d %d\n' % entry for entry in zip((indices[chunk].astype(numpy.int64) + 1).tolist(),
+                                                               (sample_of[chunk] + 1).tolist(), data[chunk].tolist()))
+
+
+def _write_csr_npz(path, n_samples, n_genes, indptr, indices, data):
+    """The keys scipy.sparse.load_npz reads.  numpy.savez stamps every member with the time of day; this container
+    holds the same members without one, so that two runs with the same counts write the same bytes."""
     arrays = {'indptr': indptr, 'indices': indices, 'data': data,
               'shape': numpy.asarray([n_samples, n_genes], dtype=numpy.int64), 'format': numpy.asarray(b'csr')}
-    with zipfile.ZipFile(str(counts_path / 'matrix.npz'), 'w', zipfile.ZIP_STORED, allowZip64=True) as container:
+    with zipfile.ZipFile(str(path), 'w', zipfile.ZIP_STORED, allowZip64=True) as container:
         for key, array in arrays.items():
             member = io.BytesIO()
             numpy.lib.format.write_array(member, numpy.ascontiguousarray(array), allow_pickle=False)
             container.writestr(zipfile.ZipInfo(key + '.npy', date_time=(1980, 1, 1, 0, 0, 0)), member.getvalue())
+
+
+MOLECULE_MATRIX_COMMENT = ('% infer-many --count-molecules: rows are genes (genes.tsv), columns are cells/samples (cells.tsv); '
+                           'a value is the distinct UMIs among the units of the cell that lie inside that one gene')
+COUNT_MOLECULES_NEEDS_UMIS = ('--count-molecules counts distinct UMIs: it needs --umi-length L, and with it a pooled run '
+                              '(--barcodes or --discover-cells)')
+
+
+def output_molecule_matrix(output_path, n_genes, n_samples, indptr, indices, data):
+    """What `infer-many --count-molecules` adds to output/counts/: molecules.mtx (the layout of matrix.mtx, rows and
+    columns those of genes.tsv and cells.tsv) and molecules.npz (the keys of matrix.npz).  (indptr, indices, data) is
+    the CSR over samples of the molecule counts, with the pattern of the count matrix."""
+    indptr = numpy.asarray(indptr, dtype=numpy.int64)
+    indices = numpy.asarray(indices, dtype=numpy.int32)
+    data = numpy.asarray(data, dtype=numpy.int64)
+    if indptr.shape != (n_samples + 1,) or indices.shape != data.shape or indptr[-1] != data.size:
+        raise ValueError('a molecule matrix of %d samples needs indptr[%d] and as many indices as data' % (n_samples, n_samples + 1))
+    counts_path = output_path / 'counts'
+    counts_path.mkdir(exist_ok=True)
+    sample_of = numpy.repeat(numpy.arange(n_samples, dtype=numpy.int64), numpy.diff(indptr))
+    _write_mtx(counts_path / 'molecules.mtx', MOLECULE_MATRIX_COMMENT, n_genes, n_samples, sample_of, indices, data)
+    _write_csr_npz(counts_path / 'molecules.npz', n_samples, n_genes, indptr, indices, data)
 
 
 MATRIX_ONLY_NEEDS_EM = ('--matrix-only stops before the EM: %s needs the EM (take --count-matrix, which writes the '
@@ -526,7 +557,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
              barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
              discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0,
-             count_matrix=False, matrix_only=False, **__):
+             count_matrix=False, matrix_only=False, count_molecules=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -600,7 +631,15 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     matrix_only: --matrix-only, which implies count_matrix.  The run stops after mapping (and demultiplexing and UMI
     collapse): no summarize(), no EM, no folder per sample; it writes counts/, samples.tsv and the barcodes.* files,
     each byte for byte that of the full run.  bootstrap, bias and genes need the EM and are refused here, before the
-    index is loaded (MATRIX_ONLY_NEEDS_EM)."""
+    index is loaded (MATRIX_ONLY_NEEDS_EM).
+
+    count_molecules: --count-molecules, which implies count_matrix and needs umi_length, hence a pooled run
+    (COUNT_MOLECULES_NEEDS_UMIS before the index is loaded).  counts/ gains molecules.mtx and molecules.npz: entry
+    (gene, cell) is the number of DISTINCT UMIs among the cell's surviving units whose class lies inside the gene,
+    UMIs compared letter for letter (SampleSet.gene_molecule_matrix: one pass over the molecule set and the class
+    table where they lie; DESIGN.md section 4, "Molecule matrix") -- matrix.mtx counts such a molecule once per class
+    its reads fell into.  Same rows, columns and pattern as matrix.mtx; every other file of the run is what it is
+    without the option.  Goes with matrix_only, umi_mismatches and strand."""
     # what the phases below share: every option under its own name (locals(): this stays the first statement, so that a
     # new option needs no second list), and with them the index, the genes and the trace's clock
     job = types.SimpleNamespace(**locals(), paired=not single_ended, pooled=barcodes is not None or discover_cells is not None,
@@ -645,11 +684,12 @@ class _Sample:
     mapper of its own; summary (SummarizedResult) or, with matrix_only, sizes (the sizes() row of its table); mean, the
     observed harmonic mean fragment length; observed, its hexamer counts (bias); gene_counts, (unique, other) of
     gene_unique_counts (genes); matrix_row, (gene indices, counts) of the count matrix, and the matrix_other pair that
-    goes with it; set_estimate, the first-pass TPM where the set or the shared bias pass made one; corrected, (summary,
-    TPM) of the set's shared bias pass; estimate, the TPM it was written with.  What was not made is None.  Host values
-    only: a record never holds the SampleSet or a MapResult, whose device memory ends where run_many says."""
+    goes with it; molecule_row, the molecule matrix's counts for the genes of matrix_row (count_molecules);
+    set_estimate, the first-pass TPM where the set or the shared bias pass made one; corrected, (summary, TPM) of the
+    set's shared bias pass; estimate, the TPM it was written with.  What was not made is None.  Host values only: a
+    record never holds the SampleSet or a MapResult, whose device memory ends where run_many says."""
     __slots__ = ('name', 'group', 'in_set', 'summary', 'sizes', 'mean', 'observed', 'gene_counts', 'matrix_row',
-                 'matrix_other', 'set_estimate', 'corrected', 'estimate')
+                 'matrix_other', 'molecule_row', 'set_estimate', 'corrected', 'estimate')
 
     def __init__(self, name, group, in_set):
         self.name, self.group, self.in_set = name, group, in_set
@@ -673,7 +713,9 @@ def _check_many_options(job, names):
     mapper.strand_mode(job.strand)
     job.length_model, _ = mapper.length_model_weights(job.length_model)
     job.umi_mismatches = mapper.check_umi_mismatches(job.umi_mismatches, job.umi_length)
-    job.count_matrix = bool(job.count_matrix) or bool(job.matrix_only)
+    job.count_matrix = bool(job.count_matrix) or bool(job.matrix_only) or bool(job.count_molecules)
+    if job.count_molecules and not (job.umi_length and job.pooled):
+        raise ValueError(COUNT_MOLECULES_NEEDS_UMIS)
     if job.matrix_only:
         for given, flag in ((job.bootstrap and job.bootstrap > 0, '-b N'), (job.bias, '--bias'), (job.genes, '--genes')):
             if given:
@@ -791,6 +833,12 @@ def _take_from_set(job, sample_set, members):
         for k, sample in enumerate(members):
             sample.matrix_row = (indices[indptr[k]:indptr[k + 1]], data[indptr[k]:indptr[k + 1]])
             sample.matrix_other = other[k]
+    if job.count_molecules:                 # (a pass over the molecule set and the table where they lie)
+        m_indptr, m_indices, m_data, m_other = sample_set.gene_molecule_matrix(job.gene_names[1], n_genes)
+        if not (numpy.array_equal(m_indptr, indptr) and numpy.array_equal(m_indices, indices) and numpy.array_equal(m_other, other)):
+            raise RuntimeError('the molecule matrix does not have the entries of the count matrix')
+        for k, sample in enumerate(members):
+            sample.molecule_row = m_data[indptr[k]:indptr[k + 1]]
     if job.matrix_only:
         for sample, row, mean in zip(members, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
             sample.sizes, sample.mean = row, mean
@@ -853,6 +901,13 @@ def _finish(job, samples):
         output_count_matrix(job.output_path, job.gene_names[0], [sample.name for sample in samples],
                             [total for total, _ in units], *stack_count_rows(sample.matrix_row for sample in samples),
                             [sample.matrix_other for sample in samples])
+    if job.count_molecules:
+        indptr, indices, _ = stack_count_rows(sample.matrix_row for sample in samples)
+        molecules = numpy.concatenate([numpy.asarray(sample.molecule_row, dtype=numpy.int64) for sample in samples])
+        output_molecule_matrix(job.output_path, job.gene_names[0].size, len(samples), indptr, indices, molecules)
+        inside = int(sum(int(sample.matrix_row[1].sum()) for sample in samples))
+        _LOG.info('Units inside one gene: %d; molecules (distinct UMIs per cell and gene): %d; %.3f units a molecule',
+                  inside, int(molecules.sum()), inside / max(int(molecules.sum()), 1))
     with (job.output_path / 'samples.tsv').open('w') as f:
         for sample, (total, aligned) in zip(samples, units):
             f.write('%s\t%d\t%d\t%.2f\n' % (sample.name, total, aligned, sample.mean))
@@ -1811,14 +1866,16 @@ def add_gene_arguments(parser):
 
 def gene_option(opts):
     """The parsed options: --gene-map implies --genes -- unless --count-matrix or --matrix-only is given, which the map
-    then serves: they need genes but do not switch the gene-level tables on.  --matrix-only implies --count-matrix."""
-    opts['count_matrix'] = bool(opts.get('count_matrix')) or bool(opts.get('matrix_only'))
+    then serves: they need genes but do not switch the gene-level tables on.  --matrix-only and --count-molecules imply
+    --count-matrix."""
+    opts['count_matrix'] = bool(opts.get('count_matrix')) or bool(opts.get('matrix_only')) or bool(opts.get('count_molecules'))
     opts['genes'] = bool(opts.get('genes')) or (opts.get('gene_map') is not None and not opts['count_matrix'])
     return opts
 
 
 def add_count_matrix_arguments(parser):
-    """--count-matrix and --matrix-only: dest 'count_matrix', 'matrix_only' (gene_option makes the second imply the first)."""
+    """--count-matrix, --matrix-only and --count-molecules: dest 'count_matrix', 'matrix_only', 'count_molecules'
+    (gene_option makes the second and the third imply the first)."""
     parser.add_argument('--count-matrix', action='store_true', dest='count_matrix',
                         help='also write output/counts/: the sparse gene x cell matrix of the units that lie inside one '
                              'gene (matrix.mtx, genes.tsv, cells.tsv, matrix.npz), made on the GPU; the genes are the '
@@ -1827,6 +1884,10 @@ def add_count_matrix_arguments(parser):
                         help='write the count matrix, samples.tsv and the barcodes.* files only: stop after mapping (and '
                              'UMI collapse), run no EM, write no folder per sample; implies --count-matrix, refuses -b, '
                              '--bias and --genes')
+    parser.add_argument('--count-molecules', action='store_true', dest='count_molecules',
+                        help='also write counts/molecules.mtx and counts/molecules.npz: per gene and cell the number of '
+                             'DISTINCT UMIs among the units inside that gene, where matrix.mtx counts a molecule once per '
+                             'equivalence class its reads fell into; implies --count-matrix, needs --umi-length')
 
 
 def add_bias_argument(parser):

@@ -100,6 +100,24 @@ def read_gene_matrix(handle):
         _native.hip().skm_gene_matrix_destroy(handle)
 
 
+def molecule_matrix(sample, gene, umi, n_samples, n_genes, device=0):
+    """(indptr, indices, data, other) of the molecule matrix of the triples (sample[i], gene[i], umi[i]): data counts the
+    distinct UMIs of every (sample, gene), other is all zero (skm_gene_matrix_from_molecules: the sort, head and fill
+    steps of DESIGN.md section 4, "Molecule matrix", on the device).  A sample outside [0, n_samples) or a gene
+    outside [0, n_genes) raises."""
+    sample = numpy.ascontiguousarray(sample, dtype=numpy.int32)
+    gene = numpy.ascontiguousarray(gene, dtype=numpy.int32)
+    umi = numpy.ascontiguousarray(umi, dtype=numpy.uint32)
+    if sample.ndim != 1 or gene.shape != sample.shape or umi.shape != sample.shape:
+        raise ValueError('sample, gene and umi are three arrays of one length')
+    handle = ctypes.c_void_p()
+    n = int(sample.size)
+    _native.check(_native.hip().skm_gene_matrix_from_molecules(
+        int(device), n, _native.ptr(sample, _native.c_i32p) if n else None, _native.ptr(gene, _native.c_i32p) if n else None,
+        _native.ptr(umi, _native.c_u32p) if n else None, int(n_samples), int(n_genes), ctypes.byref(handle)))
+    return read_gene_matrix(handle)
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
@@ -859,6 +877,17 @@ class SampleSet:
         tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
         handle = ctypes.c_void_p()
         _native.check(_native.hip().skm_sample_set_gene_matrix(
+            self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
+        return read_gene_matrix(handle)
+
+    def gene_molecule_matrix(self, tx_gene, n_genes):
+        """The arrays of gene_count_matrix with molecules for units: data[k] is the number of distinct UMIs among the
+        sample's surviving units whose class lies inside the gene (skm_sample_set_molecule_matrix; DESIGN.md section
+        4, "Molecule matrix").  indptr, indices and other are gene_count_matrix's.  A set that keeps no UMIs
+        (umi_bases=0) raises."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_sample_set_molecule_matrix(
             self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
         return read_gene_matrix(handle)
 
