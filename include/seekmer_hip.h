@@ -622,6 +622,33 @@ int skm_sample_set_molecule_matrix(skm_sample_set *set, int64_t n_tx, int64_t n_
                                    skm_gene_matrix **out);
 int skm_gene_matrix_from_molecules(int device, int64_t n, const int32_t *sample, const int32_t *gene, const uint32_t *umi,
                                    int64_t n_samples, int64_t n_genes, skm_gene_matrix **out);
+/* Resolved molecules ("Resolved molecules"): one gene per (sample, UMI).  The distinct classes
+ * among a sample's live molecules -- the population of skm_sample_set_molecule_matrix -- with one UMI form a group;
+ * G_k = { tx_gene[t] : t in class k }, -1 an element like any other, and I = the intersection of G_k over the group:
+ *   I = {g}, g >= 0   resolved: entry (sample, g) += 1; also rescued when no class of the group lies inside one gene
+ *   I = {-1}          unnamed           |
+ *   I of two or more  multi-gene        | tallied only
+ *   I empty           collision         |
+ * UMIs are compared letter for letter; the same UMI in two samples forms two groups.  Parity with other tools' UMI
+ * rules is not claimed.  The handle is an ordinary skm_gene_matrix (its pattern is NOT the count matrix's: a rescued
+ * group can make an entry that matrix lacks, a collision can take one away); other[s] = { multi-gene + collision,
+ * unnamed } in molecules.  skm_gene_matrix_read_tally gives tally[s] = { resolved, rescued, multi-gene, unnamed,
+ * collision } (rescued is a part of resolved; the other four add up to the sample's distinct UMIs), and
+ * SKM_ERR_STATE on a handle that any other call made.
+ * skm_sample_set_resolved_matrix waits and locks as skm_sample_set_molecule_matrix does and has its refusals and
+ * limits (checked before anything is allocated).  Device memory while it runs: 8 bytes per slot of the class table, 8
+ * per slot of the molecule set, 40 per live molecule, 48 per group.
+ * skm_gene_matrix_from_molecule_classes runs the sort, group, resolve and fill steps on host arrays: classes as the
+ * CSR of skm_mapper_export with a sample each (class_sample NULL: sample 0, n_samples 1), molecules as (class, UMI);
+ * two molecules with the same class and UMI count as one.  SKM_ERR_ARG for a mol_class outside [0, n_classes), a
+ * class sample outside [0, n_samples), an id not below n_tx and an empty class.  On any failure *out is NULL. */
+int skm_sample_set_resolved_matrix(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                   skm_gene_matrix **out);
+int skm_gene_matrix_from_molecule_classes(int device, int64_t n_classes, const int64_t *class_offsets,
+                                          const int32_t *class_targets, const int32_t *class_sample, int64_t n_molecules,
+                                          const int32_t *mol_class, const uint32_t *mol_umi, int64_t n_samples, int64_t n_tx,
+                                          int64_t n_genes, const int32_t *tx_gene, skm_gene_matrix **out);
+int skm_gene_matrix_read_tally(const skm_gene_matrix *matrix, int64_t *tally /*[n_samples][5]*/);
 
 /* ---------------------------------------------------------------- cell barcodes
  * ("Cell barcodes".)  A pooled run -- one barcode read per unit beside the cDNA reads --

@@ -1,6 +1,7 @@
 // C ABI of libseekmer_hip.so: gene-level tables -- sums of transcript values by gene, and the unique counts of a
 // class table given on the host, held by a mapper or held by a sample set -- as dense rows, or as the sparse count
-// matrix (skm_gene_matrix: a CSR over samples that stays in HBM until it is read), of units or of molecules.
+// matrix (skm_gene_matrix: a CSR over samples that stays in HBM until it is read), of units, of molecules or of
+// molecules resolved to one gene per UMI.
 #include "skm_abi_samples.h"
 
 #include <algorithm>
@@ -229,6 +230,8 @@ struct skm_gene_matrix {
     DBuf<int64_t> indptr;                            // [n_samples + 1]
     DBuf<int32_t> indices;                           // [nnz]
     DBuf<unsigned long long> data, other;            // [nnz], [n_samples][2]
+    DBuf<unsigned long long> tally;                  // [n_samples][MOLECULE_TALLY]: a resolved matrix alone
+    bool has_tally = false;
 };
 
 namespace {
@@ -413,6 +416,107 @@ int molecule_matrix_set(skm_sample_set *s, const GeneClasses &t, int64_t n_sampl
     return SKM_OK;
 }
 
+// ---- resolved molecules (skm_molecule_resolve.hip)
+struct ResolveKeys {              // n molecules in HBM: key (sample << 32 | UMI), class index, number 0 .. n - 1
+    DBuf<unsigned long long> key; DBuf<uint32_t> cls; DBuf<int32_t> number;
+    int ensure(int64_t n) { SKM_TRY(key.ensure(n)); SKM_TRY(cls.ensure(n)); SKM_TRY(number.ensure(n)); return SKM_OK; }
+};
+
+// Steps 3 to 5 (stream drained on return): the one sort, heads and their scan, resolve, then the molecule matrix's own
+// steps over the groups.  m is what molecule_matrix_new left; d_error[2] is zeroed or holds what the caller's kernels
+// raised (they run ahead on the stream).  n_groups and the errors come home in one synchronisation.
+int resolved_matrix_sorted(skm_gene_matrix *m, const GeneClasses &t, ResolveKeys &keys, int64_t n, int umi_bits,
+                           const int32_t *d_gene, int64_t n_tx, int *d_error, hipStream_t stream)
+{
+    const int64_t n_samples = m->n_samples;
+    DBuf<unsigned long long> d_sorted; DBuf<int32_t> d_order; DBuf<uint32_t> d_class; DBuf<int64_t> d_runs; MoleculeKeys groups;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    SKM_TRY(m->tally.ensure((size_t)std::max<int64_t>(MOLECULE_TALLY * n_samples, 1)));
+    HIP_TRY(hipMemsetAsync(m->tally.p, 0, (size_t)std::max<int64_t>(MOLECULE_TALLY * n_samples, 1) * 8, stream));
+    m->has_tally = true;
+    int64_t n_groups = 0;
+    int error[2] = {0, 0};
+    if (n && n_samples) {
+        SKM_TRY(d_sorted.ensure(n)); SKM_TRY(d_order.ensure(n)); SKM_TRY(d_class.ensure(n)); SKM_TRY(d_runs.ensure((size_t)n + 1));
+        int end_bit = 33;
+        while ((1LL << (end_bit - 32)) <= n_samples) ++end_bit;   // (a key raised with an error holds n_samples itself)
+        if (sort_pairs_u64(keys.key.p, d_sorted.p, keys.number.p, d_order.p, n, end_bit, stream) != 0)
+            return fail(SKM_ERR_HIP, "sorting %lld molecules by sample and UMI: %s", (long long)n, quant_setup_failure());
+        launch_resolve_heads(d_sorted.p, d_order.p, keys.cls.p, n, d_runs.p, d_class.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (exclusive_scan_total_i64(d_runs.p, d_runs.p, n, stream) != 0)
+            return fail(SKM_ERR_HIP, "numbering the groups of %lld molecules: %s", (long long)n, quant_setup_failure());
+        HIP_TRY(hipMemcpyAsync(&n_groups, d_runs.p + n, 8, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipMemcpyAsync(error, d_error, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (error[1]) return fail(SKM_ERR_STATE, "a surviving molecule's class is not in the class table");
+    if (n_groups < 0 || n_groups > n) return fail(SKM_ERR_HIP, "%lld groups from %lld molecules", (long long)n_groups, (long long)n);
+    if (n_groups) {
+        SKM_TRY(groups.ensure(n_groups));
+        launch_molecule_resolve(t, d_sorted.p, d_class.p, d_runs.p, n, n_groups, d_gene, n_tx, n_samples, groups.label.p,
+                                groups.umi.p, groups.number.p, m->tally.p, d_error, stream);
+        HIP_TRY(hipGetLastError());
+        launch_resolve_other(m->tally.p, n_samples, m->other.p, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    SKM_TRY(molecule_matrix_sorted(m, groups, n_groups, umi_bits, stream));     // (drains the stream: the resolve kernel has run)
+    HIP_TRY(hipMemcpyAsync(error, d_error, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    drain.dismiss();
+    if (error[0]) return fail(SKM_ERR_ARG, "a class names a transcript not below n_tx = %lld", (long long)n_tx);
+    if (error[1]) return fail(SKM_ERR_STATE, "a group's class is not one of its sample's classes");
+    return SKM_OK;
+}
+
+// Steps 1 and 2 on a set's resident state (s->mu and m->mu are held): the class of every table slot, the live
+// molecules numbered by the scan, their (key, class); then the steps above.
+int resolved_matrix_set(skm_sample_set *s, const GeneClasses &t, int64_t n_samples, int64_t n_tx, int64_t n_genes,
+                        const int32_t *tx_gene, skm_gene_matrix **out)
+{
+    skm_mapper *mp = s->m;
+    hipStream_t stream = mp->stream;
+    SKM_TRY(gene_matrix_limits(t.n_classes, n_samples));
+    SKM_TRY(molecule_limits(s->umi_entries, n_samples));
+    if (t.n_classes && n_samples && n_tx == 0) return fail(SKM_ERR_ARG, "classes over no transcripts");
+    const uint64_t class_slots = mp->t.slots ? mp->t.slot_mask + 1 : 0;
+    if (t.n_classes && (!class_slots || !mp->t.class_list)) return fail(SKM_ERR_STATE, "classes without a table");
+    std::unique_ptr<skm_gene_matrix> m;
+    DBuf<int32_t> d_gene; DBuf<unsigned long long> d_class_of; DBuf<int64_t> d_place; DBuf<int> d_error; ResolveKeys keys;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(stream); });      // (an early return: before they go)
+    SKM_TRY(molecule_matrix_new(mp->ix->device, n_samples, n_genes, stream, m));
+    SKM_TRY(d_error.ensure(2)); SKM_TRY(d_gene.ensure((size_t)std::max<int64_t>(n_tx, 1)));
+    HIP_TRY(hipMemsetAsync(d_error.p, 0, 2 * sizeof(int), stream));
+    int64_t n = 0;
+    if (t.n_classes && n_samples && s->umi_n_slots) {
+        SKM_TRY(d_class_of.ensure((size_t)class_slots));
+        HIP_TRY(hipMemcpyAsync(d_gene.p, tx_gene, n_tx * 4, hipMemcpyHostToDevice, stream));
+        launch_molecule_label_init(d_class_of.p, class_slots, n_samples, stream);
+        launch_resolve_class_slots(t, mp->t.class_list, class_slots, n_samples, d_class_of.p, d_error.p + 1, stream);
+        HIP_TRY(hipGetLastError());
+        const UmiSet set{s->umi_slots.p, s->umi_n_slots - 1, s->umi_ctl.p, mp->error.p};
+        SKM_TRY(d_place.ensure((size_t)s->umi_n_slots + 1));
+        launch_molecule_live(set, d_place.p, stream);
+        HIP_TRY(hipGetLastError());
+        if (exclusive_scan_total_i64(d_place.p, d_place.p, (int64_t)s->umi_n_slots, stream) != 0)
+            return fail(SKM_ERR_HIP, "numbering the molecules of %llu slots: %s", (unsigned long long)s->umi_n_slots, quant_setup_failure());
+        HIP_TRY(hipMemcpyAsync(&n, d_place.p + s->umi_n_slots, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (n < 0 || n > s->umi_entries)
+            return fail(SKM_ERR_STATE, "%lld live molecules in a set of %lld", (long long)n, (long long)s->umi_entries);
+        if (n) {
+            SKM_TRY(keys.ensure(n));
+            launch_resolve_keys(set, mp->t, d_class_of.p, d_place.p, n, n_samples, keys.key.p, keys.cls.p, keys.number.p,
+                                d_error.p + 1, stream);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    SKM_TRY(resolved_matrix_sorted(m.get(), t, keys, n, 2 * s->umi_bases, d_gene.p, n_tx, d_error.p, stream));
+    drain.dismiss();
+    *out = m.release();
+    return SKM_OK;
+}
+
 }  // namespace
 
 extern "C" int skm_sample_set_gene_matrix(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
@@ -507,6 +611,78 @@ extern "C" int skm_gene_matrix_from_molecules(int device, int64_t n, const int32
     SKM_TRY(molecule_matrix_sorted(m.get(), keys, n, 32, nullptr));
     drain.dismiss();
     *out = m.release();
+    return SKM_OK;
+}
+
+extern "C" int skm_sample_set_resolved_matrix(skm_sample_set *s, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                              skm_gene_matrix **out)
+{
+    int n_dev = 0;
+    SKM_TRY(skm_device_count(&n_dev));
+    if (!s || !out) return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    std::unique_lock<std::mutex> hold;
+    SKM_TRY(set_view(s, hold));
+    if (!s->umi_bases) return fail(SKM_ERR_STATE, "the set keeps no UMIs: a resolved matrix needs skm_sample_set_keep_umis");
+    skm_sample_set::View &v = s->view;
+    const int64_t n_samples = (int64_t)v.units.size();
+    skm_mapper *m = s->m;
+    std::lock_guard<std::mutex> lock(m->mu);
+    SKM_TRY(set_device(m->ix->device));
+    GeneClasses t{};
+    t.n_classes = (int64_t)v.start.size();
+    if (t.n_classes) { t.start = v.d_start.p; t.len = v.d_len.p; t.count_f64 = v.d_count.p; t.sample = v.d_sample.p; t.ids = m->arena.p; }
+    return resolved_matrix_set(s, t, n_samples, n_tx, n_genes, tx_gene, out);
+}
+
+extern "C" int skm_gene_matrix_from_molecule_classes(int device, int64_t n_classes, const int64_t *class_offsets,
+                                                     const int32_t *class_targets, const int32_t *class_sample, int64_t n,
+                                                     const int32_t *mol_class, const uint32_t *mol_umi, int64_t n_samples,
+                                                     int64_t n_tx, int64_t n_genes, const int32_t *tx_gene, skm_gene_matrix **out)
+{
+    SKM_TRY(check_device(device));
+    if (n_classes < 0 || n < 0 || n_samples < 0 || !out || (n && (!mol_class || !mol_umi))) return fail(SKM_ERR_ARG, "bad argument");
+    *out = nullptr;
+    SKM_TRY(gene_matrix_limits(n_classes, n_samples));
+    SKM_TRY(molecule_limits(n, n_samples));
+    SKM_TRY(gene_map_check(n_tx, n_genes, tx_gene));
+    const std::vector<int64_t> ones((size_t)n_classes, 1);          // (a class's count plays no part: the molecules are given)
+    SKM_TRY(host_classes_check(n_classes, class_offsets, class_targets, ones.data(), class_sample, n_samples, n_tx));
+    for (int64_t c = 0; c < n_classes; ++c)
+        if (class_offsets[c + 1] == class_offsets[c]) return fail(SKM_ERR_ARG, "class %lld is empty", (long long)c);
+    for (int64_t i = 0; i < n; ++i)
+        if (mol_class[i] < 0 || mol_class[i] >= n_classes)
+            return fail(SKM_ERR_ARG, "molecule %lld has class %d of %lld", (long long)i, mol_class[i], (long long)n_classes);
+    SKM_TRY(set_device(device));
+    HostClasses up;
+    std::unique_ptr<skm_gene_matrix> m;
+    DBuf<int32_t> d_gene, d_mol_class; DBuf<uint32_t> d_mol_umi; DBuf<int> d_error; ResolveKeys keys;
+    auto drain = on_exit([&]() { (void)hipStreamSynchronize(nullptr); });     // (an early return: before they go)
+    SKM_TRY(up.upload(n_classes, class_offsets, class_targets, ones.data(), class_sample));
+    SKM_TRY(molecule_matrix_new(device, n_samples, n_genes, nullptr, m));
+    SKM_TRY(d_error.ensure(2)); SKM_TRY(d_gene.ensure((size_t)std::max<int64_t>(n_tx, 1)));
+    HIP_TRY(hipMemset(d_error.p, 0, 2 * sizeof(int)));
+    if (n_tx) HIP_TRY(hipMemcpy(d_gene.p, tx_gene, n_tx * 4, hipMemcpyHostToDevice));
+    if (n) {
+        SKM_TRY(d_mol_class.ensure(n)); SKM_TRY(d_mol_umi.ensure(n)); SKM_TRY(keys.ensure(n));
+        HIP_TRY(hipMemcpy(d_mol_class.p, mol_class, n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_mol_umi.p, mol_umi, n * 4, hipMemcpyHostToDevice));
+        launch_resolve_pairs(up.t.sample, d_mol_class.p, d_mol_umi.p, n, keys.key.p, keys.cls.p, keys.number.p, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    SKM_TRY(resolved_matrix_sorted(m.get(), up.t, keys, n, 32, d_gene.p, n_tx, d_error.p, nullptr));
+    drain.dismiss();
+    *out = m.release();
+    return SKM_OK;
+}
+
+extern "C" int skm_gene_matrix_read_tally(const skm_gene_matrix *m, int64_t *tally)
+{
+    if (!m || !tally) return fail(SKM_ERR_ARG, "NULL argument");
+    if (!m->has_tally) return fail(SKM_ERR_STATE, "the matrix holds no tally: skm_sample_set_resolved_matrix makes one that does");
+    SKM_TRY(set_device(m->device));
+    if (m->n_samples) HIP_TRY(hipMemcpy(tally, m->tally.p, (size_t)m->n_samples * MOLECULE_TALLY * 8, hipMemcpyDeviceToHost));
     return SKM_OK;
 }
 

@@ -769,6 +769,38 @@ void launch_molecule_fill(const unsigned long long *labels, const uint32_t *firs
                           int64_t n_samples, int64_t *indptr, int32_t *indices, unsigned long long *data,
                           hipStream_t stream);
 
+// ---- resolved molecules (skm_molecule_resolve.hip; DESIGN.md section 4, "Resolved molecules"): one gene per (sample, UMI)
+// by the intersection of the gene sets of the group's classes
+enum { MOLECULE_RESOLVED = 0, MOLECULE_RESCUED = 1, MOLECULE_MULTI = 2, MOLECULE_UNNAMED = 3, MOLECULE_COLLISION = 4,
+       MOLECULE_TALLY = 5 };      // the words of a sample's tally; rescued is a part of resolved
+// words[class_list[c]] = sample << 32 | c for class c of the view `t` (words[] preset by launch_molecule_label_init); a
+// class_list entry not below n_slots or a sample outside [0, n_samples) sets *error = SKM_ERR_STATE
+void launch_resolve_class_slots(const GeneClasses &t, const int64_t *class_list, uint64_t n_slots, int64_t n_samples,
+                                unsigned long long *words, int *error, hipStream_t stream);
+// launch_molecule_keys with those words: mol_key[] = sample << 32 | UMI, mol_class[] the class index in the view,
+// mol_number[] = place[i]; a class key that the table does not hold sets *error = SKM_ERR_STATE
+void launch_resolve_keys(const UmiSet &set, const ClassTable &classes, const unsigned long long *class_of, const int64_t *place,
+                         int64_t n, int64_t n_samples, unsigned long long *mol_key, uint32_t *mol_class, int32_t *mol_number,
+                         int *error, hipStream_t stream);
+// the same three arrays from molecules (in_class[i], in_umi[i]) on the device, a class's sample from class_sample[]
+// (nullptr: 0); in_class within the table (the caller has checked)
+void launch_resolve_pairs(const int32_t *class_sample, const int32_t *in_class, const uint32_t *in_umi, int64_t n,
+                          unsigned long long *mol_key, uint32_t *mol_class, int32_t *mol_number, hipStream_t stream);
+// keys[] sorted with order[] the sort's values: heads[i] = 1 where key i differs from key i - 1 (and for i = 0),
+// class_sorted[i] = mol_class[order[i]]
+void launch_resolve_heads(const unsigned long long *keys, const int32_t *order, const uint32_t *mol_class, int64_t n,
+                          int64_t *heads, uint32_t *class_sorted, hipStream_t stream);
+// runs[n + 1] the exclusive scan of heads[] with its total n_groups: per group g (out_label, out_umi, out_number)[g] =
+// (sample << 32 | gene when resolved else n_samples << 32, UMI, g) and tally[sample][MOLECULE_TALLY] (zeroed by the
+// caller) += 1 by outcome.  error[0] = SKM_ERR_ARG for an id not below n_tx, error[1] = SKM_ERR_STATE for a class index
+// not below t.n_classes, a sample not below n_samples or a class of another sample than its molecule's.
+void launch_molecule_resolve(const GeneClasses &t, const unsigned long long *keys, const uint32_t *classes, const int64_t *runs,
+                             int64_t n, int64_t n_groups, const int32_t *tx_gene, int64_t n_tx, int64_t n_samples,
+                             unsigned long long *out_label, unsigned long long *out_umi, int32_t *out_number,
+                             unsigned long long *tally, int *error, hipStream_t stream);
+// other[s] = { multi-gene + collision, unnamed } of tally[s]
+void launch_resolve_other(const unsigned long long *tally, int64_t n_samples, unsigned long long *other, hipStream_t stream);
+
 // ---- cell discovery (skm_census.hip; DESIGN.md section 4, "Cell discovery")
 constexpr unsigned long long CENSUS_EMPTY = ~0ULL;    // the key of an empty slot; its one preimage (32 T) is counted in ctl[]
 struct alignas(16) CensusSlot {   // 16 B: one distinct barcode

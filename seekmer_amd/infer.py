@@ -369,6 +369,38 @@ def output_molecule_matrix(output_path, n_genes, n_samples, indptr, indices, dat
     _write_csr_npz(counts_path / 'molecules.npz', n_samples, n_genes, indptr, indices, data)
 
 
+RESOLVED_MATRIX_COMMENT = ('% infer-many --resolve-molecules: rows are genes (genes.tsv), columns are cells/samples (cells.tsv); '
+                           'a value is the UMIs of the cell whose classes\' gene sets intersect in that one gene')
+RESOLVED_TALLY = ('resolved', 'rescued', 'multi-gene', 'unnamed', 'collisions')
+
+
+def output_resolved_matrix(output_path, n_genes, names, indptr, indices, data, tally):
+    """What `infer-many --resolve-molecules` adds to output/counts/: molecules.resolved.mtx (the layout of matrix.mtx
+    under a comment line of its own, rows and columns those of genes.tsv and cells.tsv), molecules.resolved.npz (the
+    keys of matrix.npz) and molecules.resolved.tsv -- per sample: name, distinct UMIs, resolved, rescued, multi-gene,
+    unnamed, collisions, genes with a count; columns 3 + 5 + 6 + 7 add up to column 2, rescued is a part of resolved.
+    (indptr, indices, data) is the CSR over samples of the resolved molecules, a pattern of its own;
+    tally[n_samples, 5] in the order of RESOLVED_TALLY."""
+    indptr = numpy.asarray(indptr, dtype=numpy.int64)
+    indices = numpy.asarray(indices, dtype=numpy.int32)
+    data = numpy.asarray(data, dtype=numpy.int64)
+    tally = numpy.asarray(tally, dtype=numpy.int64).reshape(-1, len(RESOLVED_TALLY))
+    n_samples = len(names)
+    if indptr.shape != (n_samples + 1,) or indices.shape != data.shape or indptr[-1] != data.size or len(tally) != n_samples:
+        raise ValueError('a resolved matrix of %d samples needs indptr[%d], as many indices as data, and tally[%d, %d]'
+                         % (n_samples, n_samples + 1, n_samples, len(RESOLVED_TALLY)))
+    counts_path = output_path / 'counts'
+    counts_path.mkdir(exist_ok=True)
+    sample_of = numpy.repeat(numpy.arange(n_samples, dtype=numpy.int64), numpy.diff(indptr))
+    _write_mtx(counts_path / 'molecules.resolved.mtx', RESOLVED_MATRIX_COMMENT, n_genes, n_samples, sample_of, indices, data)
+    _write_csr_npz(counts_path / 'molecules.resolved.npz', n_samples, n_genes, indptr, indices, data)
+    with (counts_path / 'molecules.resolved.tsv').open('w') as f:
+        for i, name in enumerate(names):
+            resolved, rescued, multi, unnamed, collisions = (int(v) for v in tally[i])
+            f.write('%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n' % (name, resolved + multi + unnamed + collisions, resolved, rescued,
+                                                          multi, unnamed, collisions, indptr[i + 1] - indptr[i]))
+
+
 MATRIX_ONLY_NEEDS_EM = ('--matrix-only stops before the EM: %s needs the EM (take --count-matrix, which writes the '
                         'count matrix beside the full run)')
 
@@ -557,7 +589,7 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
              barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
              discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0,
-             count_matrix=False, matrix_only=False, count_molecules=False, **__):
+             count_matrix=False, matrix_only=False, count_molecules=False, resolve_molecules=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -639,7 +671,14 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     UMIs compared letter for letter (SampleSet.gene_molecule_matrix: one pass over the molecule set and the class
     table where they lie; DESIGN.md section 4, "Molecule matrix") -- matrix.mtx counts such a molecule once per class
     its reads fell into.  Same rows, columns and pattern as matrix.mtx; every other file of the run is what it is
-    without the option.  Goes with matrix_only, umi_mismatches and strand."""
+    without the option.  Goes with matrix_only, umi_mismatches and strand.
+
+    resolve_molecules: --resolve-molecules, which implies count_molecules (and so count_matrix, with its refusal
+    without umi_length).  counts/ gains molecules.resolved.mtx, molecules.resolved.npz and molecules.resolved.tsv
+    (output_resolved_matrix): the classes among a cell's live molecules with one UMI form a group, and the
+    intersection of their gene sets names the group's gene -- or makes it multi-gene, unnamed or a collision, which are
+    tallied only (SampleSet.gene_resolved_matrix; DESIGN.md section 4, "Resolved molecules").  The matrix has a
+    pattern of its own; every other file of the run, molecules.mtx among them, is what it is without the option."""
     # what the phases below share: every option under its own name (locals(): this stays the first statement, so that a
     # new option needs no second list), and with them the index, the genes and the trace's clock
     job = types.SimpleNamespace(**locals(), paired=not single_ended, pooled=barcodes is not None or discover_cells is not None,
@@ -685,11 +724,12 @@ class _Sample:
     observed harmonic mean fragment length; observed, its hexamer counts (bias); gene_counts, (unique, other) of
     gene_unique_counts (genes); matrix_row, (gene indices, counts) of the count matrix, and the matrix_other pair that
     goes with it; molecule_row, the molecule matrix's counts for the genes of matrix_row (count_molecules);
+    resolved_row, (gene indices, counts) of the resolved matrix, and the resolved_tally that goes with it (resolve_molecules);
     set_estimate, the first-pass TPM where the set or the shared bias pass made one; corrected, (summary, TPM) of the
     set's shared bias pass; estimate, the TPM it was written with.  What was not made is None.  Host values only: a
     record never holds the SampleSet or a MapResult, whose device memory ends where run_many says."""
     __slots__ = ('name', 'group', 'in_set', 'summary', 'sizes', 'mean', 'observed', 'gene_counts', 'matrix_row',
-                 'matrix_other', 'molecule_row', 'set_estimate', 'corrected', 'estimate')
+                 'matrix_other', 'molecule_row', 'resolved_row', 'resolved_tally', 'set_estimate', 'corrected', 'estimate')
 
     def __init__(self, name, group, in_set):
         self.name, self.group, self.in_set = name, group, in_set
@@ -713,6 +753,7 @@ def _check_many_options(job, names):
     mapper.strand_mode(job.strand)
     job.length_model, _ = mapper.length_model_weights(job.length_model)
     job.umi_mismatches = mapper.check_umi_mismatches(job.umi_mismatches, job.umi_length)
+    job.count_molecules = bool(job.count_molecules) or bool(job.resolve_molecules)
     job.count_matrix = bool(job.count_matrix) or bool(job.matrix_only) or bool(job.count_molecules)
     if job.count_molecules and not (job.umi_length and job.pooled):
         raise ValueError(COUNT_MOLECULES_NEEDS_UMIS)
@@ -839,6 +880,11 @@ def _take_from_set(job, sample_set, members):
             raise RuntimeError('the molecule matrix does not have the entries of the count matrix')
         for k, sample in enumerate(members):
             sample.molecule_row = m_data[indptr[k]:indptr[k + 1]]
+    if job.resolve_molecules:               # (one more pass over the same two: the classes of a UMI, intersected)
+        r_indptr, r_indices, r_data, r_tally = sample_set.gene_resolved_matrix(job.gene_names[1], n_genes)
+        for k, sample in enumerate(members):
+            sample.resolved_row = (r_indices[r_indptr[k]:r_indptr[k + 1]], r_data[r_indptr[k]:r_indptr[k + 1]])
+            sample.resolved_tally = r_tally[k]
     if job.matrix_only:
         for sample, row, mean in zip(members, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
             sample.sizes, sample.mean = row, mean
@@ -908,6 +954,13 @@ def _finish(job, samples):
         inside = int(sum(int(sample.matrix_row[1].sum()) for sample in samples))
         _LOG.info('Units inside one gene: %d; molecules (distinct UMIs per cell and gene): %d; %.3f units a molecule',
                   inside, int(molecules.sum()), inside / max(int(molecules.sum()), 1))
+    if job.resolve_molecules:
+        tally = numpy.asarray([sample.resolved_tally for sample in samples], dtype=numpy.int64).reshape(-1, len(RESOLVED_TALLY))
+        output_resolved_matrix(job.output_path, job.gene_names[0].size, [sample.name for sample in samples],
+                               *stack_count_rows(sample.resolved_row for sample in samples), tally)
+        totals = [int(v) for v in tally.sum(axis=0)]
+        _LOG.info('Distinct UMIs per cell: %d; resolved to one gene: %d (%d of them rescued), multi-gene: %d, unnamed: %d, '
+                  'collisions: %d', totals[0] + totals[2] + totals[3] + totals[4], *totals)
     with (job.output_path / 'samples.tsv').open('w') as f:
         for sample, (total, aligned) in zip(samples, units):
             f.write('%s\t%d\t%d\t%.2f\n' % (sample.name, total, aligned, sample.mean))
@@ -1867,15 +1920,17 @@ def add_gene_arguments(parser):
 def gene_option(opts):
     """The parsed options: --gene-map implies --genes -- unless --count-matrix or --matrix-only is given, which the map
     then serves: they need genes but do not switch the gene-level tables on.  --matrix-only and --count-molecules imply
-    --count-matrix."""
+    --count-matrix, --resolve-molecules implies --count-molecules."""
+    opts['count_molecules'] = bool(opts.get('count_molecules')) or bool(opts.get('resolve_molecules'))
     opts['count_matrix'] = bool(opts.get('count_matrix')) or bool(opts.get('matrix_only')) or bool(opts.get('count_molecules'))
     opts['genes'] = bool(opts.get('genes')) or (opts.get('gene_map') is not None and not opts['count_matrix'])
     return opts
 
 
 def add_count_matrix_arguments(parser):
-    """--count-matrix, --matrix-only and --count-molecules: dest 'count_matrix', 'matrix_only', 'count_molecules'
-    (gene_option makes the second and the third imply the first)."""
+    """--count-matrix, --matrix-only, --count-molecules and --resolve-molecules: dest 'count_matrix', 'matrix_only',
+    'count_molecules', 'resolve_molecules' (gene_option makes the second and the third imply the first, and the fourth
+    the third)."""
     parser.add_argument('--count-matrix', action='store_true', dest='count_matrix',
                         help='also write output/counts/: the sparse gene x cell matrix of the units that lie inside one '
                              'gene (matrix.mtx, genes.tsv, cells.tsv, matrix.npz), made on the GPU; the genes are the '
@@ -1888,6 +1943,10 @@ def add_count_matrix_arguments(parser):
                         help='also write counts/molecules.mtx and counts/molecules.npz: per gene and cell the number of '
                              'DISTINCT UMIs among the units inside that gene, where matrix.mtx counts a molecule once per '
                              'equivalence class its reads fell into; implies --count-matrix, needs --umi-length')
+    parser.add_argument('--resolve-molecules', action='store_true', dest='resolve_molecules',
+                        help='also write counts/molecules.resolved.mtx, .npz and .tsv: one gene per UMI and cell, named by '
+                             'the intersection of the gene sets of the classes the UMI was seen in; multi-gene, unnamed and '
+                             'colliding UMIs are tallied per cell; implies --count-molecules, needs --umi-length')
 
 
 def add_bias_argument(parser):

@@ -118,6 +118,53 @@ def molecule_matrix(sample, gene, umi, n_samples, n_genes, device=0):
     return read_gene_matrix(handle)
 
 
+def read_resolved_matrix(handle):
+    """(indptr, indices, data, tally int64[n_samples, 5]) of a handle that holds resolved molecules, copied home; the
+    handle is destroyed.  tally[s] = (resolved, rescued, multi-gene, unnamed, collision)."""
+    shape = ctypes.c_int64(0)
+    tally = None
+    try:
+        _native.check(_native.hip().skm_gene_matrix_shape(handle, ctypes.byref(shape), None, None))
+        tally = numpy.zeros((max(int(shape.value), 1), 5), dtype=numpy.int64)
+        _native.check(_native.hip().skm_gene_matrix_read_tally(handle, _native.ptr(tally, _native.c_i64p)))
+    except Exception:
+        _native.hip().skm_gene_matrix_destroy(handle)
+        raise
+    indptr, indices, data, _ = read_gene_matrix(handle)
+    return indptr, indices, data, tally[:int(shape.value)]
+
+
+def resolved_molecule_matrix(class_offsets, class_targets, class_sample, mol_class, mol_umi, tx_gene, n_samples, n_genes,
+                             device=0):
+    """(indptr, indices, data, tally) of the molecules (mol_class[i], mol_umi[i]) resolved to one gene per (sample, UMI):
+    the classes are a CSR (class_offsets, class_targets) with a sample each, the distinct classes of a sample's
+    molecules with one UMI form a group, and the intersection of their gene sets is the group's verdict
+    (skm_gene_matrix_from_molecule_classes: the sort, group, resolve and fill steps of DESIGN.md section 4, "Resolved
+    molecules", on the device).  Two molecules with the same class and UMI count as one.  A class index, a sample or
+    a transcript id out of range and an empty class raise."""
+    class_offsets = numpy.ascontiguousarray(class_offsets, dtype=numpy.int64)
+    class_targets = numpy.ascontiguousarray(class_targets, dtype=numpy.int32)
+    class_sample = numpy.ascontiguousarray(class_sample, dtype=numpy.int32)
+    mol_class = numpy.ascontiguousarray(mol_class, dtype=numpy.int32)
+    mol_umi = numpy.ascontiguousarray(mol_umi, dtype=numpy.uint32)
+    tx_gene = numpy.ascontiguousarray(tx_gene, dtype=numpy.int32)
+    n_classes = int(class_sample.size)
+    if class_offsets.shape != (n_classes + 1,) or mol_class.ndim != 1 or mol_umi.shape != mol_class.shape:
+        raise ValueError('class_offsets[n_classes + 1] beside class_sample[n_classes]; mol_class and mol_umi of one length')
+    if n_classes and class_targets.size != class_offsets[-1]:
+        raise ValueError('class_targets holds %d ids, class_offsets ends at %d' % (class_targets.size, class_offsets[-1]))
+    handle = ctypes.c_void_p()
+    n = int(mol_class.size)
+    _native.check(_native.hip().skm_gene_matrix_from_molecule_classes(
+        int(device), n_classes, _native.ptr(class_offsets, _native.c_i64p),
+        _native.ptr(class_targets, _native.c_i32p) if class_targets.size else None,
+        _native.ptr(class_sample, _native.c_i32p) if n_classes else None, n,
+        _native.ptr(mol_class, _native.c_i32p) if n else None, _native.ptr(mol_umi, _native.c_u32p) if n else None,
+        int(n_samples), int(tx_gene.size), int(n_genes), _native.ptr(tx_gene, _native.c_i32p) if tx_gene.size else None,
+        ctypes.byref(handle)))
+    return read_resolved_matrix(handle)
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
@@ -890,6 +937,19 @@ class SampleSet:
         _native.check(_native.hip().skm_sample_set_molecule_matrix(
             self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
         return read_gene_matrix(handle)
+
+    def gene_resolved_matrix(self, tx_gene, n_genes):
+        """(indptr, indices, data, tally int64[n_samples, 5]): one gene per (sample, UMI).  The distinct classes among a
+        sample's live molecules -- the population of gene_molecule_matrix -- with one UMI form a group; the
+        intersection of their gene sets names the group's gene (data counts such groups per gene) or makes the group
+        multi-gene, unnamed or a collision: tally[s] = (resolved, rescued, multi-gene, unnamed, collision), rescued a
+        part of resolved (skm_sample_set_resolved_matrix; DESIGN.md section 4, "Resolved molecules").  The pattern is
+        the matrix's own, not gene_count_matrix's.  A set that keeps no UMIs (umi_bases=0) raises."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_sample_set_resolved_matrix(
+            self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
+        return read_resolved_matrix(handle)
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
