@@ -917,6 +917,11 @@ int skm_quant_components(skm_quant *quant, int64_t info[8], int32_t *tx_label, i
 int skm_quant_tile_arrays(skm_quant *quant, int64_t *tile_tx, int64_t *tile_cls, int32_t *tx_list, int32_t *cls_list,
                           int64_t *tx_pair, int64_t *cls_pair, uint16_t *cls_tx, uint16_t *tx_cls, int32_t *order,
                           int32_t *perm);
+/* *built = 1 when the handle holds the whole table's transcript-major rows, 0 when no reader has asked for them
+ * yet (diagnostics, tests).  The tile EM reads none of them: a handle whose table is tiles alone builds them when the
+ * whole-table EM, the batched EM (skm_quant_em_many, _em_blend, the bootstrap) or a residual problem first needs
+ * them; a handle with components above the tile capacity, or without tiles, at the latest with its first EM. */
+int skm_quant_rows_built(skm_quant *quant, int *built);
 /* numpy.sum(values[0 .. n)) as the device adds it up for the start vector and the TPM scaling (diagnostics, tests):
  * upload, the production launches, download.  *sum = the sum (n = 0: 0.0).  SKM_ERR_ARG for n < 0, n >= 2^31, NULL. */
 int skm_device_np_sum_probe(int device, const double *values, int64_t n, double *sum);

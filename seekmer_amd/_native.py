@@ -208,6 +208,7 @@ HIP_SYMBOLS = {
     'skm_quant_components': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i32p, c_i32p, c_i32p]),
     'skm_quant_tile_arrays': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_i64p, c_i32p, c_i32p, c_i64p, c_i64p,
                                              ctypes.c_void_p, ctypes.c_void_p, c_i32p, c_i32p]),
+    'skm_quant_rows_built': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]),
     'skm_device_np_sum_probe': (ctypes.c_int, [ctypes.c_int, c_f64p, c_i64, c_f64p]),
     'skm_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_comm_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

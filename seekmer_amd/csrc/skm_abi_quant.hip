@@ -16,6 +16,34 @@
 using namespace skm;
 using namespace skm::abi;
 
+// The whole table's transcript-major rows as their readers get them (QuantRowsHolder::get)
+struct QuantRowsView {
+    int64_t n_rows;
+    const int64_t *row_start;     // [n_rows + 1]
+    const int32_t *row_tx;        // [n_rows]
+    const int32_t *tx_cls;        // [M]
+    const int64_t *tx_row;        // [T + 1]
+    unsigned int *arrivals;       // [T], zero between steps (EmProblem::arrivals)
+};
+
+// The rows of a handle, built when a reader first asks (the tile EM reads none of them: a handle whose table is
+// tiles alone never builds them).  Nothing but get() reaches the arrays, so every reader goes through it.
+class QuantRowsHolder {
+public:
+    // the rows, built now if they are not (the pair sort and the row kernels on the handle's stream, the cleared
+    // arrival counters with them).  The caller holds the handle's mutex (or owns the handle alone) and has set
+    // the device.
+    int get(skm_quant *q, QuantRowsView &view);
+    bool built() const { return built_; }
+    void reset() { built_ = false; n_rows_ = 0; }      // (the class table changes: the set driver's next group)
+private:
+    DBuf<int64_t> row_start_, tx_row_;
+    DBuf<int32_t> tx_cls_, row_tx_;
+    DBuf<unsigned int> arrivals_;
+    int64_t n_rows_ = 0;
+    bool built_ = false;
+};
+
 struct skm_quant {
     ~skm_quant()                              // (the buffers go once the stream has drained)
     {
@@ -28,12 +56,13 @@ struct skm_quant {
     PoolEvent chunk_ev[2];
     PoolPinned pinned;                        // host-pinned readback of the control block
     std::mutex mu;
-    int64_t n_tx = 0, n_classes = 0, n_ids = 0, n_rows = 0;
-    DBuf<int64_t> cls_offset, row_start, tx_row;
-    DBuf<int32_t> ids, tx_cls, row_tx, perm;      // perm[k] = caller's index of internal class k
+    int64_t n_tx = 0, n_classes = 0, n_ids = 0;
+    DBuf<int64_t> cls_offset;
+    DBuf<int32_t> ids, perm;                      // perm[k] = caller's index of internal class k
+    QuantRowsHolder rows;                         // the transcript-major rows, on first use
     DBuf<double> cls_count, cls_count_saved, inner, row_sum;
     DBuf<double> eff_len, x0, x1, acc, part_max;
-    DBuf<unsigned int> part_flags, arrivals;
+    DBuf<unsigned int> part_flags;
     DBuf<unsigned long long> ctl, cum;
     DBuf<unsigned int> tile_total;            // scratch of the tiled multinomial draw
     DBuf<double> x_start, boot_out;           // bootstrap: the common start vector, the replicates' results
@@ -194,10 +223,6 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
     SKM_TRY(q->inner.ensure(C));
     SKM_TRY(q->ids.ensure(M));
     SKM_TRY(q->perm.ensure(C));
-    SKM_TRY(q->tx_cls.ensure(M));
-    SKM_TRY(q->tx_row.ensure(T + 1));
-    SKM_TRY(q->row_start.ensure(R + 1));
-    SKM_TRY(q->row_tx.ensure(R));
     SKM_TRY(q->row_sum.ensure(R));
     SKM_TRY(q->eff_len.ensure(T));
     SKM_TRY(q->x0.ensure(T));
@@ -206,8 +231,6 @@ int quant_alloc(skm_quant *q, int device, int64_t n_tx, int64_t n_classes, int64
     SKM_TRY(q->ctl.ensure(EM_CTL_WORDS + EM_JUDGE_WORDS));       // (the tile judge's words lie behind the control block)
     SKM_TRY(q->part_max.ensure(EM_FINAL_BLOCKS));
     SKM_TRY(q->part_flags.ensure(EM_FINAL_BLOCKS));
-    SKM_TRY(q->arrivals.ensure(T));
-    HIP_TRY(hipMemsetAsync(q->arrivals.p, 0, T * sizeof(unsigned int), q->stream));
     if (em_tiles_possible(several_ranks)) {
         auto &t = q->tiles;
         SKM_TRY(t.tile_tx.ensure(T + 2)); SKM_TRY(t.tile_cls.ensure(T + 2));
@@ -230,11 +253,6 @@ QuantBuild quant_build_view(skm_quant *q)
     b.cls_offset = q->cls_offset.p;
     b.ids = q->ids.p;
     b.cls_count = q->cls_count.p;
-    b.tx_cls = q->tx_cls.p;
-    b.tx_row = q->tx_row.p;
-    b.row_start = q->row_start.p;
-    b.row_tx = q->row_tx.p;
-    b.n_rows_cap = (int64_t)q->row_tx.cap;
     if (q->tiles.tile_tx.p) {                      // (quant_alloc made room for the tiles)
         auto &t = q->tiles;
         b.tile_tx = t.tile_tx.p; b.tile_cls = t.tile_cls.p;
@@ -247,14 +265,44 @@ QuantBuild quant_build_view(skm_quant *q)
     return b;
 }
 
+}  // namespace
+
+int QuantRowsHolder::get(skm_quant *q, QuantRowsView &view)
+{
+    if (!built_) {
+        const size_t M = (size_t)std::max<int64_t>(q->n_ids, 1), T = (size_t)std::max<int64_t>(q->n_tx, 1);
+        const size_t R = (size_t)quant_rows_upper_bound(q->n_tx, q->n_ids);
+        SKM_TRY(tx_cls_.ensure(M));
+        SKM_TRY(tx_row_.ensure(T + 1));
+        SKM_TRY(row_start_.ensure(R + 1));
+        SKM_TRY(row_tx_.ensure(R));
+        SKM_TRY(arrivals_.ensure(T));
+        HIP_TRY(hipMemsetAsync(arrivals_.p, 0, T * sizeof(unsigned int), q->stream));
+        const QuantBuild b = quant_build_view(q);
+        QuantRows r{};
+        r.tx_cls = tx_cls_.p; r.tx_row = tx_row_.p; r.row_start = row_start_.p; r.row_tx = row_tx_.p;
+        r.n_rows_cap = (int64_t)std::min(row_tx_.cap, row_start_.cap - 1);
+        const int64_t n = quant_rows_build(b, r, q->stream);
+        if (n < 0) return fail(SKM_ERR_HIP, "building the transcript-major rows failed (%lld): %s", (long long)n, quant_setup_failure());
+        n_rows_ = n;
+        built_ = true;
+    }
+    view.n_rows = n_rows_;
+    view.row_start = row_start_.p; view.row_tx = row_tx_.p; view.tx_cls = tx_cls_.p; view.tx_row = tx_row_.p;
+    view.arrivals = arrivals_.p;
+    return SKM_OK;
+}
+
+namespace {
+
 int quant_finish_setup(skm_quant *q, const ClassTable *table, int64_t units_seen = -1)
 {
     STALE_CHECK("quant_finish_setup");
     QuantBuild b = quant_build_view(q);
     b.first_seen_bound = units_seen > 0 ? units_seen : 0;      // first-seen values are unit indices below this
-    const int64_t rows = quant_setup(table, b, q->perm.p, q->stream);
-    if (rows < 0) return fail(SKM_ERR_HIP, "building the class views failed (%lld): %s", (long long)rows, quant_setup_failure());
-    q->n_rows = rows;
+    q->rows.reset();
+    const int rc = quant_setup(table, b, q->perm.p, q->stream);
+    if (rc < 0) return fail(SKM_ERR_HIP, "building the class views failed (%d): %s", rc, quant_setup_failure());
     if (b.tile_tx) {
         q->tiles.built = true;
         q->tiles.n_tiles = b.tile_info[0];
@@ -267,9 +315,16 @@ int quant_finish_setup(skm_quant *q, const ClassTable *table, int64_t units_seen
         if (q->tiles.n_oversize > 0 && q->tiles.n_tiles > 0) {
             // tiles AND components above the capacity: those become the residual problem (a table that
             // is one such component has no tiles and keeps the whole-table EM as it is)
+            // (the residual is cut out of the whole table's rows: this handle builds them now)
             auto &r = q->tiles.residual;
+            QuantRowsView rv{};
+            SKM_TRY(q->rows.get(q, rv));
+            QuantRows whole{};
+            whole.tx_cls = const_cast<int32_t *>(rv.tx_cls); whole.tx_row = const_cast<int64_t *>(rv.tx_row);
+            whole.row_start = const_cast<int64_t *>(rv.row_start); whole.row_tx = const_cast<int32_t *>(rv.row_tx);
+            whole.n_rows_cap = rv.n_rows;
             int64_t counts[3] = {0, 0, 0};
-            if (quant_residual_count(b, counts, q->stream))
+            if (quant_residual_count(b, whole, counts, q->stream))
                 return fail(SKM_ERR_HIP, "sizing the residual EM problem failed: %s", quant_setup_failure());
             r.n_classes = counts[0]; r.n_ids = counts[1]; r.n_rows = counts[2];
             SKM_TRY(r.cls_offset.ensure((size_t)r.n_classes + 1)); SKM_TRY(r.ids.ensure((size_t)std::max<int64_t>(r.n_ids, 1)));
@@ -283,7 +338,7 @@ int quant_finish_setup(skm_quant *q, const ClassTable *table, int64_t units_seen
             out.n_classes = r.n_classes; out.n_ids = r.n_ids; out.n_rows = r.n_rows;
             out.cls_offset = r.cls_offset.p; out.ids = r.ids.p; out.cls_src = r.cls_src.p;
             out.row_start = r.row_start.p; out.row_tx = r.row_tx.p; out.tx_cls = r.tx_cls.p; out.tx_row = r.tx_row.p;
-            if (quant_residual_build(b, out, q->stream))
+            if (quant_residual_build(b, whole, out, q->stream))
                 return fail(SKM_ERR_HIP, "building the residual EM problem failed: %s", quant_setup_failure());
             r.built = true;
         }
@@ -348,15 +403,10 @@ EmProblem em_problem(skm_quant *q, double rel_tol, double x_floor, int64_t max_i
     EmProblem p{};
     p.n_tx = q->n_tx;
     p.n_classes = q->n_classes;
-    p.n_rows = q->n_rows;
     p.cls_offset = q->cls_offset.p;
     p.ids = q->ids.p;
     p.cls_count = q->cls_count.p;
     p.inner = q->inner.p;
-    p.row_start = q->row_start.p;
-    p.row_tx = q->row_tx.p;
-    p.tx_cls = q->tx_cls.p;
-    p.tx_row = q->tx_row.p;
     p.row_sum = q->row_sum.p;
     p.eff_len = q->eff_len.p;
     p.x[0] = q->x0.p;
@@ -372,8 +422,19 @@ EmProblem em_problem(skm_quant *q, double rel_tol, double x_floor, int64_t max_i
     p.fixed_iters = fixed_iters;
     static const bool unfused = getenv("SKM_EM_UNFUSED") != nullptr;     // tuning aid: rows and finalize as two launches
     p.fused = q->comm || unfused ? 0 : 1;      // (several ranks: the all-reduce sits between rows and finalize)
-    p.arrivals = q->arrivals.p;
     return p;
+}
+
+// the whole table's rows into the problem, for the kernels that step the whole table (built now if no reader
+// has asked before); em_problem leaves them out: the tile EM of a table without a residual reads none
+int em_problem_rows(skm_quant *q, EmProblem &p)
+{
+    QuantRowsView rv{};
+    SKM_TRY(q->rows.get(q, rv));
+    p.n_rows = rv.n_rows;
+    p.row_start = rv.row_start; p.row_tx = rv.row_tx; p.tx_cls = rv.tx_cls; p.tx_row = rv.tx_row;
+    p.arrivals = rv.arrivals;
+    return SKM_OK;
 }
 
 // one rank, every component within the tile capacity: the EM runs tile by tile in LDS (em_run_tiles)
@@ -507,13 +568,17 @@ int em_run(skm_quant *q, double rel_tol, double x_floor, int64_t max_iters, int6
     }
     EmProblem p = em_problem(q, rel_tol, x_floor, max_iters, fixed_iters);
     p.n_total = n_total;
+    const int64_t chunk = fixed_iters > 0 ? std::min<int64_t>(fixed_iters, chunk_steps) : chunk_steps;
+    const bool by_tiles = em_uses_tiles(q) && chunk <= EM_CHUNK_MAX;
+    // (the rows: for the whole-table steps, and beside tiles for the residual's launches, whose arrival counters
+    // are the whole table's -- built with the residual at the set-up)
+    if (!by_tiles || q->tiles.n_oversize > 0) SKM_TRY(em_problem_rows(q, p));
     // (with the control block the tile judge's words behind it: a run that ended in a tile fault or an error
     // leaves nothing there)
     HIP_TRY(hipMemsetAsync(q->ctl.p, 0, (EM_CTL_WORDS + EM_JUDGE_WORDS) * sizeof(unsigned long long), q->stream));
     int64_t k = 0;
-    const int64_t chunk = fixed_iters > 0 ? std::min<int64_t>(fixed_iters, chunk_steps) : chunk_steps;
     HIP_TRY(hipEventRecord(q->ev[0], q->stream));
-    if (em_uses_tiles(q) && chunk <= EM_CHUNK_MAX) return em_run_tiles(q, p, chunk, iters_out);
+    if (by_tiles) return em_run_tiles(q, p, chunk, iters_out);
     // Steps are enqueued in chunks, the control block copied to pinned memory behind each (em_run_chunks_ahead).
     static const bool unfused_rows = getenv("SKM_EM_UNFUSED") != nullptr;
     auto enqueue_chunk = [&](int slot) -> int {
@@ -733,8 +798,8 @@ extern "C" int skm_quant_infer(skm_mapper *m, skm_comm *comm, const double *leng
     lap("start vector");
     SKM_TRY(quant_finish_setup(q.get(), &m->t, m->first_seen_bound));
     lap("setup");
-    if (trace) fprintf(stderr, "[skm_quant_infer] %lld classes, %lld transcripts, %lld rows\n", (long long)C, (long long)n_tx,
-                       (long long)q->n_rows);
+    if (trace) fprintf(stderr, "[skm_quant_infer] %lld classes, %lld transcripts, rows %s\n", (long long)C, (long long)n_tx,
+                       q->rows.built() ? "built" : "not built");
     int64_t it = 0;
     SKM_TRY(em_run(q.get(), rel_tol, x_floor, max_iters, 0, &it));
     lap("em");
@@ -807,6 +872,14 @@ extern "C" int skm_quant_components(skm_quant *q, int64_t info[8], int32_t *tx_l
         HIP_TRY(hipMemcpy(perm.data(), q->perm.p, q->n_classes * 4, hipMemcpyDeviceToHost));
         for (int64_t k = 0; k < q->n_classes; ++k) class_tile[perm[k]] = tile[k];
     }
+    return SKM_OK;
+}
+
+extern "C" int skm_quant_rows_built(skm_quant *q, int *built)
+{
+    if (!q || !built) return fail(SKM_ERR_ARG, "NULL argument");
+    std::lock_guard<std::mutex> lock(q->mu);
+    *built = q->rows.built() ? 1 : 0;
     return SKM_OK;
 }
 
@@ -963,8 +1036,10 @@ int em_group_run(skm_quant *q, int64_t n_problems, Fill &&fill, bool batched, in
     // steps, one in six needs 60-90): problems that wait for the slowest of a fixed group of eight
     // waste half the working set's steps.  Every problem still runs the single-problem EM's steps bit
     // for bit, whoever its neighbours are and whenever it starts.
+    QuantRowsView rows{};                                        // (the batched EM steps the whole table)
+    SKM_TRY(q->rows.get(q, rows));
     SKM_TRY(w.cls_count.ensure((size_t)C * EM_BATCH)); SKM_TRY(w.inner.ensure((size_t)C * EM_BATCH));
-    SKM_TRY(w.row_sum.ensure((size_t)std::max<int64_t>(q->n_rows, 1) * EM_BATCH));
+    SKM_TRY(w.row_sum.ensure((size_t)std::max<int64_t>(rows.n_rows, 1) * EM_BATCH));
     SKM_TRY(w.x0.ensure((size_t)T * EM_BATCH)); SKM_TRY(w.x1.ensure((size_t)T * EM_BATCH));
     SKM_TRY(w.part_max.ensure((size_t)EM_FINAL_BLOCKS * EM_BATCH));
     SKM_TRY(w.part_flags.ensure((size_t)EM_FINAL_BLOCKS * EM_BATCH));
@@ -973,9 +1048,9 @@ int em_group_run(skm_quant *q, int64_t n_problems, Fill &&fill, bool batched, in
     SKM_TRY(w.counts_all.ensure((size_t)slots * C));
     SKM_TRY(w.iters.ensure((size_t)slots));
     EmBatchProblem p{};
-    p.n_tx = T; p.n_classes = C; p.n_rows = q->n_rows;
-    p.cls_offset = q->cls_offset.p; p.ids = q->ids.p; p.row_start = q->row_start.p; p.row_tx = q->row_tx.p;
-    p.tx_cls = q->tx_cls.p; p.tx_row = q->tx_row.p; p.eff_len = q->eff_len.p;
+    p.n_tx = T; p.n_classes = C; p.n_rows = rows.n_rows;
+    p.cls_offset = q->cls_offset.p; p.ids = q->ids.p; p.row_start = rows.row_start; p.row_tx = rows.row_tx;
+    p.tx_cls = rows.tx_cls; p.tx_row = rows.tx_row; p.eff_len = q->eff_len.p;
     p.cls_count = w.cls_count.p; p.inner = w.inner.p; p.row_sum = w.row_sum.p;
     p.x[0] = w.x0.p; p.x[1] = w.x1.p;
     p.place_total = reinterpret_cast<double *>(w.ctl.p + 32);
@@ -985,7 +1060,7 @@ int em_group_run(skm_quant *q, int64_t n_problems, Fill &&fill, bool batched, in
     p.mgr = w.mgr.p;
     p.iters_out = w.iters.p;
     p.fused = getenv("SKM_EM_UNFUSED") ? 0 : 1;
-    p.arrivals = q->arrivals.p;
+    p.arrivals = rows.arrivals;
     int64_t chunk = 16;                                          // steps queued between two looks at the progress
     if (const char *e = getenv("SKM_BOOTSTRAP_CHUNK")) chunk = std::max<int64_t>(1, atoll(e));   // (tests)
     unsigned long long *const look = q->pinned + 64;             // 64 + 8 words of the pinned block
@@ -1364,8 +1439,10 @@ int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, co
     q->n_tx = n * T; q->n_classes = C; q->n_ids = M;
     SKM_TRY(quant_finish_setup(q, nullptr));
     // every transcript has its rows, slot s those of transcripts [s T, (s + 1) T)
+    QuantRowsView rows{};                                         // (the set EM steps the stacked table whole)
+    SKM_TRY(q->rows.get(q, rows));
     std::vector<int64_t> row_cut((size_t)n + 1);
-    HIP_TRY(hipMemcpy2DAsync(row_cut.data(), 8, q->tx_row.p, (size_t)T * 8, 8, (size_t)n + 1, hipMemcpyDeviceToHost, q->stream));
+    HIP_TRY(hipMemcpy2DAsync(row_cut.data(), 8, rows.tx_row, (size_t)T * 8, 8, (size_t)n + 1, hipMemcpyDeviceToHost, q->stream));
     HIP_TRY(hipStreamSynchronize(q->stream));
     std::vector<EmSetSlot> slots((size_t)n);
     int64_t cls = 0, largest_classes = 0, largest_rows = 0;
@@ -1373,7 +1450,7 @@ int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, co
         EmSetSlot &d = slots[(size_t)i];
         d.cls_first = cls; d.cls_end = cls += slot_classes[i];
         d.row_first = row_cut[(size_t)i]; d.row_end = row_cut[(size_t)i + 1];
-        if (d.row_end - d.row_first < T || d.row_end > q->n_rows)
+        if (d.row_end - d.row_first < T || d.row_end > rows.n_rows)
             return fail(SKM_ERR_STATE, "the stacked class views give table %lld rows [%lld, %lld)", (long long)(first_table + i),
                         (long long)d.row_first, (long long)d.row_end);
         d.n_total = slot_total[i];
@@ -1387,7 +1464,7 @@ int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, co
     if (cls != C) return fail(SKM_ERR_STATE, "the tables of the group hold %lld classes, not %lld", (long long)cls, (long long)C);
     EmSetProblem p{};
     p.cls_offset = q->cls_offset.p; p.ids = q->ids.p; p.cls_count = q->cls_count.p; p.inner = q->inner.p;
-    p.row_start = q->row_start.p; p.row_tx = q->row_tx.p; p.tx_cls = q->tx_cls.p; p.tx_row = q->tx_row.p;
+    p.row_start = rows.row_start; p.row_tx = rows.row_tx; p.tx_cls = rows.tx_cls; p.tx_row = rows.tx_row;
     p.row_sum = q->row_sum.p; p.eff_len = q->eff_len.p; p.x[0] = q->x0.p; p.x[1] = q->x1.p;
     p.rel_tol = rel_tol; p.x_floor = x_floor; p.max_iters = max_iters;
     p.slots = run.slots.p; p.n_slots = (int)n;
@@ -1395,7 +1472,7 @@ int set_quant_group(SetQuantRun &run, int64_t n, const int64_t *slot_classes, co
     SKM_TRY(q->part_max.ensure((size_t)(n * p.n_parts)));
     SKM_TRY(q->part_flags.ensure((size_t)(n * p.n_parts)));
     p.part_max = q->part_max.p; p.part_flags = q->part_flags.p;
-    p.arrivals = q->arrivals.p;
+    p.arrivals = rows.arrivals;
     HIP_TRY(hipMemcpyAsync(run.slots.p, slots.data(), (size_t)n * sizeof(EmSetSlot), hipMemcpyHostToDevice, q->stream));
     // Steps are queued in chunks with the host one chunk ahead, as em_run does; what the host reads at a
     // chunk's end is the number of slots still running.

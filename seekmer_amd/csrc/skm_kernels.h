@@ -509,20 +509,15 @@ void launch_stack_tuples(const int64_t *src, const int64_t *dst, const int32_t *
 // rows 1 .. n - 1 of x[n][n_tx] = row 0 (n <= 65536)
 void launch_repeat_row(double *x, int64_t n_tx, int64_t n, hipStream_t stream);
 
-// device-side construction of the two CSR views (skm_quant_setup.hip)
+// device-side construction of the class views (skm_quant_setup.hip)
 struct QuantBuild {
     int64_t n_tx, n_classes, n_ids;
     int64_t *cls_offset;          // [C+1] out
     int32_t *ids;                 // [M]   out (class-major)
     double *cls_count;            // [C]   out
-    int32_t *tx_cls;              // [M]   out
-    int64_t *tx_row;              // [T+1] out
-    int64_t *row_start;           // [R+1] out (capacity n_rows_cap + 1)
-    int32_t *row_tx;              // [R]   out
-    int64_t n_rows_cap;
     int64_t first_seen_bound;     // every first-seen value of the table is below this (0: unknown)
     // the component tiles (EmTiles), built when tile_tx is given; tile_info[0] = tiles, [1] = components
-    // above the tile capacity (then the tiles are not used), both read by the host with the row count
+    // above the tile capacity (then the tiles are not used), both read by the host when the set-up ends
     int64_t *tile_tx, *tile_cls;  // [T + 2], [T + 2] out
     int32_t *tx_list, *cls_list;  // [T], [C] out: the tiles' members (tile_tx[tiles], tile_cls[tiles] places)
     int64_t *cls_pair, *tx_pair;  // [C + 1], [T + 1] out: for those places and the one behind them
@@ -533,13 +528,26 @@ struct QuantBuild {
 };
 // One asynchronous pipeline: classes (from a mapper's table when `table` is given, the caller's
 // order being first-seen order) in (smallest transcript id, caller's index) order for gather
-// locality, perm[k] = caller's index of internal class k -> transcript-major rows.  Returns the
-// number of rows, or < 0.
-int64_t quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipStream_t stream);
+// locality, perm[k] = caller's index of internal class k, then the component tiles from the classes
+// alone.  Returns 0, or < 0.  The transcript-major rows are no part of it: quant_rows_build.
+int quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipStream_t stream);
+// The transcript-major view of the whole table cut into rows of EM_ROW_CAP pairs, for the kernels that
+// step the whole table (em_rows*_kernel, the batched and the set EM) and for the residual below.  The
+// tile EM reads none of it, so a handle builds it when a reader first asks.  Queued on `stream`; the
+// stream has drained on return.  Returns the number of rows, -3 when they exceed n_rows_cap, or < 0.
+struct QuantRows {
+    int32_t *tx_cls;              // [M]   out
+    int64_t *tx_row;              // [T+1] out
+    int64_t *row_start;           // [R+1] out (capacity n_rows_cap + 1)
+    int32_t *row_tx;              // [R]   out
+    int64_t n_rows_cap;
+};
+int64_t quant_rows_build(const QuantBuild &q, const QuantRows &rows, hipStream_t stream);
 // The components above the tile capacity as an EM problem of their own (the "residual"): their classes
 // (internal order kept, renumbered) and the rows of their transcripts, in the form em_inner_kernel and
 // em_rows_finalize_kernel take; tx_row stays indexed by transcript id (no rows for a transcript of a tile).
 // _count: counts[0] classes, [1] pairs, [2] rows (synchronises); _build: fills arrays of those sizes.
+// Both read the whole table's rows.
 struct QuantResidual {
     int64_t n_classes, n_ids, n_rows;
     int64_t *cls_offset;          // [n_classes + 1] out
@@ -550,8 +558,8 @@ struct QuantResidual {
     int32_t *tx_cls;              // [n_ids] out: residual class index
     int64_t *tx_row;              // [T + 1] out
 };
-int quant_residual_count(const QuantBuild &q, int64_t counts[3], hipStream_t stream);
-int quant_residual_build(const QuantBuild &q, QuantResidual &r, hipStream_t stream);
+int quant_residual_count(const QuantBuild &q, const QuantRows &rows, int64_t counts[3], hipStream_t stream);
+int quant_residual_build(const QuantBuild &q, const QuantRows &rows, QuantResidual &r, hipStream_t stream);
 // y[k] = x[perm[k]] (gather) or y[perm[k]] = x[k] (scatter), n doubles
 void launch_permute_f64(const double *x, const int32_t *perm, int64_t n, double *y, bool scatter,
                         hipStream_t stream);

@@ -8,17 +8,21 @@
 // From a mapper's table the first-seen RANK of every class comes from a bitmap
 // over the unit indices (first-seen values are distinct: a unit belongs to one
 // class) and a prefix popcount -- no sort; one stable 18-bit radix sort of the
-// classes by smallest id and one of the pairs by transcript remain (the
-// hand-written sort_pairs below: no library code on the path), everything else
-// is small index-moving kernels.  The tiles of the component EM need no sort:
-// their sizes follow from the components, their members are dropped into place
-// in any order and a workgroup per tile orders them in LDS (build_tiles).
+// classes by smallest id remains (the hand-written sort_pairs below: no library
+// code on the path), everything else is small index-moving kernels.  The tiles
+// of the component EM need no sort and no transposed table: their sizes follow
+// from the components, their members are dropped into place in any order and a
+// workgroup per tile orders them and makes both of the tile's views in LDS
+// (build_tiles).  The transcript-major rows of the WHOLE table -- the second
+// stable sort, of the pairs by transcript -- are a pipeline of their own
+// (quant_rows_build), run when something first steps the whole table.
 // One-time setup per quantification, not part of the per-step hot loop.
 #include "skm_kernels.h"
 #include "skm_pool.h"
 
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
 namespace skm {
@@ -62,10 +66,15 @@ iota_kernel(int32_t *out, int64_t n)
 }
 
 // dump of the table in registry order: arena offset, length, count, first-seen per class
-// (+ the class's smallest transcript id, the locality key, when asked for)
+// (+ the class's smallest transcript id, the locality key, when asked for).
+// With `bits` (cleared beforehand) the lane also marks the class's first-seen value in the bitmap over the
+// unit indices that the first-seen ranks come from: one bit per unit index; a bit found set already means
+// two classes share a first-seen value (possible only for tables merged from hand-made input): *duplicate
+// is raised (1; 2: a value outside the bound) and the caller takes the sorting path instead.
 __global__ void __launch_bounds__(256)
 table_dump_kernel(ClassTable t, int64_t n_classes, int64_t *arena_off, int64_t *len, double *count,
-                  unsigned long long *first_seen, uint32_t *min_id)
+                  unsigned long long *first_seen, uint32_t *min_id, uint64_t bound, uint32_t *bits,
+                  unsigned int *duplicate)
 {
     for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_classes;
          k += (int64_t)gridDim.x * blockDim.x) {
@@ -77,6 +86,14 @@ table_dump_kernel(ClassTable t, int64_t n_classes, int64_t *arena_off, int64_t *
         len[k] = n;
         count[k] = (double)s.count;
         first_seen[k] = s.first_seen;
+        if (bits) {
+            const unsigned long long f = s.first_seen;
+            if (f >= bound) atomicOr(duplicate, 2u);
+            else {
+                const uint32_t bit = 1u << (f & 31);
+                if (atomicOr(&bits[f >> 5], bit) & bit) atomicOr(duplicate, 1u);
+            }
+        }
         if (min_id) {
             uint32_t m = 0xffffffffu;
             for (int64_t j = 0; j < n; ++j) m = min(m, (uint32_t)t.arena[off + j]);
@@ -85,23 +102,7 @@ table_dump_kernel(ClassTable t, int64_t n_classes, int64_t *arena_off, int64_t *
     }
 }
 
-// ---- first-seen ranks from a bitmap over the unit indices
-// one bit per unit index; a bit found set already means two classes share a first-seen value
-// (possible only for tables merged from hand-made input): *duplicate is raised and the caller
-// takes the sorting path instead
-__global__ void __launch_bounds__(256)
-mark_first_seen_kernel(const unsigned long long *first_seen, int64_t n_classes, uint64_t bound,
-                       uint32_t *bits, unsigned int *duplicate)
-{
-    for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < n_classes;
-         k += (int64_t)gridDim.x * blockDim.x) {
-        const unsigned long long f = first_seen[k];
-        if (f >= bound) { atomicOr(duplicate, 2u); continue; }
-        const uint32_t bit = 1u << (f & 31);
-        if (atomicOr(&bits[f >> 5], bit) & bit) atomicOr(duplicate, 1u);
-    }
-}
-
+// ---- first-seen ranks from the bitmap over the unit indices (table_dump_kernel marks it)
 __global__ void __launch_bounds__(256)
 word_popcount_kernel(const uint32_t *bits, int64_t n_words, int64_t *count)
 {
@@ -126,14 +127,19 @@ first_seen_rank_kernel(const unsigned long long *first_seen, const uint32_t *min
     }
 }
 
-// internal class j = the class of first-seen rank perm[j] = registry entry by_rank[perm[j]]
+// internal class j = the class of first-seen rank perm[j] = registry entry by_rank[perm[j]].
+// With *duplicate raised the ranks are not a permutation (by_rank has places nobody wrote): every class
+// is then left empty, so that what is queued behind -- the scan, the copy of the tuples, the tiles --
+// walks no tuple and stays within its arrays until the host reads the flag and starts over.
 __global__ void __launch_bounds__(256)
 gather_by_rank_kernel(const int32_t *perm, const int32_t *by_rank, int64_t n, const int64_t *len_in,
                       const double *count_in, const int64_t *arena_off_in, int64_t *len_out,
-                      double *count_out, int64_t *arena_off_out)
+                      double *count_out, int64_t *arena_off_out, const unsigned int *duplicate)
 {
+    const bool unusable = *duplicate != 0;
     for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n;
          j += (int64_t)gridDim.x * blockDim.x) {
+        if (unusable) { len_out[j] = 0; count_out[j] = 0.0; arena_off_out[j] = 0; continue; }
         const int32_t k = by_rank[perm[j]];
         len_out[j] = len_in[k];
         count_out[j] = count_in[k];
@@ -641,7 +647,8 @@ int build_from_table(Scratch &scratch, const ClassTable &t, QuantBuild &q)
     QB_ALLOC(first, unsigned long long, n_classes); QB_ALLOC(first_sorted, unsigned long long, n_classes);
     QB_ALLOC(iota, int32_t, n_classes); QB_ALLOC(perm, int32_t, n_classes);
     hipLaunchKernelGGL(table_dump_kernel, dim3(blocks_for(n_classes)), dim3(256), 0, stream,
-                       t, n_classes, arena_off, len, count, first, (uint32_t *)nullptr);
+                       t, n_classes, arena_off, len, count, first, (uint32_t *)nullptr, (uint64_t)0, (uint32_t *)nullptr,
+                       (unsigned int *)nullptr);
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(n_classes)), dim3(256), 0, stream, iota, n_classes);
     int first_bits = 64;
     if (q.first_seen_bound > 0) {
@@ -660,11 +667,13 @@ int build_from_table(Scratch &scratch, const ClassTable &t, QuantBuild &q)
 // The same result as build_from_table + localize (classes by smallest transcript id, then by
 // first-seen; perm[j] = first-seen rank of internal class j) with one sort instead of two and one
 // copy of the tuples instead of two: the first-seen rank is a prefix popcount over a bitmap of
-// the unit indices.  Returns 1 (nothing usable written) when two classes share a first-seen
-// value or one lies outside the bound: the caller falls back to the sorting path.
+// the unit indices.  *shared_first_seen (a word of the scratch, on the device; nullptr: no class)
+// != 0 once the stream has come this far: two classes share a first-seen value or one lies outside
+// the bound, nothing usable was written and the caller falls back to the sorting path.
 constexpr int64_t RANK_BITMAP_MAX_UNITS = 1LL << 31;      // 256 MiB of bits + 4 GiB of word sums at most
 
-int build_from_table_ranked(Scratch &scratch, const ClassTable &t, QuantBuild &q, int32_t *perm)
+int build_from_table_ranked(Scratch &scratch, const ClassTable &t, QuantBuild &q, int32_t *perm,
+                            const unsigned int **shared_first_seen)
 {
     hipStream_t stream = scratch.stream;
     const int64_t C = q.n_classes;
@@ -681,14 +690,12 @@ int build_from_table_ranked(Scratch &scratch, const ClassTable &t, QuantBuild &q
     QB_TRY(hipMemsetAsync(bits, 0, n_words * sizeof(uint32_t), stream));
     QB_TRY(hipMemsetAsync(duplicate, 0, sizeof(unsigned int), stream));
     hipLaunchKernelGGL(table_dump_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, t, C, arena_off, len, count,
-                       first, min_id);
-    hipLaunchKernelGGL(mark_first_seen_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, first, C, bound, bits,
-                       duplicate);
-    unsigned int shared_first_seen = 0;
-    QB_TRY(hipMemcpyAsync(&shared_first_seen, duplicate, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-    QB_TRY(hipStreamSynchronize(stream));
-    if (shared_first_seen) return 1;
-
+                       first, min_id, bound, bits, duplicate);
+    // (the host reads the flag when the whole set-up has been queued, with the copies the end of the set-up
+    // waits for anyway: a table that raises it has run the rest for nothing -- first_seen_rank_kernel keeps
+    // its writes within the arrays whatever the bitmap holds, gather_by_rank_kernel leaves every class
+    // empty -- and goes through the sorting path then)
+    *shared_first_seen = duplicate;
     QB_ALLOC(word_count, int64_t, n_words); QB_ALLOC(word_base, int64_t, n_words + 1);
     QB_ALLOC(by_rank, int32_t, C); QB_ALLOC(key_by_rank, uint32_t, C); QB_ALLOC(key_sorted, uint32_t, C);
     QB_ALLOC(iota, int32_t, C); QB_ALLOC(len_sorted, int64_t, C); QB_ALLOC(src_off, int64_t, C);
@@ -702,7 +709,7 @@ int build_from_table_ranked(Scratch &scratch, const ClassTable &t, QuantBuild &q
     while ((1LL << end_bit) < q.n_tx && end_bit < 32) ++end_bit;
     if (sort_pairs(scratch, key_by_rank, key_sorted, iota, perm, C, end_bit)) return -1;
     hipLaunchKernelGGL(gather_by_rank_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, perm, by_rank, C, len,
-                       count, arena_off, len_sorted, q.cls_count, src_off);
+                       count, arena_off, len_sorted, q.cls_count, src_off, duplicate);
     if (exclusive_scan_with_total(scratch, len_sorted, q.cls_offset, C)) return -1;
     hipLaunchKernelGGL(copy_tuples_direct_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, C, src_off, t.arena,
                        q.cls_offset, q.ids);
@@ -741,7 +748,9 @@ int localize(Scratch &scratch, QuantBuild &q, int32_t *perm)
     return 0;
 }
 
-int transpose(Scratch &scratch, QuantBuild &q)
+// The transcript-major view of the whole table and its rows (quant_rows_build): one stable sort of the
+// pairs by transcript, then the rows of at most EM_ROW_CAP pairs.
+int transpose(Scratch &scratch, const QuantBuild &q, const QuantRows &rows_out)
 {
     hipStream_t stream = scratch.stream;
     const int64_t C = q.n_classes, M = q.n_ids, T = q.n_tx;
@@ -753,15 +762,15 @@ int transpose(Scratch &scratch, QuantBuild &q)
                            pair_cls);
         int end_bit = 1;
         while ((1LL << end_bit) < T && end_bit < 31) ++end_bit;
-        if (sort_pairs(scratch, q.ids, sorted_tx, pair_cls, q.tx_cls, M, end_bit)) return -1;
+        if (sort_pairs(scratch, (const int32_t *)q.ids, sorted_tx, (const int32_t *)pair_cls, rows_out.tx_cls, M, end_bit)) return -1;
     }
     hipLaunchKernelGGL(segment_starts_kernel, dim3(blocks_for(M + 1)), dim3(256), 0, stream, sorted_tx, M,
                        T, tx_offset);
     hipLaunchKernelGGL(row_count_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, tx_offset, T, rows);
-    if (exclusive_scan_with_total(scratch, rows, q.tx_row, T)) return -1;
+    if (exclusive_scan_with_total(scratch, rows, rows_out.tx_row, T)) return -1;
     // rows <= T + M / EM_ROW_CAP, which is what row_start / row_tx were sized for
-    hipLaunchKernelGGL(row_fill_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, tx_offset, q.tx_row, T,
-                       M, q.row_start, q.row_tx);
+    hipLaunchKernelGGL(row_fill_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, tx_offset, rows_out.tx_row, T,
+                       M, rows_out.row_start, rows_out.row_tx);
     return 0;
 }
 
@@ -782,9 +791,8 @@ __device__ __forceinline__ int32_t cc_root(const int32_t *parent, int32_t v)
 // and only ever name an ancestor, so the minimum keeps both; it never touches a root (a root has no
 // grandparent), so the hooks' compare-and-swap still sees every root as it is.  Without it a table whose
 // classes form one long chain walked O(transcripts) per hook.
-__device__ __forceinline__ int32_t cc_root_halving(int32_t *parent, int32_t v)
+__device__ __forceinline__ int32_t cc_root_halving(int32_t *parent, int32_t v, int32_t p)
 {
-    int32_t p = parent[v];
     while (p != v) {
         const int32_t g = parent[p];
         if (g != p) atomicMin(&parent[v], g);
@@ -792,6 +800,23 @@ __device__ __forceinline__ int32_t cc_root_halving(int32_t *parent, int32_t v)
         p = g;
     }
     return v;
+}
+__device__ __forceinline__ int32_t cc_root_halving(int32_t *parent, int32_t v) { return cc_root_halving(parent, v, parent[v]); }
+
+// The walk of cc_hook_kernel: its first CC_PLAIN_STEPS steps are plain loads, and only a walk that is longer goes
+// on halving its path.  On a table of many small components nearly every walk ends within the plain steps, and the
+// halving atomics, which such a table never needs, were a third of the kernel (profiles/rows_on_demand_ab.log); a
+// long chain is halved as before from the step on.  cc_label_kernel, which walks every transcript once more,
+// halves from the first step.
+constexpr int CC_PLAIN_STEPS = 8;
+__device__ __forceinline__ int32_t cc_root_hook(int32_t *parent, int32_t v, int32_t p)
+{
+    for (int step = 0; step < CC_PLAIN_STEPS; ++step) {
+        if (p == v) return v;
+        v = p;
+        p = parent[v];
+    }
+    return cc_root_halving(parent, v, p);
 }
 
 // (one lane per class; several lanes per class put more swaps in flight on the same few roots and were
@@ -803,77 +828,82 @@ cc_hook_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes,
          c += (int64_t)gridDim.x * blockDim.x) {
         const int64_t begin = cls_offset[c], end = cls_offset[c + 1];
         if (begin == end) continue;
-        int32_t b = cc_root_halving(parent, ids[begin]);
+        const int32_t v0 = ids[begin];
+        int32_t b = cc_root_hook(parent, v0, parent[v0]);
         for (int64_t j = begin + 1; j < end; ++j) {
-            int32_t a = cc_root_halving(parent, ids[j]);
+            const int32_t v = ids[j];
+            int32_t a = cc_root_hook(parent, v, parent[v]);
             while (a != b) {                        // (a or b gets smaller every turn)
                 if (a < b) { const int32_t s = a; a = b; b = s; }
                 const int32_t old = atomicCAS(&parent[a], a, b);
                 if (old == a) break;
-                a = cc_root_halving(parent, old);
+                a = cc_root_hook(parent, old, parent[old]);
             }
             b = a < b ? a : b;
         }
     }
 }
 
-// label of every transcript; comp[3 r .. 3 r + 2] of root r: transcripts, pairs (classes: cc_classes_kernel).
+// label of every transcript; comp[3 r .. 3 r + 2] of root r: transcripts (pairs, classes: cc_classes_kernel).
 // The walks go on halving the paths (a chain of classes hooked root to root leaves paths as long as the
 // chain), and a wave adds once per root it meets, not once per transcript: on a table that is one
-// component every transcript would otherwise add to the same two words.
+// component every transcript would otherwise add to the same word.
 __global__ void __launch_bounds__(256)
-cc_label_kernel(int32_t *parent, const int64_t *tx_row, const int64_t *row_start, int64_t n_tx,
-                int32_t *label, int32_t *comp)
+cc_label_kernel(int32_t *parent, int64_t n_tx, int32_t *label, int32_t *comp)
 {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; t0 < n_tx; t0 += stride) {
         const int64_t t = t0 + lane;
-        int32_t r = -1, degree = 0;
+        int32_t r = -1;
         if (t < n_tx) {
             r = cc_root_halving(parent, (int32_t)t);
             label[t] = r;
-            degree = (int32_t)(row_start[tx_row[t + 1]] - row_start[tx_row[t]]);
         }
         unsigned long long todo = __ballot(r >= 0);
         while (todo) {                              // (wave-uniform: one turn per distinct root among the lanes)
             const int leader = __ffsll((long long)todo) - 1;
             const int32_t r0 = __shfl(r, leader, 64);
-            const bool mine = r == r0;
-            const unsigned long long same = __ballot(mine);
-            int sum = mine ? degree : 0;
-            for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
-            if (lane == leader) {
-                atomicAdd(&comp[3 * (int64_t)r0], (int)__popcll(same));
-                atomicAdd(&comp[3 * (int64_t)r0 + 1], sum);
-            }
+            const unsigned long long same = __ballot(r == r0);
+            if (lane == leader) atomicAdd(&comp[3 * (int64_t)r0], (int)__popcll(same));
             todo &= ~same;
         }
     }
 }
 
+// comp[3 r + 1], comp[3 r + 2] of root r: the pairs and the classes of its component, both from the classes:
+// a component's pairs are the lengths of its classes (a transcript a class names twice is two pairs).
 // (a class without transcripts belongs nowhere; it is counted, and later listed, with transcript 0)
 __global__ void __launch_bounds__(256)
 cc_classes_kernel(const int64_t *cls_offset, const int32_t *ids, int64_t n_classes, const int32_t *label,
                   int32_t *comp)
 {
     // (classes are kept by smallest transcript id, so neighbouring lanes mostly name one component: a run
-    // of lanes with the same root adds its length once)
+    // of lanes with the same root adds its length and the pairs of its classes once -- a table that is one
+    // component adds once per wave, not once per class)
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t c0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x - lane; c0 < n_classes; c0 += stride) {
         const int64_t c = c0 + lane;
-        int32_t r = -1;
+        int32_t r = -1, pairs = 0;
         if (c < n_classes) {
-            const int64_t begin = cls_offset[c];
-            r = label[begin < cls_offset[c + 1] ? ids[begin] : 0];
+            const int64_t begin = cls_offset[c], end = cls_offset[c + 1];
+            r = label[begin < end ? ids[begin] : 0];
+            pairs = (int32_t)(end - begin);
+        }
+        int32_t incl = pairs;                       // inclusive prefix sums of the lengths over the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const int32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
         }
         const int32_t before = __shfl_up(r, 1, 64);
         const unsigned long long heads = __ballot(lane == 0 || before != r);
+        const unsigned long long later = lane == 63 ? 0ULL : heads >> (lane + 1);
+        const int run = later ? __ffsll((long long)later) : 64 - lane;      // (to the next head: a head's run)
+        const int32_t through = __shfl(incl, lane + run - 1, 64);           // the sums up to my run's last lane
         if (r >= 0 && ((heads >> lane) & 1ULL)) {
-            const unsigned long long later = lane == 63 ? 0ULL : heads >> (lane + 1);
-            const int run = later ? __ffsll((long long)later) : 64 - lane;
             atomicAdd(&comp[3 * (int64_t)r + 2], run);
+            if (through - incl + pairs) atomicAdd(&comp[3 * (int64_t)r + 1], through - incl + pairs);
         }
     }
 }
@@ -1079,37 +1109,13 @@ cls_place_kernel(const int64_t *__restrict__ cls_offset, const int32_t *__restri
 #define SKM_EM_CLASS_ORDER 1
 #endif
 
-// The order of a tile's members and the prefix sums of their pairs, by the tile's workgroup of 256 lanes in LDS.
-// In: n <= CAP members in any order, s_item[i] with the DISTINCT key s_key[i] and s_off[i] pairs.  Out: s_item in
-// ascending order of the keys, s_off[0 .. n] the exclusive prefix sums of the pairs in that order and their total.
-// A member's place is the number of keys below its own: n reads of LDS, all lanes the same word, per member.
+// Exclusive prefix sums, in place, of s_off[0 .. n) with their total in s_off[n], by the tile's workgroup of 256
+// lanes in LDS (n <= CAP).  Ends with a barrier.
 template <int CAP>
-__device__ __forceinline__ void tile_rank_and_scan(int n, const unsigned long long *s_key, int32_t *s_item, int32_t *s_off,
-                                                   int32_t *s_wave)
+__device__ __forceinline__ void tile_scan(int n, int32_t *s_off, int32_t *s_wave)
 {
-    constexpr int PER = CAP / 256 + 1;                // (256 PER > CAP: the scan below reaches entry n)
+    constexpr int PER = CAP / 256 + 1;                // (256 PER > CAP: the scan reaches entry n)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long key[PER];
-    int32_t item[PER], len[PER], rank[PER];
-#pragma unroll
-    for (int p = 0; p < PER; ++p) {
-        const int i = tid + p * 256;
-        const bool mine = i < n;
-        key[p] = mine ? s_key[i] : 0ULL;
-        item[p] = mine ? s_item[i] : 0;
-        len[p] = mine ? s_off[i] : 0;
-        rank[p] = 0;
-    }
-    for (int j = 0; j < n; ++j) {
-        const unsigned long long other = s_key[j];
-#pragma unroll
-        for (int p = 0; p < PER; ++p) rank[p] += other < key[p] ? 1 : 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < PER; ++p)
-        if (tid + p * 256 < n && rank[p] < n) { s_item[rank[p]] = item[p]; s_off[rank[p]] = len[p]; }
-    __syncthreads();
     int32_t v[PER], sum = 0;
 #pragma unroll
     for (int p = 0; p < PER; ++p) { const int e = tid * PER + p; v[p] = e < n ? s_off[e] : 0; sum += v[p]; }
@@ -1132,6 +1138,113 @@ __device__ __forceinline__ void tile_rank_and_scan(int n, const unsigned long lo
     __syncthreads();
 }
 
+// The order of a tile's transcripts and the prefix sums of their pairs, by the tile's workgroup of 256 lanes in LDS.
+// In: n <= 256 members in any order, s_item[i] with the DISTINCT key s_key[i] and s_off[i] pairs; s_key has room for
+// two words behind the keys.  Out: s_item in ascending order of the keys, s_off[0 .. n] the exclusive prefix sums of
+// the pairs in that order and their total, s_place[i] = the place of the member that stood at i.
+// A member's place is the number of keys below its own: the lanes read the keys two at a time, all the same words.
+template <int CAP>
+__device__ __forceinline__ void tile_rank_and_scan(int n, unsigned long long *s_key, int32_t *s_item, int32_t *s_off,
+                                                   int32_t *s_wave, uint16_t *s_place)
+{
+    static_assert(CAP <= 256, "one member a lane");
+    const int tid = threadIdx.x;
+    const bool mine = tid < n;
+    if (tid < 2) s_key[n + tid] = ~0ULL;              // (behind the keys: below no key)
+    __syncthreads();
+    const unsigned long long key = mine ? s_key[tid] : 0ULL;
+    const int32_t item = mine ? s_item[tid] : 0, len = mine ? s_off[tid] : 0;
+    int32_t rank = 0;
+    for (int j = 0; j < n; j += 2) {
+        const unsigned long long a = s_key[j], b = s_key[j + 1];
+        rank += (a < key ? 1 : 0) + (b < key ? 1 : 0);
+    }
+    __syncthreads();
+    if (mine && rank < n) { s_item[rank] = item; s_off[rank] = len; s_place[tid] = (uint16_t)rank; }
+    __syncthreads();
+    tile_scan<CAP>(n, s_off, s_wave);
+}
+
+// the largest k in [0, n) with s_off[k] <= p, for prefix sums with s_off[0] <= p < s_off[n]: the member that holds
+// pair p (members without pairs repeat an entry and are passed over)
+__device__ __forceinline__ int tile_find(const int32_t *s_off, int n, int p)
+{
+    int k = 0, above = n;
+    while (above - k > 1) {
+        const int mid = (k + above) >> 1;
+        if (s_off[mid] <= p) k = mid; else above = mid;
+    }
+    return k;
+}
+
+// A stable counting sort of n <= 256 PER items by a key of KEY_BITS bits, by the tile's workgroup: the four waves
+// own a quarter of the items each, in order; a wave counts its keys (s_hist[wave][key]), then -- with base(key),
+// the place of the key's first item -- takes 64 items at a time and ranks the lanes that share a key by ballot
+// against the wave's running place for the key, as radix_scatter_kernel does.  emit(item, place).
+// tile_sort_count ends with a barrier, after which the caller may form what base() reads and calls tile_sort_place
+// behind a barrier of its own; tile_sort_place ends with a barrier.
+template <int KEY_BITS, class Key>
+__device__ __forceinline__ void tile_sort_count(int n, Key key, uint32_t *s_hist)
+{
+    constexpr int KEYS = 1 << KEY_BITS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int d = tid; d < 4 * KEYS; d += 256) s_hist[d] = 0;
+    __syncthreads();
+    const int per = ((n + 255) >> 8) << 6, first = wave * per;
+    for (int c0 = 0; c0 < per; c0 += 64) {
+        const int p = first + c0 + lane;
+        if (p < n) atomicAdd(&s_hist[wave * KEYS + (key(p) & (KEYS - 1))], 1u);
+    }
+    __syncthreads();
+}
+
+template <int KEY_BITS, class Key, class Base, class Emit>
+__device__ __forceinline__ void tile_sort_place(int n, Key key, Base base, uint32_t *s_hist, Emit emit)
+{
+    constexpr int KEYS = 1 << KEY_BITS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int d = tid; d < KEYS; d += 256) {           // a wave's running place: behind the earlier waves' items of the key
+        uint32_t run = base(d);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const uint32_t m = s_hist[w * KEYS + d]; s_hist[w * KEYS + d] = run; run += m; }
+    }
+    __syncthreads();
+    const int per = ((n + 255) >> 8) << 6, first = wave * per;
+    for (int c0 = 0; c0 < per; c0 += 64) {            // (wave-uniform)
+        const int p = first + c0 + lane;
+        const bool valid = p < n;
+        const uint32_t k = valid ? (key(p) & (KEYS - 1)) : 0u;
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < KEY_BITS; ++b) {
+            const bool bit = (k >> b) & 1u;
+            const unsigned long long with = __ballot(valid && bit);
+            same &= bit ? with : ~with;
+        }
+        if (valid) {
+            const uint32_t before = (uint32_t)__popcll(same & ((1ULL << lane) - 1ULL));
+            emit(p, s_hist[wave * KEYS + k] + before);
+            if (before == 0) s_hist[wave * KEYS + k] += (uint32_t)__popcll(same);       // (the key's first lane)
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the next chunk reads the places this one moved
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+}
+
+// a pair of the tile while it is being moved to the transcript-major view: its transcript's place in the tile's
+// list above its class's place (16 bits hold both at the capacities in use)
+constexpr int bits_for(int n) { int b = 0; while ((1 << b) < n) ++b; return b; }      // the bits that hold 0 .. n - 1
+constexpr int TILE_TX_BITS = bits_for(EM_TILE_TX), TILE_CLS_BITS = bits_for(EM_TILE_CLASSES);
+static_assert(TILE_TX_BITS + TILE_CLS_BITS <= 32, "a tile's pair (transcript's place, class's place) is one word");
+using TilePair = std::conditional<(TILE_TX_BITS + TILE_CLS_BITS <= 16), uint16_t, uint32_t>::type;
+using TileSlot = std::conditional<(TILE_TX_BITS <= 8), uint8_t, uint16_t>::type;
+constexpr int TILE_TURN_BITS = 5;                     // the turn values of the two orders: 0 .. 31
+constexpr int TILE_SORT_KEYS = 1 << (TILE_TX_BITS > TILE_TURN_BITS ? TILE_TX_BITS : TILE_TURN_BITS);
+constexpr int TILE_KEY_WORDS = std::max(std::max((EM_TILE_CLASSES + 8) / 2, EM_TILE_TX + 2), (2 * EM_TILE_PAIRS + 7) / 8);
+constexpr int TILE_PAIR_TURNS = (EM_TILE_PAIRS + 255) / 256, TILE_CLS_TURNS = (EM_TILE_CLASSES + 255) / 256;
+static_assert(EM_TILE_TX <= 256, "tile_rank_and_scan takes one transcript a lane");
+
 // One workgroup per tile, a fixed grid striding over the *n_tiles tiles.  It reads the tile's transcripts and
 // classes as the two placement kernels left them, puts them into the order the chunk kernel wants -- the order the
 // two sorts by (tile, turns, index) gave before:
@@ -1141,25 +1254,49 @@ __device__ __forceinline__ void tile_rank_and_scan(int n, const unsigned long lo
 //   ascending: a lane of the class phase takes its tuple EM_TILE_CLASS_BATCH entries at a time and a wave loops as
 //   long as the longest of its 64 classes
 // -- and writes tx_list / cls_list back in place, tx_pair / cls_pair (the tile's first pair plus the prefix sums
-// of degrees / lengths), the tile-local names tx_local / cls_local, and with them the tile's two views: tuples in
-// tuple order, rows in the order of the global transposed view.  A class's place in the list is a label only, so
-// no sum of the EM changes with it.  The names pass through global memory inside the workgroup (written before a
-// barrier, read after it); no workgroup reads what another wrote in this launch.
+// of degrees / lengths) and the tile's two views: tuples in tuple order, rows in the order of the whole table's
+// transcript-major view (quant_rows_build), which this kernel does not read.  Everything comes from the tile's own
+// classes, and the ids of a tuple are fetched once:
+//   the classes are ranked by index, by counting (a class's rank is the number of indices below its own: the lanes
+//   read the indices eight at a time, all the same words), and from that order a stable counting sort over the 32
+//   turn values gives the list; both orders are kept (s_name: by index -> place in the list);
+//   a lane per pair of the class-major view, in list order, finds its class in the prefix sums, fetches the id,
+//   looks up the transcript's place as the placement kernel drew it (tx_local, written at the start), keeps that
+//   place in LDS (s_slot) and counts the pair into the transcript's degree -- a class that names a transcript twice
+//   counts twice.  A lane's pairs are fetched together, not one after the other;
+//   the transcripts are ordered by those degrees, which leaves s_map: place as drawn -> place in the list, and the
+//   class-major view is s_map of s_slot, written in whole runs;
+//   the rows are the tile's pairs taken in ascending internal class index and tuple position -- the order of the
+//   class-major view of the whole table, which its stable sort keeps within a transcript -- and moved by a stable
+//   counting sort on the transcript's place in the list (tile_sort_count, tile_sort_place).
+// A class's place in the list is a label only, so no sum of the EM changes with it.  The places as drawn pass
+// through global memory inside the workgroup (written before a barrier, read after it); no workgroup reads what
+// another wrote in this launch.
 // A tile whose sizes are not what the packing promised is left alone (em_local_chunk_kernel then raises its
 // fault word from the same sizes).
 __global__ void __launch_bounds__(256)
 tile_build_kernel(const int64_t *__restrict__ n_tiles, const int64_t *__restrict__ tile_tx, const int64_t *__restrict__ tile_cls,
                   const int64_t *__restrict__ tile_pair, int64_t n_tx, int64_t n_classes, int64_t n_ids,
-                  const int64_t *__restrict__ tx_row, const int64_t *__restrict__ row_start, const int32_t *__restrict__ tx_cls,
                   const int64_t *__restrict__ cls_offset, const int32_t *__restrict__ ids, int degree_bits, int length_bits,
                   int32_t *tx_list, int32_t *cls_list, int64_t *__restrict__ tx_pair, int64_t *__restrict__ cls_pair,
-                  int32_t *tx_local, int32_t *cls_local, uint16_t *__restrict__ out_cls_tx, uint16_t *__restrict__ out_tx_cls)
+                  int32_t *tx_local, uint16_t *__restrict__ out_cls_tx, uint16_t *__restrict__ out_tx_cls)
 {
-    __shared__ unsigned long long s_key[EM_TILE_CLASSES > EM_TILE_TX ? EM_TILE_CLASSES : EM_TILE_TX];
+    // the keys of the transcripts' ranking; before that the classes' indices, and at the end the rows before they leave
+    __shared__ __attribute__((aligned(16))) unsigned long long s_key[TILE_KEY_WORDS];
     __shared__ int32_t s_tx[EM_TILE_TX], s_tx_off[EM_TILE_TX + 1];
-    __shared__ int32_t s_cls[EM_TILE_CLASSES], s_cls_off[EM_TILE_CLASSES + 1];
+    __shared__ int32_t s_cls[EM_TILE_CLASSES], s_cls_off[EM_TILE_CLASSES + 1];       // the classes as listed
+    __shared__ int32_t s_icls[EM_TILE_CLASSES], s_ioff[EM_TILE_CLASSES + 1];         // the classes in ascending index
+    __shared__ int32_t s_src[EM_TILE_CLASSES];                   // as listed: a class's first id in ids
+    __shared__ uint16_t s_name[EM_TILE_CLASSES];                 // in ascending index: a class's place in the list
+    __shared__ TileSlot s_slot[EM_TILE_PAIRS];                   // class-major pairs: the transcript's place as drawn
+    __shared__ uint16_t s_map[EM_TILE_TX];                       // place as drawn -> place in the list
+    __shared__ TilePair s_pair[EM_TILE_PAIRS];                   // the pairs by ascending class index
+    __shared__ uint32_t s_hist[4 * TILE_SORT_KEYS];              // tile_sort_count / tile_sort_place
+    __shared__ uint32_t s_turn_base[1 << TILE_TURN_BITS];        // classes of fewer turns
     __shared__ int32_t s_wave[4];
-    const int tid = threadIdx.x;
+    uint32_t *const s_index = reinterpret_cast<uint32_t *>(s_key);
+    uint16_t *const s_rows = reinterpret_cast<uint16_t *>(s_key);
+    const int tid = threadIdx.x, lane = tid & 63;
     const int64_t tiles = *n_tiles;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int64_t tx0 = tile_tx[tile], cls0 = tile_cls[tile], pair0 = tile_pair[tile];
@@ -1167,57 +1304,140 @@ tile_build_kernel(const int64_t *__restrict__ n_tiles, const int64_t *__restrict
         if (tx0 < 0 || cls0 < 0 || pair0 < 0 || tx_n < 0 || cls_n < 0 || pair_n < 0 || tx_n > EM_TILE_TX ||
             cls_n > EM_TILE_CLASSES || pair_n > EM_TILE_PAIRS || tx0 + tx_n > n_tx || cls0 + cls_n > n_classes ||
             pair0 + pair_n > n_ids) continue;                       // (block-uniform)
-        const int n_t = (int)tx_n, n_c = (int)cls_n;
+        const int n_t = (int)tx_n, n_c = (int)cls_n, n_p = (int)pair_n;
+        // ---- the members as they were placed
         for (int i = tid; i < n_t; i += 256) {
             const int32_t t = tx_list[tx0 + i];
-            const int64_t degree = row_start[tx_row[t + 1]] - row_start[tx_row[t]];
-            const int64_t longest = (1 << degree_bits) - 1;
             s_tx[i] = t;
-            s_tx_off[i] = (int32_t)degree;
-            s_key[i] = (unsigned long long)(longest - min((degree + 7) >> 3, longest)) << 32 | (uint32_t)t;
+            s_tx_off[i] = 0;
+            if ((uint64_t)t < (uint64_t)n_tx) tx_local[t] = i;
+        }
+        int32_t cls[TILE_CLS_TURNS], len[TILE_CLS_TURNS];
+#pragma unroll
+        for (int u = 0; u < TILE_CLS_TURNS; ++u) {
+            const int k = tid + 256 * u;
+            cls[u] = k < n_c ? cls_list[cls0 + k] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < TILE_CLS_TURNS; ++u) {
+            const int k = tid + 256 * u;
+            len[u] = (uint64_t)cls[u] < (uint64_t)n_classes ? (int32_t)(cls_offset[cls[u] + 1] - cls_offset[cls[u]]) : 0;
+            if (k < n_c) s_index[k] = (uint32_t)cls[u];
+        }
+        if (tid < 8) s_index[n_c + tid] = 0xffffffffu;             // (behind the indices: below no index)
+        __syncthreads();
+        // ---- the classes in ascending index, then as listed
+        {
+            int32_t rank[TILE_CLS_TURNS];
+#pragma unroll
+            for (int u = 0; u < TILE_CLS_TURNS; ++u) rank[u] = 0;
+            for (int j = 0; j < n_c; j += 8) {
+                const uint4 a = *reinterpret_cast<const uint4 *>(s_index + j), b = *reinterpret_cast<const uint4 *>(s_index + j + 4);
+#pragma unroll
+                for (int u = 0; u < TILE_CLS_TURNS; ++u) {
+                    const uint32_t mine = (uint32_t)cls[u];
+                    rank[u] += (a.x < mine ? 1 : 0) + (a.y < mine ? 1 : 0) + (a.z < mine ? 1 : 0) + (a.w < mine ? 1 : 0) +
+                               (b.x < mine ? 1 : 0) + (b.y < mine ? 1 : 0) + (b.z < mine ? 1 : 0) + (b.w < mine ? 1 : 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < TILE_CLS_TURNS; ++u)
+                if (tid + 256 * u < n_c && rank[u] < n_c) { s_icls[rank[u]] = cls[u]; s_ioff[rank[u]] = len[u]; }
         }
         __syncthreads();
-        tile_rank_and_scan<EM_TILE_TX>(n_t, s_key, s_tx, s_tx_off, s_wave);
-        for (int i = tid; i < n_t; i += 256) {
-            const int32_t t = s_tx[i];
-            tx_list[tx0 + i] = t;
-            tx_pair[tx0 + i] = pair0 + s_tx_off[i];
-            tx_local[t] = i;
-        }
-        __syncthreads();                                            // (s_key is taken again)
-        for (int k = tid; k < n_c; k += 256) {
-            const int32_t c = cls_list[cls0 + k];
-            const int64_t length = cls_offset[c + 1] - cls_offset[c];
-            const int64_t longest = (1 << length_bits) - 1;
-            s_cls[k] = c;
-            s_cls_off[k] = (int32_t)length;
-            s_key[k] = (unsigned long long)(longest - min((length + EM_TILE_CLASS_BATCH - 1) / EM_TILE_CLASS_BATCH, longest)) << 32 |
-                       (uint32_t)c;
+        const int longest_c = (1 << length_bits) - 1;
+        auto turns_of = [&](int r) -> uint32_t {
+            return (uint32_t)(longest_c - min((s_ioff[r] + EM_TILE_CLASS_BATCH - 1) / EM_TILE_CLASS_BATCH, longest_c));
+        };
+        tile_sort_count<TILE_TURN_BITS>(n_c, turns_of, s_hist);
+        if (tid < 64) {                                             // classes of fewer turns: one wave scans the 32 values
+            constexpr int TURNS = 1 << TILE_TURN_BITS;
+            uint32_t m = 0;
+            if (tid < TURNS) for (int w = 0; w < 4; ++w) m += s_hist[w * TURNS + tid];
+            uint32_t incl = m;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += up;
+            }
+            if (tid < TURNS) s_turn_base[tid] = incl - m;
         }
         __syncthreads();
-        tile_rank_and_scan<EM_TILE_CLASSES>(n_c, s_key, s_cls, s_cls_off, s_wave);
+        tile_sort_place<TILE_TURN_BITS>(n_c, turns_of, [&](int d) { return s_turn_base[d]; }, s_hist,
+                                        [&](int r, uint32_t place) {
+                                            if (place < (uint32_t)n_c) {
+                                                s_name[r] = (uint16_t)place;
+                                                s_cls[place] = s_icls[r];
+                                                s_cls_off[place] = s_ioff[r];
+                                            }
+                                        });
+        tile_scan<EM_TILE_CLASSES>(n_c, s_cls_off, s_wave);
+        tile_scan<EM_TILE_CLASSES>(n_c, s_ioff, s_wave);
         for (int k = tid; k < n_c; k += 256) {
             const int32_t c = s_cls[k];
             cls_list[cls0 + k] = c;
             cls_pair[cls0 + k] = pair0 + s_cls_off[k];
-            cls_local[c] = k;
+            s_src[k] = s_cls_off[k + 1] > s_cls_off[k] && (uint64_t)c < (uint64_t)n_classes ? (int32_t)cls_offset[c] : 0;
         }
-        __syncthreads();                                            // (the names are in memory for this workgroup)
-        // (only what adds up to the tile's pairs is written: a place past them would be another tile's)
-        if (s_tx_off[n_t] == (int32_t)pair_n && s_cls_off[n_c] == (int32_t)pair_n) {
-            for (int k = tid; k < n_c; k += 256) {
-                const int64_t src = cls_offset[s_cls[k]], dst = pair0 + s_cls_off[k];
-                const int n = s_cls_off[k + 1] - s_cls_off[k];
-                for (int j = 0; j < n; ++j) out_cls_tx[dst + j] = (uint16_t)tx_local[ids[src + j]];
+        // (only lengths that add up to the tile's pairs are walked: a place past them would be another tile's)
+        const bool classes_fit = s_cls_off[n_c] == n_p && s_ioff[n_c] == n_p;       // (block-uniform: the entries stay)
+        __syncthreads();
+        // ---- the degrees: a lane per pair of the class-major view
+        if (classes_fit) {
+            int64_t at[TILE_PAIR_TURNS];
+            int32_t id[TILE_PAIR_TURNS];
+            uint32_t slot[TILE_PAIR_TURNS];
+#pragma unroll
+            for (int u = 0; u < TILE_PAIR_TURNS; ++u) {
+                const int p = tid + 256 * u;
+                at[u] = -1;
+                if (p < n_p) { const int k = tile_find(s_cls_off, n_c, p); at[u] = (int64_t)s_src[k] + (p - s_cls_off[k]); }
             }
-            // (eight lanes per transcript: a transcript has 22 pairs on average)
-            const int sub = tid & 7;
-            for (int i = tid >> 3; i < n_t; i += 32) {
-                const int32_t t = s_tx[i];
-                const int64_t src = row_start[tx_row[t]], dst = pair0 + s_tx_off[i];
-                const int n = s_tx_off[i + 1] - s_tx_off[i];
-                for (int j = sub; j < n; j += 8) out_tx_cls[dst + j] = (uint16_t)cls_local[tx_cls[src + j]];
+#pragma unroll
+            for (int u = 0; u < TILE_PAIR_TURNS; ++u) id[u] = at[u] >= 0 && at[u] < n_ids ? ids[at[u]] : -1;
+#pragma unroll
+            for (int u = 0; u < TILE_PAIR_TURNS; ++u) slot[u] = (uint64_t)id[u] < (uint64_t)n_tx ? (uint32_t)tx_local[id[u]] : 0xffffffffu;
+#pragma unroll
+            for (int u = 0; u < TILE_PAIR_TURNS; ++u) {
+                const int p = tid + 256 * u;
+                if (p >= n_p) continue;
+                const bool listed = slot[u] < (uint32_t)n_t;
+                if (listed) atomicAdd(&s_tx_off[slot[u]], 1);
+                s_slot[p] = (TileSlot)(listed ? slot[u] : 0u);
             }
+        }
+        __syncthreads();                                            // (the degrees stand; s_key is taken again)
+        // ---- the transcripts as listed
+        for (int i = tid; i < n_t; i += 256) {
+            const int64_t degree = s_tx_off[i];
+            const int64_t longest = (1 << degree_bits) - 1;
+            s_key[i] = (unsigned long long)(longest - min((degree + 7) >> 3, longest)) << 32 | (uint32_t)s_tx[i];
+        }
+        __syncthreads();
+        tile_rank_and_scan<EM_TILE_TX>(n_t, s_key, s_tx, s_tx_off, s_wave, s_map);
+        for (int i = tid; i < n_t; i += 256) {
+            tx_list[tx0 + i] = s_tx[i];
+            tx_pair[tx0 + i] = pair0 + s_tx_off[i];
+        }
+        // ---- the two views
+        if (classes_fit && s_tx_off[n_t] == n_p) {                  // (block-uniform)
+#pragma unroll
+            for (int u = 0; u < TILE_PAIR_TURNS; ++u) {
+                const int p = tid + 256 * u;
+                if (p >= n_p) continue;
+                out_cls_tx[pair0 + p] = s_map[s_slot[p]];
+                // (pair p of the classes in ascending index: of the class at r, listed at k)
+                const int r = tile_find(s_ioff, n_c, p), k = min((int)s_name[r], n_c - 1);
+                const int from = min(s_cls_off[k] + (p - s_ioff[r]), n_p - 1);
+                s_pair[p] = (TilePair)(((uint32_t)s_map[s_slot[from]] & ((1u << TILE_TX_BITS) - 1u)) << TILE_CLS_BITS | (uint32_t)k);
+            }
+            __syncthreads();
+            auto place_of = [&](int p) -> uint32_t { return (uint32_t)s_pair[p] >> TILE_CLS_BITS; };
+            tile_sort_count<TILE_TX_BITS>(n_p, place_of, s_hist);
+            tile_sort_place<TILE_TX_BITS>(n_p, place_of, [&](int d) { return d < n_t ? (uint32_t)s_tx_off[d] : (uint32_t)n_p; }, s_hist,
+                                          [&](int p, uint32_t place) {
+                                              if (place < (uint32_t)n_p) s_rows[place] = (uint16_t)(s_pair[p] & ((1u << TILE_CLS_BITS) - 1u));
+                                          });
+            for (int j = tid; j < n_p; j += 256) out_tx_cls[pair0 + j] = s_rows[j];
         }
         __syncthreads();                                            // (the next tile takes the arrays again)
     }
@@ -1273,15 +1493,14 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
     QB_ALLOC(seg_sizes, int64_t, 4 * n_segments); QB_ALLOC(seg_base, int64_t, 4 * (n_segments + 1));
     QB_ALLOC(oversize, unsigned long long, 1);
     QB_ALLOC(tile_pair, int64_t, T + 2);
-    QB_ALLOC(tx_local, int32_t, T); QB_ALLOC(cls_local, int32_t, C);
+    QB_ALLOC(tx_local, int32_t, T);
     int32_t *cursor_tx = comp + 3 * T, *cursor_cls = cursor_tx + (T + 1);
     const int64_t *n_tiles = seg_base + n_segments;
     QB_TRY(hipMemsetAsync(comp, 0, (3 * T + 2 * (T + 1)) * sizeof(int32_t), stream));
     QB_TRY(hipMemsetAsync(oversize, 0, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(iota_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, T);
     hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, parent);
-    hipLaunchKernelGGL(cc_label_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, q.tx_row, q.row_start, T,
-                       q.tx_label, comp);
+    hipLaunchKernelGGL(cc_label_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, parent, T, q.tx_label, comp);
     hipLaunchKernelGGL(cc_classes_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C,
                        q.tx_label, comp);
     // the tiles' sizes are known from the components alone: their starts in the lists before anything is listed
@@ -1303,9 +1522,8 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
     hipLaunchKernelGGL(cls_place_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_offset, q.ids, C, T, q.tx_tile,
                        q.tile_cls, cursor_cls, q.cls_tile, q.cls_list);
     hipLaunchKernelGGL(tile_build_kernel, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(T, 1), TILE_BUILD_BLOCKS)), dim3(256),
-                       0, stream, n_tiles, q.tile_tx, q.tile_cls, tile_pair, T, C, M, q.tx_row, q.row_start, q.tx_cls,
-                       q.cls_offset, q.ids, degree_bits, length_bits, q.tx_list, q.cls_list, q.tx_pair, q.cls_pair, tx_local,
-                       cls_local, q.tile_cls_tx, q.tile_tx_cls);
+                       0, stream, n_tiles, q.tile_tx, q.tile_cls, tile_pair, T, C, M, q.cls_offset, q.ids, degree_bits,
+                       length_bits, q.tx_list, q.cls_list, q.tx_pair, q.cls_pair, tx_local, q.tile_cls_tx, q.tile_tx_cls);
     hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, stream, q.tile_cls, q.cls_pair, n_tiles, q.tile_order);
     QB_TRY(hipMemcpyAsync(&q.tile_info[0], n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     QB_TRY(hipMemcpyAsync(&q.tile_info[1], oversize, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
@@ -1317,31 +1535,44 @@ int build_tiles(Scratch &scratch, QuantBuild &q)
 // The whole setup as one asynchronous pipeline on `stream`: classes from the mapper's table (when
 // `table` is given) in locality order with perm[] back to first-seen order -- ranked by bitmap
 // when the first-seen values allow it, by two sorts otherwise -- or the caller's classes
-// reordered; then the transcript-major rows.  Returns the number of rows or a negative code.
-int64_t quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipStream_t stream)
+// reordered; then the component tiles, from the classes alone.  The host looks once, when all of it
+// has been queued and the stream has drained: a ranked attempt that found two classes with one
+// first-seen value is then thrown away and the sorting path runs.  Returns 0 or a negative code.
+int quant_setup(const ClassTable *table, QuantBuild &q, int32_t *perm, hipStream_t stream)
 {
     const bool can_rank = table && q.first_seen_bound > 0 && q.first_seen_bound <= RANK_BITMAP_MAX_UNITS;
     for (int attempt = can_rank ? 0 : 1; attempt < 2; ++attempt) {
-        int64_t n_rows = -1;
+        unsigned int shared_first_seen = 0;
         {
             Scratch scratch(stream);
+            const unsigned int *flag = nullptr;
             if (attempt == 0) {
-                const int rc = build_from_table_ranked(scratch, *table, q, perm);
-                if (rc == 1) continue;
-                if (rc) return -1;
+                if (build_from_table_ranked(scratch, *table, q, perm, &flag)) return -1;
             } else {
                 if (table && build_from_table(scratch, *table, q)) return -1;
                 if (localize(scratch, q, perm)) return -1;
             }
-            if (transpose(scratch, q)) return -1;
             if (q.tile_tx && build_tiles(scratch, q)) return -1;
             QB_TRY(hipGetLastError());
-            QB_TRY(hipMemcpyAsync(&n_rows, q.tx_row + q.n_tx, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            if (flag) QB_TRY(hipMemcpyAsync(&shared_first_seen, flag, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
         }                              // ~Scratch: the synchronisation
-        if (n_rows > q.n_rows_cap) return -3;
-        return n_rows;
+        if (shared_first_seen) continue;
+        return 0;
     }
     return -1;
+}
+
+int64_t quant_rows_build(const QuantBuild &q, const QuantRows &rows, hipStream_t stream)
+{
+    int64_t n_rows = -1;
+    {
+        Scratch scratch(stream);
+        if (transpose(scratch, q, rows)) return -1;
+        QB_TRY(hipGetLastError());
+        QB_TRY(hipMemcpyAsync(&n_rows, rows.tx_row + q.n_tx, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    }                                  // ~Scratch: the synchronisation
+    if (n_rows > rows.n_rows_cap) return -3;
+    return n_rows;
 }
 
 // ---- the residual: the components above the tile capacity as an EM problem of their own ---------
@@ -1420,20 +1651,20 @@ residual_fill_tx_kernel(const int32_t *tx_tile, int64_t n_tx, const int64_t *tx_
 
 }  // namespace
 
-int quant_residual_count(const QuantBuild &q, int64_t counts[3], hipStream_t stream)
+int quant_residual_count(const QuantBuild &q, const QuantRows &rows_in, int64_t counts[3], hipStream_t stream)
 {
     Scratch scratch(stream);
     QB_ALLOC(sums, unsigned long long, 3);
     QB_TRY(hipMemsetAsync(sums, 0, 3 * sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(residual_count_kernel, dim3(blocks_for(std::max(q.n_classes, q.n_tx))), dim3(256), 0, stream,
-                       q.cls_tile, q.cls_offset, q.n_classes, q.tx_tile, q.tx_row, q.n_tx, sums);
+                       q.cls_tile, q.cls_offset, q.n_classes, q.tx_tile, rows_in.tx_row, q.n_tx, sums);
     QB_TRY(hipGetLastError());
     QB_TRY(hipMemcpyAsync(counts, sums, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     QB_TRY(hipStreamSynchronize(stream));
     return 0;
 }
 
-int quant_residual_build(const QuantBuild &q, QuantResidual &r, hipStream_t stream)
+int quant_residual_build(const QuantBuild &q, const QuantRows &rows_in, QuantResidual &r, hipStream_t stream)
 {
     Scratch scratch(stream);
     const int64_t C = q.n_classes, T = q.n_tx;
@@ -1446,14 +1677,14 @@ int quant_residual_build(const QuantBuild &q, QuantResidual &r, hipStream_t stre
     if (exclusive_scan_with_total(scratch, len, new_offset, C)) return -1;
     hipLaunchKernelGGL(residual_fill_cls_kernel, dim3(blocks_for(C)), dim3(256), 0, stream, q.cls_tile, C, (int32_t)T, rank,
                        q.cls_offset, q.ids, new_offset, r.cls_offset, r.ids, r.cls_src, r.n_classes);
-    hipLaunchKernelGGL(residual_tx_sizes_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_tile, q.tx_row,
-                       q.row_start, T, rows, len);
+    hipLaunchKernelGGL(residual_tx_sizes_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, q.tx_tile, rows_in.tx_row,
+                       rows_in.row_start, T, rows, len);
     if (exclusive_scan_with_total(scratch, rows, r.tx_row, T)) return -1;
     if (exclusive_scan_with_total(scratch, len, new_pair, T)) return -1;
     hipLaunchKernelGGL(row_fill_kernel, dim3(blocks_for(T)), dim3(256), 0, stream, new_pair, r.tx_row, T, r.n_ids,
                        r.row_start, r.row_tx);
-    hipLaunchKernelGGL(residual_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_tile, T, q.tx_row,
-                       q.row_start, q.tx_cls, rank, new_pair, r.tx_cls);
+    hipLaunchKernelGGL(residual_fill_tx_kernel, dim3(blocks_for(8 * T)), dim3(256), 0, stream, q.tx_tile, T, rows_in.tx_row,
+                       rows_in.row_start, rows_in.tx_cls, rank, new_pair, r.tx_cls);
     QB_TRY(hipGetLastError());
     return 0;
 }

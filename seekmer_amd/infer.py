@@ -1279,6 +1279,12 @@ class _QuantHandle:
             _native.ptr(tile, _native.c_i32p), _native.ptr(class_tile, _native.c_i32p)))
         return info, label, tile, class_tile[:self.n_classes]
 
+    def rows_built(self):
+        """Whether the handle holds the whole table's transcript-major rows (skm_quant_rows_built)."""
+        built = ctypes.c_int()
+        _native.check(_native.hip().skm_quant_rows_built(self.handle, ctypes.byref(built)))
+        return bool(built.value)
+
     def set_counts(self, counts):
         counts = numpy.ascontiguousarray(counts, dtype='f8')
         _native.check(_native.hip().skm_quant_set_counts(self.handle,
