@@ -649,6 +649,46 @@ int skm_gene_matrix_from_molecule_classes(int device, int64_t n_classes, const i
                                           const int32_t *mol_class, const uint32_t *mol_umi, int64_t n_samples, int64_t n_tx,
                                           int64_t n_genes, const int32_t *tx_gene, skm_gene_matrix **out);
 int skm_gene_matrix_read_tally(const skm_gene_matrix *matrix, int64_t *tally /*[n_samples][5]*/);
+/* Distributed molecules ("Distributed molecules"): the groups and the intersection I of "Resolved
+ * molecules", with the multi-gene groups shared out among their genes by a small EM per sample.  -1 ("no gene") is the
+ * element n_genes, the sink.  A group's list is the elements of I, ascending:
+ *   one element g < n_genes   resolved      | the group adds 1 to that row of its sample
+ *   the sink alone            unnamed       |
+ *   2 to 16 elements          distributed: a set of the sample's EM
+ *   more than 16              wide          | tallied only
+ *   none                      collision     |
+ * A sample's rows are the distinct elements of its lists, u[r] the lists of one element that name row r.  From
+ * x[r] = u[r] + the sum of 1 / len(S) over the sets S that hold r, a step is d[j] = the sum of x over set j and
+ * x'[r] = u[r] + the sum of x[r] / d[j] over the sets that hold r; the sample is done when no row with x' > 0.001 has
+ * changed by more than 1 % of x', or after 1000 steps (capped).  All sums are IEEE doubles in one fixed order
+ * (DESIGN.md states it), so the result is the plain-Python reference's bit for bit.  Entry (sample, g) = x[r] for
+ * every row with g < n_genes and x[r] >= 0.001; nothing is renormalised; the sink row's x is the sample's to_unnamed.
+ * Parity with alevin or bustools is not claimed.
+ * The handle is a skm_gene_matrix whose data are doubles: skm_gene_matrix_read_weights reads them, and
+ * skm_gene_matrix_read with a non-NULL data is SKM_ERR_STATE on it (indptr, indices and other = { wide + collision,
+ * unnamed } are read as ever).  skm_gene_matrix_read_em gives tally[s] = { resolved, distributed, wide, unnamed,
+ * collision, rows, steps, capped } -- the first five add up to the sample's distinct UMIs -- and to_unnamed[s].
+ * Both are SKM_ERR_STATE on a handle that any other call made, as skm_gene_matrix_read_tally is on this one.
+ * skm_sample_set_distributed_matrix waits and locks as skm_sample_set_resolved_matrix does and has its refusals and
+ * limits (checked before anything is allocated); 2^31 - 1 list elements at most.  Device memory while it runs: that
+ * call's per slot and per molecule, then 96 bytes per group, 52 per list element, 36 per row, 16 per set and 32 per sample.
+ * skm_gene_matrix_from_molecule_sets is skm_gene_matrix_from_molecule_classes with these steps and max_steps >= 1 in
+ * the place of 1000.  skm_gene_em_cells runs the EM alone on host arrays: cell c has the rows cell_row_start[c] ..
+ * cell_row_start[c + 1] - 1 with u[] >= 0 and the sets cell_set_start[c] .. cell_set_start[c + 1] - 1, set j the
+ * cell-local rows set_rows[set_start[j] .. set_start[j + 1]); x_out[n_rows], steps_out[n_cells], capped_out[n_cells].
+ * SKM_ERR_ARG for a row outside its cell, a set of fewer than 2 or more than 16 rows, rows that do not ascend inside
+ * a set, offsets that do not begin at 0 or descend, a negative u and max_steps < 1.  On any failure *out is NULL. */
+int skm_sample_set_distributed_matrix(skm_sample_set *set, int64_t n_tx, int64_t n_genes, const int32_t *tx_gene,
+                                      skm_gene_matrix **out);
+int skm_gene_matrix_from_molecule_sets(int device, int64_t n_classes, const int64_t *class_offsets,
+                                       const int32_t *class_targets, const int32_t *class_sample, int64_t n_molecules,
+                                       const int32_t *mol_class, const uint32_t *mol_umi, int64_t n_samples, int64_t n_tx,
+                                       int64_t n_genes, const int32_t *tx_gene, int64_t max_steps, skm_gene_matrix **out);
+int skm_gene_em_cells(int device, int64_t n_cells, const int64_t *cell_row_start, const int64_t *u,
+                      const int64_t *cell_set_start, const int64_t *set_start, const int32_t *set_rows, int64_t max_steps,
+                      double *x_out, int64_t *steps_out, int64_t *capped_out);
+int skm_gene_matrix_read_weights(const skm_gene_matrix *matrix, double *data /*[nnz]*/);
+int skm_gene_matrix_read_em(const skm_gene_matrix *matrix, int64_t *tally /*[n_samples][8]*/, double *to_unnamed /*[n_samples]*/);
 
 /* ---------------------------------------------------------------- cell barcodes
  * ("Cell barcodes".)  A pooled run -- one barcode read per unit beside the cDNA reads --

@@ -168,6 +168,13 @@ HIP_SYMBOLS = {
     'skm_gene_matrix_from_molecule_classes': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_i32p, c_i32p, c_i64, c_i32p, c_u32p,
                                                              c_i64, c_i64, c_i64, c_i32p, c_void_pp]),
     'skm_gene_matrix_read_tally': (ctypes.c_int, [ctypes.c_void_p, c_i64p]),
+    'skm_sample_set_distributed_matrix': (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32p, c_void_pp]),
+    'skm_gene_matrix_from_molecule_sets': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_i32p, c_i32p, c_i64, c_i32p, c_u32p,
+                                                          c_i64, c_i64, c_i64, c_i32p, c_i64, c_void_pp]),
+    'skm_gene_em_cells': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64p, c_i64p, c_i64p, c_i64p, c_i32p, c_i64, c_f64p, c_i64p,
+                                         c_i64p]),
+    'skm_gene_matrix_read_weights': (ctypes.c_int, [ctypes.c_void_p, c_f64p]),
+    'skm_gene_matrix_read_em': (ctypes.c_int, [ctypes.c_void_p, c_i64p, c_f64p]),
     'skm_barcodes_create':(ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, c_i64, ctypes.c_int, c_void_pp]),
     'skm_barcodes_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'skm_barcodes_assign': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PackedReads), ctypes.c_int, ctypes.c_int,

@@ -809,6 +809,78 @@ void launch_molecule_resolve(const GeneClasses &t, const unsigned long long *key
 // other[s] = { multi-gene + collision, unnamed } of tally[s]
 void launch_resolve_other(const unsigned long long *tally, int64_t n_samples, unsigned long long *other, hipStream_t stream);
 
+// ---- distributed molecules (skm_molecule_em.hip; DESIGN.md section 4, "Distributed molecules"): multi-gene groups
+// shared out among their genes by an EM per cell
+constexpr int GENE_SET_MAX = 16;                  // elements of a set at most; a group with more is wide
+constexpr int GENE_EM_LDS_ROWS = 4096;            // rows of a cell whose x lives in LDS (32 KiB)
+constexpr double GENE_EM_FLOOR = 0.001;           // molecules: the stopping rule's floor and the matrix's cut
+constexpr double GENE_EM_TOL = 0.01;              // the largest relative change at which a cell is done
+enum { GENE_EM_RESOLVED = 0, GENE_EM_DISTRIBUTED = 1, GENE_EM_WIDE = 2, GENE_EM_UNNAMED = 3, GENE_EM_COLLISION = 4,
+       GENE_EM_ROWS = 5, GENE_EM_STEPS = 6, GENE_EM_CAPPED = 7, GENE_EM_TALLY = 8 };      // the words of a sample's tally
+// launch_molecule_resolve's walk with every group's element list: stage[g][GENE_SET_MAX] holds group g's group_len[g]
+// elements ascending (-1 as n_genes; 0 elements: wide or collision), group_cell[g] its sample, and
+// tally[sample][GENE_EM_TALLY] (zeroed by the caller) += 1 in one of its first five words.  error[] as there.
+void launch_molecule_sets(const GeneClasses &t, const unsigned long long *keys, const uint32_t *classes, const int64_t *runs,
+                          int64_t n, int64_t n_groups, const int32_t *tx_gene, int64_t n_tx, int64_t n_genes, int64_t n_samples,
+                          int32_t *stage, int32_t *group_len, int32_t *group_cell, unsigned long long *tally, int *error,
+                          hipStream_t stream);
+// per group: its elements, 1 where it is a set (2 elements or more), its elements where it is a set -- to be scanned
+void launch_gene_sets_sizes(const int32_t *group_len, int64_t n_groups, int64_t *elements, int64_t *is_set,
+                            int64_t *set_elements, hipStream_t stream);
+// el_start / set_of / set_place [n_groups + 1]: the scans of those three.  Element e = el_start[g] + k gets el_key[e] =
+// cell << 32 | element, el_number[e] = e, el_group[e] = g; set_start[n_sets + 1] the sets' places in the set-major lists.
+void launch_gene_sets_elements(const int32_t *stage, const int32_t *group_len, const int32_t *group_cell, int64_t n_groups,
+                               const int64_t *el_start, const int64_t *set_of, const int64_t *set_place, int64_t n_elements,
+                               int64_t n_sets, unsigned long long *el_key, int32_t *el_number, int32_t *el_group,
+                               int64_t *set_start, int *error, hipStream_t stream);
+// heads[i] = 1 where sorted key i differs from key i - 1: a row begins
+void launch_gene_rows_heads(const unsigned long long *keys, int64_t n, int64_t *heads, hipStream_t stream);
+struct GeneRows {                 // what the passes over the sorted elements read and write (n > 0)
+    const unsigned long long *keys;                   // [n] cell << 32 | element, sorted
+    const int32_t *order;                             // [n] the element's number before the sort
+    const int64_t *runs;                              // [n + 1] heads before place i; runs[n] = n_rows
+    const int32_t *el_group, *group_len;              // [n], [n_groups]
+    const int64_t *el_start, *set_of, *set_start;     // [n_groups + 1] twice, [n_sets + 1]
+    int64_t n, n_groups, n_sets, n_rows, n_cells, n_set_elements;
+    int64_t *cell_row_start;                          // [n_cells + 1]
+    int32_t *row_element;                             // [n_rows]
+    unsigned long long *u;                            // [n_rows] zeroed: the lists of one element per row
+    int64_t *in_set;                                  // [n] 1 where the element belongs to a set
+    int32_t *set_rows;                                // [n_set_elements] set-major: the rows of a set, ascending
+    int *error;                                       // [2], as above
+};
+void launch_gene_rows(const GeneRows &p, hipStream_t stream);
+// place[n + 1] the scan of p.in_set: row_set_start[n_rows + 1], row_sets[n_set_elements] (a row's sets, ascending)
+void launch_gene_rows_transpose(const GeneRows &p, const int64_t *place, int64_t *row_set_start, int32_t *row_sets,
+                                hipStream_t stream);
+// sets[s] = tally[s][GENE_EM_DISTRIBUTED]: scanned, a cell's first set
+void launch_gene_cell_sets(const unsigned long long *tally, int64_t n_cells, int64_t *sets, hipStream_t stream);
+struct GeneEm {                   // the cells of one gene_em_kernel launch, a block each; rows and sets numbered over all cells
+    int64_t n_cells, n_rows, n_sets, n_set_elements;
+    const int64_t *cell_row_start, *cell_set_start;   // [n_cells + 1]
+    const unsigned long long *u;                      // [n_rows]
+    const int64_t *set_start;                         // [n_sets + 1]
+    const int32_t *set_rows;                          // [n_set_elements] rows of the set's cell, ascending
+    const int64_t *row_set_start;                     // [n_rows + 1]
+    const int32_t *row_sets;                          // [n_set_elements] sets of the row's cell, ascending
+    double *d;                                        // [n_sets]
+    double *x;                                        // [n_rows] out
+    int64_t *steps, *capped;                          // [n_cells] out
+    int64_t max_steps;                                // >= 1
+    int64_t lds_rows;                                 // cells of more rows work in x[] itself (<= GENE_EM_LDS_ROWS counts)
+    int *error;                                       // [2]: error[1] = SKM_ERR_STATE for a range, row or set out of bounds
+};
+void launch_gene_em(const GeneEm &p, hipStream_t stream);
+// keep[r] = 1 where row r names a gene and x[r] >= GENE_EM_FLOOR
+void launch_gene_em_keep(const double *x, const int32_t *row_element, int64_t n_rows, int64_t n_genes, int64_t *keep,
+                         hipStream_t stream);
+// place[n_rows + 1] the scan of keep[] with its total nnz: indptr[n_cells + 1], indices[nnz], data[nnz]; per cell the
+// tally's rows, steps and capped words, to_unnamed (the sink row's x, 0.0 without one) and other = { wide + collision, unnamed }
+void launch_gene_em_fill(const double *x, const int32_t *row_element, const int64_t *place, const int64_t *cell_row_start,
+                         const int64_t *steps, const int64_t *capped, int64_t n_rows, int64_t nnz, int64_t n_genes,
+                         int64_t n_cells, int64_t *indptr, int32_t *indices, double *data, unsigned long long *tally,
+                         double *to_unnamed, unsigned long long *other, hipStream_t stream);
+
 // ---- cell discovery (skm_census.hip; DESIGN.md section 4, "Cell discovery")
 constexpr unsigned long long CENSUS_EMPTY = ~0ULL;    // the key of an empty slot; its one preimage (32 T) is counted in ctl[]
 struct alignas(16) CensusSlot {   // 16 B: one distinct barcode

@@ -401,6 +401,48 @@ def output_resolved_matrix(output_path, n_genes, names, indptr, indices, data, t
                                                           multi, unnamed, collisions, indptr[i + 1] - indptr[i]))
 
 
+DISTRIBUTED_MATRIX_COMMENT = ('% infer-many --distribute-molecules: rows are genes (genes.tsv), columns are cells/samples (cells.tsv); '
+                              'a value is the cell\'s UMIs inside that gene plus its share of the multi-gene UMIs, in molecules')
+DISTRIBUTED_TALLY = ('resolved', 'distributed', 'wide', 'unnamed', 'collisions', 'rows', 'steps', 'capped')
+
+
+def output_distributed_matrix(output_path, n_genes, names, indptr, indices, data, tally, to_unnamed):
+    """What `infer-many --distribute-molecules` adds to output/counts/: molecules.em.mtx (a real MatrixMarket file in the
+    layout and order of matrix.mtx under a comment line of its own, every value written with repr(float): the double
+    comes back bit for bit), molecules.em.npz (the keys of matrix.npz, data as float64) and molecules.em.tsv -- per
+    sample: name, distinct UMIs, resolved, distributed, wide, unnamed, collisions, rows and steps of its EM, capped 0/1,
+    genes with a weight, to_unnamed (what the EM gave to "no gene"); columns 3 to 7 add up to column 2.
+    (indptr, indices, data) is the CSR over samples of SampleSet.gene_distributed_matrix; tally[n_samples, 8] in the
+    order of DISTRIBUTED_TALLY."""
+    indptr = numpy.asarray(indptr, dtype=numpy.int64)
+    indices = numpy.asarray(indices, dtype=numpy.int32)
+    data = numpy.asarray(data, dtype=numpy.float64)
+    tally = numpy.asarray(tally, dtype=numpy.int64).reshape(-1, len(DISTRIBUTED_TALLY))
+    to_unnamed = numpy.asarray(to_unnamed, dtype=numpy.float64).reshape(-1)
+    n_samples = len(names)
+    if (indptr.shape != (n_samples + 1,) or indices.shape != data.shape or indptr[-1] != data.size or len(tally) != n_samples
+            or len(to_unnamed) != n_samples):
+        raise ValueError('a distributed matrix of %d samples needs indptr[%d], as many indices as data, tally[%d, %d] and '
+                         'to_unnamed[%d]' % (n_samples, n_samples + 1, n_samples, len(DISTRIBUTED_TALLY), n_samples))
+    counts_path = output_path / 'counts'
+    counts_path.mkdir(exist_ok=True)
+    sample_of = numpy.repeat(numpy.arange(n_samples, dtype=numpy.int64), numpy.diff(indptr))
+    with (counts_path / 'molecules.em.mtx').open('w') as f:
+        f.write('%%MatrixMarket matrix coordinate real general\n')
+        f.write(DISTRIBUTED_MATRIX_COMMENT + '\n')
+        f.write('%d %d %d\n' % (n_genes, n_samples, data.size))
+        for begin in range(0, data.size, 1 << 16):
+            chunk = slice(begin, begin + (1 << 16))
+            f.writelines('%d %d %r\n' % entry for entry in zip((indices[chunk].astype(numpy.int64) + 1).tolist(),
+                                                               (sample_of[chunk] + 1).tolist(), data[chunk].tolist()))
+    _write_csr_npz(counts_path / 'molecules.em.npz', n_samples, n_genes, indptr, indices, data)
+    with (counts_path / 'molecules.em.tsv').open('w') as f:
+        for i, name in enumerate(names):
+            words = [int(v) for v in tally[i]]
+            f.write('%s\t%d\t%s\t%d\t%r\n' % (name, sum(words[:5]), '\t'.join('%d' % v for v in words),
+                                               indptr[i + 1] - indptr[i], float(to_unnamed[i])))
+
+
 MATRIX_ONLY_NEEDS_EM = ('--matrix-only stops before the EM: %s needs the EM (take --count-matrix, which writes the '
                         'count matrix beside the full run)')
 
@@ -589,7 +631,8 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
              strand=None, names=None, length_model=None, bias=False, genes=False, gene_map=None, barcodes=None,
              barcode_file=None, barcode_start=0, barcode_mismatches=1, min_units=1, umi_start=0, umi_length=0,
              discover_cells=None, barcode_length=None, discover_keep_neighbours=False, umi_mismatches=0,
-             count_matrix=False, matrix_only=False, count_molecules=False, resolve_molecules=False, **__):
+             count_matrix=False, matrix_only=False, count_molecules=False, resolve_molecules=False,
+             distribute_molecules=False, **__):
     """`infer-many`: run() for many samples against ONE resident index.  output/<name>/ holds exactly
     the files `infer` writes for that sample alone (same bits but for the start time and the call), and
     output/samples.tsv one line per sample: name, units, aligned units, harmonic mean fragment length.
@@ -678,7 +721,14 @@ def run_many(index_path, output_path, fastq_paths, job_count, single_ended, boot
     (output_resolved_matrix): the classes among a cell's live molecules with one UMI form a group, and the
     intersection of their gene sets names the group's gene -- or makes it multi-gene, unnamed or a collision, which are
     tallied only (SampleSet.gene_resolved_matrix; DESIGN.md section 4, "Resolved molecules").  The matrix has a
-    pattern of its own; every other file of the run, molecules.mtx among them, is what it is without the option."""
+    pattern of its own; every other file of the run, molecules.mtx among them, is what it is without the option.
+
+    distribute_molecules: --distribute-molecules, which implies resolve_molecules (and so the refusal without
+    umi_length).  counts/ gains molecules.em.mtx, molecules.em.npz and molecules.em.tsv (output_distributed_matrix): the
+    groups that resolve_molecules tallies as multi-gene are shared out among the genes of their intersection, 16 at
+    most, by a small EM per cell (SampleSet.gene_distributed_matrix; DESIGN.md section 4, "Distributed molecules");
+    values are doubles, in molecules.  Every other file of the run is what it is without the option.  Parity with
+    alevin or bustools is not claimed."""
     # what the phases below share: every option under its own name (locals(): this stays the first statement, so that a
     # new option needs no second list), and with them the index, the genes and the trace's clock
     job = types.SimpleNamespace(**locals(), paired=not single_ended, pooled=barcodes is not None or discover_cells is not None,
@@ -725,11 +775,14 @@ class _Sample:
     gene_unique_counts (genes); matrix_row, (gene indices, counts) of the count matrix, and the matrix_other pair that
     goes with it; molecule_row, the molecule matrix's counts for the genes of matrix_row (count_molecules);
     resolved_row, (gene indices, counts) of the resolved matrix, and the resolved_tally that goes with it (resolve_molecules);
+    distributed_row, (gene indices, weights) of the distributed matrix, with its distributed_tally and to_unnamed
+    (distribute_molecules);
     set_estimate, the first-pass TPM where the set or the shared bias pass made one; corrected, (summary, TPM) of the
     set's shared bias pass; estimate, the TPM it was written with.  What was not made is None.  Host values only: a
     record never holds the SampleSet or a MapResult, whose device memory ends where run_many says."""
     __slots__ = ('name', 'group', 'in_set', 'summary', 'sizes', 'mean', 'observed', 'gene_counts', 'matrix_row',
-                 'matrix_other', 'molecule_row', 'resolved_row', 'resolved_tally', 'set_estimate', 'corrected', 'estimate')
+                 'matrix_other', 'molecule_row', 'resolved_row', 'resolved_tally', 'distributed_row', 'distributed_tally', 'to_unnamed',
+                 'set_estimate', 'corrected', 'estimate')
 
     def __init__(self, name, group, in_set):
         self.name, self.group, self.in_set = name, group, in_set
@@ -753,6 +806,7 @@ def _check_many_options(job, names):
     mapper.strand_mode(job.strand)
     job.length_model, _ = mapper.length_model_weights(job.length_model)
     job.umi_mismatches = mapper.check_umi_mismatches(job.umi_mismatches, job.umi_length)
+    job.resolve_molecules = bool(job.resolve_molecules) or bool(job.distribute_molecules)
     job.count_molecules = bool(job.count_molecules) or bool(job.resolve_molecules)
     job.count_matrix = bool(job.count_matrix) or bool(job.matrix_only) or bool(job.count_molecules)
     if job.count_molecules and not (job.umi_length and job.pooled):
@@ -885,6 +939,11 @@ def _take_from_set(job, sample_set, members):
         for k, sample in enumerate(members):
             sample.resolved_row = (r_indices[r_indptr[k]:r_indptr[k + 1]], r_data[r_indptr[k]:r_indptr[k + 1]])
             sample.resolved_tally = r_tally[k]
+    if job.distribute_molecules:            # (and one more: the multi-gene groups among them, shared out by an EM per cell)
+        d_indptr, d_indices, d_data, d_tally, d_unnamed = sample_set.gene_distributed_matrix(job.gene_names[1], n_genes)
+        for k, sample in enumerate(members):
+            sample.distributed_row = (d_indices[d_indptr[k]:d_indptr[k + 1]], d_data[d_indptr[k]:d_indptr[k + 1]])
+            sample.distributed_tally, sample.to_unnamed = d_tally[k], d_unnamed[k]
     if job.matrix_only:
         for sample, row, mean in zip(members, sample_set.sizes(), sample_set.harmonic_mean_fragment_lengths()):
             sample.sizes, sample.mean = row, mean
@@ -961,6 +1020,20 @@ def _finish(job, samples):
         totals = [int(v) for v in tally.sum(axis=0)]
         _LOG.info('Distinct UMIs per cell: %d; resolved to one gene: %d (%d of them rescued), multi-gene: %d, unnamed: %d, '
                   'collisions: %d', totals[0] + totals[2] + totals[3] + totals[4], *totals)
+    if job.distribute_molecules:
+        tally = numpy.asarray([sample.distributed_tally for sample in samples], dtype=numpy.int64).reshape(-1, len(DISTRIBUTED_TALLY))
+        indptr = numpy.concatenate([[0], numpy.cumsum([len(sample.distributed_row[0]) for sample in samples])]).astype(numpy.int64)
+        indices = numpy.concatenate([numpy.asarray(sample.distributed_row[0], dtype=numpy.int32) for sample in samples]
+                                 or [numpy.zeros(0, dtype=numpy.int32)])
+        weights = numpy.concatenate([numpy.asarray(sample.distributed_row[1], dtype=numpy.float64) for sample in samples]
+                                 or [numpy.zeros(0, dtype=numpy.float64)])
+        output_distributed_matrix(job.output_path, job.gene_names[0].size, [sample.name for sample in samples], indptr, indices,
+                                  weights, tally, [sample.to_unnamed for sample in samples])
+        totals = [int(v) for v in tally.sum(axis=0)]
+        _LOG.info('Distinct UMIs per cell: %d; resolved: %d, distributed by the EM: %d, wide: %d, unnamed: %d, collisions: %d; '
+                  'EM steps per cell: %d at most, %d cells capped; weight in genes: %.3f, to no gene: %.3f',
+                  sum(totals[:5]), *totals[:5], int(tally[:, 6].max()) if len(tally) else 0, totals[7], float(weights.sum()),
+                  float(sum(sample.to_unnamed for sample in samples)))
     with (job.output_path / 'samples.tsv').open('w') as f:
         for sample, (total, aligned) in zip(samples, units):
             f.write('%s\t%d\t%d\t%.2f\n' % (sample.name, total, aligned, sample.mean))
@@ -1926,7 +1999,8 @@ def add_gene_arguments(parser):
 def gene_option(opts):
     """The parsed options: --gene-map implies --genes -- unless --count-matrix or --matrix-only is given, which the map
     then serves: they need genes but do not switch the gene-level tables on.  --matrix-only and --count-molecules imply
-    --count-matrix, --resolve-molecules implies --count-molecules."""
+    --count-matrix, --resolve-molecules implies --count-molecules, --distribute-molecules implies --resolve-molecules."""
+    opts['resolve_molecules'] = bool(opts.get('resolve_molecules')) or bool(opts.get('distribute_molecules'))
     opts['count_molecules'] = bool(opts.get('count_molecules')) or bool(opts.get('resolve_molecules'))
     opts['count_matrix'] = bool(opts.get('count_matrix')) or bool(opts.get('matrix_only')) or bool(opts.get('count_molecules'))
     opts['genes'] = bool(opts.get('genes')) or (opts.get('gene_map') is not None and not opts['count_matrix'])
@@ -1934,9 +2008,9 @@ def gene_option(opts):
 
 
 def add_count_matrix_arguments(parser):
-    """--count-matrix, --matrix-only, --count-molecules and --resolve-molecules: dest 'count_matrix', 'matrix_only',
-    'count_molecules', 'resolve_molecules' (gene_option makes the second and the third imply the first, and the fourth
-    the third)."""
+    """--count-matrix, --matrix-only, --count-molecules, --resolve-molecules and --distribute-molecules: dest
+    'count_matrix', 'matrix_only', 'count_molecules', 'resolve_molecules', 'distribute_molecules' (gene_option makes the
+    second and the third imply the first, the fourth the third and the fifth the fourth)."""
     parser.add_argument('--count-matrix', action='store_true', dest='count_matrix',
                         help='also write output/counts/: the sparse gene x cell matrix of the units that lie inside one '
                              'gene (matrix.mtx, genes.tsv, cells.tsv, matrix.npz), made on the GPU; the genes are the '
@@ -1953,6 +2027,10 @@ def add_count_matrix_arguments(parser):
                         help='also write counts/molecules.resolved.mtx, .npz and .tsv: one gene per UMI and cell, named by '
                              'the intersection of the gene sets of the classes the UMI was seen in; multi-gene, unnamed and '
                              'colliding UMIs are tallied per cell; implies --count-molecules, needs --umi-length')
+    parser.add_argument('--distribute-molecules', action='store_true', dest='distribute_molecules',
+                        help='also write counts/molecules.em.mtx, .npz and .tsv: the multi-gene UMIs of --resolve-molecules '
+                             'shared out among the genes of their intersection (16 at most) by a small EM per cell, values in '
+                             'molecules; implies --resolve-molecules, needs --umi-length')
 
 
 def add_bias_argument(parser):

@@ -165,6 +165,84 @@ def resolved_molecule_matrix(class_offsets, class_targets, class_sample, mol_cla
     return read_resolved_matrix(handle)
 
 
+def read_distributed_matrix(handle):
+    """(indptr, indices, data float64[nnz], tally int64[n_samples, 8], to_unnamed float64[n_samples]) of a handle that
+    holds distributed molecules, copied home; the handle is destroyed.  tally[s] = (resolved, distributed, wide, unnamed,
+    collision, rows, steps, capped)."""
+    try:
+        shape = [ctypes.c_int64(0) for _ in range(3)]
+        _native.check(_native.hip().skm_gene_matrix_shape(handle, *[ctypes.byref(word) for word in shape]))
+        n_samples, _, nnz = [int(word.value) for word in shape]
+        indptr = numpy.zeros(n_samples + 1, dtype=numpy.int64)
+        indices = numpy.zeros(max(nnz, 1), dtype=numpy.int32)
+        data = numpy.zeros(max(nnz, 1), dtype=numpy.float64)
+        tally = numpy.zeros((max(n_samples, 1), 8), dtype=numpy.int64)
+        to_unnamed = numpy.zeros(max(n_samples, 1), dtype=numpy.float64)
+        _native.check(_native.hip().skm_gene_matrix_read(
+            handle, _native.ptr(indptr, _native.c_i64p), _native.ptr(indices, _native.c_i32p), None, None))
+        _native.check(_native.hip().skm_gene_matrix_read_weights(handle, _native.ptr(data, _native.c_f64p)))
+        _native.check(_native.hip().skm_gene_matrix_read_em(
+            handle, _native.ptr(tally, _native.c_i64p), _native.ptr(to_unnamed, _native.c_f64p)))
+        return indptr, indices[:nnz], data[:nnz], tally[:n_samples], to_unnamed[:n_samples]
+    finally:
+        _native.hip().skm_gene_matrix_destroy(handle)
+
+
+def distributed_molecule_matrix(class_offsets, class_targets, class_sample, mol_class, mol_umi, tx_gene, n_samples, n_genes,
+                                max_steps=1000, device=0):
+    """(indptr, indices, data, tally, to_unnamed) of the molecules (mol_class[i], mol_umi[i]) with the multi-gene groups
+    shared out among their genes: the arguments and checks of resolved_molecule_matrix, the steps of DESIGN.md section
+    4, "Distributed molecules", on the device with max_steps EM steps per sample at most
+    (skm_gene_matrix_from_molecule_sets)."""
+    class_offsets = numpy.ascontiguousarray(class_offsets, dtype=numpy.int64)
+    class_targets = numpy.ascontiguousarray(class_targets, dtype=numpy.int32)
+    class_sample = numpy.ascontiguousarray(class_sample, dtype=numpy.int32)
+    mol_class = numpy.ascontiguousarray(mol_class, dtype=numpy.int32)
+    mol_umi = numpy.ascontiguousarray(mol_umi, dtype=numpy.uint32)
+    tx_gene = numpy.ascontiguousarray(tx_gene, dtype=numpy.int32)
+    n_classes = int(class_sample.size)
+    if class_offsets.shape != (n_classes + 1,) or mol_class.ndim != 1 or mol_umi.shape != mol_class.shape:
+        raise ValueError('class_offsets[n_classes + 1] beside class_sample[n_classes]; mol_class and mol_umi of one length')
+    if n_classes and class_targets.size != class_offsets[-1]:
+        raise ValueError('class_targets holds %d ids, class_offsets ends at %d' % (class_targets.size, class_offsets[-1]))
+    handle = ctypes.c_void_p()
+    n = int(mol_class.size)
+    _native.check(_native.hip().skm_gene_matrix_from_molecule_sets(
+        int(device), n_classes, _native.ptr(class_offsets, _native.c_i64p),
+        _native.ptr(class_targets, _native.c_i32p) if class_targets.size else None,
+        _native.ptr(class_sample, _native.c_i32p) if n_classes else None, n,
+        _native.ptr(mol_class, _native.c_i32p) if n else None, _native.ptr(mol_umi, _native.c_u32p) if n else None,
+        int(n_samples), int(tx_gene.size), int(n_genes), _native.ptr(tx_gene, _native.c_i32p) if tx_gene.size else None,
+        int(max_steps), ctypes.byref(handle)))
+    return read_distributed_matrix(handle)
+
+
+def gene_em_cells(cell_row_start, u, cell_set_start, set_start, set_rows, max_steps=1000, device=0):
+    """(x float64[n_rows], steps int64[n_cells], capped int64[n_cells]): the EM of "Distributed molecules" alone, a block
+    per cell (skm_gene_em_cells).  Cell c has the rows cell_row_start[c] .. cell_row_start[c + 1] - 1 with the counts
+    u[] and the sets cell_set_start[c] .. cell_set_start[c + 1] - 1; set j holds the cell-local rows
+    set_rows[set_start[j]:set_start[j + 1]], 2 to 16 of them, ascending.  Anything else raises."""
+    cell_row_start = numpy.ascontiguousarray(cell_row_start, dtype=numpy.int64)
+    cell_set_start = numpy.ascontiguousarray(cell_set_start, dtype=numpy.int64)
+    u = numpy.ascontiguousarray(u, dtype=numpy.int64)
+    set_start = numpy.ascontiguousarray(set_start, dtype=numpy.int64)
+    set_rows = numpy.ascontiguousarray(set_rows, dtype=numpy.int32)
+    n_cells = int(cell_row_start.size) - 1
+    if n_cells < 0 or cell_set_start.shape != cell_row_start.shape or u.ndim != 1 or set_start.ndim != 1 or set_rows.ndim != 1:
+        raise ValueError('cell_row_start and cell_set_start of n_cells + 1 words, u, set_start and set_rows flat')
+    if u.size != cell_row_start[-1] or set_start.size != cell_set_start[-1] + 1 or set_rows.size != set_start[-1]:
+        raise ValueError('u[%d], set_start[%d] and set_rows[%d] do not fit the offsets' % (u.size, set_start.size, set_rows.size))
+    x = numpy.zeros(max(u.size, 1), dtype=numpy.float64)
+    steps = numpy.zeros(max(n_cells, 1), dtype=numpy.int64)
+    capped = numpy.zeros(max(n_cells, 1), dtype=numpy.int64)
+    _native.check(_native.hip().skm_gene_em_cells(
+        int(device), n_cells, _native.ptr(cell_row_start, _native.c_i64p), _native.ptr(u, _native.c_i64p) if u.size else None,
+        _native.ptr(cell_set_start, _native.c_i64p), _native.ptr(set_start, _native.c_i64p),
+        _native.ptr(set_rows, _native.c_i32p) if set_rows.size else None, int(max_steps), _native.ptr(x, _native.c_f64p),
+        _native.ptr(steps, _native.c_i64p), _native.ptr(capped, _native.c_i64p)))
+    return x[:u.size], steps[:n_cells], capped[:n_cells]
+
+
 class SummarizedResult:
     """seekmer/mapper.py:18-37"""
     __slots__ = ['aligned', 'unaligned', 'total', 'class_map', 'class_count',
@@ -950,6 +1028,19 @@ class SampleSet:
         _native.check(_native.hip().skm_sample_set_resolved_matrix(
             self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
         return read_resolved_matrix(handle)
+
+    def gene_distributed_matrix(self, tx_gene, n_genes):
+        """(indptr, indices, data float64[nnz], tally int64[n_samples, 8], to_unnamed float64[n_samples]): the groups of
+        gene_resolved_matrix with the multi-gene ones shared out among their genes by an EM per sample.  data[k] is the
+        weight of the gene in the sample, in molecules (0.001 at least); tally[s] = (resolved, distributed, wide,
+        unnamed, collision, rows, steps, capped), the first five adding up to the sample's distinct UMIs; to_unnamed[s]
+        is what the EM gave to "no gene" (skm_sample_set_distributed_matrix; DESIGN.md section 4, "Distributed
+        molecules").  A set that keeps no UMIs (umi_bases=0) raises."""
+        tx_gene = gene_numbers(tx_gene, self.index.transcripts.size)
+        handle = ctypes.c_void_p()
+        _native.check(_native.hip().skm_sample_set_distributed_matrix(
+            self._handle, tx_gene.size, int(n_genes), _native.ptr(tx_gene, _native.c_i32p), ctypes.byref(handle)))
+        return read_distributed_matrix(handle)
 
     def __del__(self):
         handle = getattr(self, '_handle', None)
